@@ -3,6 +3,12 @@
 
   python bench.py --gpus N --steps K --warmup W      (N > 1: this command starts N ranks itself, one per GPU;
                                                        under torch.distributed.run it is one of the ranks)
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the one JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step delivered to rank 0 as float32 .npy files
+(see dump_outputs); the inputs are seeded, so two builds given the same arguments can be compared file for file.
+--full adds everything below, which takes runs of its own after the timed region.
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on): synthetic windows, 500 bp backbone x
 64 reads, PacBio profile (15 % error, ins:del:sub 0.40:0.30:0.30), FASTQ weights, haplotype mode -d 0.2 -s 0.2 -k 3,
@@ -11,7 +17,7 @@ config C), inputs already resident in HBM, followed by the gather of the correct
 xGMI when N > 1).  Weak scaling: every rank gets its own `--windows` windows of the stream (N = 8: 800 000 windows
 per step, config D's shape).
 
-The one JSON line also carries
+With --full the JSON line also carries
   value_e2e   the same windows from host memory to host memory (vc_submit -> vc_run -> vc_collect, H2D and D2H
               included), batches of 32 768 windows queued behind each other in one context -- SURVEY 8(d)'s definition
               of the metric; `value` is the resident-input rate the driver's contract asks for
@@ -279,6 +285,45 @@ def files_to_fasta(params):
     return res
 
 
+DUMP_WINDOWS = 1 << 20        # per-window arrays of the dump: every window up to this many, else a seeded sample of them
+DUMP_CONS_BYTES = 40 << 20    # the consensus matrix of the dump: at most this many bytes of float32 (the whole dump stays under 64 MB)
+
+
+def _sample(n, k, seed):
+    """range(n) when k >= n, else k of its indices picked with a fixed seed, in ascending order"""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(d, cons, lens, status, length):
+    """What the timed path delivered to rank 0 in its last step, as float32 .npy files under `d`:
+      lengths.npy            consensus length of each window (window order, every rank's windows as gathered to rank 0)
+      status.npy             VC_WIN_* status of each of those windows that rank 0 ran
+      windows.npy            the window index of each entry of lengths.npy / status.npy
+      consensus.npy          [rows, longest] consensus bytes of a fixed, seeded sample of the windows, -1 past a window's end
+      consensus_windows.npy  the window index of each row of consensus.npy
+    Which windows are sampled depends on the window count and --length only, so two builds run with the same arguments dump the
+    same windows."""
+    os.makedirs(d, exist_ok=True)
+    lens = lens.cpu().numpy().astype(np.int64)
+    cons = cons.cpu().numpy()
+    n = lens.size
+    off = np.concatenate([[0], np.cumsum(lens)])
+    wi = _sample(n, DUMP_WINDOWS, 1)
+    mine = wi[wi < status.size]
+    rows = _sample(n, max(1, DUMP_CONS_BYTES // (4 * 2 * (length + 256))), 2)     # room for consensus up to twice the backbone + 256
+    width = int(lens[rows].max()) if rows.size else 0
+    rows = rows[:max(1, DUMP_CONS_BYTES // (4 * max(width, 1)))]                   # (cuts only where a consensus outgrows that room)
+    col = np.arange(width)
+    inside = col[None, :] < lens[rows][:, None]
+    mat = np.full((rows.size, width), -1, dtype=np.float32)
+    mat[inside] = cons[(off[rows][:, None] + col[None, :])[inside]]
+    out = {"lengths": lens[wi], "status": status[mine], "windows": wi, "consensus": mat, "consensus_windows": rows}
+    for name, v in out.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def stub_main(a, world):
     """Launch-plumbing check for boxes without a GPU (tests/test_shard.py): the same rank fan-out, barrier, MAX-over-ranks
     timing and gather, over gloo, with the kernels replaced by "consensus = backbone".  Never a measurement: the line says
@@ -320,11 +365,19 @@ def main():
     ap.add_argument("--length", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--streams", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also: the roofline (with its VALU calibration run), the per-kernel profiled pass, value_e2e, "
+                         "the other configs, the files-to-FASTA runs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step delivered to rank 0 as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_e2e, the per-kernel profile pass and the config B / E lines")
-    ap.add_argument("--ab", action="store_true", help="development: only the per-kernel profile pass of the extras")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_e2e, the per-kernel profile pass and the config B / E lines")
+    ap.add_argument("--ab", action="store_true", help="development: only the per-kernel profile pass of the extras (implies --full)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = a.full or a.ab
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # one process per GPU: start N ranks of this same command line (rank r on device r), as the reference fans one
@@ -428,81 +481,85 @@ def main():
         bases = int(lens_all.sum().item()) * a.steps
         s = ctx.stats()
         status = d_status.cpu().numpy()
-        khash = kernel_hash()
-        simds = torch.cuda.get_device_properties(local).multi_processor_count * 4
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, cons_all, lens_all, status, a.length)
         wall_s = dt / a.steps
-        cal = valu_peak_now(local)
-        peak_pk16, peak_src = cal["pk16"], cal["source"]
-        peak_mix, mix_detail = mix_peak(cal["classes"], khash)
-        peak_now = peak_pk16                 # ONE denominator, always -- the packed-int16 issue rate measured in this run (rounds 2-4's); the mix-weighted view is frac_vs_mix
-        # The forward DP keeps its predecessor rows in registers / LDS and stores a byte-packed band: it moves ~0.5 B per cell, an
-        # eighth of SURVEY 8(d)'s 4 B/cell model, so the bound that holds is the instruction stream ("then the VALU
-        # issue bound is the honest limiter and must be stated").  achieved = VALU wave-instructions of ALL kernels of a step
-        # (rocprofv3 PMC SQ_INSTS_VALU per window of this workload, measured on these kernel sources) / step wall time / SIMDs;
-        # peak = the issue rate of k_fwd's OWN instruction mix (peak_mix: packed int16 max / add, v_perm / v_alignbit, DPP forms, lane
-        # moves, 32-bit odds and ends weighted by the histogram of its row loop), every class measured on THIS device in THIS run;
-        # peak_pk16 = the packed-int16 class alone (what rounds 2-4 priced against), frac_vs_pk16 beside it.
-        roof = {"bound": "valu_issue", "kernel": "all kernels of a step (k_fwd alone: roofline.k_fwd)", "achieved": None, "peak": peak_now,
-                "peak_mix": peak_mix, "peak_pk16": peak_pk16, "peak_mix_detail": mix_detail,
-                "unit": "VALU wave-instructions / us / SIMD", "frac": None, "traffic": None, "peak_source": peak_src, "simds": simds,
-                "kernel_hash": khash,
-                # the shader clock: s_memtime ticks (one per shader cycle) over s_memrealtime ticks (100 MHz), wave by wave -- under the job
-                # (summed over k_fwd's row loops inside the timed region) and under the calibration loops.  The chip clocks to its power
-                # budget (MI355X_MICROARCH.md, DVFS): a dense vector stream runs well below the 2.4 GHz the device reports.
-                "sclk_mhz": {"timed_region_k_fwd": s.get("fwd_sclk_mhz"), "calibration_pk16": cal.get("pk16_sclk_mhz"), "device_reports": torch.cuda.get_device_properties(local).clock_rate / 1e3 if hasattr(torch.cuda.get_device_properties(local), "clock_rate") else None},
-                "pk16_simd_cycles_per_inst": cal.get("pk16_simd_cycles_per_inst")}
-        hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s", "algorithmic_bytes_per_cell": BYTES_PER_CELL, "cells_per_step": cells / a.steps,
-               "algorithmic_gbs_over_wall": BYTES_PER_CELL * cells / a.steps / wall_s / 1e9}
-        hbm["algorithmic_model_exceeds_peak"] = hbm["algorithmic_gbs_over_wall"] > HBM_PEAK_GBS
-        hbm["algorithmic_frac"] = None if hbm["algorithmic_model_exceeds_peak"] else hbm["algorithmic_gbs_over_wall"] / HBM_PEAK_GBS
-        kf = {"avg_launch_ms": fwd_ms / max(fwd_launches, 1), "launches_per_step": fwd_launches / a.steps, "busy_ms_per_step": fwd_busy_ms / a.steps,
-              "dp_rows_per_step": rows / a.steps,
-              "timing": "HIP events around every k_fwd launch on its own stream, inside the timed region (vc_params.profile = 2); the chunk streams "
-                        "overlap, so launches run beside each other: busy_ms = time during which at least one k_fwd launch was running"}
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", "r6_hbm_traffic.json")))
-            if tj.get("kernel_hash") != khash:
-                roof["counts_note"] = f"profiles/r6_hbm_traffic.json was measured for kernels {tj.get('kernel_hash')}, these are {khash}: not used"
-            else:
-                roof["counts_source"] = ("rocprofv3 --pmc passes over the same kernel sources (profiles/r6_hbm_traffic.json from profiles/r6_pmc_counters.txt: "
-                                         "SQ_INSTS_VALU, FETCH_SIZE, WRITE_SIZE, one counter group per pass) scaled by this run's windows / DP rows / cells")
-                wps = a.windows * world                                             # windows per step
-                job_valu = tj["valu_insts_per_window_all_kernels"] * wps
-                roof["valu_wave_insts_per_step"] = job_valu
-                if peak_now:
-                    roof["achieved"] = job_valu / (wall_s * 1e6 * simds)
-                    roof["frac"] = roof["achieved"] / peak_now
-                    roof["frac_vs_pk16"] = roof["frac"]
-                    if peak_mix:
-                        roof["frac_vs_mix"] = roof["achieved"] / peak_mix
-                roof["_valu_per_window_by_config"] = tj.get("valu_insts_per_window_by_config", {})
-                # Second view, the one that explains why nothing moves this design by much any more: EVERY instruction the SQ counts (vector,
-                # scalar, branch, LDS, memory) of a step over the same time, against what a SIMD issues when vector and scalar instructions
-                # come 1 : 1 (independent v_pk_max / v_pk_add_i16 interleaved with independent s_add / s_and / s_max / s_lshl, same run) --
-                # roughly k_fwd's own ratio.  A SIMD issues a packed-int16 instruction every ~4.2 cycles, a scalar one every ~4.7, and
-                # both side by side at ~2.8 cycles per instruction: the scalar half of a DP row is not free.
-                ipw = tj.get("insts_per_window_all_kernels")
-                if ipw and cal.get("mixed_issue"):
-                    tot = sum(ipw.values())
-                    ach = tot * wps / (wall_s * 1e6 * simds)
-                    roof["instruction_issue"] = {"insts_per_window_by_class": ipw, "achieved": ach, "unit": "wave-instructions of any class / us / SIMD",
-                                                 "peak_1to1_vector_scalar": cal["mixed_issue"]["inst_per_us_per_simd"], "frac": ach / cal["mixed_issue"]["inst_per_us_per_simd"],
-                                                 "peak_detail": cal["mixed_issue"], "salu_only_rate": cal.get("salu_only"),
-                                                 "note": "not a hard ceiling (the attainable total depends on the mix); reported beside roofline.frac, which stays the vector-issue fraction"}
-                ipr = tj["instructions_per_dp_row"]["VALU"]
-                kf.update({"valu_insts_per_dp_row": ipr, "valu_wave_insts_per_step": ipr * rows / a.steps})
-                if peak_now:
-                    kf["frac_of_valu_issue_peak_over_wall"] = ipr * rows / a.steps / (wall_s * 1e6 * simds * peak_now)
-                    if fwd_busy_ms > 0:
-                        kf["frac_of_valu_issue_peak_over_busy_time"] = ipr * rows / (fwd_busy_ms * 1e3 * simds * peak_now)
-                roof["traffic"] = tj["bytes_per_cell"] * cells / max(fwd_launches, 1)       # measured HBM bytes per k_fwd launch
-                hbm.update({"measured_bytes_per_cell": tj["bytes_per_cell"], "measured_gbs_over_wall": tj["bytes_per_cell"] * cells / a.steps / wall_s / 1e9,
-                            "measured_frac": tj["bytes_per_cell"] * cells / a.steps / wall_s / 1e9 / HBM_PEAK_GBS,
-                            "k_tracew_bytes_fetched_per_move": tj.get("k_tracew_bytes_fetched_per_move")})
-        except Exception as e:
-            roof["counts_note"] = repr(e)
-        roof["k_fwd"] = kf
-        roof["hbm"] = hbm
+        roof = None
+        if full:
+            khash = kernel_hash()
+            simds = torch.cuda.get_device_properties(local).multi_processor_count * 4
+            cal = valu_peak_now(local)
+            peak_pk16, peak_src = cal["pk16"], cal["source"]
+            peak_mix, mix_detail = mix_peak(cal["classes"], khash)
+            peak_now = peak_pk16                 # ONE denominator, always -- the packed-int16 issue rate measured in this run (rounds 2-4's); the mix-weighted view is frac_vs_mix
+            # The forward DP keeps its predecessor rows in registers / LDS and stores a byte-packed band: it moves ~0.5 B per cell, an
+            # eighth of SURVEY 8(d)'s 4 B/cell model, so the bound that holds is the instruction stream ("then the VALU
+            # issue bound is the honest limiter and must be stated").  achieved = VALU wave-instructions of ALL kernels of a step
+            # (rocprofv3 PMC SQ_INSTS_VALU per window of this workload, measured on these kernel sources) / step wall time / SIMDs;
+            # peak = the issue rate of k_fwd's OWN instruction mix (peak_mix: packed int16 max / add, v_perm / v_alignbit, DPP forms, lane
+            # moves, 32-bit odds and ends weighted by the histogram of its row loop), every class measured on THIS device in THIS run;
+            # peak_pk16 = the packed-int16 class alone (what rounds 2-4 priced against), frac_vs_pk16 beside it.
+            roof = {"bound": "valu_issue", "kernel": "all kernels of a step (k_fwd alone: roofline.k_fwd)", "achieved": None, "peak": peak_now,
+                    "peak_mix": peak_mix, "peak_pk16": peak_pk16, "peak_mix_detail": mix_detail,
+                    "unit": "VALU wave-instructions / us / SIMD", "frac": None, "traffic": None, "peak_source": peak_src, "simds": simds,
+                    "kernel_hash": khash,
+                    # the shader clock: s_memtime ticks (one per shader cycle) over s_memrealtime ticks (100 MHz), wave by wave -- under the job
+                    # (summed over k_fwd's row loops inside the timed region) and under the calibration loops.  The chip clocks to its power
+                    # budget (DVFS): a dense vector stream runs well below the 2.4 GHz the device reports.
+                    "sclk_mhz": {"timed_region_k_fwd": s.get("fwd_sclk_mhz"), "calibration_pk16": cal.get("pk16_sclk_mhz"), "device_reports": torch.cuda.get_device_properties(local).clock_rate / 1e3 if hasattr(torch.cuda.get_device_properties(local), "clock_rate") else None},
+                    "pk16_simd_cycles_per_inst": cal.get("pk16_simd_cycles_per_inst")}
+            hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s", "algorithmic_bytes_per_cell": BYTES_PER_CELL, "cells_per_step": cells / a.steps,
+                   "algorithmic_gbs_over_wall": BYTES_PER_CELL * cells / a.steps / wall_s / 1e9}
+            hbm["algorithmic_model_exceeds_peak"] = hbm["algorithmic_gbs_over_wall"] > HBM_PEAK_GBS
+            hbm["algorithmic_frac"] = None if hbm["algorithmic_model_exceeds_peak"] else hbm["algorithmic_gbs_over_wall"] / HBM_PEAK_GBS
+            kf = {"avg_launch_ms": fwd_ms / max(fwd_launches, 1), "launches_per_step": fwd_launches / a.steps, "busy_ms_per_step": fwd_busy_ms / a.steps,
+                  "dp_rows_per_step": rows / a.steps,
+                  "timing": "HIP events around every k_fwd launch on its own stream, inside the timed region (vc_params.profile = 2); the chunk streams "
+                            "overlap, so launches run beside each other: busy_ms = time during which at least one k_fwd launch was running"}
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", "r6_hbm_traffic.json")))
+                if tj.get("kernel_hash") != khash:
+                    roof["counts_note"] = f"profiles/r6_hbm_traffic.json was measured for kernels {tj.get('kernel_hash')}, these are {khash}: not used"
+                else:
+                    roof["counts_source"] = ("rocprofv3 --pmc passes over the same kernel sources (profiles/r6_hbm_traffic.json from profiles/r6_pmc_counters.txt: "
+                                             "SQ_INSTS_VALU, FETCH_SIZE, WRITE_SIZE, one counter group per pass) scaled by this run's windows / DP rows / cells")
+                    wps = a.windows * world                                             # windows per step
+                    job_valu = tj["valu_insts_per_window_all_kernels"] * wps
+                    roof["valu_wave_insts_per_step"] = job_valu
+                    if peak_now:
+                        roof["achieved"] = job_valu / (wall_s * 1e6 * simds)
+                        roof["frac"] = roof["achieved"] / peak_now
+                        roof["frac_vs_pk16"] = roof["frac"]
+                        if peak_mix:
+                            roof["frac_vs_mix"] = roof["achieved"] / peak_mix
+                    roof["_valu_per_window_by_config"] = tj.get("valu_insts_per_window_by_config", {})
+                    # Second view, the one that explains why nothing moves this design by much any more: EVERY instruction the SQ counts (vector,
+                    # scalar, branch, LDS, memory) of a step over the same time, against what a SIMD issues when vector and scalar instructions
+                    # come 1 : 1 (independent v_pk_max / v_pk_add_i16 interleaved with independent s_add / s_and / s_max / s_lshl, same run) --
+                    # roughly k_fwd's own ratio.  A SIMD issues a packed-int16 instruction every ~4.2 cycles, a scalar one every ~4.7, and
+                    # both side by side at ~2.8 cycles per instruction: the scalar half of a DP row is not free.
+                    ipw = tj.get("insts_per_window_all_kernels")
+                    if ipw and cal.get("mixed_issue"):
+                        tot = sum(ipw.values())
+                        ach = tot * wps / (wall_s * 1e6 * simds)
+                        roof["instruction_issue"] = {"insts_per_window_by_class": ipw, "achieved": ach, "unit": "wave-instructions of any class / us / SIMD",
+                                                     "peak_1to1_vector_scalar": cal["mixed_issue"]["inst_per_us_per_simd"], "frac": ach / cal["mixed_issue"]["inst_per_us_per_simd"],
+                                                     "peak_detail": cal["mixed_issue"], "salu_only_rate": cal.get("salu_only"),
+                                                     "note": "not a hard ceiling (the attainable total depends on the mix); reported beside roofline.frac, which stays the vector-issue fraction"}
+                    ipr = tj["instructions_per_dp_row"]["VALU"]
+                    kf.update({"valu_insts_per_dp_row": ipr, "valu_wave_insts_per_step": ipr * rows / a.steps})
+                    if peak_now:
+                        kf["frac_of_valu_issue_peak_over_wall"] = ipr * rows / a.steps / (wall_s * 1e6 * simds * peak_now)
+                        if fwd_busy_ms > 0:
+                            kf["frac_of_valu_issue_peak_over_busy_time"] = ipr * rows / (fwd_busy_ms * 1e3 * simds * peak_now)
+                    roof["traffic"] = tj["bytes_per_cell"] * cells / max(fwd_launches, 1)       # measured HBM bytes per k_fwd launch
+                    hbm.update({"measured_bytes_per_cell": tj["bytes_per_cell"], "measured_gbs_over_wall": tj["bytes_per_cell"] * cells / a.steps / wall_s / 1e9,
+                                "measured_frac": tj["bytes_per_cell"] * cells / a.steps / wall_s / 1e9 / HBM_PEAK_GBS,
+                                "k_tracew_bytes_fetched_per_move": tj.get("k_tracew_bytes_fetched_per_move")})
+            except Exception as e:
+                roof["counts_note"] = repr(e)
+            roof["k_fwd"] = kf
+            roof["hbm"] = hbm
         line = {
             "metric": "POA windows/sec (500 bp x 64-read)", "value": total_windows / dt, "unit": "windows/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
@@ -517,15 +574,16 @@ def main():
             "corrected_bases_per_s": bases * world / dt if world == 1 else bases / dt,
             "gcups": cells * world / dt / 1e9,
             "windows_not_ok": int((status > 1).sum()),
-            "roofline": roof,
         }
+        if full:
+            line["roofline"] = roof
         if world > 1 or force_dist:
             line["world_size"] = dist.get_world_size()           # as RCCL reports it
             line["gather_ms"] = times["gather_s"] / a.steps * 1e3
             if per_rank is not None:
                 line["per_rank_windows_per_s"] = {"min": float(per_rank[:, 0].min()), "max": float(per_rank[:, 0].max())}
                 line["per_rank_gather_ms"] = {"min": float(per_rank[:, 1].min()), "max": float(per_rank[:, 1].max())}
-        if world == 1 and not a.no_extras and cfg_name == "C":
+        if full and world == 1 and not a.no_extras and cfg_name == "C":
             # separate pass with every kernel class bracketed by events: the breakdown, not part of `value`
             ctx.lib.vc_set_profile(ctx.h, 1)
             ctx.run(); ctx.sync()
@@ -534,7 +592,7 @@ def main():
             line["kernel_ms_note"] = "separate profiled pass (vc_params.profile = 1); sums exceed ms_per_step because chunk streams overlap"
             ctx.lib.vc_set_profile(ctx.h, 2)
     ctx_params = ctx.params
-    if rank == 0 and world == 1 and not a.no_extras and not a.ab and cfg_name == "C":
+    if rank == 0 and full and world == 1 and not a.no_extras and not a.ab and cfg_name == "C":
         cons_np = cons_all.cpu().numpy()
         off = np.concatenate([[0], np.cumsum(lens_all.cpu().numpy())])
         ctx.close()                                     # its workspaces go back before the two e2e contexts plan theirs
@@ -569,13 +627,13 @@ def main():
                 ach = v * cfg_line["windows_per_s"] / 1e6 / line["roofline"]["simds"]
                 pc[name] = {"valu_wave_insts_per_window": v, "windows_per_s": cfg_line["windows_per_s"], "achieved": ach, "frac": ach / line["roofline"]["peak"]}
         line["roofline"]["per_config"] = pc
-    if rank == 0:
+    if rank == 0 and full:
         line["roofline"].pop("_valu_per_window_by_config", None)
-    if rank == 0 and world == 1 and not a.no_extras and not a.ab and cfg_name == "C":
+    if rank == 0 and full and world == 1 and not a.no_extras and not a.ab and cfg_name == "C":
         line["files_to_fasta"] = files_to_fasta(ctx_params)
         if os.environ.get("VC_BENCH_LARGE_FILES", "1") != "0":
             line["files_to_fasta_large"] = files_to_fasta_large()
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and full and world == 1 and not a.no_cpu:
         cb, ref_out = cpu_baseline(batch, ctx_params, a.cpu_seconds)
         cons_np = cons_all.cpu().numpy()
         off = np.concatenate([[0], np.cumsum(lens_all.cpu().numpy())])

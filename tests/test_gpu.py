@@ -781,6 +781,33 @@ def test_bench_single_rank_through_rccl(built):
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["windows_not_ok"] == 0
 
 
+def test_bench_dump_outputs_are_what_the_path_computes(built, tmp_path):
+    """A plain bench run (no --full) with --dump-outputs: the line carries the headline keys and none of --full's, and the dumped
+    arrays are what a HipContext computes for the same seeded windows (bench's batch: seed 1002, PacBio profile, from window 0)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--windows", "512",
+                          "--layers", "16", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and "roofline" not in line and "cpu_baseline" not in line
+    f = {p.stem: np.load(p) for p in d.glob("*.npy")}
+    assert set(f) == {"lengths", "status", "windows", "consensus", "consensus_windows"}
+    assert all(v.dtype == np.float32 for v in f.values()) and sum(p.stat().st_size for p in d.glob("*.npy")) <= 64 << 20
+    batch = capi.synth_batch(capi.synth_cfg(1002, 500, 16, profile=capi.PACBIO), 0, 512)
+    ctx = HipContext(device=0)
+    cons, status = ctx.consensus(batch, retry_overflow=False)         # (the timed path does not retry)
+    ctx.close()
+    assert (f["windows"] == np.arange(512)).all() and (f["consensus_windows"] == np.arange(512)).all()
+    assert [int(x) for x in f["lengths"]] == [len(c) for c in cons]
+    assert [int(x) for x in f["status"]] == [int(x) for x in status]
+    for w, row in enumerate(f["consensus"]):
+        assert row[:len(cons[w])].astype(np.uint8).tobytes() == cons[w] and (row[len(cons[w]):] == -1).all()
+
+
 def _recode(batch, alphabet, rate, seed):
     """Windows of `batch` with a fraction of the layer bases replaced by letters of `alphabet` (columns then hold many
     distinct bytes: aligned groups larger than A/C/G/T/N)."""

@@ -5,7 +5,7 @@ for rep in 1 2; do
   for spec in "$@"; do
     IFS='|' read -r label envs lib <<< "$spec"
     path=vechat_amd/lib/libvechat_hip.so; [ "$lib" != "main" ] && path=vechat_amd/lib/variants/libvechat_hip_$lib.so
-    env $envs VECHAT_HIP_LIB=$path timeout 300 python bench.py --no-cpu --no-extras --steps 3 > $O/ab_${label}_$rep.json 2> $O/ab_${label}_$rep.err
+    env $envs VECHAT_HIP_LIB=$path timeout 300 python bench.py --full --no-cpu --no-extras --steps 3 > $O/ab_${label}_$rep.json 2> $O/ab_${label}_$rep.err
     python - "$label" "$rep" "$O/ab_${label}_$rep.json" <<'PY'
 import json, sys
 try:

@@ -24,10 +24,10 @@ $R/vechat_amd/lib/valu_peak.bin > $O/valu_peak.txt
 python $R/tools/make_traffic_json.py /tmp/pmc $O/pmc_stats.json $O/valu_peak.txt $O E=/tmp/pmcE:$O/pmc_stats_E.json W=/tmp/pmcW:$O/pmc_stats_W.json
 cp $O/r6_hbm_traffic.json $R/profiles/r6_hbm_traffic.json      # (on this box: the bench below prices its step against these counts)
 cd $R
-timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 1500 $O/bench.json
+timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 1500 $O/bench.json
 cd /tmp
 rm -rf /tmp/prof_stats
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python $R/bench.py --no-cpu --no-extras > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python $R/bench.py --full --no-cpu --no-extras > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 f=$(grep -l k_fwd $(find /tmp/prof_stats -name "*kernel_stats.csv") /dev/null < /dev/null | head -1); cp "$f" $O/kernel_stats.csv; head -12 $O/kernel_stats.csv      # (the calibration binary the bench starts writes a stats file of its own)
 # the same bench with the process pinned to two cores (an 8-rank node leaves each rank about two): stream workers and the host side must not need more
 cd $R
