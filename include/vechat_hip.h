@@ -50,7 +50,7 @@ enum {
 enum {
     VC_WIN_OK          = 0,  /* consensus produced; generate_consensus() would return true      */
     VC_WIN_UNPOLISHED  = 1,  /* < 3 sequences: backbone copied, returns false (window.cpp:188-192) */
-    VC_WIN_OVERFLOW    = 2,  /* graph outgrew max_nodes/max_edges/stack: resubmit with larger caps */
+    VC_WIN_OVERFLOW    = 2,  /* graph outgrew max_nodes/max_edges/stack: resubmit with larger caps, then vc_large_run */
     VC_WIN_UNSUPPORTED = 3,  /* reserved: no longer produced (every valid window is computed on the device) */
     VC_WIN_INVALID     = 4   /* input the reference would throw on (graph.cpp:191-231)          */
 };
@@ -333,6 +333,22 @@ int         vc_align(int device, const vc_align_batch* b, char* cigar, uint64_t 
 const char* vc_align_last_error(void);
 /* the aligner keeps its (large) matrix buffer between calls; this gives it back */
 void        vc_align_release(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * The large-graph path: windows the fast path hands back as VC_WIN_OVERFLOW (a graph beyond max_nodes / max_edges after
+ * the capacity retries -- 16-bit ids, at most 59 968 nodes / 32 000 edges -- or a layer too long for k_addaln's LDS notes).
+ * The same per-window algorithm with 32-bit ids and int32 scores on tables in HBM sized per window (grown and run again
+ * when they fill): byte-identical results, no size limit but the device memory, and much slower per window than the fast
+ * path.  A caller runs its overflowed windows through it where the reference's accelerated polisher runs them on the CPU
+ * (src/cuda/cudapolisher.cpp:355-379).
+ * Synchronous: computes every window of b and fills r like vc_collect (cons_cap >= the batch's bases is always enough);
+ * statuses VC_WIN_OK / UNPOLISHED / INVALID as vc_collect, VC_WIN_OVERFLOW only for a window the device memory cannot hold
+ * at all.  Honours device, the scores, mode, the thresholds, num_prune, trim and window_type; the capacity fields are ignored.
+ * ------------------------------------------------------------------------------------------------ */
+int         vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r);
+const char* vc_large_last_error(void);
+/* the large path keeps its window tables and matrix buffer between calls; this gives them back */
+void        vc_large_release(void);
 
 #ifdef __cplusplus
 }

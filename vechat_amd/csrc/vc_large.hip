@@ -1,0 +1,1057 @@
+// The large-graph path: the whole per-window algorithm on the device without the fast path's limits.
+//
+// The fast path (vc_api.hip) holds 16-bit node ids, LDS graph images and 16-bit adjacency offsets, so a window's graph stops at
+// 59 968 nodes / 32 000 edges and a window with a longer layer stops at k_addaln's LDS notes; such windows come back
+// VC_WIN_OVERFLOW.  vc_large_run computes them here: every id is 32 bits, every score int32 (int64 inside the horizontal scan),
+// every table lives in HBM and is sized from what the window needs; a window whose tables fill is run again with larger ones.
+// Slow by design: correctness counts here, not speed.
+//
+// Semantics: oracle/vc_oracle.c, function by function (the names below are the oracle's).  The order-sensitive parts -- the
+// insertion order of in-/out-edges and aligned nodes, the DFS topological order, the DFS preorder of the largest component,
+// the fp64 prune thresholds, average_weight (FASTA-backbone quirk included) and the tie rules of the backtrack and the heaviest
+// bundle -- are restated literally.  Per-node lists are linked lists through the edges (in / out) and through cells (aligned
+// nodes, edge labels) with head, tail and count per node, so appending keeps the oracle's order and nothing is ever moved.
+//
+// Kernels (gfx950, wave64), one launch per stage per alignment step over all windows in flight (lock-step, like vc_run's chunks):
+//   k_lg_init   one lane per window: backbone chain, topological order, the backbone's share of average_weight;
+//   k_lg_prep   one lane per window: the next alignment of the window's schedule (subgraph of a partial-span layer when the
+//               build needs one), its rank-ordered predecessor lists (CSR of row indices), row bytes and sink flags;
+//   k_lg_fwd    one wave per alignment: rows in rank order, columns over the 64 lanes; predecessor rows are read back from the
+//               int32 matrix (rows + 1) x (len + 1) in HBM; the horizontal move is a wave prefix maximum on tilted scores;
+//   k_lg_back   one lane per alignment: walks the stored matrix in the oracle's order of candidates;
+//   k_lg_apply  one lane per window: add-alignment + topological sort, or add-weights; prune + largest component at the end of
+//               the build and of every round; the corrected sequence (mode 0) or heaviest bundle + coverage + trim (mode 1).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "vechat_hip.h"
+
+namespace {
+
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+constexpr int32_t KNEG = INT32_MIN + 1024;             // the reference's engines' floor (oracle: KNEG)
+constexpr int64_t TNEG = INT64_MIN / 4;                // tilted score of a lane beyond the sequence
+constexpr uint32_t kCols = 8;                          // consecutive columns per lane in k_lg_fwd
+
+enum : uint32_t { PH_BUILD = 0, PH_ROUND = 1, PH_FINAL = 2, PH_DONE = 3 };
+// which table filled (LWin::grow): the host doubles it and runs the window again
+enum : uint32_t { G_NODES = 1, G_EDGES = 2, G_ALIGNED = 4, G_LABELS = 8, G_STACK = 16, G_PAIRS = 32 };
+
+struct LGraph {
+    uint32_t n_nodes, n_edges, n_al, n_lb, n_rank, nseq;
+    uint32_t labels;                                   // 1: edges keep sequence labels (only the racon-linear overload's coverage reads them)
+    uint8_t* code;                                     // [NC]
+    uint32_t *in_h, *in_t, *in_n, *out_h, *out_t, *out_n, *al_h, *al_t, *al_n, *rank;   // [NC]
+    uint32_t *tail, *head, *nx_in, *nx_out, *lb_h, *lb_t;                               // [EC]
+    int64_t* weight;                                   // [EC]
+    uint8_t* alive;                                    // [EC]
+    uint32_t *al_v, *al_nx;                            // [AC] aligned-node cells
+    uint32_t *lb_v, *lb_nx;                            // [LC] label cells
+};
+
+struct LWin {
+    uint32_t s0, nseq, L, fasta;                       // window: first sequence, sequences, backbone length, if_fasta
+    uint32_t NC, EC, AC, LC, SC, PC;                   // capacities
+    uint32_t phase, j, k, cur, sub, grow, status;      // schedule; cur = graph slot of G / P; sub = the alignment ran on a subgraph
+    uint32_t num_codes;
+    double total, avg;
+    uint32_t rows, qlen, qs, type;                     // the current alignment: graph rows, query length, query (sequence index), 0 SW / 1 NW
+    int32_t m, x, g;
+    uint32_t max_i, max_j, npairs, cons_n;
+    LGraph gr[2];
+    int32_t *coder, *decoder;                          // [256]
+    uint8_t *mark, *ign;                               // [NC]
+    uint32_t *stack;                                   // [SC]
+    uint32_t *node_rank, *map, *g2s, *fr_v, *fr_e, *comp, *best, *pred, *stamp;   // [NC] (stamp: [nseq + 1])
+    uint8_t* fr_p;                                     // [NC]
+    int64_t* scores;                                   // [NC]
+    uint8_t *rchar, *sink;                             // [NC]
+    uint32_t *poff, *prank;                            // [NC + 1], [EC]
+    int32_t* pairs;                                    // [2 PC]
+    uint8_t* cons;                                     // [NC]
+};
+
+struct LArgs {
+    LWin* win;
+    uint32_t n;
+    const uint64_t* seq_off;
+    const uint32_t *seq_begin, *seq_end;
+    const uint8_t *has_qual, *bases, *quals;
+    const uint32_t* lut_w;                             // vc_weight_lut
+    const double* lut_d;                               // 1 - 10^((33 - q) / 10), window.cpp:235,295
+    int32_t match, mismatch, gap, sw_match, sw_mismatch, sw_gap;
+    double min_conf, min_sup;
+    uint32_t num_prune, mode, trim, window_type;
+    // k_lg_fwd / k_lg_back: windows of this launch and their matrices
+    const uint32_t* list;
+    const uint64_t* hoff;
+    int32_t* H;
+};
+
+// ------------------------------------------------------------------ graph tables
+__device__ uint32_t add_node(LWin& W, LGraph& g, uint32_t code) {
+    if (g.n_nodes >= W.NC) { W.grow |= G_NODES; return NONE; }
+    const uint32_t id = g.n_nodes++;
+    g.code[id] = (uint8_t)code;
+    g.in_h[id] = g.in_t[id] = g.out_h[id] = g.out_t[id] = g.al_h[id] = g.al_t[id] = NONE;
+    g.in_n[id] = g.out_n[id] = g.al_n[id] = 0;
+    return id;
+}
+
+__device__ bool push_label(LWin& W, LGraph& g, uint32_t e, uint32_t label) {
+    if (!g.labels) return true;
+    if (g.n_lb >= W.LC) { W.grow |= G_LABELS; return false; }
+    const uint32_t c = g.n_lb++;
+    g.lb_v[c] = label; g.lb_nx[c] = NONE;
+    if (g.lb_t[e] == NONE) g.lb_h[e] = c; else g.lb_nx[g.lb_t[e]] = c;
+    g.lb_t[e] = c;
+    return true;
+}
+
+__device__ bool push_aligned(LWin& W, LGraph& g, uint32_t v, uint32_t a) {
+    if (g.n_al >= W.AC) { W.grow |= G_ALIGNED; return false; }
+    const uint32_t c = g.n_al++;
+    g.al_v[c] = a; g.al_nx[c] = NONE;
+    if (g.al_t[v] == NONE) g.al_h[v] = c; else g.al_nx[g.al_t[v]] = c;
+    g.al_t[v] = c; g.al_n[v]++;
+    return true;
+}
+
+// g_new_edge
+__device__ bool new_edge(LWin& W, LGraph& g, uint32_t tail, uint32_t head, uint32_t label, uint32_t w) {
+    if (g.n_edges >= W.EC) { W.grow |= G_EDGES; return false; }
+    const uint32_t e = g.n_edges++;
+    g.tail[e] = tail; g.head[e] = head; g.weight[e] = (int64_t)w; g.alive[e] = 1;
+    g.nx_in[e] = g.nx_out[e] = NONE; g.lb_h[e] = g.lb_t[e] = NONE;
+    if (!push_label(W, g, e, label)) return false;
+    if (g.out_t[tail] == NONE) g.out_h[tail] = e; else g.nx_out[g.out_t[tail]] = e;
+    g.out_t[tail] = e; g.out_n[tail]++;
+    if (g.in_t[head] == NONE) g.in_h[head] = e; else g.nx_in[g.in_t[head]] = e;
+    g.in_t[head] = e; g.in_n[head]++;
+    return true;
+}
+
+// g_add_edge: find by head in tail's out-list, else append
+__device__ bool add_edge(LWin& W, LGraph& g, uint32_t tail, uint32_t head, uint32_t w) {
+    for (uint32_t e = g.out_h[tail]; e != NONE; e = g.nx_out[e]) {
+        if (g.head[e] == head) {
+            if (!push_label(W, g, e, g.nseq)) return false;
+            g.weight[e] += (int64_t)w;
+            return true;
+        }
+    }
+    return new_edge(W, g, tail, head, g.nseq, w);
+}
+
+__device__ __forceinline__ uint32_t weight_of(const LArgs& a, uint32_t s, uint32_t i, bool use_qual) {
+    return use_qual ? a.lut_w[a.quals[a.seq_off[s] + i]] : 1u;
+}
+
+// g_add_chain: fresh chain for seq[begin, end); *first = first node or NONE
+__device__ bool add_chain(const LArgs& a, LWin& W, LGraph& g, uint32_t s, bool uq, uint32_t begin, uint32_t end, uint32_t* first) {
+    *first = NONE;
+    const uint8_t* seq = a.bases + a.seq_off[s];
+    uint32_t prev = NONE;
+    for (uint32_t i = begin; i < end; ++i) {
+        const uint32_t curr = add_node(W, g, (uint32_t)W.coder[seq[i]]);
+        if (curr == NONE) return false;
+        if (*first == NONE) *first = curr;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, s, i - 1, uq) + weight_of(a, s, i, uq))) return false;
+        prev = curr;
+    }
+    return true;
+}
+
+// g_toposort: iterative DFS over ids in order; in-edge tails then aligned nodes pushed; a node is emitted followed by its aligned nodes
+__device__ bool toposort(LWin& W, LGraph& g) {
+    g.n_rank = 0;
+    const uint32_t N = g.n_nodes;
+    uint8_t* marks = W.mark;
+    uint8_t* ignored = W.ign;
+    for (uint32_t v = 0; v < N; ++v) { marks[v] = 0; ignored[v] = 0; }
+    uint32_t sp = 0;
+    for (uint32_t s = 0; s < N; ++s) {
+        if (marks[s] != 0) continue;
+        if (sp >= W.SC) { W.grow |= G_STACK; return false; }
+        W.stack[sp++] = s;
+        while (sp) {
+            const uint32_t c = W.stack[sp - 1];
+            bool valid = true;
+            if (marks[c] != 2) {
+                for (uint32_t e = g.in_h[c]; e != NONE; e = g.nx_in[e]) {
+                    const uint32_t t = g.tail[e];
+                    if (marks[t] != 2) {
+                        if (sp >= W.SC) { W.grow |= G_STACK; return false; }
+                        W.stack[sp++] = t; valid = false;
+                    }
+                }
+                if (!ignored[c]) {
+                    for (uint32_t q = g.al_h[c]; q != NONE; q = g.al_nx[q]) {
+                        const uint32_t al = g.al_v[q];
+                        if (marks[al] != 2) {
+                            if (sp >= W.SC) { W.grow |= G_STACK; return false; }
+                            W.stack[sp++] = al; ignored[al] = 1; valid = false;
+                        }
+                    }
+                }
+                if (valid) {
+                    marks[c] = 2;
+                    if (!ignored[c]) {
+                        if (g.n_rank + 1 + g.al_n[c] > W.NC) { W.grow |= G_NODES; return false; }   // (an aligned group is emitted once)
+                        g.rank[g.n_rank++] = c;
+                        for (uint32_t q = g.al_h[c]; q != NONE; q = g.al_nx[q]) g.rank[g.n_rank++] = g.al_v[q];
+                    }
+                } else {
+                    marks[c] = 1;
+                }
+            }
+            if (valid) sp--;
+        }
+    }
+    return true;
+}
+
+// g_add_alignment.  Returns 0, -1 where the reference throws, -2 when a table filled.
+__device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* A, uint32_t np, uint32_t s, bool uq) {
+    const uint32_t len = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
+    const uint8_t* seq = a.bases + a.seq_off[s];
+    if (len == 0) return 0;
+    for (uint32_t i = 0; i < len; ++i) {
+        if (W.coder[seq[i]] == -1) {
+            W.coder[seq[i]] = (int32_t)W.num_codes;
+            W.decoder[W.num_codes++] = seq[i];
+        }
+    }
+    uint32_t first;
+    if (np == 0) {
+        if (!add_chain(a, W, g, s, uq, 0, len, &first)) return -2;
+        g.nseq++;
+        return toposort(W, g) ? 0 : -2;
+    }
+    int32_t vfront = -1, vback = -1;
+    for (uint32_t k = 0; k < np; ++k) {
+        const int32_t q = A[2 * k + 1];
+        if (q != -1) {
+            if (q < 0 || q >= (int32_t)len) return -1;
+            if (vfront == -1) vfront = q;
+            vback = q;
+        }
+    }
+    if (vfront == -1) return -1;
+    uint32_t begin, last;
+    if (!add_chain(a, W, g, s, uq, 0, (uint32_t)vfront, &begin)) return -2;
+    uint32_t prev = (begin != NONE) ? g.n_nodes - 1 : NONE;
+    if (!add_chain(a, W, g, s, uq, (uint32_t)vback + 1, len, &last)) return -2;
+    for (uint32_t k = 0; k < np; ++k) {
+        const int32_t n = A[2 * k], q = A[2 * k + 1];
+        if (q == -1) continue;
+        const uint32_t c = (uint32_t)W.coder[seq[q]];
+        uint32_t curr = NONE;
+        if (n == -1) {
+            if ((curr = add_node(W, g, c)) == NONE) return -2;
+        } else {
+            const uint32_t jn = (uint32_t)n;
+            if (jn >= g.n_nodes) return -1;
+            if (g.code[jn] == c) {
+                curr = jn;
+            } else {
+                for (uint32_t t = g.al_h[jn]; t != NONE; t = g.al_nx[t]) {
+                    if (g.code[g.al_v[t]] == c) { curr = g.al_v[t]; break; }
+                }
+                if (curr == NONE) {
+                    if ((curr = add_node(W, g, c)) == NONE) return -2;
+                    // jn's own list only grows after the walk, so the walk sees the oracle's snapshot
+                    for (uint32_t t = g.al_h[jn]; t != NONE; t = g.al_nx[t]) {
+                        const uint32_t al = g.al_v[t];
+                        if (!push_aligned(W, g, al, curr) || !push_aligned(W, g, curr, al)) return -2;
+                    }
+                    if (!push_aligned(W, g, jn, curr) || !push_aligned(W, g, curr, jn)) return -2;
+                }
+            }
+        }
+        if (begin == NONE) begin = curr;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, s, q - 1, uq) + weight_of(a, s, q, uq))) return -2;
+        prev = curr;
+    }
+    if (last != NONE && !add_edge(W, g, prev, last, weight_of(a, s, vback, uq) + weight_of(a, s, vback + 1, uq))) return -2;
+    g.nseq++;
+    return toposort(W, g) ? 0 : -2;
+}
+
+__device__ void reset_graph(LGraph& g) { g.n_nodes = g.n_edges = g.n_al = g.n_lb = g.n_rank = g.nseq = 0; }
+
+// g_subgraph: the nodes reachable backwards from `end` (in-edges and aligned nodes) with id >= begin; W.map[new] = old
+__device__ bool subgraph(LWin& W, const LGraph& g, LGraph& sub, uint32_t begin, uint32_t end) {
+    const uint32_t N = g.n_nodes;
+    uint8_t* in_sub = W.mark;
+    for (uint32_t v = 0; v < N; ++v) in_sub[v] = 0;
+    uint32_t sp = 0;
+    W.stack[sp++] = end;
+    while (sp) {
+        const uint32_t c = W.stack[--sp];
+        if (!in_sub[c] && c >= begin) {
+            for (uint32_t e = g.in_h[c]; e != NONE; e = g.nx_in[e]) {
+                if (sp >= W.SC) { W.grow |= G_STACK; return false; }
+                W.stack[sp++] = g.tail[e];
+            }
+            for (uint32_t q = g.al_h[c]; q != NONE; q = g.al_nx[q]) {
+                if (sp >= W.SC) { W.grow |= G_STACK; return false; }
+                W.stack[sp++] = g.al_v[q];
+            }
+            in_sub[c] = 1;
+        }
+    }
+    reset_graph(sub);
+    sub.labels = 0;
+    uint32_t nm = 0;
+    for (uint32_t v = 0; v < N; ++v) {
+        W.g2s[v] = NONE;
+        if (!in_sub[v]) continue;
+        if ((W.g2s[v] = add_node(W, sub, g.code[v])) == NONE) return false;
+        W.map[nm++] = v;
+    }
+    for (uint32_t v = 0; v < N; ++v) {
+        if (!in_sub[v]) continue;
+        const uint32_t jt = W.g2s[v];
+        for (uint32_t e = g.in_h[v]; e != NONE; e = g.nx_in[e]) {
+            if (W.g2s[g.tail[e]] != NONE && !add_edge(W, sub, W.g2s[g.tail[e]], jt, (uint32_t)g.weight[e])) return false;
+        }
+        for (uint32_t q = g.al_h[v]; q != NONE; q = g.al_nx[q]) {
+            if (W.g2s[g.al_v[q]] != NONE && !push_aligned(W, sub, jt, W.g2s[g.al_v[q]])) return false;
+        }
+    }
+    return toposort(W, sub);
+}
+
+// g_prune (min_weight 0).  A decision reads weights only, never another edge's alive flag, so the tombstones are set in place.
+__device__ void prune(LGraph& g, double d, double s, double avg) {
+    for (uint32_t e = 0; e < g.n_edges; ++e) {
+        if (!g.alive[e]) continue;
+        if (g.weight[e] < 0) { g.alive[e] = 0; continue; }
+        int64_t tot = 0;
+        for (uint32_t o = g.out_h[g.tail[e]]; o != NONE; o = g.nx_out[o]) tot += g.weight[o];
+        const double conf_uv = (double)g.weight[e] / (double)tot;
+        const double support = (double)g.weight[e] / avg;
+        tot = 0;
+        for (uint32_t o = g.in_h[g.head[e]]; o != NONE; o = g.nx_in[o]) tot += g.weight[o];
+        const double conf_vu = (double)g.weight[e] / (double)tot;
+        if (!(conf_uv >= d && conf_vu >= d && support >= s)) g.alive[e] = 0;
+    }
+}
+
+// g_dfs_component: recursive preorder with explicit frames; neighbours = live in-edge tails, then live out-edge heads
+__device__ uint32_t dfs_component(LWin& W, const LGraph& g, uint32_t v0, uint32_t* comp) {
+    uint8_t* visited = W.mark;
+    uint32_t n = 0, sp = 0;
+    visited[v0] = 1; comp[n++] = v0;
+    W.fr_v[sp] = v0; W.fr_p[sp] = 0; W.fr_e[sp] = g.in_h[v0]; sp++;
+    while (sp) {
+        const uint32_t f = sp - 1;
+        uint32_t u = NONE;
+        while (u == NONE) {
+            uint32_t e = W.fr_e[f];
+            if (e == NONE) {
+                if (W.fr_p[f] == 0) { W.fr_p[f] = 1; W.fr_e[f] = g.out_h[W.fr_v[f]]; continue; }
+                break;
+            }
+            const bool in = W.fr_p[f] == 0;
+            W.fr_e[f] = in ? g.nx_in[e] : g.nx_out[e];
+            if (!g.alive[e]) continue;
+            const uint32_t cand = in ? g.tail[e] : g.head[e];
+            if (!visited[cand]) u = cand;
+        }
+        if (u == NONE) { sp--; continue; }
+        visited[u] = 1; comp[n++] = u;
+        W.fr_v[sp] = u; W.fr_p[sp] = 0; W.fr_e[sp] = g.in_h[u]; sp++;
+    }
+    return n;
+}
+
+// g_largest_subgraph: the last component of the largest size (`>=`), nodes in its DFS preorder, live out-edges without dedup
+__device__ bool largest_subgraph(LWin& W, const LGraph& g, LGraph& sub) {
+    const uint32_t N = g.n_nodes;
+    for (uint32_t v = 0; v < N; ++v) W.mark[v] = 0;
+    uint32_t *comp = W.comp, *best = W.best, best_size = 0;
+    for (uint32_t v = 0; v < N; ++v) {
+        if (W.mark[v]) continue;
+        const uint32_t n = dfs_component(W, g, v, comp);
+        if (n >= best_size) { best_size = n; uint32_t* t = best; best = comp; comp = t; }
+    }
+    reset_graph(sub);
+    sub.labels = 0;
+    for (uint32_t k = 0; k < best_size; ++k)
+        if ((W.g2s[best[k]] = add_node(W, sub, g.code[best[k]])) == NONE) return false;
+    for (uint32_t k = 0; k < best_size; ++k) {
+        const uint32_t v = best[k];
+        for (uint32_t e = g.out_h[v]; e != NONE; e = g.nx_out[e]) {
+            if (!g.alive[e]) continue;
+            if (!new_edge(W, sub, W.g2s[v], W.g2s[g.head[e]], 0, 0)) return false;
+        }
+    }
+    return toposort(W, sub);
+}
+
+// g_add_weights
+__device__ bool add_weights(const LArgs& a, LWin& W, LGraph& g, const int32_t* A, uint32_t np, uint32_t s, bool uq) {
+    const uint32_t len = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
+    if (len == 0 || np == 0) return true;
+    uint32_t prev = NONE;
+    for (uint32_t k = 0; k < np; ++k) {
+        const int32_t n = A[2 * k], q = A[2 * k + 1];
+        if (n == -1 || q == -1) { prev = NONE; continue; }
+        const uint32_t curr = (uint32_t)n;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, s, q - 1, uq) + weight_of(a, s, q, uq))) return false;
+        prev = curr;
+    }
+    return true;
+}
+
+// g_branch_completion
+__device__ uint32_t branch_completion(LWin& W, const LGraph& g, uint32_t rank) {
+    int64_t* scores = W.scores;
+    uint32_t* pred = W.pred;
+    const uint32_t start = g.rank[rank];
+    for (uint32_t o = g.out_h[start]; o != NONE; o = g.nx_out[o]) {
+        const uint32_t h = g.head[o];
+        for (uint32_t e = g.in_h[h]; e != NONE; e = g.nx_in[e]) {
+            if (g.tail[e] != start) scores[g.tail[e]] = -1;
+        }
+    }
+    uint32_t mx = NONE;
+    for (uint32_t i = rank + 1; i < g.n_rank; ++i) {
+        const uint32_t it = g.rank[i];
+        scores[it] = -1; pred[it] = NONE;
+        for (uint32_t e = g.in_h[it]; e != NONE; e = g.nx_in[e]) {
+            const uint32_t tl = g.tail[e];
+            if (scores[tl] == -1) continue;
+            if (scores[it] < g.weight[e] || (scores[it] == g.weight[e] && pred[it] != NONE && scores[pred[it]] <= scores[tl])) {
+                scores[it] = g.weight[e]; pred[it] = tl;
+            }
+        }
+        if (pred[it] != NONE) scores[it] += scores[pred[it]];
+        if (mx == NONE || scores[mx] < scores[it]) mx = it;
+    }
+    return mx;
+}
+
+// g_heaviest_bundle -> W.comp[0 .. n) (node ids, source first)
+__device__ uint32_t heaviest_bundle(LWin& W, const LGraph& g) {
+    if (g.n_rank == 0) return 0;
+    const uint32_t N = g.n_nodes;
+    int64_t* scores = W.scores;
+    uint32_t* pred = W.pred;
+    for (uint32_t i = 0; i < N; ++i) { pred[i] = NONE; scores[i] = -1; }
+    uint32_t mx = NONE;
+    for (uint32_t r = 0; r < g.n_rank; ++r) {
+        const uint32_t it = g.rank[r];
+        for (uint32_t e = g.in_h[it]; e != NONE; e = g.nx_in[e]) {
+            const uint32_t tl = g.tail[e];
+            if (scores[it] < g.weight[e] || (scores[it] == g.weight[e] && pred[it] != NONE && scores[pred[it]] <= scores[tl])) {
+                scores[it] = g.weight[e]; pred[it] = tl;
+            }
+        }
+        if (pred[it] != NONE) scores[it] += scores[pred[it]];
+        if (mx == NONE || scores[mx] < scores[it]) mx = it;
+    }
+    if (g.out_n[mx] != 0) {
+        for (uint32_t r = 0; r < g.n_rank; ++r) W.node_rank[g.rank[r]] = r;
+        while (g.out_n[mx] != 0) mx = branch_completion(W, g, W.node_rank[mx]);
+    }
+    uint32_t n = 0;
+    while (pred[mx] != NONE) { W.comp[n++] = mx; mx = pred[mx]; }
+    W.comp[n++] = mx;
+    for (uint32_t x = 0, y = n - 1; x < y; ++x, --y) { const uint32_t t = W.comp[x]; W.comp[x] = W.comp[y]; W.comp[y] = t; }
+    return n;
+}
+
+// g_coverage: distinct labels on v's in- and out-edges
+__device__ uint32_t coverage(LWin& W, const LGraph& g, uint32_t v, uint32_t tick) {
+    uint32_t cnt = 0;
+    for (int dir = 0; dir < 2; ++dir) {
+        for (uint32_t e = dir ? g.out_h[v] : g.in_h[v]; e != NONE; e = dir ? g.nx_out[e] : g.nx_in[e]) {
+            for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) {
+                const uint32_t l = g.lb_v[c];
+                if (W.stamp[l] != tick) { W.stamp[l] = tick; cnt++; }
+            }
+        }
+    }
+    return cnt;
+}
+
+// window_linear after build_graph: heaviest bundle, coverage, TGS trim
+__device__ void finish_linear(const LArgs& a, LWin& W) {
+    const LGraph& G = W.gr[W.cur];
+    const uint32_t n = heaviest_bundle(W, G);
+    uint32_t* cov = W.best;
+    for (uint32_t i = 0; i <= G.nseq; ++i) W.stamp[i] = 0;
+    uint32_t tick = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t v = W.comp[i];
+        cov[i] = coverage(W, G, v, ++tick);
+        for (uint32_t q = G.al_h[v]; q != NONE; q = G.al_nx[q]) cov[i] += coverage(W, G, G.al_v[q], ++tick);
+    }
+    int32_t begin = 0, end = (int32_t)n - 1;
+    if (a.window_type == 1 && a.trim) {
+        const uint32_t avgc = (W.nseq - 1) / 2;
+        for (; begin < (int32_t)n; ++begin) if (cov[begin] >= avgc) break;
+        for (; end >= 0; --end) if (cov[end] >= avgc) break;
+        if (begin >= end) { begin = 0; end = (int32_t)n - 1; }
+    }
+    W.cons_n = 0;
+    for (int32_t i = begin; i <= end; ++i) W.cons[W.cons_n++] = (uint8_t)W.decoder[G.code[W.comp[i]]];
+    W.status = VC_WIN_OK;
+    W.phase = PH_DONE;
+}
+
+__device__ __forceinline__ bool full_span(const LArgs& a, const LWin& W, uint32_t s) {
+    const uint32_t offset = (uint32_t)(0.01 * W.L);
+    return a.seq_begin[s] < offset && a.seq_end[s] > W.L - offset;
+}
+
+__device__ void fail_window(LWin& W, uint32_t status) { W.status = status; W.phase = PH_DONE; W.rows = 0; }
+
+// prune + largest component of G into the other slot (window_hap:715-719 / :738-743)
+__device__ bool prune_and_keep_largest(const LArgs& a, LWin& W) {
+    prune(W.gr[W.cur], a.min_conf, a.min_sup, W.avg);
+    if (!largest_subgraph(W, W.gr[W.cur], W.gr[1 - W.cur])) return false;
+    W.cur = 1 - W.cur;
+    return true;
+}
+
+// AlignmentEngine::WorstCaseAlignmentScore with e = q = c = g
+__device__ int64_t worst_case(int64_t m, int64_t gp, int64_t i, int64_t j) {
+    const int64_t d = i > j ? i - j : j - i, mn = i < j ? i : j;
+    const int64_t gs_d = d == 0 ? 0 : gp + (d - 1) * gp;
+    const int64_t gs_i = i == 0 ? 0 : gp + (i - 1) * gp;
+    const int64_t gs_j = j == 0 ? 0 : gp + (j - 1) * gp;
+    const int64_t x = -1 * (m * mn + gs_d), y = gs_i + gs_j;
+    return x < y ? x : y;
+}
+
+// ------------------------------------------------------------------ kernels
+__global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
+    const uint32_t w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= a.n) return;
+    LWin& W = a.win[w];
+    for (int c = 0; c < 256; ++c) { W.coder[c] = -1; W.decoder[c] = -1; }
+    W.num_codes = 0;
+    reset_graph(W.gr[0]); reset_graph(W.gr[1]);
+    W.gr[0].labels = a.mode == 1; W.gr[1].labels = 0;
+    W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
+    if (W.nseq < 3) {                                                      // window.cpp:188-192: the backbone, unpolished
+        const uint8_t* bb = a.bases + a.seq_off[W.s0];
+        for (uint32_t i = 0; i < W.L; ++i) W.cons[i] = bb[i];
+        W.cons_n = W.L;
+        fail_window(W, VC_WIN_UNPOLISHED);
+        return;
+    }
+    const int rc = add_alignment(a, W, W.gr[0], nullptr, 0, W.s0, true);  // the backbone always takes the quality overload
+    if (rc == -2) return;
+    if (rc) { fail_window(W, VC_WIN_INVALID); return; }
+    if (a.mode == 0) {
+        if (W.fasta) W.total += (double)W.L;
+        else for (uint32_t q = 0; q < W.L; ++q) W.total += a.lut_d[a.quals[a.seq_off[W.s0] + q]];
+    }
+    W.phase = PH_BUILD; W.j = 1; W.k = 0;
+}
+
+__global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
+    const uint32_t w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= a.n) return;
+    LWin& W = a.win[w];
+    W.rows = 0; W.npairs = 0; W.max_i = W.max_j = 0; W.sub = 0;
+    if (W.phase == PH_DONE || W.grow) return;
+    uint32_t gi = W.cur;
+    bool nw = true;
+    if (W.phase == PH_BUILD) {
+        W.qs = W.s0 + W.j;
+        if (!full_span(a, W, W.qs)) {
+            if (!subgraph(W, W.gr[W.cur], W.gr[1 - W.cur], a.seq_begin[W.qs], a.seq_end[W.qs])) return;
+            gi = 1 - W.cur; W.sub = 1;
+        }
+    } else if (W.phase == PH_ROUND) {
+        W.qs = W.s0 + W.j;
+        nw = W.j == 0 || full_span(a, W, W.qs);
+    } else {
+        W.qs = W.s0; nw = false;
+    }
+    W.type = nw ? 1 : 0;
+    W.m = nw ? a.match : a.sw_match; W.x = nw ? a.mismatch : a.sw_mismatch; W.g = nw ? a.gap : a.sw_gap;
+    const LGraph& g = W.gr[gi];
+    const uint32_t N = g.n_nodes, len = (uint32_t)(a.seq_off[W.qs + 1] - a.seq_off[W.qs]);
+    if (N == 0 || len == 0) return;                                       // an empty alignment
+    if (worst_case(W.m, W.g, (int64_t)len + 8, N) < (int64_t)KNEG) { fail_window(W, VC_WIN_INVALID); return; }
+    for (uint32_t r = 0; r < N; ++r) W.node_rank[g.rank[r]] = r;
+    uint32_t cnt = 0;
+    for (uint32_t r = 0; r < N; ++r) {
+        const uint32_t v = g.rank[r];
+        W.rchar[r] = (uint8_t)W.decoder[g.code[v]];
+        W.sink[r] = g.out_n[v] == 0;
+        W.poff[r] = cnt;
+        for (uint32_t e = g.in_h[v]; e != NONE; e = g.nx_in[e]) W.prank[cnt++] = W.node_rank[g.tail[e]] + 1;
+    }
+    W.poff[N] = cnt;
+    W.rows = N; W.qlen = len;
+}
+
+__device__ __forceinline__ bool better(int32_t s, uint32_t i, uint32_t j, int32_t bs, uint32_t bi, uint32_t bj) {
+    return s > bs || (s == bs && (i < bi || (i == bi && j < bj)));
+}
+
+// One wave per alignment (g_align's forward pass).  Row i = rank i - 1; lane l holds columns 512 c + 8 l + 1 .. + 8 of chunk c.
+// Diagonal / vertical moves from every predecessor row give x[j]; SW clamps it at 0 first (C[j] = max(0, x[j], C[j-1] + g) is the
+// plain recurrence on max(0, x)); the horizontal move H[j] = max_k<=j (x[k] + (j - k) g) is a prefix maximum of the tilted
+// T[k] = x[k] - k g, carried from chunk to chunk.  The matrix row is stored and the next row may read it after the barrier.
+__global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
+    LWin& W = a.win[a.list[blockIdx.x]];
+    const uint32_t lane = threadIdx.x;
+    int32_t* H = a.H + a.hoff[blockIdx.x];
+    const uint32_t N = W.rows, len = W.qlen;
+    const uint64_t w = (uint64_t)len + 1;
+    const bool sw = W.type == 0;
+    const int32_t m = W.m, x = W.x, gp = W.g;
+    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    for (uint32_t j = lane; j <= len; j += 64) H[j] = (sw || j == 0) ? 0 : (int32_t)j * gp;
+    __syncthreads();
+    int32_t bs = sw ? 0 : KNEG;
+    uint32_t bi = 0, bj = 0;
+    for (uint32_t r = 0; r < N; ++r) {
+        const uint64_t i = (uint64_t)r + 1;
+        const uint32_t po = W.poff[r], pe = W.poff[r + 1];
+        const uint8_t c = W.rchar[r];
+        const bool sink = W.sink[r] != 0;
+        int32_t h0 = 0;
+        if (!sw) {
+            int32_t pen = pe == po ? 0 : KNEG;
+            for (uint32_t k = po; k < pe; ++k) pen = max(pen, H[(uint64_t)W.prank[k] * w]);
+            h0 = pen + gp;
+        }
+        int32_t* Hr = H + i * w;
+        if (lane == 0) Hr[0] = h0;
+        int64_t carry = h0;
+        // a chunk is 64 lanes x kCols consecutive columns: the prefix maximum runs inside a lane first, then once across the lanes
+        for (uint32_t cb = 0; cb < len; cb += 64 * kCols) {
+            const uint32_t j0 = cb + lane * kCols + 1;
+            int64_t t[kCols];
+#pragma unroll
+            for (uint32_t q = 0; q < kCols; ++q) {
+                const uint32_t j = j0 + q;
+                t[q] = TNEG;
+                if (j <= len) {
+                    const int32_t s = seq[j - 1] == c ? m : x;
+                    const int32_t* Hp = H + (pe == po ? 0 : (uint64_t)W.prank[po] * w);
+                    int32_t v = max(Hp[j - 1] + s, Hp[j] + gp);
+                    for (uint32_t k = po + 1; k < pe; ++k) {
+                        Hp = H + (uint64_t)W.prank[k] * w;
+                        v = max(v, max(Hp[j - 1] + s, Hp[j] + gp));
+                    }
+                    if (sw) v = max(v, 0);
+                    t[q] = (int64_t)v - (int64_t)j * gp;
+                }
+                if (q > 0 && t[q - 1] > t[q]) t[q] = t[q - 1];
+            }
+            int64_t T = t[kCols - 1];                                      // inclusive scan of the lanes' maxima
+            for (uint32_t d = 1; d < 64; d <<= 1) {
+                const int64_t o = __shfl_up(T, d, 64);
+                if (lane >= d && o > T) T = o;
+            }
+            int64_t before = __shfl_up(T, 1, 64);                          // what the lanes in front (and the chunks before) reached
+            if (lane == 0 || carry > before) before = carry;
+            const int64_t last = __shfl(T, 63, 64);
+            if (last > carry) carry = last;
+#pragma unroll
+            for (uint32_t q = 0; q < kCols; ++q) {
+                const uint32_t j = j0 + q;
+                if (j > len) break;
+                const int32_t h = (int32_t)((t[q] > before ? t[q] : before) + (int64_t)j * gp);
+                Hr[j] = h;
+                if (sw ? h > bs : (sink && j == len && h > bs)) { bs = h; bi = (uint32_t)i; bj = j; }
+            }
+        }
+        __syncthreads();
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int32_t os = __shfl_xor(bs, d, 64);
+        const uint32_t oi = __shfl_xor(bi, d, 64), oj = __shfl_xor(bj, d, 64);
+        if (better(os, oi, oj, bs, bi, bj)) { bs = os; bi = oi; bj = oj; }
+    }
+    if (lane == 0) { W.max_i = bi; W.max_j = bj; }
+}
+
+// g_align's backtrack, one lane per alignment: diagonal from each predecessor (in in-edge order), vertical likewise, then horizontal
+__global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    LWin& W = a.win[a.list[b]];
+    const int32_t* H = a.H + a.hoff[b];
+    const uint64_t w = (uint64_t)W.qlen + 1;
+    const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
+    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    const bool sw = W.type == 0;
+    W.npairs = 0;
+    uint32_t i = W.max_i, j = W.max_j, np = 0;
+    if (i == 0 && j == 0) return;
+    for (;;) {
+        if (sw) { if (H[(uint64_t)i * w + j] == 0) break; }
+        else if (i == 0 && j == 0) break;
+        const int32_t Hij = H[(uint64_t)i * w + j];
+        uint32_t pi = 0, pj = 0;
+        bool found = false;
+        const uint32_t po = i ? W.poff[i - 1] : 0, pe = i ? W.poff[i] : 0;
+        const uint32_t ncand = pe > po ? pe - po : 1;
+        if (i != 0 && j != 0) {
+            const int32_t s = seq[j - 1] == W.rchar[i - 1] ? W.m : W.x;
+            for (uint32_t k = 0; k < ncand; ++k) {
+                const uint32_t p = pe > po ? W.prank[po + k] : 0;
+                if (Hij == H[(uint64_t)p * w + (j - 1)] + s) { pi = p; pj = j - 1; found = true; break; }
+            }
+        }
+        if (!found && i != 0) {
+            for (uint32_t k = 0; k < ncand; ++k) {
+                const uint32_t p = pe > po ? W.prank[po + k] : 0;
+                if (Hij == H[(uint64_t)p * w + j] + W.g) { pi = p; pj = j; found = true; break; }
+            }
+        }
+        if (!found && j != 0 && Hij == H[(uint64_t)i * w + j - 1] + W.g) { pi = i; pj = j - 1; found = true; }
+        if (!found) { fail_window(W, VC_WIN_INVALID); return; }             // cannot happen on a DAG
+        if (np >= W.PC) { W.grow |= G_PAIRS; return; }
+        W.pairs[2 * np] = i == pi ? -1 : (int32_t)g.rank[i - 1];
+        W.pairs[2 * np + 1] = j == pj ? -1 : (int32_t)j - 1;
+        ++np;
+        i = pi; j = pj;
+    }
+    for (uint32_t x = 0; x < np / 2; ++x) {
+        const uint32_t y = np - 1 - x;
+        const int32_t t0 = W.pairs[2 * x], t1 = W.pairs[2 * x + 1];
+        W.pairs[2 * x] = W.pairs[2 * y]; W.pairs[2 * x + 1] = W.pairs[2 * y + 1];
+        W.pairs[2 * y] = t0; W.pairs[2 * y + 1] = t1;
+    }
+    W.npairs = np;
+}
+
+__global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
+    const uint32_t w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= a.n) return;
+    LWin& W = a.win[w];
+    if (W.phase == PH_DONE || W.grow) return;
+    const uint32_t s = W.qs, np = W.npairs;
+    const bool hq = a.has_qual[s] != 0;
+    if (W.phase == PH_BUILD) {
+        if (W.sub)                                                         // UpdateAlignment, graph.cpp:734-745
+            for (uint32_t k = 0; k < np; ++k) if (W.pairs[2 * k] != -1) W.pairs[2 * k] = (int32_t)W.map[W.pairs[2 * k]];
+        const int rc = add_alignment(a, W, W.gr[W.cur], W.pairs, np, s, hq);
+        if (rc == -2) return;
+        if (rc) { fail_window(W, VC_WIN_INVALID); return; }
+        if (a.mode == 0) {
+            const uint32_t len = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
+            if (!hq) W.total += (double)len;
+            else for (uint32_t q = 0; q < len; ++q) W.total += a.lut_d[a.quals[a.seq_off[s] + q]];
+        }
+        if (++W.j < W.nseq) return;
+        if (a.mode == 1) { finish_linear(a, W); return; }
+        const uint16_t window_len = (uint16_t)W.L;                         // window.cpp:216
+        W.avg = W.fasta ? 2.0 * W.total / window_len : 2.0 * W.total / window_len * 1000;
+        if (!prune_and_keep_largest(a, W)) return;
+        W.j = 0; W.k = 0;
+        W.phase = a.num_prune > 1 ? PH_ROUND : PH_FINAL;
+    } else if (W.phase == PH_ROUND) {
+        // the backbone's qualities_[0].first is never nullptr: quality overload (a dummy '!' gives 0)
+        if (!add_weights(a, W, W.gr[W.cur], W.pairs, np, s, W.j == 0 ? true : hq)) return;
+        if (++W.j < W.nseq) return;
+        if (!prune_and_keep_largest(a, W)) return;
+        W.j = 0;
+        if (++W.k + 1 >= a.num_prune) W.phase = PH_FINAL;
+    } else {                                                               // GenerateCorrectedSequence, graph.cpp:1167-1179
+        const LGraph& P = W.gr[W.cur];
+        W.cons_n = 0;
+        for (uint32_t k = 0; k < np; ++k) {
+            if (W.pairs[2 * k] == -1) continue;
+            W.cons[W.cons_n++] = (uint8_t)W.decoder[P.code[W.pairs[2 * k]]];
+        }
+        W.status = VC_WIN_OK;
+        W.phase = PH_DONE;
+    }
+}
+
+// ------------------------------------------------------------------ host
+thread_local std::string g_err;
+int fail(int rc, const char* m) { g_err = m; return rc; }
+
+struct Caps { uint64_t NC, EC, AC, LC, SC, PC, nseq; };
+
+// bytes of a window's tables, and (base != nullptr) the pointers into them
+uint64_t layout(LWin* W, uint8_t* base, const Caps& c, bool labels) {
+    uint64_t off = 0;
+    auto take = [&](auto** p, uint64_t n) {
+        using T = std::remove_pointer_t<std::remove_reference_t<decltype(p)>>;
+        off = (off + 15) & ~15ull;
+        if (base) *p = (T)(base + off);
+        off += n * sizeof(**p);
+    };
+    LWin tmp{};
+    LWin* x = base ? W : &tmp;
+    for (int k = 0; k < 2; ++k) {
+        LGraph& g = x->gr[k];
+        take(&g.code, c.NC);
+        for (uint32_t** p : {&g.in_h, &g.in_t, &g.in_n, &g.out_h, &g.out_t, &g.out_n, &g.al_h, &g.al_t, &g.al_n, &g.rank}) take(p, c.NC);
+        for (uint32_t** p : {&g.tail, &g.head, &g.nx_in, &g.nx_out, &g.lb_h, &g.lb_t}) take(p, c.EC);
+        take(&g.weight, c.EC);
+        take(&g.alive, c.EC);
+        take(&g.al_v, c.AC); take(&g.al_nx, c.AC);
+        const uint64_t lc = (k == 0 && labels) ? c.LC : 1;
+        take(&g.lb_v, lc); take(&g.lb_nx, lc);
+    }
+    take(&x->coder, 256); take(&x->decoder, 256);
+    take(&x->mark, c.NC); take(&x->ign, c.NC);
+    take(&x->stack, c.SC);
+    for (uint32_t** p : {&x->node_rank, &x->map, &x->g2s, &x->fr_v, &x->fr_e, &x->comp, &x->best, &x->pred}) take(p, c.NC);
+    take(&x->stamp, c.nseq + 1);
+    take(&x->fr_p, c.NC);
+    take(&x->scores, c.NC);
+    take(&x->rchar, c.NC); take(&x->sink, c.NC);
+    take(&x->poff, c.NC + 1); take(&x->prank, c.EC);
+    take(&x->pairs, 2 * c.PC);
+    take(&x->cons, c.NC);
+    return (off + 255) & ~255ull;
+}
+
+// device buffers kept between calls (grow-only, one device) and given back by vc_large_release()
+struct Buf { void* p = nullptr; uint64_t bytes = 0; };
+struct Cache { int device = -1; Buf arena, mat; } g_cache;
+
+void* cached(Buf& b, uint64_t bytes) {
+    if (b.p && b.bytes >= bytes) return b.p;
+    if (b.p) { (void)hipFree(b.p); b = Buf{}; }
+    if (hipMalloc(&b.p, std::max<uint64_t>(bytes, 256)) != hipSuccess) { (void)hipGetLastError(); b = Buf{}; return nullptr; }
+    b.bytes = std::max<uint64_t>(bytes, 256);
+    return b.p;
+}
+
+void release_cache() {
+    if (g_cache.device >= 0) (void)hipSetDevice(g_cache.device);
+    if (g_cache.arena.p) (void)hipFree(g_cache.arena.p);
+    if (g_cache.mat.p) (void)hipFree(g_cache.mat.p);
+    g_cache = Cache{};
+}
+
+template <class T> bool dalloc(std::vector<void*>& l, T** p, size_t n, const void* src = nullptr) {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    l.push_back(q);
+    *p = (T*)q;
+    return !src || n == 0 || hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* vc_large_last_error(void) { return g_err.c_str(); }
+
+void vc_large_release(void) { release_cache(); }
+
+int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
+    if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(VC_ERR_NO_DEVICE, "no HIP device visible; the large-graph path has no CPU fallback");
+    }
+    if (p->device < 0 || p->device >= ndev) return fail(VC_ERR_NO_DEVICE, "no HIP device with this ordinal");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, p->device) != hipSuccess) return fail(VC_ERR_HIP, "hipGetDeviceProperties failed");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(VC_ERR_NO_DEVICE, "the kernels are built for gfx950 only");
+    if (p->mode != 0 && p->mode != 1) return fail(VC_ERR_ARG, "mode must be 0 or 1");
+    if (p->num_prune == 0) return fail(VC_ERR_ARG, "num_prune must be >= 1");
+    const uint32_t nw = b->n_windows;
+    r->cons_off[0] = 0;
+    if (nw == 0) return VC_OK;
+    if (!b->win_seq_off || !b->seq_off || !b->seq_begin || !b->seq_end || !b->seq_has_qual || !b->bases || !b->quals || !b->win_fasta)
+        return fail(VC_ERR_ARG, "null array in batch");
+    // validation: what vc_submit enforces (createWindow / add_layer, window.cpp:22-27,56-67)
+    const uint64_t nseq_all = b->win_seq_off[nw], nbytes = b->seq_off[nseq_all];
+    std::vector<Caps> caps(nw);
+    for (uint32_t w = 0; w < nw; ++w) {
+        const uint32_t s0 = b->win_seq_off[w], s1 = b->win_seq_off[w + 1];
+        if (s1 <= s0) return fail(VC_ERR_ARG, "a window has no backbone");
+        const uint64_t L = b->seq_off[s0 + 1] - b->seq_off[s0];
+        if (L == 0 || L >= 65535) return fail(VC_ERR_ARG, "backbone length unsupported");
+        if (!b->seq_has_qual[s0]) return fail(VC_ERR_ARG, "the backbone needs a quality string (dummy '!' for FASTA targets)");
+        uint64_t sum = 0, mx = 0;
+        for (uint32_t s = s0; s < s1; ++s) {
+            const uint64_t len = b->seq_off[s + 1] - b->seq_off[s];
+            if (len == 0 || len >= 65535) return fail(VC_ERR_ARG, "sequence length unsupported");
+            if (s > s0 && (b->seq_begin[s] >= b->seq_end[s] || b->seq_begin[s] > L || b->seq_end[s] >= L)) return fail(VC_ERR_ARG, "invalid layer positions");
+            sum += len; mx = std::max(mx, len);
+        }
+        // nodes: every node is made from one base of one sequence, so the sum of lengths bounds them; the rest starts from
+        // what such graphs use and doubles when a table fills
+        Caps& c = caps[w];
+        c.NC = sum + 1; c.EC = sum + 64; c.AC = 2 * sum + 64; c.LC = sum + 64; c.SC = c.NC + c.EC + c.AC; c.PC = sum + mx + 2;
+        c.nseq = s1 - s0;
+    }
+    if (hipSetDevice(p->device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
+    if (g_cache.device != p->device) { release_cache(); g_cache.device = p->device; }
+
+    std::vector<void*> fixed;
+    auto cleanup = [&]() { for (void* q : fixed) (void)hipFree(q); fixed.clear(); };
+    uint32_t lut_w[256];
+    double lut_d[256];
+    vc_weight_lut(lut_w);
+    for (int c = 0; c < 256; ++c) lut_d[c] = 1 - pow(10, (33 - (int)(signed char)c) / 10.0);
+    LArgs a{};
+    uint64_t* d_so = nullptr; uint32_t *d_sb = nullptr, *d_se = nullptr, *d_lw = nullptr; uint8_t *d_hq = nullptr, *d_b = nullptr, *d_q = nullptr;
+    double* d_ld = nullptr;
+    if (!dalloc(fixed, &d_so, nseq_all + 1, b->seq_off) || !dalloc(fixed, &d_sb, nseq_all, b->seq_begin) || !dalloc(fixed, &d_se, nseq_all, b->seq_end) ||
+        !dalloc(fixed, &d_hq, nseq_all, b->seq_has_qual) || !dalloc(fixed, &d_b, nbytes, b->bases) || !dalloc(fixed, &d_q, nbytes, b->quals) ||
+        !dalloc(fixed, &d_lw, 256, lut_w) || !dalloc(fixed, &d_ld, 256, lut_d)) {
+        cleanup(); return fail(VC_ERR_HIP, "device allocation or copy of the batch failed");
+    }
+    a.seq_off = d_so; a.seq_begin = d_sb; a.seq_end = d_se; a.has_qual = d_hq; a.bases = d_b; a.quals = d_q; a.lut_w = d_lw; a.lut_d = d_ld;
+    a.match = p->match; a.mismatch = p->mismatch; a.gap = p->gap; a.sw_match = p->sw_match; a.sw_mismatch = p->sw_mismatch; a.sw_gap = p->sw_gap;
+    a.min_conf = p->min_confidence; a.min_sup = p->min_support; a.num_prune = p->num_prune; a.mode = (uint32_t)p->mode;
+    a.trim = (uint32_t)p->trim; a.window_type = (uint32_t)p->window_type;
+
+    // budgets from free device memory (what this library keeps cached counts as free)
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const uint64_t avail = free_b + g_cache.arena.bytes + g_cache.mat.bytes;
+    const uint64_t arena_budget = std::min<uint64_t>(avail / 4, 16ull << 30), mat_budget = std::min<uint64_t>(avail / 2, 48ull << 30);
+
+    std::vector<std::vector<uint8_t>> out(nw);
+    std::vector<uint8_t> status(nw, VC_WIN_OVERFLOW);
+    std::vector<uint32_t> pending(nw);
+    for (uint32_t w = 0; w < nw; ++w) pending[w] = w;
+    uint32_t *d_list = nullptr; uint64_t* d_hoff = nullptr; LWin* d_win = nullptr;
+    const bool labels = p->mode == 1;
+    while (!pending.empty()) {
+        // windows in flight: as many as the arena budget holds, in order (at least one)
+        std::vector<uint32_t> grp;
+        std::vector<uint64_t> aoff;
+        uint64_t abytes = 0;
+        std::vector<uint32_t> rest;
+        for (uint32_t w : pending) {
+            const uint64_t need = layout(nullptr, nullptr, caps[w], labels);
+            if (grp.empty() && need > arena_budget * 2) { status[w] = VC_WIN_OVERFLOW; continue; }     // the device cannot hold its tables
+            if (!grp.empty() && abytes + need > arena_budget) { rest.push_back(w); continue; }
+            grp.push_back(w); aoff.push_back(abytes); abytes += need;
+        }
+        pending.swap(rest);
+        if (grp.empty()) continue;
+        const uint32_t n = (uint32_t)grp.size();
+        uint8_t* arena = (uint8_t*)cached(g_cache.arena, abytes);
+        std::vector<void*> tmp;
+        auto done_tmp = [&]() { for (void* q : tmp) (void)hipFree(q); tmp.clear(); };
+        if (!arena || !dalloc(tmp, &d_win, n) || !dalloc(tmp, &d_list, n) || !dalloc(tmp, &d_hoff, n)) {
+            done_tmp();
+            if (n == 1) { status[grp[0]] = VC_WIN_OVERFLOW; continue; }
+            cleanup(); return fail(VC_ERR_HIP, "device allocation of the window tables failed");
+        }
+        std::vector<LWin> hw(n);
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t w = grp[k];
+            LWin& W = hw[k];
+            W = LWin{};
+            layout(&W, arena + aoff[k], caps[w], labels);
+            const Caps& c = caps[w];
+            W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
+            W.L = (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]); W.fasta = b->win_fasta[w] ? 1 : 0;
+            W.NC = (uint32_t)c.NC; W.EC = (uint32_t)c.EC; W.AC = (uint32_t)c.AC; W.LC = (uint32_t)c.LC; W.SC = (uint32_t)c.SC; W.PC = (uint32_t)c.PC;
+        }
+        a.win = d_win; a.n = n;
+        const dim3 lanes((n + 63) / 64);
+        bool ok = hipMemcpy(d_win, hw.data(), n * sizeof(LWin), hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) { hipLaunchKernelGGL(k_lg_init, lanes, dim3(64), 0, 0, a); ok = hipGetLastError() == hipSuccess; }
+        // the lock-step schedule: one alignment of every window in flight per step
+        while (ok) {
+            hipLaunchKernelGGL(k_lg_prep, lanes, dim3(64), 0, 0, a);
+            if (hipMemcpy(hw.data(), d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
+            bool live = false;
+            std::vector<uint32_t> act;
+            for (uint32_t k = 0; k < n; ++k) {
+                if (hw[k].phase != PH_DONE && !hw[k].grow) live = true;
+                if (hw[k].rows) act.push_back(k);
+            }
+            if (!live) break;
+            // matrices of this step, in launches that fit the budget; a matrix the device cannot hold takes its window out
+            for (size_t k0 = 0; k0 < act.size() && ok;) {
+                std::vector<uint32_t> list;
+                std::vector<uint64_t> hoff;
+                uint64_t cells = 0;
+                size_t k1 = k0;
+                for (; k1 < act.size(); ++k1) {
+                    const LWin& W = hw[act[k1]];
+                    const uint64_t need = ((uint64_t)W.rows + 1) * ((uint64_t)W.qlen + 1);
+                    if (!list.empty() && (cells + need) * 4 > mat_budget) break;
+                    list.push_back(act[k1]); hoff.push_back(cells); cells += need;
+                }
+                k0 = k1;
+                int32_t* H = (int32_t*)cached(g_cache.mat, cells * 4);
+                if (!H) {
+                    if (list.size() > 1) { ok = false; break; }
+                    LWin& W = hw[list[0]];
+                    W.phase = PH_DONE; W.status = VC_WIN_OVERFLOW; W.rows = 0;
+                    ok = hipMemcpy(d_win + list[0], &W, sizeof(LWin), hipMemcpyHostToDevice) == hipSuccess;
+                    continue;
+                }
+                const uint32_t nl = (uint32_t)list.size();
+                ok = hipMemcpy(d_list, list.data(), nl * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                     hipMemcpy(d_hoff, hoff.data(), nl * 8, hipMemcpyHostToDevice) == hipSuccess;
+                if (!ok) break;
+                LArgs f = a;
+                f.list = d_list; f.hoff = d_hoff; f.H = H;
+                hipLaunchKernelGGL(k_lg_fwd, dim3(nl), dim3(64), 0, 0, f);
+                hipLaunchKernelGGL(k_lg_back, dim3((nl + 63) / 64), dim3(64), 0, 0, f, nl);
+                ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+            }
+            if (!ok) break;
+            hipLaunchKernelGGL(k_lg_apply, lanes, dim3(64), 0, 0, a);
+            ok = hipGetLastError() == hipSuccess;
+        }
+        ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(hw.data(), d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) == hipSuccess;
+        if (!ok) { done_tmp(); cleanup(); return fail(VC_ERR_HIP, "a large-graph kernel failed"); }
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t w = grp[k];
+            const LWin& W = hw[k];
+            if (W.grow) {                                                  // a table filled: larger tables, the window runs again
+                Caps& c = caps[w];
+                if (W.grow & G_NODES) c.NC *= 2;
+                if (W.grow & G_EDGES) c.EC *= 2;
+                if (W.grow & G_ALIGNED) c.AC *= 2;
+                if (W.grow & G_LABELS) c.LC *= 2;
+                if (W.grow & G_PAIRS) c.PC *= 2;
+                c.SC = std::max<uint64_t>(c.SC * ((W.grow & G_STACK) ? 2 : 1), c.NC + c.EC + c.AC);
+                if (c.NC >= (1ull << 31) || c.EC >= (1ull << 31) || c.AC >= (1ull << 31) || c.SC >= (1ull << 31) || c.PC >= (1ull << 30))
+                    status[w] = VC_WIN_OVERFLOW;
+                else
+                    pending.push_back(w);
+                continue;
+            }
+            status[w] = (uint8_t)W.status;
+            out[w].resize(W.cons_n);
+            if (W.cons_n && hipMemcpy(out[w].data(), W.cons, W.cons_n, hipMemcpyDeviceToHost) != hipSuccess) {
+                done_tmp(); cleanup(); return fail(VC_ERR_HIP, "copy of a consensus failed");
+            }
+        }
+        done_tmp();
+    }
+    cleanup();
+    uint64_t o = 0;
+    for (uint32_t w = 0; w < nw; ++w) {
+        if (o + out[w].size() > r->cons_cap) return fail(VC_ERR_CAPACITY, "consensus buffer too small");
+        if (!out[w].empty()) std::memcpy(r->cons + o, out[w].data(), out[w].size());
+        o += out[w].size();
+        r->cons_off[w + 1] = o;
+        r->status[w] = status[w];
+    }
+    return VC_OK;
+}
+
+}  // extern "C"

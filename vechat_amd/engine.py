@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
+from . import capi, large
 
 
 class VcError(RuntimeError):
@@ -37,6 +37,7 @@ class HipContext:
             raise VcError(f"vc_create failed ({rc}): {self.lib.vc_last_error(None).decode()}")
         self.h = h
         self._batch = None
+        self.large_windows = 0                  # windows this context sent through the large-graph path (vc_large_run)
         if pipeline is not None:
             fw, bw = pipeline if isinstance(pipeline, tuple) else (0, 0)
             self._chk(self.lib.vc_set_pipeline(self.h, 1 if pipeline else 0, fw, bw), "vc_set_pipeline")
@@ -191,32 +192,56 @@ class HipContext:
     def consensus(self, batch: capi.Batch, retry_overflow=True):
         """submit + run + collect.  Windows whose graph outgrew the capacity estimate come back as
         VC_WIN_OVERFLOW with no bytes; with retry_overflow they are resubmitted (on the device, never on
-        the CPU) in a context with doubled capacities, as INTEGRATION.md section 4 describes."""
+        the CPU) in a context with doubled capacities, as INTEGRATION.md section 4 describes, and what is still
+        VC_WIN_OVERFLOW once the capacities cannot grow (or the retry context cannot be made) goes through the
+        large-graph path (vc_large_run)."""
         self.submit(batch)
         self.run()
         self.sync()
         cons, status = self.collect()
         over = [w for w in range(batch.n_windows) if int(status[w]) == capi.VC_WIN_OVERFLOW]
         if retry_overflow and over:
-            st = self.stats()
-            p = capi.VcParams.from_buffer_copy(self.params)
-            p.max_nodes = min(2 * st["max_nodes"], MAX_NODES)
-            p.max_edges = min(2 * st["max_edges"], MAX_EDGES)
-            if p.max_nodes > st["max_nodes"] or p.max_edges > st["max_edges"]:
-                self.lib.vc_release(self.h)             # this context's workspaces (up to 60 % of the device) go back first: the retry plans on what is free
-                try:
-                    sub = HipContext(params=p)
-                except VcError:
-                    return cons, status
-                try:
-                    c2, s2 = sub.consensus(batch.select(over), retry_overflow=True)
-                except VcError:
-                    return cons, status              # the larger capacities do not fit this device: the windows stay VC_WIN_OVERFLOW
-                finally:
-                    sub.close()
-                for k, w in enumerate(over):
-                    cons[w], status[w] = c2[k], s2[k]
+            self._retry_larger(batch, over, cons, status)
+            self._run_large(batch, cons, status)
         return cons, status
+
+    def _retry_larger(self, batch, over, cons, status):
+        """The capacity retry: the overflowed windows in a context with doubled capacities, up to MAX_NODES / MAX_EDGES."""
+        st = self.stats()
+        p = capi.VcParams.from_buffer_copy(self.params)
+        p.max_nodes = min(2 * st["max_nodes"], MAX_NODES)
+        p.max_edges = min(2 * st["max_edges"], MAX_EDGES)
+        if p.max_nodes > st["max_nodes"] or p.max_edges > st["max_edges"]:
+            self.lib.vc_release(self.h)             # this context's workspaces (up to 60 % of the device) go back first: the retry plans on what is free
+            try:
+                sub = HipContext(params=p)
+            except VcError:
+                return                              # the windows stay VC_WIN_OVERFLOW (the large path takes them)
+            try:
+                c2, s2 = sub.consensus(batch.select(over), retry_overflow=True)
+                self.large_windows += sub.large_windows
+            except VcError:
+                return                              # the larger capacities do not fit this device: the windows stay VC_WIN_OVERFLOW
+            finally:
+                sub.close()
+            for k, w in enumerate(over):
+                cons[w], status[w] = c2[k], s2[k]
+
+    def _run_large(self, batch, cons, status):
+        """Windows still VC_WIN_OVERFLOW after the capacity retries: the large-graph path, on the device.  Its tables go back to the
+        device afterwards, so that the fast path's workspaces find the memory they had."""
+        over = [w for w in range(batch.n_windows) if int(status[w]) == capi.VC_WIN_OVERFLOW]
+        if not over:
+            return
+        try:
+            c2, s2 = large.large_consensus(batch.select(over), self.params, lib=self.lib)
+        except large.LargeError as e:
+            raise VcError(str(e)) from None
+        finally:
+            large.release(self.lib)
+        for k, w in enumerate(over):
+            cons[w], status[w] = c2[k], s2[k]
+        self.large_windows += sum(int(s) != capi.VC_WIN_OVERFLOW for s in s2)
 
 
 class Window:

@@ -164,7 +164,7 @@ def main(argv=None, shared=None):
             keep_r = {o.q_name for o in overlaps} | keep_t
 
     text = b""
-    n_targets = n_windows = n_polished = kept = n_aligned = 0
+    n_targets = n_windows = n_polished = kept = n_aligned = n_large = 0
     failure = None                                                # (exit code, message): reported by every rank through the collective below
     try:
         targets = native_targets if native else read_sequences(a.targets, keep_t)
@@ -211,11 +211,14 @@ def main(argv=None, shared=None):
                     except Exception:                       # noqa: BLE001
                         pass
                 # (a large input goes through the context in slices queued behind each other: copies in and out run beside the kernels)
+                large0 = getattr(ctx, "large_windows", 0)
                 cons, status = ctx.consensus_batched(batch, retry_overflow=not a.no_capacity_retry, fill=fill_windows)
+                n_large = getattr(ctx, "large_windows", 0) - large0
                 if shared is None or distributed:
                     ctx.close()
-                # Every valid window is computed on the device.  What can remain is a graph beyond the 16-bit id space after the
-                # capacity retries (VC_WIN_OVERFLOW) or input the reference would throw on (VC_WIN_INVALID).  The reference's
+                # Every valid window is computed on the device: a graph beyond the 16-bit id space after the capacity retries goes
+                # through the large-graph path.  What can remain is a window the device memory cannot hold at all, or one that
+                # --no-capacity-retry left as it came back (VC_WIN_OVERFLOW), or input the reference would throw on (VC_WIN_INVALID).  The reference's
                 # accelerated polisher re-runs such windows on the CPU (cudapolisher.cpp:355-379); this command has no CPU path,
                 # so it refuses to print bytes the reference would not print: it names the windows and exits non-zero, unless
                 # --keep-going asks for their backbones to be kept as unpolished stretches.
@@ -249,7 +252,7 @@ def main(argv=None, shared=None):
         except Exception:                                         # noqa: BLE001
             pass
     print(f"[vechat_amd] rank {rank}/{world}: {n_targets} targets, {kept} overlaps ({n_aligned} aligned on the device), {n_windows} windows, "
-          f"{n_polished} polished", file=sys.stderr)
+          f"{n_polished} polished ({n_large} on the large-graph path)", file=sys.stderr)
     if distributed:
         # error flags first, so that no rank is left waiting in the gather for one that failed
         codes = torch.tensor([failure[0] if failure else 0], dtype=torch.int64, device=dev)
