@@ -21,6 +21,16 @@
 //   k_lg_back   one lane per alignment: walks the stored matrix in the oracle's order of candidates;
 //   k_lg_apply  one lane per window: add-alignment + topological sort, or add-weights; prune + largest component at the end of
 //               the build and of every round; the corrected sequence (mode 0) or heaviest bundle + coverage + trim (mode 1).
+//
+// Development knobs, read on every call (unset: the behaviour above, and nothing is printed).  They only make tables and budgets
+// smaller, so that the tests can reach the host schedule's rarer paths with small windows:
+//   VC_LARGE_CAPS=n:4,a:6   a table starts at max(1, size >> shift): n nodes, e edges, a aligned cells, l labels, s stack, p pairs
+//                           (the stack then also grows from (nodes + edges + aligned) >> shift, not from the unshifted sum);
+//   VC_LARGE_ARENA_MB=x     arena budget (window tables per group; a window above twice the budget is refused) in MiB, fractions allowed;
+//   VC_LARGE_MAT_MB=x       matrix budget (int32 matrices per forward launch) in MiB;
+//   VC_LARGE_LOG=1          one stderr line per event: "vc_large: regrow window=W flags=nodes,... caps n=.. e=.. a=.. l=.. s=.. p=..",
+//                           "vc_large: group windows=N bytes=B ids=W,.. need=B,..", "vc_large: step launches=K over=O" (steps of more than one
+//                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B".
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -546,6 +556,7 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     W.gr[0].labels = a.mode == 1; W.gr[1].labels = 0;
     W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
     if (W.nseq < 3) {                                                      // window.cpp:188-192: the backbone, unpolished
+        if (W.L > W.NC) { W.grow |= G_NODES; return; }                    // cons holds NC bytes (only a shrunk table is shorter)
         const uint8_t* bb = a.bases + a.seq_off[W.s0];
         for (uint32_t i = 0; i < W.L; ++i) W.cons[i] = bb[i];
         W.cons_n = W.L;
@@ -588,6 +599,7 @@ __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
     const uint32_t N = g.n_nodes, len = (uint32_t)(a.seq_off[W.qs + 1] - a.seq_off[W.qs]);
     if (N == 0 || len == 0) return;                                       // an empty alignment
     if (worst_case(W.m, W.g, (int64_t)len + 8, N) < (int64_t)KNEG) { fail_window(W, VC_WIN_INVALID); return; }
+    if (g.n_rank != N) { fail_window(W, VC_WIN_INVALID); return; }      // the rows below read rank[0 .. N)
     for (uint32_t r = 0; r < N; ++r) W.node_rank[g.rank[r]] = r;
     uint32_t cnt = 0;
     for (uint32_t r = 0; r < N; ++r) {
@@ -849,6 +861,39 @@ template <class T> bool dalloc(std::vector<void*>& l, T** p, size_t n, const voi
     return !src || n == 0 || hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
 }
 
+// the development knobs of the header comment; false: VC_LARGE_CAPS does not parse
+constexpr char kTables[] = "nealsp";                   // Knobs::shift order
+struct Knobs { uint32_t shift[6] = {0, 0, 0, 0, 0, 0}; uint64_t arena = 0, mat = 0; bool log = false; };
+
+bool read_knobs(Knobs& k) {
+    k = Knobs{};
+    auto mib = [](const char* name) -> uint64_t {
+        const char* v = getenv(name);
+        const double x = v ? std::atof(v) : 0.0;
+        return x > 0 ? std::max<uint64_t>((uint64_t)(x * 1048576.0), 1) : 0;
+    };
+    k.arena = mib("VC_LARGE_ARENA_MB");
+    k.mat = mib("VC_LARGE_MAT_MB");
+    const char* lg = getenv("VC_LARGE_LOG");
+    k.log = lg && std::atoi(lg) != 0;
+    const char* c = getenv("VC_LARGE_CAPS");
+    if (!c) return true;
+    while (*c) {
+        const char* t = std::strchr(kTables, *c);
+        if (!t || c[1] != ':') return false;
+        char* end = nullptr;
+        const long s = std::strtol(c + 2, &end, 10);
+        if (end == c + 2 || s < 0 || s > 40) return false;
+        k.shift[t - kTables] = (uint32_t)s;
+        c = end;
+        if (*c == ',') ++c;
+        else if (*c) return false;
+    }
+    return true;
+}
+
+uint64_t shrunk(uint64_t v, uint32_t s) { return std::max<uint64_t>(v >> s, 1); }
+
 }  // namespace
 
 extern "C" {
@@ -870,6 +915,8 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(VC_ERR_NO_DEVICE, "the kernels are built for gfx950 only");
     if (p->mode != 0 && p->mode != 1) return fail(VC_ERR_ARG, "mode must be 0 or 1");
     if (p->num_prune == 0) return fail(VC_ERR_ARG, "num_prune must be >= 1");
+    Knobs kn;
+    if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
     const uint32_t nw = b->n_windows;
     r->cons_off[0] = 0;
     if (nw == 0) return VC_OK;
@@ -896,6 +943,8 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
         Caps& c = caps[w];
         c.NC = sum + 1; c.EC = sum + 64; c.AC = 2 * sum + 64; c.LC = sum + 64; c.SC = c.NC + c.EC + c.AC; c.PC = sum + mx + 2;
         c.nseq = s1 - s0;
+        c.NC = shrunk(c.NC, kn.shift[0]); c.EC = shrunk(c.EC, kn.shift[1]); c.AC = shrunk(c.AC, kn.shift[2]);
+        c.LC = shrunk(c.LC, kn.shift[3]); c.SC = shrunk(c.SC, kn.shift[4]); c.PC = shrunk(c.PC, kn.shift[5]);
     }
     if (hipSetDevice(p->device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
     if (g_cache.device != p->device) { release_cache(); g_cache.device = p->device; }
@@ -923,7 +972,8 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     const uint64_t avail = free_b + g_cache.arena.bytes + g_cache.mat.bytes;
-    const uint64_t arena_budget = std::min<uint64_t>(avail / 4, 16ull << 30), mat_budget = std::min<uint64_t>(avail / 2, 48ull << 30);
+    const uint64_t arena_budget = kn.arena ? kn.arena : std::min<uint64_t>(avail / 4, 16ull << 30);
+    const uint64_t mat_budget = kn.mat ? kn.mat : std::min<uint64_t>(avail / 2, 48ull << 30);
 
     std::vector<std::vector<uint8_t>> out(nw);
     std::vector<uint8_t> status(nw, VC_WIN_OVERFLOW);
@@ -939,13 +989,26 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
         std::vector<uint32_t> rest;
         for (uint32_t w : pending) {
             const uint64_t need = layout(nullptr, nullptr, caps[w], labels);
-            if (grp.empty() && need > arena_budget * 2) { status[w] = VC_WIN_OVERFLOW; continue; }     // the device cannot hold its tables
+            if (grp.empty() && need > arena_budget * 2) {                  // the device cannot hold its tables
+                status[w] = VC_WIN_OVERFLOW;
+                if (kn.log) std::fprintf(stderr, "vc_large: refuse window=%u bytes=%llu budget=%llu\n", w, (unsigned long long)need, (unsigned long long)arena_budget);
+                continue;
+            }
             if (!grp.empty() && abytes + need > arena_budget) { rest.push_back(w); continue; }
             grp.push_back(w); aoff.push_back(abytes); abytes += need;
         }
         pending.swap(rest);
         if (grp.empty()) continue;
         const uint32_t n = (uint32_t)grp.size();
+        if (kn.log) {
+            std::string ids, needs;
+            for (uint32_t k = 0; k < n; ++k) {
+                const uint64_t end = k + 1 < n ? aoff[k + 1] : abytes;
+                ids += (k ? "," : "") + std::to_string(grp[k]);
+                needs += (k ? "," : "") + std::to_string(end - aoff[k]);
+            }
+            std::fprintf(stderr, "vc_large: group windows=%u bytes=%llu ids=%s need=%s\n", n, (unsigned long long)abytes, ids.c_str(), needs.c_str());
+        }
         uint8_t* arena = (uint8_t*)cached(g_cache.arena, abytes);
         std::vector<void*> tmp;
         auto done_tmp = [&]() { for (void* q : tmp) (void)hipFree(q); tmp.clear(); };
@@ -981,6 +1044,7 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
             }
             if (!live) break;
             // matrices of this step, in launches that fit the budget; a matrix the device cannot hold takes its window out
+            uint32_t launches = 0, over = 0;
             for (size_t k0 = 0; k0 < act.size() && ok;) {
                 std::vector<uint32_t> list;
                 std::vector<uint64_t> hoff;
@@ -1010,8 +1074,11 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
                 hipLaunchKernelGGL(k_lg_fwd, dim3(nl), dim3(64), 0, 0, f);
                 hipLaunchKernelGGL(k_lg_back, dim3((nl + 63) / 64), dim3(64), 0, 0, f, nl);
                 ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+                launches++;
+                if (cells * 4 > mat_budget) over++;
             }
             if (!ok) break;
+            if (kn.log && launches > 1) std::fprintf(stderr, "vc_large: step launches=%u over=%u\n", launches, over);
             hipLaunchKernelGGL(k_lg_apply, lanes, dim3(64), 0, 0, a);
             ok = hipGetLastError() == hipSuccess;
         }
@@ -1027,7 +1094,15 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
                 if (W.grow & G_ALIGNED) c.AC *= 2;
                 if (W.grow & G_LABELS) c.LC *= 2;
                 if (W.grow & G_PAIRS) c.PC *= 2;
-                c.SC = std::max<uint64_t>(c.SC * ((W.grow & G_STACK) ? 2 : 1), c.NC + c.EC + c.AC);
+                c.SC = std::max<uint64_t>(c.SC * ((W.grow & G_STACK) ? 2 : 1), (c.NC + c.EC + c.AC) >> kn.shift[4]);
+                if (kn.log) {
+                    std::string fl;
+                    static const char* const names[] = {"nodes", "edges", "aligned", "labels", "stack", "pairs"};
+                    for (int t = 0; t < 6; ++t) if (W.grow & (1u << t)) { if (!fl.empty()) fl += ','; fl += names[t]; }
+                    std::fprintf(stderr, "vc_large: regrow window=%u flags=%s caps n=%llu e=%llu a=%llu l=%llu s=%llu p=%llu\n", w, fl.c_str(),
+                                 (unsigned long long)c.NC, (unsigned long long)c.EC, (unsigned long long)c.AC, (unsigned long long)c.LC,
+                                 (unsigned long long)c.SC, (unsigned long long)c.PC);
+                }
                 if (c.NC >= (1ull << 31) || c.EC >= (1ull << 31) || c.AC >= (1ull << 31) || c.SC >= (1ull << 31) || c.PC >= (1ull << 30))
                     status[w] = VC_WIN_OVERFLOW;
                 else

@@ -195,6 +195,13 @@ class HipContext:
         the CPU) in a context with doubled capacities, as INTEGRATION.md section 4 describes, and what is still
         VC_WIN_OVERFLOW once the capacities cannot grow (or the retry context cannot be made) goes through the
         large-graph path (vc_large_run)."""
+        cons, status = self._consensus(batch, retry_overflow)
+        if retry_overflow:
+            self._run_large(batch, cons, status)    # here only: the retry contexts leave what still overflows to this call
+        return cons, status
+
+    def _consensus(self, batch, retry_overflow):
+        """submit + run + collect, and the capacity retries"""
         self.submit(batch)
         self.run()
         self.sync()
@@ -202,7 +209,6 @@ class HipContext:
         over = [w for w in range(batch.n_windows) if int(status[w]) == capi.VC_WIN_OVERFLOW]
         if retry_overflow and over:
             self._retry_larger(batch, over, cons, status)
-            self._run_large(batch, cons, status)
         return cons, status
 
     def _retry_larger(self, batch, over, cons, status):
@@ -218,8 +224,7 @@ class HipContext:
             except VcError:
                 return                              # the windows stay VC_WIN_OVERFLOW (the large path takes them)
             try:
-                c2, s2 = sub.consensus(batch.select(over), retry_overflow=True)
-                self.large_windows += sub.large_windows
+                c2, s2 = sub._consensus(batch.select(over), retry_overflow=True)
             except VcError:
                 return                              # the larger capacities do not fit this device: the windows stay VC_WIN_OVERFLOW
             finally:
