@@ -23,6 +23,23 @@
  *     submit(b0) run   submit(b1) run   collect -> b0   submit(b2) run   collect -> b1   ...
  * on one thread, with H2D, kernels and D2H overlapping and no gap on the device between batches.  The
  * serial order (submit, run, [sync,] collect, submit ...) works as before and uses one batch slot.
+ *
+ * Environment variables.  This is every one the library reads; none is needed, and unset each leaves the default behaviour.
+ * Read once per vc_create (vc_api.hip) -- a context keeps what it saw:
+ *   VC_RESOLVE_FORCE_DFS   set: every end-cell tie is settled by the exact DFS as well (test_gpu::test_tie_resolution_by_exact_dfs)
+ *   VC_HOST_THREADS=0      one host thread walks the chunk streams in lock-step, the scheduler of vc_debug_stop_after
+ *                          (test_gpu::test_threaded_and_single_thread_host_schedulers_agree)
+ *   VC_DT=0                global alignments on byte-packed rows stay on k_fwd instead of k_fwd_dt
+ *                          (test_gpu::test_both_forward_kernels_give_the_same_bytes, tools/gpu_dt_ab.sh)
+ *   VC_AUTO_ARENA=0        vc_submit does not make the workspace arena itself for the first large batch (development)
+ *   VC_SCRATCH_CAP_GB=x    cap of the default workspace budget in GiB, x >= 1 (default 128; development, budget A/B runs)
+ *   VC_TIME_SUBMIT         set: phases of vc_submit and of the arena's allocation on stderr (development)
+ * Read by the host I/O (vc_io.cpp, vc_windows.cpp, vc_hostbuf.h) when a call needs them:
+ *   VC_IO_THREADS=n        threads of the file readers and of the window builder (default: the host's cores, bounded)
+ *   VC_IO_TIMING           set: phase times of the file readers on stderr (tools/gpu_files_host.sh)
+ *   VC_HOSTBUF=0|1|2       host buffers: malloc / mmap + huge pages (default) / mmap; read once per process (tools/gpu_files_host.sh)
+ * Read on every vc_large_run call (vc_large.hip, whose header describes them; tests/test_large_schedule.py):
+ *   VC_LARGE_CAPS, VC_LARGE_ARENA_MB, VC_LARGE_MAT_MB, VC_LARGE_LOG
  */
 #ifndef VECHAT_HIP_H_
 #define VECHAT_HIP_H_
@@ -149,22 +166,12 @@ int vc_debug_errinfo(vc_ctx* ctx, uint32_t* out /*[n_windows]*/);
  * where it stands, in the record format of the oracle's vco_window_stages.  Single-chunk batches. */
 int vc_debug_stop_after(vc_ctx* ctx, uint32_t kind, uint32_t index);
 int vc_debug_stage_digest(vc_ctx* ctx, uint32_t window, int with_pairs, uint64_t* out /*[8], [0..1] untouched*/);
-/* development: the row records (16 B each) the next alignment of window w will use, after a stopped run (tools/gpu_rowstats.py);
- * the persistent pipeline's counters / per-window words, and its waves' phase clocks (tools/gpu_pipe_dbg.py) */
+/* development: the row records (16 B each) the next alignment of window w will use, after a stopped run (tools/gpu_rowstats.py) */
 int vc_debug_rows(vc_ctx* ctx, uint32_t window, uint32_t* out, uint32_t cap_rows, uint32_t* nrows);
-int vc_debug_pipe_state(vc_ctx* ctx, uint32_t* out, uint32_t n);
-int vc_debug_pipe_prof(vc_ctx* ctx, unsigned long long* out);
 void* vc_stream(vc_ctx* ctx);                         /* the context's own hipStream_t (copies, fills); the kernels run on the process's chunk streams */
 int   vc_set_profile(vc_ctx* ctx, int profile);       /* change vc_params.profile of a live context (0, 1, 2)  */
-/* Execution plan of the build loop (src/window.cpp:239-298).  0 (default): lock-step -- one launch per kernel per layer for a
- * whole chunk.  1: persistent pipeline -- two resident kernels per chunk (forward + AddAlignment waves, backtrack waves) that
- * hand windows to each other through device-side queues, no launch and no lock-step per layer (vechat_amd/csrc/vc_pipe.h).
- * Results are identical either way; the environment variable VC_PIPE=0/1 sets the default of a new context.
- * forward_waves / backtrack_waves: resident workgroups of the two kernels (0: 15 and 5 per CU). */
-int   vc_set_pipeline(vc_ctx* ctx, int on, uint32_t forward_waves, uint32_t backtrack_waves);
-/* 1 when the library was built with -DVC_EXPERIMENTS (VC_EXPERIMENTS=1 python __graft_entry__.py): the persistent pipeline above is a
- * measured experiment (bit-identical, slower than the lock-step plan) and is left out of the default build -- vc_set_pipeline(ctx, 1, ..)
- * then returns VC_ERR_ARG, as do vc_debug_pipe_state / vc_debug_pipe_prof. */
+/* Always 0.  The library once carried measured-and-shelved experiments behind a build flag (the persistent build pipeline, an
+ * LDS-row backtrack); they were removed, the export stays for callers that ask. */
 int   vc_has_experiments(void);
 /* Allocates the workspaces' memory now, in one piece (bytes = 0: the default budget, vc_params.scratch_bytes or 60 % of the free
  * memory up to 128 GiB), instead of under the first vc_submit; batches of any shape are then laid out inside it without further

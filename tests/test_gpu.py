@@ -56,11 +56,31 @@ def test_golden_windows_through_the_c_abi(built, mode, key):
     (13, 500, 40, 6, dict(n_haplotypes=2, snp_rate=0.02, frac_partial=0.2)),
     (1005, 1000, 48, 2, dict(profile=capi.ONT)),              # ONT-profile 1 kb windows (config E shape, shallower)
     (17, 250, 20, 8, dict(fastq=0, backbone_fastq=1, frac_partial=0.25)),
+    (1002, 500, 24, 24, {}),                                  # (this and the next three: batches of the removed backtrack / plan cross-checks)
+    (13, 300, 20, 6, dict(n_haplotypes=2, snp_rate=0.02, frac_partial=0.3)),
+    (1005, 1000, 40, 6, dict(profile=capi.ONT)),
+    (33, 2100, 6, 4, dict(profile=capi.ONT)),                 # 48 columns per lane: raw int16 rows under the default scores
 ])
 def test_parity_with_oracle_on_seeded_windows(ctx, seed, L, D, n, kw):
     batch = capi.synth_batch(capi.synth_cfg(seed, L, D, **kw), 0, n)
     st = _check(ctx, batch, f"seed{seed}")
     assert ctx.stats()["cells"] == st.cells                   # same DP work counted on both sides
+
+
+@pytest.mark.parametrize("seed,L,D,n,kw,ctx_kw", [
+    (31, 500, 24, 8, {}, dict(match=12, mismatch=-12, gap=-20)),      # (cpl - 1) * (m - 2 g) > 255 from 6 columns per lane up: raw int16 rows
+    (32, 300, 16, 8, dict(frac_partial=0.3, n_haplotypes=2, snp_rate=0.02), dict(match=12, mismatch=-12, gap=-20)),
+    (13, 400, 20, 40, dict(n_haplotypes=2, snp_rate=0.02, frac_partial=0.3), dict(chunk_windows=16, n_streams=2)),
+    (77, 250, 12, 30, dict(frac_partial=0.5, fastq=0, backbone_fastq=0), dict(mode=1)),
+    (5, 300, 30, 12, {}, dict(max_nodes=512, max_edges=1408)),        # most windows outgrow 512 nodes: the capacity retry computes them
+    (4242, 200, 12, 8, dict(frac_partial=0.25), {}),
+])
+def test_parity_with_oracle_under_context_options(built, seed, L, D, n, kw, ctx_kw):
+    """Seeded batches of the removed cross-checks (thread-per-alignment and LDS-row backtracks, raw-row band, persistent pipeline), through
+    the default path with the scores, chunking, overload and capacities they were run with, against the oracle."""
+    c = HipContext(device=0, **ctx_kw)
+    _check(c, capi.synth_batch(capi.synth_cfg(seed, L, D, **kw), 0, n), f"seed{seed} {ctx_kw}")
+    c.close()
 
 
 @pytest.mark.parametrize("seed,L,D,n,kw", [
@@ -165,15 +185,6 @@ def test_polish_loop_compiled_against_the_reference(built, mode, key):
     assert ncpu == 3 and small == want
 
 
-def test_thread_per_alignment_backtrack_agrees(built, monkeypatch):
-    """The simple one-thread-per-alignment backtrack (kept as a cross-check of the cooperative k_tracew)."""
-    monkeypatch.setenv("VC_TRACE_THREAD", "1")
-    c = HipContext(device=0)
-    for seed, L, D, n, kw in [(1002, 500, 24, 4, {}), (13, 300, 20, 6, dict(n_haplotypes=2, snp_rate=0.02, frac_partial=0.3))]:
-        _check(c, capi.synth_batch(capi.synth_cfg(seed, L, D, **kw), 0, n), f"thread trace seed{seed}")
-    c.close()
-
-
 def test_tie_resolution_by_exact_dfs(built, monkeypatch):
     """End-cell ties are normally settled by the closure shortcut; force the exact-DFS fallback (which works
     out of an HBM workspace) on every tie and require the same bytes."""
@@ -182,82 +193,6 @@ def test_tie_resolution_by_exact_dfs(built, monkeypatch):
     for seed, L, D, n, kw in [(1001, 500, 32, 8, {}), (13, 500, 40, 6, dict(n_haplotypes=2, snp_rate=0.02, frac_partial=0.2))]:
         _check(c, capi.synth_batch(capi.synth_cfg(seed, L, D, **kw), 0, n), f"dfs seed{seed}")
     c.close()
-
-
-def test_raw_rows_with_a_stored_band(built, monkeypatch):
-    """VC_BAND_RAW=1 in a VC_EXPERIMENTS=1 build (round 6; measured slower on 3 kb windows, so not in the default library): rows that stay raw int16 -- scores outside the byte form -- store the band
-    of the rank diagonal like byte-packed rows do, and the backtrack reads it.  Same bytes as the oracle; alignments that leave the band are redone."""
-    if not capi.load_hip().vc_has_experiments():
-        pytest.skip("library built without VC_EXPERIMENTS")
-    monkeypatch.setenv("VC_BAND_RAW", "1")
-    c = HipContext(device=0, match=12, mismatch=-12, gap=-20)            # (cpl - 1) * (m - 2 g) > 255 from 6 columns per lane up: raw rows, still int16
-    for seed, L, D, n, kw in [(31, 500, 24, 8, {}), (32, 300, 16, 8, dict(frac_partial=0.3, n_haplotypes=2, snp_rate=0.02))]:
-        _check(c, capi.synth_batch(capi.synth_cfg(seed, L, D, **kw), 0, n), f"raw band seed{seed}")
-    c.close()
-    c = HipContext(device=0)                                             # default scores at 48 columns per lane (the shape of the bench's config W): raw rows as well
-    st = _check(c, capi.synth_batch(capi.synth_cfg(33, 2100, 6, profile=capi.ONT), 0, 4), "raw band, 2.1 kb windows")
-    c.close()
-
-
-def test_lds_row_backtrack_agrees_with_the_speculative_one(built, monkeypatch):
-    """k_traceb (vc_traceb.h): the backtrack walked out of LDS-resident blocks of stored rows, an experiment of round 6 (bit-identical, slower;
-    profiles/r6_ab_traceb.txt) that only VC_EXPERIMENTS=1 builds carry.  Same pairs -> same bytes, statuses and work counters as k_tracew, on
-    build-phase bands, re-alignment bands, whole rows of the redo pass, partial-span (local) layers and both overloads."""
-    if not capi.load_hip().vc_has_experiments():
-        pytest.skip("library built without VC_EXPERIMENTS")
-    cases = [(capi.synth_cfg(1002, 500, 24), 16, {}),
-             (capi.synth_cfg(13, 400, 20, n_haplotypes=2, snp_rate=0.02, frac_partial=0.3), 24, dict(chunk_windows=16, n_streams=2)),
-             (capi.synth_cfg(77, 250, 12, frac_partial=0.5, fastq=0, backbone_fastq=0), 16, dict(mode=1)),
-             (capi.synth_cfg(1005, 1000, 40, profile=capi.ONT), 6, {})]
-    for cfg, n, kw in cases:
-        batch = capi.synth_batch(cfg, 0, n)
-        out = []
-        for tb in ("0", "1"):
-            monkeypatch.setenv("VC_TRACEB", tb)               # (read by vc_create)
-            c = HipContext(device=0, **kw)
-            cons, status = c.consensus(batch)
-            st = c.stats()
-            out.append((cons, [int(x) for x in status], st["cells"], st["dp_rows"], st["band_redo"], st["trace_steps"], st["trace_spec"]))
-            c.close()
-        assert out[0][6] > 0 and out[1][6] == 0               # the walks really were different ones: only k_tracew speculates
-        assert out[0][:6] == out[1][:6], (kw, [o[1:] for o in out])
-    _check(HipContext(device=0), capi.synth_batch(capi.synth_cfg(4242, 200, 12, frac_partial=0.25), 0, 8), "k_traceb against the oracle")
-
-
-def test_persistent_build_pipeline_agrees_with_the_lock_step_plan(built):
-    """The two execution plans of the build loop (vc_set_pipeline): lock-step launches per layer, and the persistent pipeline of
-    resident forward / backtrack waves handing windows over through device-side queues.  Same bytes, same statuses, same work
-    counters (cells, rows, alignments that left the band); partial-span layers (Subgraph rows inside the forward wave), two
-    haplotypes, ragged depths, a window that overflows its capacity, several chunks, both overloads, and a pipeline squeezed
-    into very few resident waves (every hand-over then waits for a free wave).  The pipeline is an experiment (measured slower): it is
-    compiled only with VC_EXPERIMENTS=1, the default library refuses vc_set_pipeline(on)."""
-    if not capi.load_hip().vc_has_experiments():
-        c = HipContext(device=0)
-        assert c.lib.vc_set_pipeline(c.h, 1, 0, 0) == capi.VC_ERR_ARG
-        c.close()
-        pytest.skip("library built without VC_EXPERIMENTS")
-    cases = [(capi.synth_cfg(1002, 500, 24), 24, {}),
-             (capi.synth_cfg(13, 400, 20, n_haplotypes=2, snp_rate=0.02, frac_partial=0.3), 40, dict(chunk_windows=16, n_streams=2)),
-             (capi.synth_cfg(77, 250, 12, frac_partial=0.5, fastq=0, backbone_fastq=0), 30, dict(mode=1)),
-             (capi.synth_cfg(5, 300, 30), 12, dict(max_nodes=512, max_edges=1408))]            # most windows outgrow 512 nodes: reported, not hidden
-    for cfg, n, kw in cases:
-        batch = capi.synth_batch(cfg, 0, n)
-        out = []
-        for pipeline in (False, True, (3, 1)):
-            c = HipContext(device=0, pipeline=pipeline, **kw)
-            c.submit(batch); c.run(); c.sync()
-            cons, status = c.collect()
-            st = c.stats()
-            out.append((cons, [int(x) for x in status], st["cells"], st["dp_rows"], st["band_redo"], st["kernels"]["k_pipe"]["launches"]))
-            c.close()
-        assert out[0][5] == 0 and out[1][5] > 0 and out[2][5] > 0          # the plans really were different ones
-        assert out[0][:4] == out[1][:4] == out[2][:4], (kw, [o[1:] for o in out])
-        # (how many backtracks leave the stored band depends on the width class a short partial-span layer is run in: the
-        # pipeline takes everything below the batch's two widest classes in the lower of them)
-        assert out[1][4] == out[2][4] and (cfg.frac_partial > 0 or out[0][4] == out[1][4])
-        if "max_nodes" not in kw:
-            ref, pol, _ = oa.oracle_run(batch, capi.default_params(**{k: v for k, v in kw.items() if k not in ('chunk_windows', 'n_streams')}))
-            assert out[1][0] == ref
 
 
 def test_threaded_and_single_thread_host_schedulers_agree(built, monkeypatch):
@@ -301,29 +236,22 @@ def test_reserved_workspace_serves_batches_of_any_shape(built):
     tiny.close()
 
 
-def test_launch_plans_of_round_four_agree(built, monkeypatch):
-    """Three choices the host makes for speed must not show in the bytes: layers whose sequences fall into more than two width
-    classes run as ONE forward launch built for the two widest (VC_NO_FOLD=1: one launch per class); the backtrack walks eight
-    alignments of eight lanes per wave (VC_TRACE_TL=16: four of sixteen); the chunk streams are picked per batch."""
+def test_launch_plans_of_round_four_agree(built):
+    """Two choices the host makes for speed must not show in the bytes: layers whose sequences fall into more than two width
+    classes run as ONE forward launch built for the two widest (the backtrack reads the narrower rows in the lower class); the
+    chunk streams are picked per batch."""
     batch = capi.synth_batch(capi.synth_cfg(71, 500, 20, frac_partial=0.5, n_haplotypes=2, snp_rate=0.02), 0, 48)
     lens = np.diff(batch.seq_off)
     classes = {next(c for c in (4, 6, 8, 10, 12, 16, 20, 24, 32) if 64 * c >= int(x)) for x in lens if x > 0}      # vc_cpl_for
     assert len(classes) > 2                                                   # the batch really spans more than two width classes
-    out = []
-    for env in ({}, {"VC_NO_FOLD": "1"}, {"VC_TRACE_TL": "16"}, {"VC_NO_FOLD": "1", "VC_TRACE_TL": "16"}):
-        for k in ("VC_NO_FOLD", "VC_TRACE_TL"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        c = HipContext(device=0, chunk_windows=16)
-        cons, status = c.consensus(batch)
-        st = c.stats()
-        out.append((cons, [int(x) for x in status], st["cells"], st["trace_steps"]))
-        assert st["n_streams"] == 4                                           # a small batch: four chunk streams
-        c.close()
-    assert all(o == out[0] for o in out[1:])
-    ref, _, _ = oa.oracle_run(batch, capi.default_params(), 0, 8)
-    assert out[0][0][:8] == list(ref)
+    c = HipContext(device=0, chunk_windows=16)
+    cons, status = c.consensus(batch)
+    st = c.stats()
+    c.close()
+    assert st["n_streams"] == 4                                               # a small batch: four chunk streams
+    ref, pol, ost = oa.oracle_run(batch, capi.default_params())               # every one of the 48 windows against the oracle
+    assert cons == list(ref) and st["cells"] == ost.cells
+    assert [int(x) for x in status] == [capi.VC_WIN_OK if x else capi.VC_WIN_UNPOLISHED for x in pol]
     # from 12 288 windows up a context with n_streams = 0 takes eight streams; an explicit count is kept
     many = capi.synth_batch(capi.synth_cfg(72, 60, 3), 0, 12288)
     c = HipContext(device=0)
@@ -331,7 +259,7 @@ def test_launch_plans_of_round_four_agree(built, monkeypatch):
     assert c.stats()["n_streams"] == 8
     assert len(c.collect()[0]) == 12288                                        # (results are handed out in the order of the runs)
     c.submit(batch); c.run(); c.sync()
-    assert c.stats()["n_streams"] == 4 and c.collect()[0] == out[0][0]
+    assert c.stats()["n_streams"] == 4 and c.collect()[0] == cons
     c.close()
     c = HipContext(device=0, n_streams=3)
     c.submit(many); c.run(); c.sync()

@@ -1,5 +1,5 @@
 """Where does the device phase of files -> FASTA go on a small batch?  Builds the batch of tools/gpu_files_e2e.py (host side only), then
-times submit / run+sync / collect separately, cold (workspaces of another shape) and warm, for several stream counts and the pipeline.
+times submit / run+sync / collect separately, cold (workspaces of another shape) and warm, for several stream counts.
 
 usage: gpu_files_probe.py [targets=200]"""
 import os
@@ -30,10 +30,10 @@ def timed(ctx, label):
 
 
 ref = None
-for streams, pipe in ((4, 0), (4, 0), (2, 0), (1, 0), (8, 0), (1, 1), (2, 1), (4, 1)):
-    ctx = HipContext(device=0, mode=0, min_confidence=0.2, min_support=0.2, num_prune=3, n_streams=streams, pipeline=bool(pipe))
+for streams in (4, 4, 2, 1, 8):
+    ctx = HipContext(device=0, mode=0, min_confidence=0.2, min_support=0.2, num_prune=3, n_streams=streams)
     ctx.consensus(capi.synth_batch(capi.synth_cfg(1, 200, 8), 0, 64))
-    print(f"streams {streams} pipeline {pipe}")
+    print(f"streams {streams}")
     c0 = timed(ctx, "cold (other-shape workspaces)")
     c1 = timed(ctx, "warm")
     c1 = timed(ctx, "warm")

@@ -303,8 +303,6 @@ def load_hip():
         lib.vc_debug_stage_digest.restype = C.c_int
         lib.vc_set_profile.argtypes = [vp, C.c_int]
         lib.vc_set_profile.restype = C.c_int
-        lib.vc_set_pipeline.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32]
-        lib.vc_set_pipeline.restype = C.c_int
         try:                                  # (development: an A/B variant library built before an entry point was added still loads)
             lib.vc_set_polish_params.argtypes = [vp, C.POINTER(VcParams)]
             lib.vc_set_polish_params.restype = C.c_int

@@ -32,19 +32,14 @@
 #include <vector>
 
 #include "vc_kernels.h"
-// The persistent build pipeline (vc_pipe.h: built, bit-identical, slower than the lock-step plan -- DESIGN section 10) is an experiment:
-// compiled only with -DVC_EXPERIMENTS (VC_EXPERIMENTS=1 python __graft_entry__.py); without it vc_set_pipeline(on) is refused.
-#ifdef VC_EXPERIMENTS
-#include "vc_pipe.h"
-#endif
 
 namespace {
 
 thread_local std::string g_create_error;
 
-enum KClass { KC_AVG = 0, KC_INIT, KC_TOPO, KC_FWD, KC_TRACE, KC_ADDALN, KC_PRUNE, KC_ADDW, KC_FINISH, KC_ROWS, KC_RESOLVE, KC_CONS, KC_PIPE, KC_N };
+enum KClass { KC_AVG = 0, KC_INIT, KC_TOPO, KC_FWD, KC_TRACE, KC_ADDALN, KC_PRUNE, KC_ADDW, KC_FINISH, KC_ROWS, KC_RESOLVE, KC_CONS, KC_N };
 const char* kClassNames[KC_N] = {"k_avg", "k_init", "k_topo", "k_fwd", "k_trace", "k_addaln", "k_prune_lcc",
-                                 "k_addw", "k_finish", "k_rows", "k_resolve", "k_consensus", "k_pipe"};
+                                 "k_addw", "k_finish", "k_rows", "k_resolve", "k_consensus"};
 
 #ifndef VC_RING
 #define VC_RING 8
@@ -94,13 +89,7 @@ struct Work {
     uint16_t* d_scratch16 = nullptr;                                 // k_addaln per-pair notes
     uint32_t* d_submask = nullptr;                                   // [CW*(NC/32+1)] Subgraph membership by node id
     uint32_t* h_maxn = nullptr;                                      // pinned: [0] max rows, [1] max edges after a prune round
-    // persistent build pipeline (vc_pipe.h): counters, three queues, the layer every window is at; the backtrack and resolver
-    // kernels run beside the forward kernel on streams of their own
-    uint32_t* d_pipe_ctl = nullptr; unsigned long long* d_pipe_slots = nullptr; uint32_t* d_cur_layer = nullptr;
-    uint32_t pipe_cap = 0;
-    uint8_t* d_pipe_ws = nullptr; size_t pipe_ws_bytes = 0;
-    hipStream_t st_t = nullptr;
-    hipEvent_t ev_seed = nullptr, ev_t = nullptr;
+    uint32_t* d_cur_layer = nullptr;                                 // [CW] the layer every window is at (build_layer)
     bool pruned_known = false;                                       // h_maxn describes the current graphs
     // state of the chunk currently in flight
     uint32_t w0 = 0, ns = 0, layers = 0, nseq_max = 0;
@@ -170,7 +159,9 @@ struct vc_ctx {
     bool ws_packed = false;             // the workspaces hold band space (the batch they were made for stores byte-packed rows)
     bool auto_streams = false;          // vc_params.n_streams was 0: vc_submit picks the chunk streams per batch
     uint32_t streams_made = 0;          // streams created (>= n_streams)
-    bool auto_arena = true;             // vc_submit makes the arena itself for the first large batch (development: VC_AUTO_ARENA=0)
+    bool auto_arena = true;             // vc_submit makes the arena itself for the first large batch (VC_AUTO_ARENA=0: it does not)
+    uint64_t scratch_cap = 128ull << 30;   // cap of the default workspace budget (default_budget; VC_SCRATCH_CAP_GB)
+    bool time_submit = false;           // VC_TIME_SUBMIT: phases of vc_submit / make_arena on stderr
     bool have_ws = false;               // workspaces exist (out of the arena or allocated piece by piece)
 
     Batch bt[2];
@@ -187,19 +178,9 @@ struct vc_ctx {
     uint64_t hmat_dwords = 0;
     uint32_t big_ws_stride = 0;          // bytes per window of the HBM workspace for oversized graph images (0: all fit the LDS)
     bool big_ws_topo = false;            // the workspace also backs k_topo's optimistic LDS image of the first pruned graphs
-    bool trace_wave = true;
-    int prune_hbm = 1;              // 1: the first prune of a chunk works from the HBM workspace instead of LDS; 2: every prune; 0: LDS
-    bool topo_hbm = false;          // k_topo of the pruned graphs from the HBM workspace
     uint32_t dbg_stop_kind = 0, dbg_stop_index = 0;   // vc_debug_stop_after: leave the chunk's graphs as they are after that stage
-    bool force_dfs = false;       // test knob: settle every end-cell tie with the exact DFS as well
-    bool trace_block = false;     // VC_EXPERIMENTS builds, VC_TRACEB=1: k_traceb (the walk out of LDS, vc_traceb.h) for byte-packed rows
-    uint32_t trace_tl = 8;        // lanes per alignment of the lock-step k_tracew (development: VC_TRACE_TL=16)
-    bool dt = true;               // global alignments on byte-packed rows run on k_fwd_dt (development: VC_DT=0 keeps them on k_fwd)
-    bool band_raw = false;        // -DVC_EXPERIMENTS builds, VC_BAND_RAW=1: raw int16 rows (widest classes, scores outside the byte form) store the band as well -- bit-identical,
-                                  //   6 % slower on 3 kb windows (profiles/r6_ab_raw_band.txt: 4.7 % of their alignments leave 384 columns), so off
-    bool inline_redo = false;     // development (VC_INLINE_REDO=1, read once at vc_create): the redo pair inside every build round instead of catch-up rounds
-    bool fold = true;             // launch_fwd: more than two width classes in one launch (development: VC_NO_FOLD=1 launches once per class)
-    uint32_t dup = 0;             // development (VC_DUP): launch idempotent kernel classes twice to measure their marginal cost inside the job
+    bool force_dfs = false;       // test knob (VC_RESOLVE_FORCE_DFS): settle every end-cell tie with the exact DFS as well
+    bool dt = true;               // global alignments on byte-packed rows run on k_fwd_dt (test knob: VC_DT=0 keeps them on k_fwd)
     Work works[kMaxStreams];
     hipStream_t streams[kMaxStreams]{};      // the process's chunk streams of this device (pooled_stream): not owned
     hipStream_t own_stream = nullptr;        // this context's stream for copies, fills and small kernels
@@ -207,15 +188,7 @@ struct vc_ctx {
     // drives each through its phases on that stream: the one host wait of the path -- the pruned graphs' height before a
     // re-alignment round -- then stalls that stream only, a stream takes its next chunk as soon as it has queued the last one,
     // and when a batch has no chunk left it goes on with the next batch of the queue: no barrier between chunks, none between batches.
-    bool host_threads = true;
-    // persistent build pipeline: the build loop of a chunk as three resident kernels and device-side queues instead of six launches
-    // per layer (vc_pipe.h); pipe_f / pipe_t / pipe_r: resident workgroups of the forward / backtrack / resolver kernels (0: default)
-    bool pipe = false;
-    uint32_t pipe_f = 0, pipe_t = 0;
-    uint32_t pipe_patience_s = 20;       // seconds a wave of the pipeline waits for an item before it declares the run failed (VC_PIPE_PATIENCE)
-    unsigned long long* d_pipe_prof = nullptr;   // [VC_PP_N] phase clocks of the pipeline's waves, summed over a run (vc_debug_pipe_prof)
-    uint32_t* d_pipe_abort = nullptr;    // != 0: a wave of the pipeline ran out of patience (site code): the run failed
-    uint32_t n_cu = 256;
+    bool host_threads = true;            // (VC_HOST_THREADS=0: one host thread walks the streams in lock-step, as vc_debug_stop_after does)
     std::thread workers[kMaxStreams];
     uint32_t workers_made = 0;
     bool stop = false;                   // vc_destroy: the workers leave
@@ -259,23 +232,21 @@ int fail(vc_ctx* c, int code, const char* fmt, ...) {
 // Contexts that run at the same time then interleave their launches on the same streams, which orders them but changes no result.
 struct StreamSet {
     hipStream_t chunk[kMaxStreams]{};          // the chunk streams, priorities cycling (never two neighbours on one hardware queue)
-    hipStream_t side[kMaxStreams]{};           // persistent pipeline only: the stream its backtrack kernel runs on beside chunk stream s
 };
 std::mutex g_streams_mu;
 std::map<int, StreamSet> g_streams;            // by device
 
-int stream_priority(uint32_t s, uint32_t shift) {
+int stream_priority(uint32_t s) {
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     const int n_prio = prio_least - prio_greatest + 1;
-    return n_prio > 1 && !getenv("VC_SAME_PRIORITY") ? prio_least - (int)((s + shift) % (uint32_t)n_prio) : 0;
+    return n_prio > 1 ? prio_least - (int)(s % (uint32_t)n_prio) : 0;
 }
-// stream s of the device's set (made on first use); side = the pipeline's second stream.  nullptr: creation failed
-hipStream_t pooled_stream(int device, uint32_t s, bool side) {
+// stream s of the device's set (made on first use).  nullptr: creation failed
+hipStream_t pooled_stream(int device, uint32_t s) {
     std::lock_guard<std::mutex> lk(g_streams_mu);
-    StreamSet& set = g_streams[device];
-    hipStream_t& st = side ? set.side[s] : set.chunk[s];
-    if (!st && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, stream_priority(s, side ? 1u : 0u)) != hipSuccess) st = nullptr;
+    hipStream_t& st = g_streams[device].chunk[s];
+    if (!st && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, stream_priority(s)) != hipSuccess) st = nullptr;
     return st;
 }
 
@@ -309,7 +280,6 @@ int wait_batch(vc_ctx* c, Batch* bt) {
         if (!bt->ev_rec[s]) continue;
         hipError_t e = hipEventSynchronize(bt->done_ev[s]);
         if (e != hipSuccess) return fail(c, VC_ERR_HIP, "waiting for chunk stream %u failed: %s", s, hipGetErrorString(e));
-        if (c->works[s].st_t) (void)hipStreamSynchronize(c->works[s].st_t);      // (persistent pipeline: the backtrack kernel's stream)
     }
     return VC_OK;
 }
@@ -323,10 +293,8 @@ void drain(vc_ctx* c) {
 // ... and nothing a stopped run (vc_debug_stop_after) left on the chunk streams either
 void sync_all(vc_ctx* c) {
     drain(c);
-    for (uint32_t k = 0; k < kMaxStreams; ++k) {
-        if (c->works[k].st_t) (void)hipStreamSynchronize(c->works[k].st_t);
+    for (uint32_t k = 0; k < kMaxStreams; ++k)
         if (c->streams[k]) (void)hipStreamSynchronize(c->streams[k]);
-    }
 }
 
 template <typename T>
@@ -384,14 +352,12 @@ void free_arena(vc_ctx* c) {
     c->arena.clear();
     c->arena_bytes = 0; c->arena_cur = 0;
 }
-// Default workspace budget: 60 % of what is free, capped.  The cap was 96 GiB until the end of round 6; larger chunks run faster (config C,
+// Default workspace budget: 60 % of what is free, capped (vc_ctx::scratch_cap).  The cap was 96 GiB until the end of round 6; larger chunks run faster (config C,
 // tools/gpu_scale.py 100000 64 500: 64 GiB 36.0 k, 96 GiB 38.6 k, 160 GiB 39.1 k, 220 GiB 39.5 k windows/s -- profiles/r6_ab_workspace_budget.txt), and an
 // MI355X has 288 GB.  The cap is 128 GiB now: four arena segments of 32 GiB, the largest hipMalloc that comes back at once -- 4 x 43 GiB (a cap of 176)
 // take 3.4 s and turn the cold start of a process from 2.9 into 6.3 s.  VC_SCRATCH_CAP_GB overrides the cap, vc_params.scratch_bytes the whole rule.
-uint64_t default_budget(size_t free_b) {
-    uint64_t cap = 128ull << 30;
-    if (const char* d = getenv("VC_SCRATCH_CAP_GB")) { const double g = std::atof(d); if (g >= 1.0) cap = (uint64_t)(g * 1073741824.0); }
-    return std::min<uint64_t>((uint64_t)(free_b * 0.6), cap);
+uint64_t default_budget(const vc_ctx* c, size_t free_b) {
+    return std::min<uint64_t>((uint64_t)(free_b * 0.6), c->scratch_cap);
 }
 // bytes = 0: the default budget (vc_params.scratch_bytes, or 60 % of the free memory up to the cap of default_budget).  One segment per chunk stream.
 int make_arena(vc_ctx* c, uint64_t bytes) {
@@ -399,9 +365,9 @@ int make_arena(vc_ctx* c, uint64_t bytes) {
     if (!bytes) {
         size_t free_b = 0, total_b = 0;
         HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        bytes = c->prm.scratch_bytes ? c->prm.scratch_bytes : default_budget(free_b);
+        bytes = c->prm.scratch_bytes ? c->prm.scratch_bytes : default_budget(c, free_b);
     }
-    const bool tm = getenv("VC_TIME_SUBMIT") != nullptr;
+    const bool tm = c->time_submit;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_0 = now();
     // four segments whatever the streams: a batch on four chunk streams lays a workspace into each, one on eight two, on sixteen four --
@@ -457,8 +423,8 @@ int alloc_work(vc_ctx* c, Work* wk) {
         (rc = dalloc(c, c->chunk_allocs, &wk->dp.fie, CW * (NC + 4) + 64)) ||      // (+ 64: k_tracew reads whole 8-byte chunks of a window's entries)
         (rc = dalloc(c, c->chunk_allocs, &wk->dp.rank2node, CW * NC)) ||
         (rc = dalloc(c, c->chunk_allocs, &wk->dp.ovf, CW * EC)) ||
-        (rc = dalloc(c, c->chunk_allocs, &wk->d_hmat, c->hmat_dwords + 64)) ||      // (+ 64: k_traceb reads whole 48-byte windows of a row)
-        (rc = dalloc(c, c->chunk_allocs, &wk->d_bmat, ((c->ws_packed || c->band_raw) ? c->hmat_dwords / 4 + (size_t)c->jobs_cap * VC_BAND_JOB_PAD_DWORDS : 0) + 64)) ||
+        (rc = dalloc(c, c->chunk_allocs, &wk->d_hmat, c->hmat_dwords + 64)) ||          // (+ 64: slack past the last row)
+        (rc = dalloc(c, c->chunk_allocs, &wk->d_bmat, (c->ws_packed ? c->hmat_dwords / 4 + (size_t)c->jobs_cap * VC_BAND_JOB_PAD_DWORDS : 0) + 64)) ||
         (rc = dalloc(c, c->chunk_allocs, &wk->d_band_par, (size_t)c->jobs_cap * 2)) ||
         (rc = dalloc(c, c->chunk_allocs, &wk->d_redo_list, c->jobs_cap)) ||
         (rc = dalloc(c, c->chunk_allocs, &wk->d_redo_n, 4)) ||
@@ -479,22 +445,9 @@ int alloc_work(vc_ctx* c, Work* wk) {
         (rc = dalloc(c, c->chunk_allocs, &wk->d_rnpairs, CW * c->max_nseq)) ||
         (rc = dalloc(c, c->chunk_allocs, &wk->d_scratch16, CW * (4 * PC + NC))) ||
         (rc = dalloc(c, c->chunk_allocs, &wk->d_submask, CW * (NC / 32 + 1))) ||
-        (rc = dalloc(c, c->chunk_allocs, &wk->d_maxn, 2)))
+        (rc = dalloc(c, c->chunk_allocs, &wk->d_maxn, 2)) ||
+        (rc = dalloc(c, c->chunk_allocs, &wk->d_cur_layer, CW)))
         return rc;
-    {
-        uint32_t cap = 64;
-        while (cap < CW) cap <<= 1;
-        wk->pipe_cap = cap;
-        // (the exact-DFS fallback of the end-cell resolver works from an HBM image of the graph: one per backtrack workgroup)
-        wk->pipe_ws_bytes = (size_t)std::min<uint64_t>((CW + VC_TG - 1) / VC_TG, 256u * 8u) * ((topo_lds_bytes(NC, c->EC, c->STK, c->MA) + 15u) & ~15u);
-        if ((rc = dalloc(c, c->chunk_allocs, &wk->d_cur_layer, CW))) return rc;
-#ifdef VC_EXPERIMENTS
-        if ((rc = dalloc(c, c->chunk_allocs, &wk->d_pipe_ctl, (size_t)VC_PC_N * VC_PIPE_CTL_STRIDE)) ||
-            (rc = dalloc(c, c->chunk_allocs, &wk->d_pipe_slots, (size_t)2 * cap)) ||
-            (rc = dalloc(c, c->chunk_allocs, &wk->d_pipe_ws, wk->pipe_ws_bytes)))
-            return rc;
-#endif
-    }
     return VC_OK;
 }
 
@@ -603,17 +556,16 @@ void launch_fwd_t(hipStream_t st, const VcFwdArgs& a, uint32_t jobs, bool packed
 }
 
 // lower class of a folded launch (launch_fwd), 0 when the batch's classes need no folding: what the backtrack reads the rows with
-uint32_t fold_lo(const vc_ctx* c, const Batch* bt) {
+uint32_t fold_lo(const Batch* bt) {
     const uint32_t opts[] = {4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64};
     int lo = -1, hi = -1;
     for (int i = 0; i < 11; ++i) { if (opts[i] == bt->cpl_min) lo = i; if (opts[i] == bt->cpl) hi = i; }
-    return (c->fold && lo >= 0 && hi - lo > 1) ? opts[hi - 1] : 0u;
+    return (lo >= 0 && hi - lo > 1) ? opts[hi - 1] : 0u;
 }
 
 // One launch when the batch's sequences fall into one width class or two adjacent ones (the usual case:
 // read pieces of a window differ by a few percent in length); otherwise one launch per class.
 int launch_fwd(vc_ctx* c, const Batch* bt, hipStream_t st, const VcFwdArgs& a0, uint32_t jobs, const Work* wk = nullptr, bool nwonly = false) {
-    if (c->dup & 16u) { const uint32_t d = c->dup; c->dup = 0; (void)launch_fwd(c, bt, st, a0, jobs, wk, nwonly); c->dup = d; (void)hipMemsetAsync(a0.tie_n, 0, 4, st); }
     const uint32_t opts[] = {4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64};
     VcFwdArgs a = a0;
     a.do_init = 1;
@@ -625,7 +577,7 @@ int launch_fwd(vc_ctx* c, const Batch* bt, hipStream_t st, const VcFwdArgs& a0, 
     };
     // more than two classes (partial-span layers: pieces of reads of any length): one launch built for the two widest ones, every
     // narrower sequence in the lower of them -- four launches per layer, each waiting for its slowest alignment, become one
-    if (hi - lo > 1 && c->fold) { lo = hi - 1; a.fold = 1; }
+    if (hi - lo > 1) { lo = hi - 1; a.fold = 1; }
     // the doubly tilted form (vc_fwd_dt.h): judged on the workspaces' row capacity, so that every window of the batch takes the same kernel
     const bool dt = c->dt && bt->packed && bt->cpl < 32 && vc_dt_ok(c->prm.match, c->prm.mismatch, c->prm.gap, c->NC, bt->cpl);
     if (hi - lo == 1) {
@@ -679,44 +631,6 @@ int launch_fwd(vc_ctx* c, const Batch* bt, hipStream_t st, const VcFwdArgs& a0, 
     return VC_OK;
 }
 
-#ifdef VC_EXPERIMENTS
-// the forward kernel of the persistent build pipeline for this batch's width classes (one class, or two adjacent ones)
-template <int CA, int CB>
-int launch_pipe_fwd_t(vc_ctx* c, hipStream_t st, const VcPipeFwdArgs& a, uint32_t grid, uint32_t lds) {
-    auto k = k_pipe_fwd<CA, CB, (kKept ? kKept : 1), true>;
-    { int rc_ = lds_limit(c, (const void*)k, lds); if (rc_) return rc_; }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, a);
-    return VC_OK;
-}
-// The pipeline's forward kernel is built for the widest class of the batch and the one below it (everything narrower runs
-// in that lower class: partial-span layers are short).  -> (CA, CB), CA == CB when the batch has one class.
-bool pipe_classes(const Batch* bt, uint32_t* ca, uint32_t* cb) {
-    const uint32_t opts[] = {4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64};
-    int lo = -1, hi = -1;
-    for (int i = 0; i < 11; ++i) { if (opts[i] == bt->cpl_min) lo = i; if (opts[i] == bt->cpl) hi = i; }
-    if (lo < 0 || hi < 0) return false;
-    *cb = opts[hi]; *ca = lo < hi ? opts[hi - 1] : opts[hi];
-#ifdef VC_FAST_BUILD
-    return *cb == 10 || *cb == 8;
-#else
-    return *cb < 32;                   // (the wide classes -- 32 columns per lane and up -- run with their own ring / kept-row parameters, kKeptWide and
-                                       //  bt->ring: build_pipe and k_pipe_fwd are written for kKept / kRing, so those batches take the lock-step plan)
-#endif
-}
-int launch_pipe_fwd(vc_ctx* c, const Batch* bt, hipStream_t st, const VcPipeFwdArgs& a, uint32_t grid, uint32_t lds) {
-    uint32_t lo = 0, hi = 0;
-    if (!pipe_classes(bt, &lo, &hi)) return fail(c, VC_ERR_ARG, "persistent pipeline: unsupported cells-per-lane %u..%u", bt->cpl_min, bt->cpl);
-#define VC_PF(A, B) if (lo == A && hi == B) return launch_pipe_fwd_t<A, B>(c, st, a, grid, lds);
-    VC_PF(8, 10) VC_PF(8, 8) VC_PF(10, 10) VC_PF(6, 8)
-#ifndef VC_FAST_BUILD
-    VC_PF(4, 4) VC_PF(4, 6) VC_PF(6, 6) VC_PF(10, 12) VC_PF(12, 12) VC_PF(12, 16) VC_PF(16, 16) VC_PF(16, 20) VC_PF(20, 20)
-    VC_PF(20, 24) VC_PF(24, 24)
-#endif
-#undef VC_PF
-    return fail(c, VC_ERR_ARG, "persistent pipeline: width classes %u..%u not built", lo, hi);
-}
-#endif
-
 uint32_t pick_cpl(uint32_t max_len) {
     const uint32_t opts[] = {4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64};
     for (uint32_t o : opts) if (64 * o >= max_len) return o;
@@ -752,32 +666,17 @@ struct Plan {
         ta.stat = c->d_stat; ta.hmat = wk.d_hmat; ta.c0 = wk.d_c0; ta.job_end = wk.d_job_end; ta.job_type = wk.d_job_type; ta.PC = PC; ta.packed = bt->packed ? 1 : 0; ta.kept = 0;
         ta.bmat = wk.d_bmat; ta.band_par = wk.d_band_par; ta.band = bt->band ? 1 : 0; ta.redo_list = nullptr; ta.redo_n = nullptr;
         ta.redo_out = wk.d_redo_list; ta.redo_out_n = wk.d_redo_n;
-        ta.cpl_lo = fold_lo(c, bt);       // (the pipeline sets its own)
+        ta.cpl_lo = fold_lo(bt);
         return ta;
     }
 
     // the backtrack of `njobs` alignments (gsz per window) whose graphs have at most `max_rows` rows
     void launch_trace(Work& wk, VcTraceArgs& ta, uint32_t njobs, uint32_t gsz, uint32_t max_rows) {
-        if (c->dup & 1u) { const uint32_t d = c->dup; c->dup = 0; launch_trace(wk, ta, njobs, gsz, max_rows); c->dup = d; }
         Timer t(c, KC_TRACE, wk.stream);
-        if (!c->trace_wave) {
-            hipLaunchKernelGGL(k_trace, dim3((njobs + VC_TRACE_LANES - 1) / VC_TRACE_LANES), dim3(64), 0, wk.stream, ta);
-            return;
-        }
-        // eight alignments per wave, eight lanes each (development: VC_TRACE_TL=16 -- four alignments of sixteen lanes, the form the pipeline uses)
-#ifdef VC_EXPERIMENTS
-        if (c->trace_block && ta.packed) {
-            // the walk out of LDS (vc_traceb.h; VC_TRACEB=1): bit-identical and a quarter SLOWER than k_tracew (profiles/r6_ab_traceb.txt) -- an experiment
-            hipLaunchKernelGGL(k_traceb, dim3((njobs + 7) / 8), dim3(64), vc_traceb_lds_bytes(), wk.stream, ta);
-            if (c->wcols) { ta.only_wide = 1; hipLaunchKernelGGL(k_trace, dim3((njobs + VC_TRACE_LANES - 1) / VC_TRACE_LANES), dim3(64), 0, wk.stream, ta); ta.only_wide = 0; }
-            return;
-        }
-#endif
-        const uint32_t tg = c->trace_tl == 16 ? 4u : 8u;
-        ta.shared_table = gsz % tg == 0; ta.tab_rows = std::min(max_rows, kTraceTabRows);
-        const uint32_t lds = vc_tracew_lds_bytes(ta.tab_rows, ta.shared_table != 0, tg);
-        if (tg == 4) hipLaunchKernelGGL(k_tracew<16>, dim3((njobs + 3) / 4), dim3(64), lds, wk.stream, ta);
-        else hipLaunchKernelGGL(k_tracew<8>, dim3((njobs + 7) / 8), dim3(64), lds, wk.stream, ta);
+        // k_tracew: eight alignments per wave, eight lanes each; k_trace then walks what only the int32 matrices hold
+        ta.shared_table = gsz % VC_TG == 0; ta.tab_rows = std::min(max_rows, kTraceTabRows);
+        const uint32_t lds = vc_tracew_lds_bytes(ta.tab_rows, ta.shared_table != 0);
+        hipLaunchKernelGGL(k_tracew, dim3((njobs + VC_TG - 1) / VC_TG), dim3(64), lds, wk.stream, ta);
         if (c->wcols) { ta.only_wide = 1; hipLaunchKernelGGL(k_trace, dim3((njobs + VC_TRACE_LANES - 1) / VC_TRACE_LANES), dim3(64), 0, wk.stream, ta); ta.only_wide = 0; }
     }
 
@@ -862,7 +761,7 @@ struct Plan {
     // every layer of every window of the chunk: `layers` rounds, then as many catch-up rounds as the slowest window is behind
     int build_loop(Work& wk) {
         int rc;
-        const bool defer = bt->band && !c->inline_redo;                 // (development: VC_INLINE_REDO=1 keeps the redo pair in every round)
+        const bool defer = bt->band;
         for (uint32_t j = 1; j <= wk.layers; ++j) if ((rc = build_layer(wk, j, !defer))) return rc;
         if (!defer) return VC_OK;
         // (the one host wait of the build phase; the re-alignment rounds have theirs: Plan::realign)
@@ -875,82 +774,6 @@ struct Plan {
         for (uint32_t r = 0; r < lag; ++r) if ((rc = build_layer(wk, wk.layers, true))) return rc;
         return VC_OK;
     }
-
-#ifndef VC_EXPERIMENTS
-    bool pipe_ok() const { return false; }
-    int build_pipe(Work&) { return VC_ERR_STATE; }
-#else
-    // The whole build loop of the chunk (window.cpp:239-298, every layer of every window) as ONE set of resident kernels working
-    // off device-side queues (vc_pipe.h) instead of build_layer() once per layer.
-    bool pipe_ok() const {
-        uint32_t ca_ = 0, cb_ = 0;
-        return c->pipe && bt->kept && bt->packed && bt->band && c->wcols == 0 && c->dbg_stop_kind == 0 && c->trace_wave && pipe_classes(bt, &ca_, &cb_);
-    }
-    int build_pipe(Work& wk) {
-        const uint32_t ns = wk.ns, cap = wk.pipe_cap;
-        uint32_t shift = 0;
-        while ((1u << shift) < cap) ++shift;
-        HIPCHK(c, hipMemsetAsync(wk.d_pipe_ctl, 0, (size_t)VC_PC_N * VC_PIPE_CTL_STRIDE * 4, wk.stream));
-        HIPCHK(c, hipMemsetAsync(wk.d_pipe_slots, 0, (size_t)2 * cap * 8, wk.stream));
-        VcPipe p{};
-        auto ctl = [&](int i) { return wk.d_pipe_ctl + (size_t)i * VC_PIPE_CTL_STRIDE; };
-        p.fq = VcQueue{wk.d_pipe_slots, ctl(VC_PC_FQ_RES), ctl(VC_PC_FQ_HEAD), cap - 1, shift};
-        p.tq = VcQueue{wk.d_pipe_slots + cap, ctl(VC_PC_TQ_RES), ctl(VC_PC_TQ_HEAD), cap - 1, shift};
-        p.n_active = ctl(VC_PC_ACTIVE); p.done = ctl(VC_PC_DONE); p.finished = ctl(VC_PC_FINISHED); p.abort_code = c->d_pipe_abort;
-        p.cur_layer = wk.d_cur_layer;
-        p.prof = c->d_pipe_prof;
-        p.pub_time = getenv("VC_PIPE_PUBTIME") ? reinterpret_cast<unsigned long long*>(wk.d_scratch16 + (size_t)c->CW * (4 * PC + NC)) - c->CW : nullptr;   // development: tail of the note blocks
-        p.spin_limit = c->pipe_patience_s * 100000000u;       // ticks of the 100 MHz clock: this long without an item is a protocol error
-        if (!wk.st_t) {                                       // the backtrack kernel's stream beside this chunk stream, on first use
-            wk.st_t = pooled_stream(c->device, (uint32_t)(&wk - c->works), true);
-            if (!wk.st_t) return fail(c, VC_ERR_HIP, "hipStreamCreate failed");
-        }
-        hipLaunchKernelGGL(k_pipe_seed, dim3((ns + 255) / 256), dim3(256), 0, wk.stream, bt->b, p, wk.w0, ns);
-        HIPCHK(c, hipEventRecord(wk.ev_seed, wk.stream));
-        HIPCHK(c, hipStreamWaitEvent(wk.st_t, wk.ev_seed, 0));
-
-        // Resident workgroups.  Both kernels take 96 registers -- five waves per SIMD in all -- so the forward kernel must leave
-        // the backtrack waves their share: a forward grid that fills the device alone would wait for backtracks that can never start.
-        const uint32_t GF = std::max(1u, std::min(ns, c->pipe_f ? c->pipe_f : c->n_cu * 15u));
-        const uint32_t GT = std::max(1u, std::min((ns + VC_TG - 1) / VC_TG, c->pipe_t ? c->pipe_t : c->n_cu * 5u));
-
-        VcPipeTraceArgs pt{};
-        pt.ta = trace_args(wk);
-        pt.ta.group = 1; pt.ta.k0 = 0; pt.ta.hstride = (uint64_t)NC * rowd;
-        pt.ta.pairs = wk.d_pairs; pt.ta.npairs = wk.d_npairs; pt.ta.pair_group = 1; pt.ta.pair_k0 = 0; pt.ta.kept = bt->kept;
-        pt.ta.shared_table = 0; pt.ta.tab_rows = std::min(NC, kTraceTabRows);
-        { uint32_t cb_ = 0; (void)pipe_classes(bt, &pt.ta.cpl_lo, &cb_); }
-        pt.p = p;
-        pt.g = wk.gr[wk.cur]; pt.STK = c->STK;
-        pt.tie_rows = wk.d_tie_rows; pt.tie_cnt = wk.d_tie_cnt; pt.tie_over = wk.d_pairs; pt.tie_over_stride = PC; pt.job_end = wk.d_job_end;
-        pt.submask = wk.d_submask; pt.workspace = wk.d_pipe_ws; pt.ws_bytes = (topo_lds + 15u) & ~15u; pt.force_dfs = c->force_dfs ? 1 : 0;
-        if ((size_t)GT * pt.ws_bytes > wk.pipe_ws_bytes) return fail(c, VC_ERR_ARG, "persistent pipeline: resolver workspace too small");
-        { Timer t(c, KC_TRACE, wk.st_t);
-          const uint32_t t_lds = std::max(vc_tracew_lds_bytes(pt.ta.tab_rows, false), 4 * ((NC + 31) / 32 + 1) + 2 * 256 + 16);
-          hipLaunchKernelGGL(k_pipe_trace, dim3(GT), dim3(VC_TG * VC_TL), t_lds, wk.st_t, pt); }
-        HIPCHK(c, hipEventRecord(wk.ev_t, wk.st_t));
-
-        VcPipeFwdArgs pf{};
-        pf.fa = fwd_args(wk);
-        pf.fa.group = 1; pf.fa.k0 = 0; pf.fa.mode = 0; pf.fa.hstride = (uint64_t)NC * rowd; pf.fa.do_init = 1;
-        pf.fa.tie_over = wk.d_pairs; pf.fa.tie_over_stride = PC;
-        pf.aa.b = bt->b; pf.aa.g = wk.gr[wk.cur]; pf.aa.dp = wk.dp; pf.aa.w0 = wk.w0; pf.aa.nslots = ns; pf.aa.NC = NC; pf.aa.EC = EC; pf.aa.layer = 0;
-        pf.aa.pairs = wk.d_pairs; pf.aa.npairs = wk.d_npairs; pf.aa.PC = PC; pf.aa.scratch = wk.d_scratch16; pf.aa.ring = (uint32_t)kRing;
-        pf.aa.make_rows = 1; pf.aa.kept = bt->kept; pf.aa.tie_n = wk.d_tie_n; pf.aa.redo_n = wk.d_redo_n;
-        pf.p = p; pf.submask = wk.d_submask; pf.force_fail_site = 0;
-        bool any_partial = false;
-        for (uint8_t x : bt->h_layer_partial) any_partial = any_partial || x;
-        uint32_t lds = std::max((uint32_t)(kKept ? kKept : 1) * (bt->cpl / 2) * 64u * 4u, add_lds);
-        if (any_partial) lds = std::max(lds, vc_rows_sub_lds_bytes(NC, bt->kept));
-        lds = (lds + 255u) & ~255u;
-        if (lds > kLdsCap) return fail(c, VC_ERR_ARG, "persistent pipeline: %u bytes of LDS per forward wave", lds);
-        int rc;
-        { Timer t(c, KC_PIPE, wk.stream);
-          if ((rc = launch_pipe_fwd(c, bt, wk.stream, pf, std::min(GF, c->CW), lds))) return rc; }
-        HIPCHK(c, hipStreamWaitEvent(wk.stream, wk.ev_t, 0));
-        return VC_OK;
-    }
-#endif
 
     // PruneGraph + LargestSubgraph + its TopologicalSort (window.cpp:318-321,374-383); `more` = a
     // re-alignment round follows, so ask the device how tall the pruned graphs are
@@ -970,15 +793,15 @@ struct Plan {
         pa.NCl = NCl; pa.ECl = ECl;
         // the first prune works on the whole graph (60 KB image at 2 240 nodes): in LDS only two windows fit a CU, and beside a
         // full house of k_fwd waves not even one until eight of them retire; from the HBM workspace every window of the chunk
-        // is resident at once: 76 -> 34 ms per 32 768 windows alone, 250 -> 53 ms beside k_fwd, the job + 4 % (VC_PRUNE_HBM=0 / 2:
-        // development switch; the later prunes work on graphs a quarter of the size and are faster from LDS).  The same for
-        // k_topo (VC_TOPO_HBM=1) and for k_addaln's per-pair notes was measured and does not pay: k_addaln with 1.4 instead of
-        // 7 KB of LDS is placed sooner, waits on HBM instead, and its 8 192 waves then sit on the slots k_tracew needs.
-        const bool first_hbm = c->prune_hbm && (!wk.pruned_known || c->prune_hbm >= 2) && c->big_ws_stride >= vc_prune_lds_bytes(NCl, ECl);
+        // is resident at once: 76 -> 34 ms per 32 768 windows alone, 250 -> 53 ms beside k_fwd, the job + 4 % (the later prunes
+        // work on graphs a quarter of the size and are faster from LDS).  The same for k_topo and for k_addaln's per-pair notes
+        // was measured and does not pay: k_addaln with 1.4 instead of 7 KB of LDS is placed sooner, waits on HBM instead, and its
+        // 8 192 waves then sit on the slots k_tracew needs.
+        const bool first_hbm = !wk.pruned_known && c->big_ws_stride >= vc_prune_lds_bytes(NCl, ECl);
         const bool pws = first_hbm || vc_prune_lds_bytes(NCl, ECl) > kLdsCap, tws = topo_lds_bytes(NCl, ECl, c->STK, c->MA) > kLdsCap;
         pa.ws = pws ? wk.d_big_ws : nullptr; pa.ws_stride = c->big_ws_stride;
         pa.min_conf = c->prm.min_confidence; pa.min_supp = c->prm.min_support;
-        for (uint32_t rep = 0; rep < ((c->dup & 4u) ? 2u : 1u); ++rep) { Timer t(c, KC_PRUNE, wk.stream); hipLaunchKernelGGL(k_prune_lcc, dim3(ns), dim3(64), pws ? 0 : vc_prune_lds_bytes(NCl, ECl), wk.stream, pa); }
+        { Timer t(c, KC_PRUNE, wk.stream); hipLaunchKernelGGL(k_prune_lcc, dim3(ns), dim3(64), pws ? 0 : vc_prune_lds_bytes(NCl, ECl), wk.stream, pa); }
         wk.cur ^= 1;
         {
             // before the first re-alignment round the host does not know how small the pruned graphs are: size the LDS image
@@ -989,9 +812,8 @@ struct Plan {
                 NCt = std::min(NC, (uint32_t)((bt->max_backbone * 5 / 4 + 127) & ~63u));
                 ECt = std::min(EC, (uint32_t)((bt->max_backbone * 2 + 127) & ~63u));
             }
-            bool tw = topo_lds_bytes(NCt, ECt, c->STK, c->MA) > kLdsCap;
-            if (c->topo_hbm && c->big_ws_stride >= topo_lds_bytes(NCl, ECl, c->STK, c->MA)) { tw = true; NCt = NCl; ECt = ECl; }
-            for (uint32_t rep = 0; rep < ((c->dup & 8u) ? 2u : 1u); ++rep) { Timer t(c, KC_TOPO, wk.stream);
+            const bool tw = topo_lds_bytes(NCt, ECt, c->STK, c->MA) > kLdsCap;
+            { Timer t(c, KC_TOPO, wk.stream);
               hipLaunchKernelGGL(k_topo, dim3(ns), dim3(64), tw ? 0 : topo_lds_bytes(NCt, ECt, c->STK, c->MA), wk.stream, bt->b, wk.gr[wk.cur], wk.dp, wk.w0, ns, NC, EC, c->STK, -1, 0, bt->ring_pruned, NCt, ECt,
                                  (tw || c->big_ws_topo) ? wk.d_big_ws : nullptr, c->big_ws_stride, tw ? 1 : 0); }
         }
@@ -1025,7 +847,7 @@ struct Plan {
             if (bt->band) HIPCHK(c, hipMemsetAsync(wk.d_redo_n, 0, 4, wk.stream));
             bool nwonly = true;                                // no partial-span layer among these sequences in any window of the batch?
             for (uint32_t k = std::max(k0, 1u); k < k0 + gsz; ++k) nwonly = nwonly && !(k < bt->h_layer_partial.size() && bt->h_layer_partial[k]);
-            ta.cpl_lo = fold_lo(c, bt);
+            ta.cpl_lo = fold_lo(bt);
             int rc = launch_fwd(c, bt, wk.stream, fa, ns * gsz, &wk, nwonly);
             if (rc) return rc;
             ta.group = gsz; ta.k0 = k0; ta.hstride = stride; ta.band_chain = 1;      // (mode 1 launches run the forward kernels with KEPT = false)
@@ -1078,8 +900,7 @@ struct Plan {
     int run_chunk(Work& wk, uint32_t w0, uint32_t ns) {
         int rc;
         begin(wk, w0, ns);
-        if (wk.layers && pipe_ok()) { if ((rc = build_pipe(wk))) return rc; }
-        else if ((rc = build_loop(wk))) return rc;
+        if ((rc = build_loop(wk))) return rc;
         if (!wk.layers) { wk.active = false; return VC_OK; }
         if (c->prm.mode == 1) return linear_tail(wk);
         for (uint32_t r = 0; r < c->prm.num_prune; ++r) {
@@ -1172,28 +993,13 @@ int vc_create(vc_ctx** out, const vc_params* p) {
     c->auto_streams = p->n_streams == 0;
     c->n_streams = p->n_streams ? std::min<uint32_t>(p->n_streams, kMaxStreams) : 4;
     c->streams_made = c->auto_streams ? kAutoStreamsMany : c->n_streams;
+    // the environment variables of this file, read here once (the list and what each does: include/vechat_hip.h)
     c->force_dfs = getenv("VC_RESOLVE_FORCE_DFS") != nullptr;
-    if (const char* d = getenv("VC_DUP")) c->dup = (uint32_t)std::atoi(d);
-    c->fold = getenv("VC_NO_FOLD") == nullptr;
-    if (const char* d = getenv("VC_INLINE_REDO")) c->inline_redo = std::atoi(d) != 0;
-#ifdef VC_EXPERIMENTS
-    if (const char* d = getenv("VC_BAND_RAW")) c->band_raw = std::atoi(d) != 0;
-#endif
-    if (const char* d = getenv("VC_TRACE_TL")) c->trace_tl = std::atoi(d) == 16 ? 16u : 8u;
-    if (const char* d = getenv("VC_TRACEB")) c->trace_block = std::atoi(d) != 0;
-    if (const char* d = getenv("VC_HOST_THREADS")) c->host_threads = std::atoi(d) != 0;      // development: 0 = one host thread walks the streams in lockstep
-    c->trace_wave = getenv("VC_TRACE_THREAD") == nullptr;      // development switch: the thread-per-alignment backtrack
+    if (const char* d = getenv("VC_HOST_THREADS")) c->host_threads = std::atoi(d) != 0;
     if (const char* d = getenv("VC_DT")) c->dt = std::atoi(d) != 0;
     if (const char* d = getenv("VC_AUTO_ARENA")) c->auto_arena = std::atoi(d) != 0;
-#ifdef VC_EXPERIMENTS
-    if (const char* d = getenv("VC_PIPE")) c->pipe = std::atoi(d) != 0;
-#endif
-    if (const char* d = getenv("VC_PIPE_F")) c->pipe_f = (uint32_t)std::atoi(d);
-    if (const char* d = getenv("VC_PIPE_T")) c->pipe_t = (uint32_t)std::atoi(d);
-    if (const char* d = getenv("VC_PIPE_PATIENCE")) c->pipe_patience_s = std::min(40u, std::max(1u, (uint32_t)std::atoi(d)));
-    c->n_cu = (uint32_t)prop.multiProcessorCount;
-    if (const char* d = getenv("VC_PRUNE_HBM")) c->prune_hbm = std::atoi(d);
-    if (const char* d = getenv("VC_TOPO_HBM")) c->topo_hbm = std::atoi(d) != 0;
+    if (const char* d = getenv("VC_SCRATCH_CAP_GB")) { const double g = std::atof(d); if (g >= 1.0) c->scratch_cap = (uint64_t)(g * 1073741824.0); }
+    c->time_submit = getenv("VC_TIME_SUBMIT") != nullptr;
     if (hipSetDevice(c->device) != hipSuccess) { delete c; return fail(nullptr, VC_ERR_HIP, "hipSetDevice failed"); }
     // The chunk streams must run CONCURRENTLY.  HIP multiplexes streams of one priority onto a small pool of
     // hardware queues (GPU_MAX_HW_QUEUES, default 4) round-robin, so two of ours can land on the same queue
@@ -1202,31 +1008,19 @@ int vc_create(vc_ctx** out, const vc_params* p) {
     // priority never share a hardware queue, so the chunk streams cycle through the priority levels.
     // (the streams themselves belong to the process: pooled_stream)
     for (uint32_t s = 0; s < c->streams_made; ++s) {
-        c->streams[s] = pooled_stream(c->device, s, false);
+        c->streams[s] = pooled_stream(c->device, s);
         if (!c->streams[s]) { delete c; return fail(nullptr, VC_ERR_HIP, "hipStreamCreate failed"); }
         c->works[s].stream = c->streams[s];
         if (hipHostMalloc((void**)&c->works[s].h_maxn, 64) != hipSuccess) { delete c; return fail(nullptr, VC_ERR_HIP, "hipHostMalloc failed"); }
-        Work& wk = c->works[s];
-        if (hipEventCreateWithFlags(&wk.ev_seed, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&wk.ev_t, hipEventDisableTiming) != hipSuccess) {
-            delete c; return fail(nullptr, VC_ERR_HIP, "event creation failed");
-        }
     }
     // the context's own stream for its copies, fills and small kernels: those must be able to run beside another context's chunks
-    {
-        int own_prio = 0;                                  // development: VC_OWN_PRIO = 0 / 1 / 2 picks the priority level of this stream
-        if (const char* d = getenv("VC_OWN_PRIO")) own_prio = stream_priority((uint32_t)std::atoi(d), 0u);
-        if (hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, own_prio) != hipSuccess) { delete c; return fail(nullptr, VC_ERR_HIP, "hipStreamCreate failed"); }
-    }
+    if (hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, 0) != hipSuccess) { delete c; return fail(nullptr, VC_ERR_HIP, "hipStreamCreate failed"); }
     c->stream = c->own_stream;
     // lookup tables from this host's libm, like the reference computes them (graph.cpp:169, window.cpp:235)
     uint32_t lw[256]; double ld[256];
     vc_weight_lut(lw);
     for (int ch = 0; ch < 256; ++ch) ld[ch] = 1 - pow(10, (33 - (int)(signed char)ch) / 10.0);
-    if (dalloc(c, c->allocs, &c->d_lut_w, 256) || dalloc(c, c->allocs, &c->d_lut_d, 256) || dalloc(c, c->allocs, &c->d_stat, VC_STAT_WORDS)
-#ifdef VC_EXPERIMENTS
-        || dalloc(c, c->allocs, &c->d_pipe_abort, 64) || dalloc(c, c->allocs, &c->d_pipe_prof, VC_PP_TOTAL)
-#endif
-        ) {
+    if (dalloc(c, c->allocs, &c->d_lut_w, 256) || dalloc(c, c->allocs, &c->d_lut_d, 256) || dalloc(c, c->allocs, &c->d_stat, VC_STAT_WORDS)) {
         g_create_error = c->err; vc_destroy(c); return VC_ERR_HIP;
     }
     (void)hipMemcpy(c->d_lut_w, lw, sizeof(lw), hipMemcpyHostToDevice);
@@ -1263,7 +1057,6 @@ void vc_destroy(vc_ctx* c) {
     for (int i = 0; i < 2; ++i) { if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]); if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]); }
     for (uint32_t s = 0; s < kMaxStreams; ++s) {
         if (c->works[s].h_maxn) (void)hipHostFree(c->works[s].h_maxn);
-        for (hipEvent_t e : {c->works[s].ev_seed, c->works[s].ev_t}) if (e) (void)hipEventDestroy(e);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -1278,23 +1071,7 @@ int vc_set_profile(vc_ctx* c, int profile) {
     return VC_OK;
 }
 
-int vc_has_experiments(void) {
-#ifdef VC_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
-}
-
-int vc_set_pipeline(vc_ctx* c, int on, uint32_t forward_waves, uint32_t backtrack_waves) {
-    if (!c) return VC_ERR_ARG;
-#ifndef VC_EXPERIMENTS
-    if (on) return fail(c, VC_ERR_ARG, "the persistent build pipeline is an experiment: this library was built without -DVC_EXPERIMENTS");
-#endif
-    drain(c);
-    c->pipe = on != 0; c->pipe_f = forward_waves; c->pipe_t = backtrack_waves;
-    return VC_OK;
-}
+int vc_has_experiments(void) { return 0; }
 
 int vc_reserve(vc_ctx* c, uint64_t bytes) {
     if (!c) return VC_ERR_ARG;
@@ -1425,7 +1202,7 @@ int vc_submit(vc_ctx* c, const vc_batch* hb) {
     VcBatchDev& b = bt->b;
     b = VcBatchDev{};
     b.n_windows = nw;
-    const bool tm_s = getenv("VC_TIME_SUBMIT") != nullptr;          // development: phases of a submit on stderr
+    const bool tm_s = c->time_submit;                                // (phases of a submit on stderr)
     auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double ts_0 = now_s();
     uint32_t* d_wso; uint64_t* d_so; uint32_t *d_sb, *d_se; uint8_t *d_hq, *d_ba, *d_qu, *d_wf;
@@ -1535,7 +1312,7 @@ int vc_submit(vc_ctx* c, const vc_batch* hb) {
     const uint32_t S = c->have_ws ? std::max(want_streams, c->n_streams) : want_streams;
     // default budget: 60 % of what is free, capped (default_budget) -- config C runs at 91 % of its 220-GiB rate with 64 GiB, 97.7 % with 96
     // (chunks of 4 096 windows) and at 86 % with 32 GiB (2 048), so holding more than that buys nothing (profiles/r3c_footprint.txt)
-    uint64_t budget = (c->prm.scratch_bytes ? c->prm.scratch_bytes : default_budget(free_b)) / S;
+    uint64_t budget = (c->prm.scratch_bytes ? c->prm.scratch_bytes : default_budget(c, free_b)) / S;
     const uint64_t budget_default = budget;
     if (!c->arena.empty()) {                             // the arena IS the budget: a segment per stream (less the padding between its pieces)
         const uint64_t per_seg = (S + c->arena.size() - 1) / c->arena.size();          // workspaces that share a segment
@@ -1552,8 +1329,8 @@ int vc_submit(vc_ctx* c, const vc_batch* hb) {
         !vc_int16_ok(c->prm.sw_match, c->prm.sw_mismatch, c->prm.sw_gap, NC, cpl, false)) maybe_wide = true;
     if (cpl >= 32 && bt->lean != 3u) maybe_wide = true;       // classes of 32+ columns per lane exist in the lean form only: other alphabets / scores take k_fwd_wide
     const uint32_t wcols = maybe_wide ? ((ws_max_len + 64 * VC_WIDE_CPL - 1) / (64 * VC_WIDE_CPL)) * (64 * VC_WIDE_CPL) : 0;
-    // whole rows, + a quarter for the band (byte-packed rows; raw int16 rows -- wide classes, unusual scores -- only with VC_BAND_RAW=1)
-    const uint64_t per_job = NC * rowd * ((bt->packed || c->band_raw) ? 5 : 4) + NC * 2 + 24 + 2 * VC_MAXTIE + 8 + (maybe_wide ? (uint64_t)NC * wcols * 4 + NC * 4ull : 0ull);
+    // whole rows, + a quarter for the band (byte-packed rows only)
+    const uint64_t per_job = NC * rowd * (bt->packed ? 5 : 4) + NC * 2 + 24 + 2 * VC_MAXTIE + 8 + (maybe_wide ? (uint64_t)NC * wcols * 4 + NC * 4ull : 0ull);
     // big alignments (3 kb reads: 58 MB of raw rows each; the int32 matrices of k_fwd_wide: 86 MB more): there the chunk size IS the
     // budget, and the 96-GiB cap would leave a few hundred alignments per stream -- take the 60 % whole
     if (!c->prm.scratch_bytes && c->arena.empty() && (per_slot_fixed + per_job) * 1024ull > budget) budget = std::max<uint64_t>(budget, (uint64_t)(free_b * 0.6) / S);
@@ -1576,7 +1353,7 @@ int vc_submit(vc_ctx* c, const vc_batch* hb) {
     const bool same = have_ws && S == c->n_streams && c->ws_packed == bt->packed && c->wcols == wcols && c->MA == MA && c->NC == NC && c->EC == EC && c->CW >= CW && c->ws_cpl == cpl && c->PC == PC &&
                       c->big_ws_stride == big && c->max_nseq == max_nseq;
     if (!same) {
-        const bool tm = getenv("VC_TIME_SUBMIT") != nullptr;          // development: where a submit that re-creates the workspaces spends its time
+        const bool tm = c->time_submit;                               // (where a submit that re-creates the workspaces spends its time)
         auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_0 = now();
         drain(c);                           // the other batch may be running on the workspaces that go
@@ -1606,10 +1383,10 @@ int vc_submit(vc_ctx* c, const vc_batch* hb) {
     }
     b.cons_cap = NC;
     const bool wide_cls = bt->cpl >= 32;                 // (launch_fwd_t instantiates the forward kernel with the same numbers)
-    bt->kept = (kKept && NC < 32768 && !getenv("VC_PLAIN_RING")) ? (uint32_t)(wide_cls ? kKeptWide : kKept) : 0u;
+    bt->kept = (kKept && NC < 32768) ? (uint32_t)(wide_cls ? kKeptWide : kKept) : 0u;
     bt->ring = (uint32_t)(wide_cls ? kRingWide : kRing); bt->ring_pruned = (uint32_t)(wide_cls ? kRingPrunedWide : kRingPruned);
-    // (round 6, VC_BAND_RAW=1: raw int16 rows banded too -- the widest classes and scores outside the byte form; measured slower, off)
-    bt->band = (bt->packed || c->band_raw) && bt->kept && c->trace_wave && !getenv("VC_NO_BAND");
+    // (round 6: raw int16 rows banded too -- the widest classes and scores outside the byte form -- was 6 % slower, profiles/r6_ab_raw_band.txt)
+    bt->band = bt->packed && bt->kept;
     if ((rc = salloc(c, bt, 12, &b.cons, (size_t)nw * b.cons_cap))) return rc;
     HIPCHK(c, hipMemsetAsync(b.status, 0, nw, c->stream));
     HIPCHK(c, hipMemsetAsync(b.cons_len, 0, nw * 4, c->stream));
@@ -1654,10 +1431,6 @@ int vc_run(vc_ctx* c) {
     { std::lock_guard<std::mutex> lk(c->qmu); alone = c->runq.empty(); }
     if (alone) {
         HIPCHK(c, hipMemsetAsync(c->d_stat, 0, 8 * VC_STAT_WORDS, c->stream));
-#ifdef VC_EXPERIMENTS
-        HIPCHK(c, hipMemsetAsync(c->d_pipe_abort, 0, 64, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_pipe_prof, 0, VC_PP_TOTAL * 8, c->stream));
-#endif
     }
     HIPCHK(c, hipMemsetAsync(b.status, 0, b.n_windows, c->stream));
     if (!bt->h_pre_status.empty()) HIPCHK(c, hipMemcpyAsync(b.status, bt->h_pre_status.data(), b.n_windows, hipMemcpyHostToDevice, c->stream));
@@ -1743,12 +1516,6 @@ int finish_run(vc_ctx* c, Batch* bt) {
     int rc = wait_batch(c, bt);
     if (rc) { bt->ran = false; return rc; }
     if (bt->run_rc != VC_OK) { bt->ran = false; return bt->run_rc; }       // the run failed: its own error text stands (vc_last_error)
-    if (c->pipe && c->d_pipe_abort) {
-        uint32_t ab = 0;
-        HIPCHK(c, hipMemcpyAsync(&ab, c->d_pipe_abort, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (ab) { bt->ran = false; bt->run_rc = VC_ERR_HIP; return fail(c, VC_ERR_HIP, "persistent build pipeline gave up waiting (site %u): the run has no result", ab); }
-    }
     return VC_OK;
 }
 // the batch vc_collect / vc_result_size speak of: the oldest run whose results nobody has taken; none such: the latest run
@@ -2006,54 +1773,6 @@ int vc_debug_fwd_lab(vc_ctx* c, uint32_t layer, uint32_t reps, uint32_t flags, f
     return VC_OK;
 }
 #endif
-
-// development: the persistent pipeline's counters and the per-window words its waves hand to each other, for the first `n` windows
-// of chunk stream 0: out[0..VC_PC_N) counters, then per window {layer, job_end, job_type, npairs}
-int vc_debug_pipe_state(vc_ctx* c, uint32_t* out, uint32_t n) {
-    if (!c || !out || !(c->cur && c->cur->have)) return VC_ERR_ARG;
-#ifndef VC_EXPERIMENTS
-    (void)n;
-    return fail(c, VC_ERR_ARG, "built without -DVC_EXPERIMENTS: no persistent pipeline");
-#else
-    HIPCHK(c, hipSetDevice(c->device));
-    sync_all(c);
-    const Work& wk = c->works[c->cur->first_stream];
-    std::vector<uint32_t> ctl((size_t)VC_PC_N * VC_PIPE_CTL_STRIDE);
-    HIPCHK(c, hipMemcpy(ctl.data(), wk.d_pipe_ctl, ctl.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 10; ++i) out[i] = i < VC_PC_N ? ctl[(size_t)i * VC_PIPE_CTL_STRIDE] : 0u;
-    HIPCHK(c, hipMemcpy(&out[9], c->d_pipe_abort, 4, hipMemcpyDeviceToHost));
-    n = std::min(n, c->cur->cw_run);
-    std::vector<uint32_t> a(n), b(n), d(n); std::vector<uint8_t> t(n);
-    HIPCHK(c, hipMemcpy(a.data(), wk.d_cur_layer, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(b.data(), wk.d_job_end, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(t.data(), wk.d_job_type, n, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(d.data(), wk.d_npairs, n * 4, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; ++i) {
-        out[10 + 4 * i] = a[i]; out[10 + 4 * i + 1] = b[i]; out[10 + 4 * i + 2] = t[i]; out[10 + 4 * i + 3] = d[i];
-        if (d[i] && d[i] <= c->PC) {                       // pairs with a sequence position, in place of job_type
-            std::vector<uint32_t> pr(d[i]);
-            HIPCHK(c, hipMemcpy(pr.data(), wk.d_pairs + (size_t)i * c->PC, (size_t)d[i] * 4, hipMemcpyDeviceToHost));
-            uint32_t nv = 0;
-            for (uint32_t x : pr) nv += (x & 0xFFFF) != 0;
-            out[10 + 4 * i + 2] = nv;
-        }
-    }
-    return VC_OK;
-#endif
-}
-
-// development: phase clocks of the persistent pipeline's waves over the last run (VC_PP_* order, ticks of 100 MHz / counts)
-int vc_debug_pipe_prof(vc_ctx* c, unsigned long long* out) {
-    if (!c || !out) return VC_ERR_ARG;
-#ifndef VC_EXPERIMENTS
-    return fail(c, VC_ERR_ARG, "built without -DVC_EXPERIMENTS: no persistent pipeline");
-#else
-    HIPCHK(c, hipSetDevice(c->device));
-    sync_all(c);
-    HIPCHK(c, hipMemcpy(out, c->d_pipe_prof, VC_PP_TOTAL * 8, hipMemcpyDeviceToHost));
-    return VC_OK;
-#endif
-}
 
 int vc_get_stats(vc_ctx* c, vc_stats* s) {
     if (!c || !s) return VC_ERR_ARG;

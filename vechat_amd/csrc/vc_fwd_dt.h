@@ -434,7 +434,7 @@ __device__ __forceinline__ uint32_t vc_fwd_dt(const VcFwdArgs& a, uint32_t* ring
 
 // CA <= CB: the two adjacent width classes of a batch share one launch; each alignment takes the narrowest body that holds its sequence
 template <int CA, int CB, int RING, bool KEPT>
-VC_KL __global__ __launch_bounds__(64) void k_fwd_dt(VcFwdArgs a) {
+__global__ __launch_bounds__(64) void k_fwd_dt(VcFwdArgs a) {
     __shared__ uint32_t ring_raw[RING * (CB / 2) * 64];
     VcJob jb;
     if (!vc_fwd_pick(a, jb)) return;

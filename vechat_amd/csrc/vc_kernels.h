@@ -9,8 +9,8 @@
 //   k_topo          wave / window          graph.cpp:301-371 TopologicalSort (exact DFS) + row records, after a prune
 //   k_fwd<CA,CB>    wave / alignment       sisd_alignment_engine.cpp:118-254 Initialize, :292-360 Linear (NW/SW)
 //   k_resolve       wave / tied alignment  sisd :353-355 "first sink in rank order" among equal end scores
-//   k_tracew        16 lanes / alignment   sisd_alignment_engine.cpp:362-459 (backtrack), speculative and cooperative
-//   k_trace         thread / alignment     the same backtrack, plain (cross-check, VC_TRACE_THREAD=1)
+//   k_tracew        8 lanes / alignment    sisd_alignment_engine.cpp:362-459 (backtrack), speculative and cooperative
+//   k_trace         thread / alignment     the same backtrack, plain: the int32 matrices of k_fwd_wide
 //   k_addaln        wave / window          graph.cpp:182-299 AddAlignment (+ :94-107 AddEdge) + order maintenance
 //   k_prune_lcc     wave / window          graph.cpp:811-982 PruneGraph, :984-1102 DfsUtil/LargestSubgraph
 //   k_addw          wave / window          graph.cpp:1104-1165 AddWeights (+ window.cpp:351-372 weights)
@@ -24,12 +24,6 @@
 #include "vechat_hip.h"
 
 #define VC_INT_MIN (-2147483647 - 1)
-// linkage of the kernels: external in vc_api.hip; `static` in a second translation unit that includes this header for a few templates only
-// (vc_fwdn.hip), so that the host stubs of the non-template kernels are not defined twice
-#ifndef VC_KL
-#define VC_KL
-#endif
-#define VC_RING_PRUNED_N 4     // rows of the plain ring on pruned graphs (vc_api.hip: VC_RING_PRUNED; vc_fwdn.hip instantiates k_fwdn with it)
 // The latency-bound single-lane kernels of one chunk run next to the throughput-bound k_fwd of another
 // chunk (separate streams).  The CU issues the oldest ready wave first, which starves them; raising the
 // wave priority lets their few instructions through at once and costs k_fwd almost nothing.
@@ -156,7 +150,7 @@ __device__ __forceinline__ uint4 vc_make_frec(uint32_t code, uint32_t fl, uint32
 // in rank order, window.cpp:225-236,283,292-296), so the ORDER of the additions is kept; what is parallel is
 // only the fetch: 64 lanes load 64 qualities and their table values at once, then every lane performs the
 // same 64 dependent additions on values broadcast with v_readlane.
-VC_KL __global__ __launch_bounds__(64) void k_avg(VcBatchDev b, uint32_t w0, uint32_t nw) {
+__global__ __launch_bounds__(64) void k_avg(VcBatchDev b, uint32_t w0, uint32_t nw) {
     VC_LATENCY_KERNEL_PRIO();
     const uint32_t t = blockIdx.x;
     if (t >= nw) return;
@@ -194,7 +188,7 @@ __device__ __forceinline__ void vc_rows_full(const VcBatchDev& b, const VcGraph&
 // ------------------------------------------------------------------------------------------------
 // k_init: backbone chain graph (AddAlignment with an empty alignment, graph.cpp:207-212)
 // ------------------------------------------------------------------------------------------------
-VC_KL __global__ __launch_bounds__(64) void k_init(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
+__global__ __launch_bounds__(64) void k_init(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
                                              uint32_t NC, uint32_t EC, uint32_t ring, uint32_t kept, uint32_t* cursor) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];          // kept != 0: vc_kept_lds_bytes(NC)
     uint32_t slot = blockIdx.x;
@@ -375,7 +369,7 @@ __device__ int vc_topo_dfs(const VcTopoLds& ls, uint32_t N, uint32_t STK, bool m
     return err;
 }
 
-VC_KL __global__ __launch_bounds__(64) void k_topo(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
+__global__ __launch_bounds__(64) void k_topo(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
                                              uint32_t NC, uint32_t EC, uint32_t STK, int next_layer, int only_masked, uint32_t ring,
                                              uint32_t NCl, uint32_t ECl, uint8_t* ws, uint32_t ws_stride, int ws_only) {
     // ws != nullptr: the graph image does not fit the 160 KB LDS; work from this workgroup's HBM workspace
@@ -984,7 +978,7 @@ __device__ __forceinline__ void vc_rows_sub_body(const VcBatchDev& b, const VcGr
     }
 }
 
-VC_KL __global__ __launch_bounds__(64) void k_rows_sub(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
+__global__ __launch_bounds__(64) void k_rows_sub(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
                                                  uint32_t NC, uint32_t EC, int next_layer, uint32_t ring, uint32_t* submask, uint32_t kept,
                                                  const uint32_t* cursor) {
     VC_LATENCY_KERNEL_PRIO();
@@ -1159,7 +1153,7 @@ __device__ void vc_resolve_one(uint8_t* smem, uint8_t* gws, uint32_t slot, const
 #ifndef VC_RESOLVE_OCC
 #define VC_RESOLVE_OCC __attribute__((amdgpu_waves_per_eu(7, 8)))
 #endif
-VC_KL __global__ __launch_bounds__(64) VC_RESOLVE_OCC void k_resolve(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
+__global__ __launch_bounds__(64) VC_RESOLVE_OCC void k_resolve(VcBatchDev b, VcGraph g, VcDp dp, uint32_t w0, uint32_t nslots,
                                                 uint32_t NC, uint32_t EC, uint32_t STK,
                                                 const uint16_t* tie_rows, const uint32_t* tie_cnt, const uint32_t* tie_over, uint32_t tie_over_stride, uint32_t* job_end,
                                                 const uint32_t* tie_list, const uint32_t* tie_n,
@@ -1373,8 +1367,7 @@ __device__ __forceinline__ int vc_dt_cell(int v, uint32_t row, int g) { return (
 //     max_p (H[p][j-1] + P[j]) = (max_p H[p][j-1]) + P[j],   max_p (H[p][j] + g) = (max_p H[p][j]) + g,
 // so each additional in-edge costs one packed max per register instead of a full relaxation, and the
 // order of the in-edges is irrelevant here (it matters only to the backtrack, which follows it).
-// The alignment a forward wave works on.  Lock-step launches derive it from the workgroup index (vc_fwd_pick); the waves of the
-// persistent build pipeline (vc_pipe.h) take it from their work queue.
+// The alignment a forward wave works on, derived from the workgroup index (vc_fwd_pick).
 struct VcJob {
     uint32_t job;       // index of the per-alignment buffers (stored matrix, column 0, end cell, ties)
     uint32_t slot;      // window of the chunk
@@ -1386,7 +1379,7 @@ struct VcJob {
 #define VC_FWD_DONE 1u
 #define VC_FWD_TIE  2u      // done, and the end cell is tied between sinks on a non-reference order: the resolver decides
 
-template <int CPL, int RING, bool NWT, bool PACKED, bool KEPT, bool PIPE = false>
+template <int CPL, int RING, bool NWT, bool PACKED, bool KEPT>
 __device__ __forceinline__ uint32_t vc_fwd_body(const VcFwdArgs& a, uint32_t* ring_raw, const VcJob& jb) {
     // KEPT: the LDS ring holds RING SLOTS for the rows a later row reads back (vc_frec_kept gave every such row its slot);
     // otherwise the last RING rows, slot = row % RING
@@ -1404,11 +1397,10 @@ __device__ __forceinline__ uint32_t vc_fwd_body(const VcFwdArgs& a, uint32_t* ri
     if (k >= ns) return VC_FWD_NONE;
     const uint64_t so = a.b.seq_off[s0 + k];
     const uint32_t len = (uint32_t)(a.b.seq_off[s0 + k + 1] - so);
-    // another width class handles this sequence.  (A folded launch -- the persistent pipeline always, a lock-step launch over more
-    // than two classes -- is built for the two widest classes of a batch and takes everything narrower in the lower of them: a lane
+    // another width class handles this sequence.  (A folded launch -- one over more than two classes -- is built for the two widest classes of a batch and takes everything narrower in the lower of them: a lane
     // simply owns more columns than the sequence needs, the matrix is the same -- its backtrack reads the rows in the same class,
     // VcTraceArgs::cpl_lo.)
-    if ((PIPE || a.fold) ? len > 64u * CPL : vc_cpl_for(len) != (uint32_t)CPL) return VC_FWD_NONE;
+    if (a.fold ? len > 64u * CPL : vc_cpl_for(len) != (uint32_t)CPL) return VC_FWD_NONE;
     const uint32_t L = (uint32_t)(a.b.seq_off[s0 + 1] - a.b.seq_off[s0]);
     // NW or SW is fixed per instantiation (the caller looked at the layer, window.cpp:336-349): the row loop
     // then carries no alignment-type branches
@@ -1482,14 +1474,7 @@ __device__ __forceinline__ uint32_t vc_fwd_body(const VcFwdArgs& a, uint32_t* ri
     uint32_t* const hrow0 = a.hmat + (uint64_t)job * a.hstride;
     constexpr bool packed = PACKED;           // the stored row form is a property of the launch (host: both score sets fit the byte bound)
     // banded store: global alignments only (a local alignment may end and start anywhere), byte-packed rows only
-    // (round 6, -DVC_EXPERIMENTS builds with VC_BAND_RAW=1: raw int16 rows too -- the widest classes, and scores whose rows do not fit the byte
-    // form: [row][band lane][ND dwords]; bit-identical and 6 % slower on 3 kb windows, profiles/r6_ab_raw_band.txt)
-#ifdef VC_EXPERIMENTS
-    constexpr bool RAW_BAND = true;
-#else
-    constexpr bool RAW_BAND = false;
-#endif
-    const bool band = NWT && (PACKED || RAW_BAND) && a.band && !redo;
+    const bool band = NWT && PACKED && a.band && !redo;
     const char* const brow0 = reinterpret_cast<const char*>(a.bmat + (uint64_t)job * vc_band_job_dwords(a.hstride));
     __amdgpu_buffer_rsrc_t brs;                                // the job's band rows behind a buffer descriptor (wave-uniform by construction)
     {
@@ -1863,7 +1848,7 @@ __device__ __forceinline__ uint32_t vc_fwd_body(const VcFwdArgs& a, uint32_t* ri
       __threadfence_block();
     }
     if (lane == 0 && far_reads && !redo) atomicAdd(vc_stat_slot(a.stat) + 3, (unsigned long long)far_reads);
-    if (!PIPE) {
+    {
         const unsigned long long dc = clock64() - clk_c0, dw = wall_clock64() - clk_w0;
         if (lane == 0) { unsigned long long* ck = vc_clk_slot(a.stat); atomicAdd(ck, dc); atomicAdd(ck + 1, dw); }
     }
@@ -1875,8 +1860,8 @@ __device__ __forceinline__ uint32_t vc_fwd_body(const VcFwdArgs& a, uint32_t* ri
     if (nw) {
         end = (best_row << 16) | len;
         if (ntie > 1 && (a.dp.flags[slot] & 2u)) {          // tie on a non-reference order: k_resolve decides
-            if (lane == 0) { a.tie_cnt[job] = ntie; if (!PIPE) a.tie_list[atomicAdd(a.tie_n, 1u)] = slot; }
-            outcome = VC_FWD_TIE;                           // (the persistent pipeline hands the window to its resolver wave instead of the list)
+            if (lane == 0) { a.tie_cnt[job] = ntie; a.tie_list[atomicAdd(a.tie_n, 1u)] = slot; }
+            outcome = VC_FWD_TIE;
         }
     } else {
         const int gmax = wave_max_i32(best);
@@ -1955,7 +1940,7 @@ __device__ __forceinline__ void vc_fwd_any(const VcFwdArgs& a, uint32_t* ring_ra
 #define VC_FWD_OCC            // development: e.g. -DVC_FWD_OCC='__attribute__((amdgpu_waves_per_eu(4,4)))' caps the forward kernel's waves per SIMD
 #endif
 template <int CA, int CB, int RING, bool PACKED, bool KEPT, bool NWONLY>
-VC_KL __global__ __launch_bounds__(64) VC_FWD_OCC void k_fwd(VcFwdArgs a) {
+__global__ __launch_bounds__(64) VC_FWD_OCC void k_fwd(VcFwdArgs a) {
     __shared__ uint32_t ring_raw[RING * (CB / 2) * 64];
 #ifdef VC_FWD_VGPR_PAD
     asm volatile("; keep the register allocation at 104: four forward waves per SIMD leave LDS and registers to the other kernels" ::: "v103");
@@ -1987,7 +1972,7 @@ VC_KL __global__ __launch_bounds__(64) VC_FWD_OCC void k_fwd(VcFwdArgs a) {
 #define VC_WIDE_CPL 8
 #define VC_WIDE_RING 8          // rows of the current tile kept in LDS (16 KB per wave; this kernel never fills a CU)
 #define VC_WIDE_NEG (-(1 << 29))
-VC_KL __global__ __launch_bounds__(64) void k_fwd_wide(VcFwdArgs a, int* wmat, uint64_t wstride, uint32_t wcols, int* c0w) {
+__global__ __launch_bounds__(64) void k_fwd_wide(VcFwdArgs a, int* wmat, uint64_t wstride, uint32_t wcols, int* c0w) {
     // the last VC_WIDE_RING rows of the tile in LDS (slot = row % VC_WIDE_RING): the predecessors that are not the row directly
     // above are nearly always among them, and a read back from the stored matrix costs a fence and a memory round trip
     __shared__ int wring[VC_WIDE_RING][VC_WIDE_CPL][64];
@@ -2237,7 +2222,7 @@ struct VcTraceArgs {
 // stream (wave-per-alignment and LDS-tiled variants were measured slower end to end: they take issue
 // slots and CUs away from k_fwd).  Loads stop at the first matching move, like the reference's scan.
 #define VC_TRACE_LANES 8     // alignments per wave: lanes walk in lockstep, so fewer per wave = less waiting on the slowest
-VC_KL __global__ void k_trace(VcTraceArgs a) {
+__global__ void k_trace(VcTraceArgs a) {
     VC_LATENCY_KERNEL_PRIO();
     if (threadIdx.x >= VC_TRACE_LANES) return;
     const uint32_t job = blockIdx.x * VC_TRACE_LANES + threadIdx.x;
@@ -2342,7 +2327,7 @@ VC_KL __global__ void k_trace(VcTraceArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_tracew: the same backtrack, cooperative: VC_TG alignments per wave, VC_TL = 16 lanes each.  The walk
+// k_tracew: the same backtrack, cooperative: VC_TG = 8 alignments per wave, VC_TL = 8 lanes each.  The walk
 // is a chain of dependent HBM round trips, and ~85 % of its moves are "diagonal through the first
 // in-edge".  Each round therefore
 //   A. follows first in-edges for up to VC_SPECW positions using a per-graph table in LDS (no HBM; 4-bit entries, see
@@ -2351,19 +2336,21 @@ VC_KL __global__ void k_trace(VcTraceArgs a) {
 //      one round trip for all of them,
 //   C. accepts the longest prefix whose cells confirm the move (exactly the reference's first test at
 //      each of those cells, so nothing is skipped), and
-//   D. takes one fully general step at the first position that did not confirm: lanes 0..6 of the group
-//      test the diagonal through in-edge p, lanes 8..14 the vertical one, lane 15 the horizontal move,
-//      all in one round trip; ballots pick the first match in the reference's order (sisd :392-448).
-// Four alignments share every instruction of the round.  Measured with the cycle counter: B's loads (HBM misses, one
+//   D. takes one fully general step at the first position that did not confirm: lanes 0..2 of the group
+//      test the diagonal through in-edge p, lanes 4..6 the vertical one, lane 7 the horizontal move,
+//      all in one round trip (in-degrees beyond three take another pass); ballots pick the first match in
+//      the reference's order (sisd :392-448).
+// Eight alignments share every instruction of the round.  Measured with the cycle counter: B's loads (HBM misses, one
 // 128-B line per cell) are ~75 % of a round, D's mostly hit the lines B brought in (~7 %).  A step taken locally for
 // single-in-edge rows (vertical / horizontal cells fetched in B) was tried and is slower: a wave still runs D when any of
-// its four groups needs it, and the extra scattered loads lengthen B.
+// its groups needs it, and the extra scattered loads lengthen B.  (Round 4 measured groups of sixteen lanes, four alignments
+// per wave, seven in-edges per pass: slower, profiles/r4_trace_tl_ab.txt.)
 // ------------------------------------------------------------------------------------------------
-#define VC_TG 4
+#define VC_TG 8
 #ifndef VC_SPECW
 #define VC_SPECW 8         // positions speculated per round: 6..10 measured equal and 5 % better than 16 (fewer lines fetched for moves that get rejected)
 #endif
-#define VC_TL 16
+#define VC_TL 8
 // first-in-edge table of k_tracew: one 4-bit entry per row (distance to the row of the first in-edge; 0: do not speculate --
 // also for distances beyond 15, which the general step then takes).  Half a byte instead of a byte per row: what the job is
 // short of is LDS x time (k_fwd alone fills the LDS of every CU; a backtrack wave that waits on memory with 9 KB of tables
@@ -2374,26 +2361,19 @@ __host__ __device__ inline uint32_t vc_tracew_tab_len(uint32_t max_rows) { retur
 // instead of a table of the graph's height (1.1 KB at 2 240 rows; 9 KB per wave of eight alignments, which is what kept a second
 // backtrack wave off a CU whose LDS five forward waves per SIMD fill to 10 KB): the walk only ever looks at the rows just below it.
 #define VC_TW_WIN 256u       // rows of the sliding window (four blocks of 64; a power of two)
-__host__ __device__ inline uint32_t vc_tracew_lds_bytes(uint32_t max_rows, bool shared_table, uint32_t tg = VC_TG) { return shared_table ? vc_tracew_tab_len(max_rows) / 2u : tg * (VC_TW_WIN / 2u); }
+__host__ __device__ inline uint32_t vc_tracew_lds_bytes(uint32_t max_rows, bool shared_table) { return shared_table ? vc_tracew_tab_len(max_rows) / 2u : VC_TG * (VC_TW_WIN / 2u); }
 __device__ __forceinline__ int vc_row_shr1(int v, int first) {          // value of the lane to the left inside a 16-lane row
     return __builtin_amdgcn_update_dpp(first, v, 0x111, 0xF, 0xF, false);
 }
 
-// The walk of the VC_TG alignments of one wave.  Group g (lanes 16 g .. 16 g + 15) walks alignment `job` of window `slot`,
-// sequence k, pair list pj; `redo`: its matrix was stored whole (no band).  Lock-step launches take these from the workgroup
-// index (k_tracew), the persistent build pipeline (vc_pipe.h) from its work queue -- there the groups of a wave hold alignments
-// of different windows AND different layers.  Returns (per lane of the group) whether the alignment left the band; PIPE: the
-// caller puts it on its own redo queue instead of the launch's redo list.
-template <bool PIPE, int TL = VC_TL>
+// The walk of the VC_TG alignments of one wave.  Group g (lanes 8 g .. 8 g + 7) walks alignment `job` of window `slot`,
+// sequence k, pair list pj; `redo`: its matrix was stored whole (no band).  k_tracew takes these from the workgroup index.
+// Returns (per lane of the group) whether the alignment left the band.
 __device__ __forceinline__ bool vc_tracew_body(const VcTraceArgs& a, uint8_t* smem, uint32_t job, const uint32_t slot, const uint32_t k,
                                                const uint64_t pj, bool valid, const bool redo) {
-    // TL lanes per alignment, TG = 64 / TL alignments per wave.  16 x 4: the general step looks at seven in-edges x {diagonal,
-    // vertical} + the horizontal move in one round trip.  8 x 8: three in-edges x {diagonal, vertical} + horizontal per round trip
-    // (in-degrees beyond three take another pass), the eight speculated positions of a round fill the group exactly, and a
-    // wave-instruction serves twice the alignments -- what the lock-step launches use.
-    static_assert(TL == 16 || TL == 8, "group width");
-    constexpr int TG = 64 / TL;
-    constexpr uint32_t ND_ = TL == 16 ? 7u : 3u;             // in-edges per pass of the general step; vertical candidates sit ND_ + 1 lanes up
+    // TL lanes per alignment, TG alignments per wave: the eight speculated positions of a round fill the group exactly
+    constexpr int TL = VC_TL, TG = VC_TG;
+    constexpr uint32_t ND_ = 3u;                              // in-edges per pass of the general step; vertical candidates sit ND_ + 1 lanes up
     const int lane = vc_lane();
     const uint32_t grp = (uint32_t)lane / TL, gl = (uint32_t)lane % TL, gbase = grp * TL;
     // first in-edge distance of row r (0: do not speculate).  In the re-alignment rounds the alignments of a
@@ -2464,8 +2444,8 @@ __device__ __forceinline__ bool vc_tracew_body(const VcTraceArgs& a, uint8_t* sm
     auto gmask = [&](unsigned long long mm) __attribute__((always_inline)) -> uint32_t { return (uint32_t)(mm >> gbase) & ((1u << TL) - 1u); };
     // value of the lane to the left inside the group; the group's first lane takes `first`
     auto shr1 = [&](int v, int first) __attribute__((always_inline)) -> int {
-        const int x = vc_row_shr1(v, first);                  // (rows of 16 lanes: right for TL == 16, and for every lane but the first of an upper half-row)
-        return (TL == 8 && gl == 0) ? first : x;
+        const int x = vc_row_shr1(v, first);                  // (rows of 16 lanes: right for every lane but the first of an upper half-row)
+        return gl == 0 ? first : x;
     };
 
     bool walking = valid && end != 0;
@@ -2679,13 +2659,13 @@ __device__ __forceinline__ bool vc_tracew_body(const VcTraceArgs& a, uint8_t* sm
         }
     }
     if (valid && gl == 0) {
-        if (gredo) { gnout = 0; if (!PIPE) a.redo_out[atomicAdd(a.redo_out_n, 1u)] = job; }
+        if (gredo) { gnout = 0; a.redo_out[atomicAdd(a.redo_out_n, 1u)] = job; }
         else if (gbroken) { vc_fail(a.b, w, VC_WIN_INVALID, 17, gi); gnout = 0; }
         else if (govf) { vc_fail(a.b, w, VC_WIN_OVERFLOW, 5, gnout); gnout = 0; }
         a.npairs[pj] = gnout;
         // the window stays at this layer when the walk left the band (k_addaln passes it over, the next forward pass stores its rows
         // whole); a walk over whole rows cannot leave anything: the flag goes
-        if (!PIPE && a.cursor) a.cursor[slot] = k | (gredo ? 0x80000000u : 0u);
+        if (a.cursor) a.cursor[slot] = k | (gredo ? 0x80000000u : 0u);
     }
     {   // statistics: summed over the wave first, then one of VC_STAT_SLOTS counter sets (a single set serialises in the L2)
         uint32_t s0 = (valid && gl == 0) ? gnout : 0u, s1 = (valid && gl == 0) ? nspec_ok : 0u, s2 = (valid && gl == 0) ? nrounds : 0u;
@@ -2700,11 +2680,10 @@ __device__ __forceinline__ bool vc_tracew_body(const VcTraceArgs& a, uint8_t* sm
 }
 
 // (112 VGPRs: what is left on a SIMD beside five forward waves of 80)
-template <int TL>
-VC_KL __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(112))) void k_tracew(VcTraceArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(112))) void k_tracew(VcTraceArgs a) {
     VC_LATENCY_KERNEL_PRIO();
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    constexpr int TG = 64 / TL;
+    constexpr int TL = VC_TL, TG = VC_TG;
     const uint32_t grp = (uint32_t)vc_lane() / TL;
     const uint32_t njobs = a.nslots * a.group;
     const bool redo = a.redo_list != nullptr;
@@ -2725,12 +2704,8 @@ VC_KL __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(112))) voi
         whole = redo || (cv >> 31) != 0;
     }
     const uint64_t pj = a.cursor ? (uint64_t)slot : (uint64_t)slot * a.pair_group + (k - a.pair_k0);
-    (void)vc_tracew_body<false, TL>(a, smem, job, slot, k, pj, valid, whole);
+    (void)vc_tracew_body(a, smem, job, slot, k, pj, valid, whole);
 }
-
-#ifdef VC_EXPERIMENTS
-#include "vc_traceb.h"     // k_traceb: the backtrack walked out of LDS -- measured slower than k_tracew, kept as an experiment
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // k_addaln: Graph::AddAlignment (graph.cpp:182-299) for the layer just aligned, wave-parallel.
@@ -2758,8 +2733,7 @@ struct VcAddArgs {
 };
 
 // AddAlignment of sequence `layer` of window `slot` (+ the row records of the next layer when it is full-span).  `scr`: which of the
-// per-wave note blocks in VcAddArgs::scratch this wave uses (lock-step launches: the workgroup index; persistent pipeline: the
-// index of the resident wave).  smem: 2 * (PC + longest sequence) bytes, and vc_kept_lds_bytes(NC) for the row records.
+// per-wave note blocks in VcAddArgs::scratch this wave uses (the workgroup index).  smem: 2 * (PC + longest sequence) bytes, and vc_kept_lds_bytes(NC) for the row records.
 #ifdef VC_ADD_PROF          // development (tools/build_variant.sh addprof -DVC_ADD_PROF): shader-clock ticks of k_addaln's phases, summed over waves
 __device__ unsigned long long vc_add_prof[8];
 #define VC_ADD_STAMP(i) do { const long long n_ = clock64(); if (vc_lane() == 0) atomicAdd(&vc_add_prof[i], (unsigned long long)(n_ - t_prof)); t_prof = n_; } while (0)
@@ -3112,7 +3086,7 @@ __device__ __forceinline__ bool vc_addaln_body(const VcAddArgs& a, uint8_t* smem
     return true;
 }
 
-VC_KL __global__ __launch_bounds__(64) void k_addaln(VcAddArgs a) {
+__global__ __launch_bounds__(64) void k_addaln(VcAddArgs a) {
     VC_LATENCY_KERNEL_PRIO();
     // every reader of the layer's counters (k_resolve, the redo pass) is an earlier kernel of this stream; a memset per counter
     // per layer was 2 000 tiny launches per step, each waiting ~100 us for a slot beside k_fwd
@@ -3147,7 +3121,7 @@ __host__ __device__ inline uint32_t vc_prune_lds_bytes(uint32_t NC, uint32_t EC)
     return ((2 * (NC + 1) + 15) & ~15u) + 4 * EC + 2 * NC + 2 * NC + ((EC + 15) & ~15u) + 8 * NC + 64;
 }
 
-VC_KL __global__ __launch_bounds__(64) void k_prune_lcc(VcPruneArgs a) {
+__global__ __launch_bounds__(64) void k_prune_lcc(VcPruneArgs a) {
     VC_LATENCY_KERNEL_PRIO();
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t slot = blockIdx.x;
@@ -3334,7 +3308,7 @@ struct VcAddwArgs {
     const uint32_t* pairs; const uint32_t* npairs; uint32_t PC; uint32_t pair_group;
 };
 
-VC_KL __global__ __launch_bounds__(64) void k_addw(VcAddwArgs a) {
+__global__ __launch_bounds__(64) void k_addw(VcAddwArgs a) {
     VC_LATENCY_KERNEL_PRIO();
     const uint32_t slot = blockIdx.x;
     if (slot >= a.nslots) return;
@@ -3382,7 +3356,7 @@ struct VcFinishArgs {
     const uint32_t* pairs; const uint32_t* npairs; uint32_t PC;
 };
 
-VC_KL __global__ __launch_bounds__(64) void k_finish(VcFinishArgs a) {
+__global__ __launch_bounds__(64) void k_finish(VcFinishArgs a) {
     VC_LATENCY_KERNEL_PRIO();
     const uint32_t slot = blockIdx.x;
     if (slot >= a.nslots) return;
@@ -3430,7 +3404,7 @@ struct VcConsArgs {
 
 __host__ __device__ inline uint32_t vc_cons_lds_bytes(uint32_t NC, uint32_t EC) { return 12 * NC + 12 * EC + 8 * NC + 128; }
 
-VC_KL __global__ __launch_bounds__(64) void k_consensus(VcConsArgs a) {
+__global__ __launch_bounds__(64) void k_consensus(VcConsArgs a) {
     VC_LATENCY_KERNEL_PRIO();
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t slot = blockIdx.x;
@@ -3540,7 +3514,7 @@ VC_KL __global__ __launch_bounds__(64) void k_consensus(VcConsArgs a) {
 }
 
 // which byte values occur in the batch (256-bit mask): sizes the aligned lists (VcGraph::ma)
-VC_KL __global__ void k_byte_presence(const uint8_t* bases, uint64_t n, uint32_t* mask) {
+__global__ void k_byte_presence(const uint8_t* bases, uint64_t n, uint32_t* mask) {
     __shared__ uint32_t s_m[8];
     if (threadIdx.x < 8) s_m[threadIdx.x] = 0;
     __syncthreads();
@@ -3564,14 +3538,14 @@ VC_KL __global__ void k_byte_presence(const uint8_t* bases, uint64_t n, uint32_t
     if (threadIdx.x < 8 && s_m[threadIdx.x]) atomicOr(&mask[threadIdx.x], s_m[threadIdx.x]);
 }
 
-VC_KL __global__ void k_max_u32(const uint32_t* v, uint32_t n, uint32_t* out) {
+__global__ void k_max_u32(const uint32_t* v, uint32_t n, uint32_t* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) atomicMax(out, v[i]);
 }
 
 // build phase with a layer cursor per window: how many layers the slowest window of the chunk still has to go (windows that had
 // to repeat a layer with whole rows are behind the launch count)
-VC_KL __global__ void k_lag(VcBatchDev b, const uint32_t* cursor, uint32_t w0, uint32_t nslots, uint32_t* out) {
+__global__ void k_lag(VcBatchDev b, const uint32_t* cursor, uint32_t w0, uint32_t nslots, uint32_t* out) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t lag = 0;
     if (slot < nslots) {
@@ -3583,7 +3557,7 @@ VC_KL __global__ void k_lag(VcBatchDev b, const uint32_t* cursor, uint32_t w0, u
 }
 
 // compacts the per-window consensus slots into one contiguous buffer (offsets from an exclusive scan)
-VC_KL __global__ void k_gather_cons(VcBatchDev b, const uint64_t* off, uint8_t* out, uint64_t cap) {
+__global__ void k_gather_cons(VcBatchDev b, const uint64_t* off, uint8_t* out, uint64_t cap) {
     const uint32_t w = blockIdx.x;
     if (w >= b.n_windows) return;
     const uint64_t o = off[w];

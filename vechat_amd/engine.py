@@ -25,10 +25,12 @@ class HipContext:
     (include/vechat_hip.h, "Pipelining inside one context")."""
 
     def __init__(self, params=None, pipeline=None, reserve=None, **kw):
-        """pipeline: None = the library's default (lock-step, or what VC_PIPE says); True / False = the persistent build
-        pipeline on / off (vc_set_pipeline); a (forward_waves, backtrack_waves) pair also sizes its two kernels.
+        """pipeline: None or False -- the lock-step build loop, the only plan (the persistent build pipeline was measured slower
+        and removed); anything else raises ValueError.
         reserve: None = workspaces are allocated under the first batch; a byte count (0 = the default budget) = allocated now,
         in one piece, and laid out per batch without further allocations (vc_reserve)."""
+        if pipeline not in (None, False):
+            raise ValueError(f"pipeline={pipeline!r}: the lock-step build loop is the only plan")
         self.lib = capi.load_hip()
         self.params = params or capi.default_params(**kw)
         h = C.c_void_p()
@@ -38,9 +40,6 @@ class HipContext:
         self.h = h
         self._batch = None
         self.large_windows = 0                  # windows this context sent through the large-graph path (vc_large_run)
-        if pipeline is not None:
-            fw, bw = pipeline if isinstance(pipeline, tuple) else (0, 0)
-            self._chk(self.lib.vc_set_pipeline(self.h, 1 if pipeline else 0, fw, bw), "vc_set_pipeline")
         if reserve is not None:
             self._chk(self.lib.vc_reserve(self.h, int(reserve)), "vc_reserve")
 
