@@ -38,7 +38,7 @@
  *   VC_IO_THREADS=n        threads of the file readers and of the window builder (default: the host's cores, bounded)
  *   VC_IO_TIMING           set: phase times of the file readers on stderr (tools/gpu_files_host.sh)
  *   VC_HOSTBUF=0|1|2       host buffers: malloc / mmap + huge pages (default) / mmap; read once per process (tools/gpu_files_host.sh)
- * Read on every vc_large_run call (vc_large.hip, whose header describes them; tests/test_large_schedule.py):
+ * Read on every vc_large_run and vc_poa_run call (vc_large.hip, whose header describes them; tests/test_large_schedule.py):
  *   VC_LARGE_CAPS, VC_LARGE_ARENA_MB, VC_LARGE_MAT_MB, VC_LARGE_LOG
  */
 #ifndef VECHAT_HIP_H_
@@ -354,8 +354,37 @@ void        vc_align_release(void);
  * ------------------------------------------------------------------------------------------------ */
 int         vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r);
 const char* vc_large_last_error(void);
-/* the large path keeps its window tables and matrix buffer between calls; this gives them back */
+/* the large path keeps its window tables and matrix buffer between calls; this gives them back (vc_poa_run's too: they share them) */
 void        vc_large_release(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * Consensus of read groups (POA groups).  Stands in for spoa's public flow, the general engine the reference vendors beneath its
+ * windows (vendor/spoa; the flow of vendor/spoa/test/spoa_test.cpp:38-52 and of spoa's command line, src/main.cpp:270-323 with
+ * -r 0), once per group of a batch:
+ *     auto engine = spoa::AlignmentEngine::Create(algorithm, match, mismatch, gap);    alignment_engine.hpp:16-20, .cpp:15-70
+ *     for every sequence, in the order given:
+ *         graph.AddAlignment(engine->Align(sequence, graph), sequence[, quality]);      graph.cpp:132-300
+ *     graph.GenerateConsensus();                                                         graph.cpp:450-459
+ * A group is a window of vc_batch: win_seq_off delimits the groups, and a group may hold no sequence (empty consensus).  A
+ * sequence with seq_has_qual takes the quality overload (weights as vc_weight_lut, the vendored graph.cpp:160-171), the others
+ * weight 1; an empty sequence adds nothing (graph.cpp:187-190).  seq_begin, seq_end and win_fasta may be NULL and are ignored,
+ * and so may quals when no sequence has a quality: no window rule applies (rank order, spans, subgraphs, "< 3 sequences",
+ * prune, trim, window type).  Linear gaps only (spoa's kLinear: e = q = c = g).
+ * Synchronous, on the large-graph path's kernels (schedule 2 in vc_large.hip) and its buffer cache: fills r like vc_large_run
+ * (cons_cap >= the batch's bases is always enough).  Status per group: VC_WIN_OK; VC_WIN_INVALID where the reference throws (the
+ * group is left out, the others are computed); VC_WIN_OVERFLOW for a group the device memory cannot hold at all.
+ * Envelope: sequences shorter than 65 535 bases; scores in -128..127 (spoa takes them as int8_t); otherwise the device memory.
+ * Arguments are checked before the device is touched -- NULL pointers, algorithm outside 0..2, gap > 0 (alignment_engine.cpp:46-49),
+ * a score outside -128..127, offsets that do not start at 0 or decrease, a sequence of 65 535 bases or more: VC_ERR_ARG -- and
+ * only then the device: VC_ERR_NO_DEVICE without a gfx950 device.  vc_poa_last_error has the text of the last failure.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct vc_poa_params {
+    int32_t device;
+    int32_t algorithm;              /* 0 local (kSW), 1 global (kNW), 2 semi-global (kOV): spoa::AlignmentType   */
+    int32_t match, mismatch, gap;   /* linear gaps (kLinear); gap <= 0 as spoa requires (alignment_engine.cpp:46-49) */
+} vc_poa_params;
+int         vc_poa_run(const vc_poa_params* p, const vc_batch* b, vc_result* r);
+const char* vc_poa_last_error(void);
 
 #ifdef __cplusplus
 }

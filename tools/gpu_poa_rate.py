@@ -1,0 +1,166 @@
+"""POA-group rate on one MI355X (vc_poa_run, vechat_amd/poa.py), the shape nobody had measured: 4 096 groups of 32 x 1 kb.  Groups come
+from vc_synth windows with frac_partial=0 -- the backbone and its 31 layers become one group, in stored order, with their qualities.
+
+For each algorithm (local, global, semi-global) one warm-up call -- on all groups for the first, so that the buffer cache has grown
+to the batch, on 64 for the others -- then one timed call on all of them (host clock around
+the synchronous call), reported as groups/s and GCUPS with cells = sum over alignments of graph rows x sequence length (the
+large path's VC_LARGE_LOG "done" line).  Then, in a run of its own per algorithm, the same call under
+`rocprofv3 --kernel-trace --stats` for the time shares of the k_lg_* kernels.  Last, the reference's spoa (oracle/_ref
+libvcref_sse41.so, vcref_spoa_consensus) on a sample of the same groups on 16 host threads (ctypes releases the GIL), its consensus
+compared with the device's.
+
+  python tools/gpu_poa_rate.py [--groups 4096] [--len 1000] [--depth 32] [--cpu-sample 256] [--out profiles/poa_rate.txt]
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import time
+from collections import defaultdict
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+from vechat_amd import capi, large, poa  # noqa: E402
+
+NAMES = {0: "local (kSW)", 1: "global (kNW)", 2: "semi-global (kOV)"}
+
+
+def synth_groups(a):
+    cfg = capi.synth_cfg(seed=4100, backbone_len=a.len, n_layers=a.depth - 1, frac_partial=0.0)
+    return capi.synth_batch(cfg, 0, a.groups)
+
+
+def timed(batch, alg, warm):
+    """-> (seconds, consensus, statuses, alignments, cells) of one vc_poa_run on the batch, VC_LARGE_LOG read from stderr.
+    warm: "full" -- one untimed call on the whole batch first, so that the large path's buffer cache has grown to the batch's size
+    (the first call of a process allocates it); "small" -- 64 groups (code objects loaded)."""
+    p = capi.VcPoaParams(device=0, algorithm=alg, match=5, mismatch=-4, gap=-8)
+    if warm:
+        poa.run_batch(batch if warm == "full" else batch.slice(0, min(64, batch.n_windows)), p)
+    import tempfile
+    with tempfile.TemporaryFile() as log:          # the library's stderr lines, into a file (a pipe could fill and block it)
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            cons, status = poa.run_batch(batch, p)
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read()
+    done = [l for l in err.decode().splitlines() if l.startswith("vc_large: done")][-1]
+    kv = dict(t.split("=") for t in done.split()[2:])
+    return dt, cons, status, int(kv["alignments"]), int(kv["cells"])
+
+
+def kernel_shares(trace_dir):
+    """{kernel: ms} from a rocprofv3 kernel trace"""
+    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
+    ms = defaultdict(float)
+    for f in files:
+        for row in csv.DictReader(open(f)):
+            k = row["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0].strip()
+            k = k.split("::")[-1]
+            ms[k] += (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e6
+    return dict(ms)
+
+
+def child(a):
+    """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    batch = synth_groups(a)
+    dt, _, status, n_al, cells = timed(batch, a.child, "small")
+    print(json.dumps(dict(seconds=dt, alignments=n_al, cells=cells, ok=int((status == 0).sum()))))
+
+
+def cpu_reference(batch, idx, alg, threads, kind="sse41"):
+    import make_poa
+    import oracle_api as oa
+    lib = oa.load_ref(kind)
+
+    def one(w):
+        seqs, quals, _, _ = batch.window(w)
+        return make_poa.ref_consensus(lib, list(zip(seqs, quals)), alg, 5, -4, -8)
+    t0 = time.perf_counter()
+    with ThreadPoolExecutor(threads) as ex:
+        out = list(ex.map(one, idx))
+    return time.perf_counter() - t0, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--groups", type=int, default=4096)
+    ap.add_argument("--len", type=int, default=1000)
+    ap.add_argument("--depth", type=int, default=32)
+    ap.add_argument("--cpu-sample", type=int, default=256)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "poa_rate.txt"))
+    ap.add_argument("--trace-dir", default="/tmp/poa_rate_trace")
+    ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child is not None:
+        return child(a)
+    batch = synth_groups(a)
+    bases = int(batch.seq_off[-1])
+    lines = [f"POA groups: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100, PacBio-like errors, frac_partial=0, FASTQ), "
+             f"{bases} bases; scores 5/-4/-8; one MI355X; vc_poa_run, synchronous; host clock around one call; before it one untimed call on all groups (the first algorithm: the buffer cache grows) or on 64"]
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+
+    def emit(line):                               # the file is rewritten after every line: a run cut short keeps what it measured
+        lines.append(line)
+        print(line, flush=True)
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    emit(lines.pop())
+    results = {}
+    for alg in (0, 1, 2):
+        dt, cons, status, n_al, cells = timed(batch, alg, "full" if alg == 0 else "small")
+        results[alg] = dict(seconds=dt, cons=cons, ok=int((status == 0).sum()), alignments=n_al, cells=cells)
+        emit(f"{NAMES[alg]:18s} {dt:8.2f} s  {a.groups / dt:8.1f} groups/s  {cells / dt / 1e9:7.2f} GCUPS  "
+             f"({n_al} alignments, {cells / 1e9:.2f} G cells, {results[alg]['ok']} of {a.groups} VC_WIN_OK)")
+    large.release()
+    if a.cpu_sample:
+        import random
+        idx = sorted(random.Random(1).sample(range(a.groups), min(a.cpu_sample, a.groups)))
+        emit(f"reference: spoa (oracle/_ref libvcref_sse41.so, vcref_spoa_consensus) on {len(idx)} of the groups, {a.threads} host threads; "
+             f"device consensus compared with it and with the scalar build (libvcref_sisd.so):")
+        for alg in (0, 1, 2):
+            dt, out = cpu_reference(batch, idx, alg, a.threads)
+            _, scalar = cpu_reference(batch, idx, alg, a.threads, "sisd")
+            dev = results[alg]["cons"]
+            same = sum(1 for w, (rc, c) in zip(idx, out) if rc == 0 and c == dev[w])
+            same_s = sum(1 for w, (rc, c) in zip(idx, scalar) if rc == 0 and c == dev[w])
+            rate = len(idx) / dt
+            emit(f"  {NAMES[alg]:18s} {dt:7.2f} s  {rate:8.1f} groups/s  device / reference {a.groups / results[alg]['seconds'] / rate:.2f}x  "
+                 f"consensus equal to the SIMD build in {same}, to the scalar build in {same_s} of {len(idx)}")
+    if not a.no_trace:
+        emit("kernel time shares, each algorithm's call in a run of its own under rocprofv3 --kernel-trace --stats:")
+        for alg in (0, 1, 2):
+            d = os.path.join(a.trace_dir, f"alg{alg}")
+            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+                   sys.executable, os.path.abspath(__file__), "--child", str(alg), "--groups", str(a.groups), "--len", str(a.len),
+                   "--depth", str(a.depth)]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"  {NAMES[alg]}: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                break
+            ms = kernel_shares(d)
+            tot = sum(ms.values())
+            shares = ", ".join(f"{k} {v / tot * 100:.1f} % ({v / 1e3:.2f} s)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1]))
+            wall = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            emit(f"  {NAMES[alg]:18s} kernels {tot / 1e3:.2f} s of {wall:.2f} s wall (traced; a fresh process, its first call allocates the buffer cache): {shares}")
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -54,6 +54,14 @@ class VcResult(C.Structure):
     ]
 
 
+class VcPoaParams(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("algorithm", C.c_int32),
+        ("match", C.c_int32), ("mismatch", C.c_int32), ("gap", C.c_int32),
+    ]
+
+
 class VcStats(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64), ("alignments", C.c_uint64), ("dp_rows", C.c_uint64),
@@ -313,6 +321,8 @@ def load_hip():
         lib.vc_reserve.argtypes = [vp, C.c_uint64]; lib.vc_reserve.restype = C.c_int
         lib.vc_release.argtypes = [vp]; lib.vc_release.restype = C.c_int
         lib.vc_set_window_type.argtypes = [vp, C.c_int]; lib.vc_set_window_type.restype = C.c_int
+        lib.vc_poa_run.argtypes = [C.POINTER(VcPoaParams), C.POINTER(VcBatch), C.POINTER(VcResult)]; lib.vc_poa_run.restype = C.c_int
+        lib.vc_poa_last_error.argtypes = []; lib.vc_poa_last_error.restype = C.c_char_p
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

@@ -6,6 +6,22 @@
 // every table lives in HBM and is sized from what the window needs; a window whose tables fill is run again with larger ones.
 // Slow by design: correctness counts here, not speed.
 //
+// Three schedules (LArgs::mode), each a window / group per lane of the kernels below:
+//   0 haplotype overload (window.cpp:176-428): rank-ordered layers, subgraphs of partial-span layers, prune rounds, the final
+//     local alignment of the backbone -- vc_large_run;
+//   1 racon-linear overload (window.cpp:74-170): the same build, then heaviest bundle + coverage + TGS trim -- vc_large_run;
+//   2 POA group, vc_poa_run: spoa's public flow (vendor/spoa/test/spoa_test.cpp:38-52) -- sequences in the order given, each
+//     aligned against the WHOLE graph (sequence 0 against the empty graph: an empty alignment), AddAlignment with the quality
+//     overload where a sequence has one (weights vc_weight_lut, graph.cpp:160-171) and weight 1 otherwise, GenerateConsensus at
+//     the end (graph.cpp:450-459, the heaviest bundle with branch completion).  One engine for every alignment of the batch,
+//     kSW / kNW / kOV with the caller's linear scores.  None of the window rules apply: no rank sort, spans, subgraph,
+//     UpdateAlignment, "< 3 sequences", prune, trim, window type or FASTA-backbone quirk; seq_begin / seq_end / win_fasta are
+//     never uploaded.  An empty sequence adds nothing (graph.cpp:187-190); a group of none, or of empty ones only, has the
+//     empty consensus (graph.cpp:534-537).
+//   kOV (semi-global, sisd_alignment_engine.cpp:227-247, 350-358, 380-382) differs from kNW in three places: column 0 of every
+//   graph row is 0 (row 0 stays j * g); the end cell is the first maximum in (rank, column) order over the cells j >= 1 of the
+//   sink rows; the backtrack stops at i == 0 || j == 0.
+//
 // Semantics: oracle/vc_oracle.c, function by function (the names below are the oracle's).  The order-sensitive parts -- the
 // insertion order of in-/out-edges and aligned nodes, the DFS topological order, the DFS preorder of the largest component,
 // the fp64 prune thresholds, average_weight (FASTA-backbone quirk included) and the tie rules of the backtrack and the heaviest
@@ -13,16 +29,22 @@
 // nodes, edge labels) with head, tail and count per node, so appending keeps the oracle's order and nothing is ever moved.
 //
 // Kernels (gfx950, wave64), one launch per stage per alignment step over all windows in flight (lock-step, like vc_run's chunks):
-//   k_lg_init   one lane per window: backbone chain, topological order, the backbone's share of average_weight;
+//   k_lg_init   one lane per window: backbone chain, topological order, the backbone's share of average_weight (mode 2: the
+//               empty graph, or at once the empty consensus of an empty group);
 //   k_lg_prep   one lane per window: the next alignment of the window's schedule (subgraph of a partial-span layer when the
 //               build needs one), its rank-ordered predecessor lists (CSR of row indices), row bytes and sink flags;
 //   k_lg_fwd    one wave per alignment: rows in rank order, columns over the 64 lanes; predecessor rows are read back from the
 //               int32 matrix (rows + 1) x (len + 1) in HBM; the horizontal move is a wave prefix maximum on tilted scores;
 //   k_lg_back   one lane per alignment: walks the stored matrix in the oracle's order of candidates;
 //   k_lg_apply  one lane per window: add-alignment + topological sort, or add-weights; prune + largest component at the end of
-//               the build and of every round; the corrected sequence (mode 0) or heaviest bundle + coverage + trim (mode 1).
+//               the build and of every round; the corrected sequence (mode 0), heaviest bundle + coverage + trim (mode 1) or the
+//               heaviest bundle alone (mode 2).
 //
-// Development knobs, read on every call (unset: the behaviour above, and nothing is printed).  They only make tables and budgets
+// Limits, every schedule: a sequence is shorter than 65 535 bases; beyond that only the device memory bounds a window or group,
+// and one whose tables or matrix it cannot hold at all comes back VC_WIN_OVERFLOW.  Where the reference throws (an invalid
+// alignment, the score floor of WorstCaseAlignmentScore) that window or group is VC_WIN_INVALID and the rest are computed.
+//
+// Development knobs, read on every call of vc_large_run and vc_poa_run (unset: the behaviour above, and nothing is printed).  They only make tables and budgets
 // smaller, so that the tests can reach the host schedule's rarer paths with small windows:
 //   VC_LARGE_CAPS=n:4,a:6   a table starts at max(1, size >> shift): n nodes, e edges, a aligned cells, l labels, s stack, p pairs
 //                           (the stack then also grows from (nodes + edges + aligned) >> shift, not from the unshifted sum);
@@ -30,7 +52,9 @@
 //   VC_LARGE_MAT_MB=x       matrix budget (int32 matrices per forward launch) in MiB;
 //   VC_LARGE_LOG=1          one stderr line per event: "vc_large: regrow window=W flags=nodes,... caps n=.. e=.. a=.. l=.. s=.. p=..",
 //                           "vc_large: group windows=N bytes=B ids=W,.. need=B,..", "vc_large: step launches=K over=O" (steps of more than one
-//                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B".
+//                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B",
+//                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes run, their rows x columns
+//                           summed; a regrown window's are counted again).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -72,7 +96,7 @@ struct LWin {
     uint32_t phase, j, k, cur, sub, grow, status;      // schedule; cur = graph slot of G / P; sub = the alignment ran on a subgraph
     uint32_t num_codes;
     double total, avg;
-    uint32_t rows, qlen, qs, type;                     // the current alignment: graph rows, query length, query (sequence index), 0 SW / 1 NW
+    uint32_t rows, qlen, qs, type;                     // the current alignment: graph rows, query length, query (sequence index), 0 SW / 1 NW / 2 OV
     int32_t m, x, g;
     uint32_t max_i, max_j, npairs, cons_n;
     LGraph gr[2];
@@ -98,7 +122,8 @@ struct LArgs {
     const double* lut_d;                               // 1 - 10^((33 - q) / 10), window.cpp:235,295
     int32_t match, mismatch, gap, sw_match, sw_mismatch, sw_gap;
     double min_conf, min_sup;
-    uint32_t num_prune, mode, trim, window_type;
+    uint32_t num_prune, mode, trim, window_type;       // mode 0 haplotype, 1 racon-linear, 2 POA group
+    uint32_t algorithm;                                // mode 2: spoa::AlignmentType of every alignment (0 kSW, 1 kNW, 2 kOV)
     // k_lg_fwd / k_lg_back: windows of this launch and their matrices
     const uint32_t* list;
     const uint64_t* hoff;
@@ -520,6 +545,16 @@ __device__ void finish_linear(const LArgs& a, LWin& W) {
     W.phase = PH_DONE;
 }
 
+// Graph::GenerateConsensus of a POA group (graph.cpp:450-459): the heaviest bundle, no coverage, no trim
+__device__ void finish_poa(LWin& W) {
+    const LGraph& G = W.gr[W.cur];
+    const uint32_t n = heaviest_bundle(W, G);
+    W.cons_n = 0;
+    for (uint32_t i = 0; i < n; ++i) W.cons[W.cons_n++] = (uint8_t)W.decoder[G.code[W.comp[i]]];
+    W.status = VC_WIN_OK;
+    W.phase = PH_DONE;
+}
+
 __device__ __forceinline__ bool full_span(const LArgs& a, const LWin& W, uint32_t s) {
     const uint32_t offset = (uint32_t)(0.01 * W.L);
     return a.seq_begin[s] < offset && a.seq_end[s] > W.L - offset;
@@ -555,6 +590,11 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     reset_graph(W.gr[0]); reset_graph(W.gr[1]);
     W.gr[0].labels = a.mode == 1; W.gr[1].labels = 0;
     W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
+    if (a.mode == 2) {                                                     // POA group: sequence 0 meets the empty graph in k_lg_prep
+        W.phase = PH_BUILD; W.j = 0; W.k = 0;
+        if (W.nseq == 0) finish_poa(W);                                    // no sequence: the empty consensus
+        return;
+    }
     if (W.nseq < 3) {                                                      // window.cpp:188-192: the backbone, unpolished
         if (W.L > W.NC) { W.grow |= G_NODES; return; }                    // cons holds NC bytes (only a shrunk table is shorter)
         const uint8_t* bb = a.bases + a.seq_off[W.s0];
@@ -580,21 +620,26 @@ __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
     W.rows = 0; W.npairs = 0; W.max_i = W.max_j = 0; W.sub = 0;
     if (W.phase == PH_DONE || W.grow) return;
     uint32_t gi = W.cur;
-    bool nw = true;
-    if (W.phase == PH_BUILD) {
+    if (a.mode == 2) {                                                     // POA group: the next sequence against the whole graph
         W.qs = W.s0 + W.j;
-        if (!full_span(a, W, W.qs)) {
-            if (!subgraph(W, W.gr[W.cur], W.gr[1 - W.cur], a.seq_begin[W.qs], a.seq_end[W.qs])) return;
-            gi = 1 - W.cur; W.sub = 1;
-        }
-    } else if (W.phase == PH_ROUND) {
-        W.qs = W.s0 + W.j;
-        nw = W.j == 0 || full_span(a, W, W.qs);
+        W.type = a.algorithm; W.m = a.match; W.x = a.mismatch; W.g = a.gap;
     } else {
-        W.qs = W.s0; nw = false;
+        bool nw = true;
+        if (W.phase == PH_BUILD) {
+            W.qs = W.s0 + W.j;
+            if (!full_span(a, W, W.qs)) {
+                if (!subgraph(W, W.gr[W.cur], W.gr[1 - W.cur], a.seq_begin[W.qs], a.seq_end[W.qs])) return;
+                gi = 1 - W.cur; W.sub = 1;
+            }
+        } else if (W.phase == PH_ROUND) {
+            W.qs = W.s0 + W.j;
+            nw = W.j == 0 || full_span(a, W, W.qs);
+        } else {
+            W.qs = W.s0; nw = false;
+        }
+        W.type = nw ? 1 : 0;
+        W.m = nw ? a.match : a.sw_match; W.x = nw ? a.mismatch : a.sw_mismatch; W.g = nw ? a.gap : a.sw_gap;
     }
-    W.type = nw ? 1 : 0;
-    W.m = nw ? a.match : a.sw_match; W.x = nw ? a.mismatch : a.sw_mismatch; W.g = nw ? a.gap : a.sw_gap;
     const LGraph& g = W.gr[gi];
     const uint32_t N = g.n_nodes, len = (uint32_t)(a.seq_off[W.qs + 1] - a.seq_off[W.qs]);
     if (N == 0 || len == 0) return;                                       // an empty alignment
@@ -621,13 +666,15 @@ __device__ __forceinline__ bool better(int32_t s, uint32_t i, uint32_t j, int32_
 // Diagonal / vertical moves from every predecessor row give x[j]; SW clamps it at 0 first (C[j] = max(0, x[j], C[j-1] + g) is the
 // plain recurrence on max(0, x)); the horizontal move H[j] = max_k<=j (x[k] + (j - k) g) is a prefix maximum of the tilted
 // T[k] = x[k] - k g, carried from chunk to chunk.  The matrix row is stored and the next row may read it after the barrier.
+// kOV: column 0 of a graph row is 0 instead of the vertical chain (so the horizontal move starts from 0), and every cell of a
+// sink row is an end-cell candidate, not only the last column.
 __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
     LWin& W = a.win[a.list[blockIdx.x]];
     const uint32_t lane = threadIdx.x;
     int32_t* H = a.H + a.hoff[blockIdx.x];
     const uint32_t N = W.rows, len = W.qlen;
     const uint64_t w = (uint64_t)len + 1;
-    const bool sw = W.type == 0;
+    const bool sw = W.type == 0, ov = W.type == 2;
     const int32_t m = W.m, x = W.x, gp = W.g;
     const uint8_t* seq = a.bases + a.seq_off[W.qs];
     for (uint32_t j = lane; j <= len; j += 64) H[j] = (sw || j == 0) ? 0 : (int32_t)j * gp;
@@ -639,8 +686,8 @@ __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
         const uint32_t po = W.poff[r], pe = W.poff[r + 1];
         const uint8_t c = W.rchar[r];
         const bool sink = W.sink[r] != 0;
-        int32_t h0 = 0;
-        if (!sw) {
+        int32_t h0 = 0;                                                    // SW and OV (sisd_alignment_engine.cpp:182-190, 227-247)
+        if (!sw && !ov) {
             int32_t pen = pe == po ? 0 : KNEG;
             for (uint32_t k = po; k < pe; ++k) pen = max(pen, H[(uint64_t)W.prank[k] * w]);
             h0 = pen + gp;
@@ -684,7 +731,7 @@ __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
                 if (j > len) break;
                 const int32_t h = (int32_t)((t[q] > before ? t[q] : before) + (int64_t)j * gp);
                 Hr[j] = h;
-                if (sw ? h > bs : (sink && j == len && h > bs)) { bs = h; bi = (uint32_t)i; bj = j; }
+                if (sw ? h > bs : (sink && (ov || j == len) && h > bs)) { bs = h; bi = (uint32_t)i; bj = j; }
             }
         }
         __syncthreads();
@@ -706,12 +753,13 @@ __global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
     const uint64_t w = (uint64_t)W.qlen + 1;
     const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
     const uint8_t* seq = a.bases + a.seq_off[W.qs];
-    const bool sw = W.type == 0;
+    const bool sw = W.type == 0, ov = W.type == 2;
     W.npairs = 0;
     uint32_t i = W.max_i, j = W.max_j, np = 0;
-    if (i == 0 && j == 0) return;
-    for (;;) {
+    if (i == 0 && j == 0) return;                                          // an empty alignment
+    for (;;) {                                                             // sisd_alignment_engine.cpp:374-389
         if (sw) { if (H[(uint64_t)i * w + j] == 0) break; }
+        else if (ov) { if (i == 0 || j == 0) break; }
         else if (i == 0 && j == 0) break;
         const int32_t Hij = H[(uint64_t)i * w + j];
         uint32_t pi = 0, pj = 0;
@@ -768,6 +816,7 @@ __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
         }
         if (++W.j < W.nseq) return;
         if (a.mode == 1) { finish_linear(a, W); return; }
+        if (a.mode == 2) { finish_poa(W); return; }
         const uint16_t window_len = (uint16_t)W.L;                         // window.cpp:216
         W.avg = W.fasta ? 2.0 * W.total / window_len : 2.0 * W.total / window_len * 1000;
         if (!prune_and_keep_largest(a, W)) return;
@@ -894,6 +943,33 @@ bool read_knobs(Knobs& k) {
 
 uint64_t shrunk(uint64_t v, uint32_t s) { return std::max<uint64_t>(v >> s, 1); }
 
+// initial tables of a window or group from its sum of sequence lengths and its longest sequence.  Nodes: every node is made from
+// one base of one sequence, so the sum bounds them; the rest starts from what such graphs use and doubles when a table fills.
+Caps initial_caps(uint64_t sum, uint64_t mx, uint64_t nseq, const Knobs& kn) {
+    Caps c;
+    c.NC = sum + 1; c.EC = sum + 64; c.AC = 2 * sum + 64; c.LC = sum + 64; c.SC = c.NC + c.EC + c.AC; c.PC = sum + mx + 2;
+    c.nseq = nseq;
+    c.NC = shrunk(c.NC, kn.shift[0]); c.EC = shrunk(c.EC, kn.shift[1]); c.AC = shrunk(c.AC, kn.shift[2]);
+    c.LC = shrunk(c.LC, kn.shift[3]); c.SC = shrunk(c.SC, kn.shift[4]); c.PC = shrunk(c.PC, kn.shift[5]);
+    return c;
+}
+
+// VC_OK, or the error of a device the kernels cannot run on
+int check_device(int32_t device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(VC_ERR_NO_DEVICE, "no HIP device visible; the large-graph path has no CPU fallback");
+    }
+    if (device < 0 || device >= ndev) return fail(VC_ERR_NO_DEVICE, "no HIP device with this ordinal");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(VC_ERR_HIP, "hipGetDeviceProperties failed");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(VC_ERR_NO_DEVICE, "the kernels are built for gfx950 only");
+    return VC_OK;
+}
+
+int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r);
+
 }  // namespace
 
 extern "C" {
@@ -904,15 +980,7 @@ void vc_large_release(void) { release_cache(); }
 
 int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VC_ERR_NO_DEVICE, "no HIP device visible; the large-graph path has no CPU fallback");
-    }
-    if (p->device < 0 || p->device >= ndev) return fail(VC_ERR_NO_DEVICE, "no HIP device with this ordinal");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device) != hipSuccess) return fail(VC_ERR_HIP, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(VC_ERR_NO_DEVICE, "the kernels are built for gfx950 only");
+    if (const int rc = check_device(p->device)) return rc;
     if (p->mode != 0 && p->mode != 1) return fail(VC_ERR_ARG, "mode must be 0 or 1");
     if (p->num_prune == 0) return fail(VC_ERR_ARG, "num_prune must be >= 1");
     Knobs kn;
@@ -923,7 +991,6 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     if (!b->win_seq_off || !b->seq_off || !b->seq_begin || !b->seq_end || !b->seq_has_qual || !b->bases || !b->quals || !b->win_fasta)
         return fail(VC_ERR_ARG, "null array in batch");
     // validation: what vc_submit enforces (createWindow / add_layer, window.cpp:22-27,56-67)
-    const uint64_t nseq_all = b->win_seq_off[nw], nbytes = b->seq_off[nseq_all];
     std::vector<Caps> caps(nw);
     for (uint32_t w = 0; w < nw; ++w) {
         const uint32_t s0 = b->win_seq_off[w], s1 = b->win_seq_off[w + 1];
@@ -938,16 +1005,70 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
             if (s > s0 && (b->seq_begin[s] >= b->seq_end[s] || b->seq_begin[s] > L || b->seq_end[s] >= L)) return fail(VC_ERR_ARG, "invalid layer positions");
             sum += len; mx = std::max(mx, len);
         }
-        // nodes: every node is made from one base of one sequence, so the sum of lengths bounds them; the rest starts from
-        // what such graphs use and doubles when a table fills
-        Caps& c = caps[w];
-        c.NC = sum + 1; c.EC = sum + 64; c.AC = 2 * sum + 64; c.LC = sum + 64; c.SC = c.NC + c.EC + c.AC; c.PC = sum + mx + 2;
-        c.nseq = s1 - s0;
-        c.NC = shrunk(c.NC, kn.shift[0]); c.EC = shrunk(c.EC, kn.shift[1]); c.AC = shrunk(c.AC, kn.shift[2]);
-        c.LC = shrunk(c.LC, kn.shift[3]); c.SC = shrunk(c.SC, kn.shift[4]); c.PC = shrunk(c.PC, kn.shift[5]);
+        caps[w] = initial_caps(sum, mx, s1 - s0, kn);
     }
-    if (hipSetDevice(p->device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
-    if (g_cache.device != p->device) { release_cache(); g_cache.device = p->device; }
+    LArgs a{};
+    a.match = p->match; a.mismatch = p->mismatch; a.gap = p->gap; a.sw_match = p->sw_match; a.sw_mismatch = p->sw_mismatch; a.sw_gap = p->sw_gap;
+    a.min_conf = p->min_confidence; a.min_sup = p->min_support; a.num_prune = p->num_prune; a.mode = (uint32_t)p->mode;
+    a.trim = (uint32_t)p->trim; a.window_type = (uint32_t)p->window_type;
+    return run_windows(p->device, a, b, caps, p->mode == 1, true, kn, r);
+}
+
+const char* vc_poa_last_error(void) { return g_err.c_str(); }
+
+int vc_poa_run(const vc_poa_params* p, const vc_batch* b, vc_result* r) {
+    // the arguments first, without the device (alignment_engine.cpp:39-57; spoa takes the scores as int8_t)
+    if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+    if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
+    if (p->gap > 0) return fail(VC_ERR_ARG, "gap must be <= 0 (linear gaps: spoa's gap opening penalty must be non-positive)");
+    for (const int32_t s : {p->match, p->mismatch, p->gap})
+        if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
+    Knobs kn;
+    if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
+    const uint32_t nw = b->n_windows;
+    std::vector<Caps> caps(nw);
+    if (nw) {
+        if (!b->win_seq_off || !b->seq_off || !b->seq_has_qual) return fail(VC_ERR_ARG, "null array in batch");
+        if (b->win_seq_off[0] != 0) return fail(VC_ERR_ARG, "win_seq_off[0] must be 0");
+        for (uint32_t w = 0; w < nw; ++w)
+            if (b->win_seq_off[w + 1] < b->win_seq_off[w]) return fail(VC_ERR_ARG, "win_seq_off decreases");
+        const uint32_t nseq_all = b->win_seq_off[nw];
+        if (b->seq_off[0] != 0) return fail(VC_ERR_ARG, "seq_off[0] must be 0");
+        bool any_qual = false;
+        for (uint32_t s = 0; s < nseq_all; ++s) {
+            if (b->seq_off[s + 1] < b->seq_off[s]) return fail(VC_ERR_ARG, "seq_off decreases");
+            if (b->seq_off[s + 1] - b->seq_off[s] >= 65535) return fail(VC_ERR_ARG, "sequence length unsupported (at most 65 534 bases)");
+            any_qual |= b->seq_has_qual[s] != 0;
+        }
+        if (b->seq_off[nseq_all] && !b->bases) return fail(VC_ERR_ARG, "null bases");
+        if (b->seq_off[nseq_all] && any_qual && !b->quals) return fail(VC_ERR_ARG, "null quals beside seq_has_qual");
+        for (uint32_t w = 0; w < nw; ++w) {
+            const uint32_t s0 = b->win_seq_off[w], s1 = b->win_seq_off[w + 1];
+            uint64_t mx = 0;
+            for (uint32_t s = s0; s < s1; ++s) mx = std::max<uint64_t>(mx, b->seq_off[s + 1] - b->seq_off[s]);
+            caps[w] = initial_caps(b->seq_off[s1] - b->seq_off[s0], mx, s1 - s0, kn);
+        }
+    }
+    if (const int rc = check_device(p->device)) return rc;
+    r->cons_off[0] = 0;
+    if (nw == 0) return VC_OK;
+    LArgs a{};
+    a.match = p->match; a.mismatch = p->mismatch; a.gap = p->gap; a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)p->algorithm;
+    return run_windows(p->device, a, b, caps, false, false, kn, r);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The host schedule of vc_large_run and vc_poa_run: the batch on the device (seq_begin / seq_end only with spans), windows in
+// flight in groups that fit the arena budget, one alignment of each per lock-step step with the forward passes in launches that
+// fit the matrix budget, and a window whose table filled run again with larger tables.  `a` holds the scores and the schedule.
+int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r) {
+    const uint32_t nw = b->n_windows;
+    const uint64_t nseq_all = b->win_seq_off[nw], nbytes = b->seq_off[nseq_all];
+    if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
+    if (g_cache.device != device) { release_cache(); g_cache.device = device; }
 
     std::vector<void*> fixed;
     auto cleanup = [&]() { for (void* q : fixed) (void)hipFree(q); fixed.clear(); };
@@ -955,18 +1076,15 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     double lut_d[256];
     vc_weight_lut(lut_w);
     for (int c = 0; c < 256; ++c) lut_d[c] = 1 - pow(10, (33 - (int)(signed char)c) / 10.0);
-    LArgs a{};
     uint64_t* d_so = nullptr; uint32_t *d_sb = nullptr, *d_se = nullptr, *d_lw = nullptr; uint8_t *d_hq = nullptr, *d_b = nullptr, *d_q = nullptr;
     double* d_ld = nullptr;
-    if (!dalloc(fixed, &d_so, nseq_all + 1, b->seq_off) || !dalloc(fixed, &d_sb, nseq_all, b->seq_begin) || !dalloc(fixed, &d_se, nseq_all, b->seq_end) ||
+    if (!dalloc(fixed, &d_so, nseq_all + 1, b->seq_off) ||
+        (spans && (!dalloc(fixed, &d_sb, nseq_all, b->seq_begin) || !dalloc(fixed, &d_se, nseq_all, b->seq_end))) ||
         !dalloc(fixed, &d_hq, nseq_all, b->seq_has_qual) || !dalloc(fixed, &d_b, nbytes, b->bases) || !dalloc(fixed, &d_q, nbytes, b->quals) ||
         !dalloc(fixed, &d_lw, 256, lut_w) || !dalloc(fixed, &d_ld, 256, lut_d)) {
         cleanup(); return fail(VC_ERR_HIP, "device allocation or copy of the batch failed");
     }
     a.seq_off = d_so; a.seq_begin = d_sb; a.seq_end = d_se; a.has_qual = d_hq; a.bases = d_b; a.quals = d_q; a.lut_w = d_lw; a.lut_d = d_ld;
-    a.match = p->match; a.mismatch = p->mismatch; a.gap = p->gap; a.sw_match = p->sw_match; a.sw_mismatch = p->sw_mismatch; a.sw_gap = p->sw_gap;
-    a.min_conf = p->min_confidence; a.min_sup = p->min_support; a.num_prune = p->num_prune; a.mode = (uint32_t)p->mode;
-    a.trim = (uint32_t)p->trim; a.window_type = (uint32_t)p->window_type;
 
     // budgets from free device memory (what this library keeps cached counts as free)
     size_t free_b = 0, total_b = 0;
@@ -980,7 +1098,7 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     std::vector<uint32_t> pending(nw);
     for (uint32_t w = 0; w < nw; ++w) pending[w] = w;
     uint32_t *d_list = nullptr; uint64_t* d_hoff = nullptr; LWin* d_win = nullptr;
-    const bool labels = p->mode == 1;
+    uint64_t n_align = 0, n_cells = 0;                                     // forward passes run (VC_LARGE_LOG's "done" line)
     while (!pending.empty()) {
         // windows in flight: as many as the arena budget holds, in order (at least one)
         std::vector<uint32_t> grp;
@@ -1025,7 +1143,8 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
             layout(&W, arena + aoff[k], caps[w], labels);
             const Caps& c = caps[w];
             W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
-            W.L = (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]); W.fasta = b->win_fasta[w] ? 1 : 0;
+            W.L = W.nseq ? (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]) : 0;     // (POA groups: unused, and may be empty)
+            W.fasta = b->win_fasta && b->win_fasta[w] ? 1 : 0;
             W.NC = (uint32_t)c.NC; W.EC = (uint32_t)c.EC; W.AC = (uint32_t)c.AC; W.LC = (uint32_t)c.LC; W.SC = (uint32_t)c.SC; W.PC = (uint32_t)c.PC;
         }
         a.win = d_win; a.n = n;
@@ -1074,6 +1193,8 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
                 hipLaunchKernelGGL(k_lg_fwd, dim3(nl), dim3(64), 0, 0, f);
                 hipLaunchKernelGGL(k_lg_back, dim3((nl + 63) / 64), dim3(64), 0, 0, f, nl);
                 ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+                for (const uint32_t k : list) n_cells += (uint64_t)hw[k].rows * hw[k].qlen;
+                n_align += nl;
                 launches++;
                 if (cells * 4 > mat_budget) over++;
             }
@@ -1118,6 +1239,7 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
         done_tmp();
     }
     cleanup();
+    if (kn.log) std::fprintf(stderr, "vc_large: done alignments=%llu cells=%llu\n", (unsigned long long)n_align, (unsigned long long)n_cells);
     uint64_t o = 0;
     for (uint32_t w = 0; w < nw; ++w) {
         if (o + out[w].size() > r->cons_cap) return fail(VC_ERR_CAPACITY, "consensus buffer too small");
@@ -1129,4 +1251,4 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     return VC_OK;
 }
 
-}  // extern "C"
+}  // namespace

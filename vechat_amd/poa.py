@@ -1,0 +1,157 @@
+"""Consensus of read groups on the device: spoa's public flow (AlignmentEngine::Create, Align + Graph::AddAlignment per
+sequence in the order given, GenerateConsensus) for every group of a batch, over the C ABI `vc_poa_run` (schedule 2 of
+vechat_amd/csrc/vc_large.hip; include/vechat_hip.h has the semantics).  Local (kSW), global (kNW) and semi-global (kOV)
+alignment with linear gaps; no window rules.  No CPU path: without a device the calls raise.
+
+    python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [-l 0|1|2] [--device D] FILE [FILE ...]
+
+prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`.
+The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
+as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
+non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
+consensus sequences.  poa_consensus() takes sequences and qualities as given.
+"""
+import argparse
+import ctypes as C
+import sys
+
+import numpy as np
+
+from . import capi
+
+ALGORITHMS = {"local": 0, "global": 1, "semi-global": 2}          # spoa::AlignmentType kSW, kNW, kOV
+_STATUS = {capi.VC_WIN_INVALID: "VC_WIN_INVALID (input the reference throws on)",
+           capi.VC_WIN_OVERFLOW: "VC_WIN_OVERFLOW (the device memory cannot hold it)"}
+
+
+class PoaError(RuntimeError):
+    """A failed vc_poa_run (rc, the library's message), or groups that were not computed (groups: {index: status})."""
+
+    def __init__(self, msg, rc=None, groups=None):
+        super().__init__(msg)
+        self.rc = rc
+        self.groups = groups or {}
+
+
+def algorithm_code(algorithm):
+    """0 / 1 / 2 or "local" / "global" / "semi-global" -> spoa::AlignmentType"""
+    if isinstance(algorithm, str):
+        if algorithm not in ALGORITHMS:
+            raise ValueError(f"algorithm must be one of {sorted(ALGORITHMS)} or 0 / 1 / 2, not {algorithm!r}")
+        return ALGORITHMS[algorithm]
+    if isinstance(algorithm, (int, np.integer)) and not isinstance(algorithm, bool) and int(algorithm) in (0, 1, 2):
+        return int(algorithm)
+    raise ValueError(f"algorithm must be 0, 1, 2 or one of {sorted(ALGORITHMS)}, not {algorithm!r}")
+
+
+def _bytes(x, what):
+    if isinstance(x, str):
+        return x.encode("ascii")
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        return bytes(x)
+    raise TypeError(f"a {what} is str or bytes, not {type(x).__name__}")
+
+
+def _member(m):
+    """a sequence, or a (sequence, quality or None) pair -> (bytes, bytes | None)"""
+    if isinstance(m, (tuple, list)):
+        if len(m) != 2:
+            raise ValueError("a group member is a sequence or a (sequence, quality or None) pair")
+        seq, qual = m
+    else:
+        seq, qual = m, None
+    seq = _bytes(seq, "sequence")
+    if qual is None:
+        return seq, None
+    qual = _bytes(qual, "quality string")
+    if len(qual) != len(seq):                     # spoa throws: "sequence and weights are of unequal size" (graph.cpp:191-196)
+        raise ValueError(f"quality string of {len(qual)} bytes for a sequence of {len(seq)}")
+    return seq, qual
+
+
+def group_batch(groups):
+    """groups (list of lists of sequences or (sequence, quality or None) pairs) -> capi.Batch, one window per group, sequences in
+    the order given.  seq_begin / seq_end / win_fasta are zeros: vc_poa_run ignores them."""
+    wso, so, hq, bases, quals = [0], [0], [], [], []
+    for g in groups:
+        if isinstance(g, (str, bytes)):
+            raise TypeError("a group is a list of sequences, not a single sequence")
+        for m in g:
+            seq, qual = _member(m)
+            bases.append(seq)
+            quals.append(qual if qual is not None else bytes(len(seq)))
+            so.append(so[-1] + len(seq))
+            hq.append(0 if qual is None else 1)
+        wso.append(len(hq))
+    n = len(hq)
+    return capi.Batch(np.array(wso, np.uint32), np.array(so, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32),
+                      np.array(hq, np.uint8), np.frombuffer(b"".join(bases), np.uint8), np.frombuffer(b"".join(quals), np.uint8),
+                      np.zeros(len(groups), np.uint8))
+
+
+def run_batch(batch, params, lib=None):
+    """vc_poa_run on a capi.Batch (its seq_begin / seq_end / win_fasta are passed as NULL) -> (consensus bytes per group, status
+    array).  Raises PoaError on a library error."""
+    lib = lib or capi.load_hip()
+    n = batch.n_windows
+    cons = np.zeros(max(int(batch.bases.size), 1), np.uint8)       # a group's consensus is never longer than its sequences
+    off = np.zeros(n + 1, np.uint64)
+    status = np.zeros(max(n, 1), np.uint8)
+    r = capi.VcResult(off.ctypes.data_as(C.POINTER(C.c_uint64)), cons.ctypes.data_as(C.POINTER(C.c_uint8)), cons.size,
+                      status.ctypes.data_as(C.POINTER(C.c_uint8)))
+    vb = batch.as_struct()
+    vb.seq_begin = vb.seq_end = vb.win_fasta = None
+    rc = lib.vc_poa_run(C.byref(params), C.byref(vb), C.byref(r))
+    if rc != 0:
+        raise PoaError(f"vc_poa_run failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    return [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n]
+
+
+def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None):
+    """Consensus of every group -> list of bytes.  The defaults are spoa's -m / -n / -g.  A group the device could not compute
+    (VC_WIN_INVALID: the reference throws on it; VC_WIN_OVERFLOW: too large for the device memory) raises PoaError with the
+    indices, or with strict=False comes back as None."""
+    batch = group_batch(groups)
+    p = capi.VcPoaParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap=gap)
+    cons, status = run_batch(batch, p, lib)
+    bad = {w: int(s) for w, s in enumerate(status) if int(s) != capi.VC_WIN_OK}
+    if bad and strict:
+        what = ", ".join(f"{w}: {_STATUS.get(s, s)}" for w, s in list(bad.items())[:8])
+        raise PoaError(f"{len(bad)} group(s) not computed: {what}{' ...' if len(bad) > 8 else ''}", groups=bad)
+    return [None if w in bad else c for w, c in enumerate(cons)]
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(
+        prog="python -m vechat_amd.poa",
+        description="Partial-order consensus of each FASTA/FASTQ(.gz) file on the device, as spoa computes it (one file = one group; "
+                    "records in file order, quality strings as weights; read as the polisher reads them: upper-cased, an all-'!' quality "
+                    "string counts as none). Gaps are linear only: spoa's -e / -q / -c (affine and convex "
+                    "gaps) are not accepted.")
+    ap.add_argument("-m", type=int, default=5, help="score for matching bases (default 5)")
+    ap.add_argument("-n", type=int, default=-4, help="score for mismatching bases (default -4)")
+    ap.add_argument("-g", type=int, default=-8, help="linear gap penalty, <= 0 (default -8)")
+    ap.add_argument("-l", type=int, default=0, choices=(0, 1, 2), help="alignment mode: 0 local (SW), 1 global (NW), 2 semi-global (OV); default 0")
+    ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
+    ap.add_argument("files", nargs="+", metavar="FILE")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from . import seqio
+    try:
+        groups = [[(data, qual) for _, data, qual in seqio.read_sequences(f)] for f in a.files]
+        cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device)
+    except (PoaError, ValueError, OSError) as e:
+        print(f"vechat_amd.poa: {e}", file=sys.stderr)
+        return 1
+    out = sys.stdout.buffer
+    for c in cons:
+        out.write(b">Consensus LN:i:%d\n%s\n" % (len(c), c))
+    out.flush()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
