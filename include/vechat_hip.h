@@ -369,7 +369,7 @@ void        vc_large_release(void);
  * sequence with seq_has_qual takes the quality overload (weights as vc_weight_lut, the vendored graph.cpp:160-171), the others
  * weight 1; an empty sequence adds nothing (graph.cpp:187-190).  seq_begin, seq_end and win_fasta may be NULL and are ignored,
  * and so may quals when no sequence has a quality: no window rule applies (rank order, spans, subgraphs, "< 3 sequences",
- * prune, trim, window type).  Linear gaps only (spoa's kLinear: e = q = c = g).
+ * prune, trim, window type).  Linear gaps (spoa's kLinear: e = q = c = g); vc_poa_run_gaps below takes affine and convex ones.
  * Synchronous, on the large-graph path's kernels (schedule 2 in vc_large.hip) and its buffer cache: fills r like vc_large_run
  * (cons_cap >= the batch's bases is always enough).  Status per group: VC_WIN_OK; VC_WIN_INVALID where the reference throws (the
  * group is left out, the others are computed); VC_WIN_OVERFLOW for a group the device memory cannot hold at all.
@@ -385,6 +385,27 @@ typedef struct vc_poa_params {
 } vc_poa_params;
 int         vc_poa_run(const vc_poa_params* p, const vc_batch* b, vc_result* r);
 const char* vc_poa_last_error(void);
+
+/* Affine and convex gaps: the same flow with the engine of
+ *     spoa::AlignmentEngine::Create(algorithm, match, mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+ * whose subtype is chosen as alignment_engine.cpp:59-69 does: gap_open >= gap_extend selects linear gaps (with gap_extend =
+ * gap_open), else gap_open <= gap_open2 or gap_extend >= gap_extend2 selects affine gaps (gap_open2 = gap_open, gap_extend2 =
+ * gap_extend), else convex gaps (the better of two affine models).  spoa's own command line defaults are -g -8 -e -6 -q -10 -c -4:
+ * convex.  Everything else as vc_poa_run: the batch, the result, the statuses, the envelope, vc_poa_last_error.  A parameter set
+ * that selects linear gaps computes what vc_poa_run computes with gap = gap_open; only WorstCaseAlignmentScore, whose "possible
+ * overflow" refusal (VC_WIN_INVALID) spoa takes from all four gap scores, may differ, on graphs of millions of nodes.
+ * Affine alignments hold 3 int32 matrices (H, F, E), convex ones 5 (H, F, E, O, Q) of (nodes + 1) x (length + 1) cells each, on
+ * the device.  Checked before the device, in spoa's order: NULL pointers, algorithm outside 0..2, gap_open or gap_open2 > 0,
+ * gap_extend or gap_extend2 > 0, any of the six scores outside -128..127, then the batch as vc_poa_run: VC_ERR_ARG; then
+ * VC_ERR_NO_DEVICE without a gfx950 device. */
+typedef struct vc_poa_gap_params {
+    int32_t device;
+    int32_t algorithm;              /* 0 local (kSW), 1 global (kNW), 2 semi-global (kOV)                           */
+    int32_t match, mismatch;
+    int32_t gap_open, gap_extend;   /* spoa's g and e                                                               */
+    int32_t gap_open2, gap_extend2; /* spoa's q and c (the second affine model of convex gaps)                      */
+} vc_poa_gap_params;
+int         vc_poa_run_gaps(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,11 @@ libvcref_sse41.so, vcref_spoa_consensus) on a sample of the same groups on 16 ho
 compared with the device's.
 
   python tools/gpu_poa_rate.py [--groups 4096] [--len 1000] [--depth 32] [--cpu-sample 256] [--out profiles/poa_rate.txt]
+                               [--gaps linear|affine|convex]
+
+--gaps affine / convex runs vc_poa_run_gaps with spoa's affine known-answer scores (5 -4 -8 -6) or its command-line defaults
+(5 -4 -8 -6 -10 -4, convex); the cells are still rows x columns (not x planes).  The reference in oracle/_ref only takes linear
+gaps, so those runs have no host comparison.
 """
 import argparse
 import csv
@@ -30,6 +35,14 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from vechat_amd import capi, large, poa  # noqa: E402
 
 NAMES = {0: "local (kSW)", 1: "global (kNW)", 2: "semi-global (kOV)"}
+GAPS = {"linear": None, "affine": (-8, -6, -8, -6), "convex": (-8, -6, -10, -4)}    # gap_open, gap_extend, gap_open2, gap_extend2
+
+
+def params(alg, gaps):
+    if GAPS[gaps] is None:
+        return capi.VcPoaParams(device=0, algorithm=alg, match=5, mismatch=-4, gap=-8)
+    g, e, q, c = GAPS[gaps]
+    return capi.VcPoaGapParams(device=0, algorithm=alg, match=5, mismatch=-4, gap_open=g, gap_extend=e, gap_open2=q, gap_extend2=c)
 
 
 def synth_groups(a):
@@ -37,11 +50,11 @@ def synth_groups(a):
     return capi.synth_batch(cfg, 0, a.groups)
 
 
-def timed(batch, alg, warm):
+def timed(batch, alg, warm, gaps="linear"):
     """-> (seconds, consensus, statuses, alignments, cells) of one vc_poa_run on the batch, VC_LARGE_LOG read from stderr.
     warm: "full" -- one untimed call on the whole batch first, so that the large path's buffer cache has grown to the batch's size
     (the first call of a process allocates it); "small" -- 64 groups (code objects loaded)."""
-    p = capi.VcPoaParams(device=0, algorithm=alg, match=5, mismatch=-4, gap=-8)
+    p = params(alg, gaps)
     if warm:
         poa.run_batch(batch if warm == "full" else batch.slice(0, min(64, batch.n_windows)), p)
     import tempfile
@@ -79,7 +92,7 @@ def kernel_shares(trace_dir):
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
     batch = synth_groups(a)
-    dt, _, status, n_al, cells = timed(batch, a.child, "small")
+    dt, _, status, n_al, cells = timed(batch, a.child, "small", a.gaps)
     print(json.dumps(dict(seconds=dt, alignments=n_al, cells=cells, ok=int((status == 0).sum()))))
 
 
@@ -107,14 +120,17 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "poa_rate.txt"))
     ap.add_argument("--trace-dir", default="/tmp/poa_rate_trace")
     ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--gaps", choices=sorted(GAPS), default="linear")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
         return child(a)
     batch = synth_groups(a)
     bases = int(batch.seq_off[-1])
+    scores, entry = ("5/-4/-8", "vc_poa_run") if GAPS[a.gaps] is None else \
+        (f"5/-4/{'/'.join(map(str, GAPS[a.gaps]))} ({a.gaps} gaps)", "vc_poa_run_gaps")
     lines = [f"POA groups: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100, PacBio-like errors, frac_partial=0, FASTQ), "
-             f"{bases} bases; scores 5/-4/-8; one MI355X; vc_poa_run, synchronous; host clock around one call; before it one untimed call on all groups (the first algorithm: the buffer cache grows) or on 64"]
+             f"{bases} bases; scores {scores}; one MI355X; {entry}, synchronous; host clock around one call; before it one untimed call on all groups (the first algorithm: the buffer cache grows) or on 64"]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 
     def emit(line):                               # the file is rewritten after every line: a run cut short keeps what it measured
@@ -124,12 +140,14 @@ def main():
     emit(lines.pop())
     results = {}
     for alg in (0, 1, 2):
-        dt, cons, status, n_al, cells = timed(batch, alg, "full" if alg == 0 else "small")
+        dt, cons, status, n_al, cells = timed(batch, alg, "full" if alg == 0 else "small", a.gaps)
         results[alg] = dict(seconds=dt, cons=cons, ok=int((status == 0).sum()), alignments=n_al, cells=cells)
         emit(f"{NAMES[alg]:18s} {dt:8.2f} s  {a.groups / dt:8.1f} groups/s  {cells / dt / 1e9:7.2f} GCUPS  "
              f"({n_al} alignments, {cells / 1e9:.2f} G cells, {results[alg]['ok']} of {a.groups} VC_WIN_OK)")
     large.release()
-    if a.cpu_sample:
+    if a.cpu_sample and GAPS[a.gaps] is not None:
+        emit("reference: none -- oracle/_ref builds spoa's engine through Create(type, m, n, g) only (linear gaps)")
+    elif a.cpu_sample:
         import random
         idx = sorted(random.Random(1).sample(range(a.groups), min(a.cpu_sample, a.groups)))
         emit(f"reference: spoa (oracle/_ref libvcref_sse41.so, vcref_spoa_consensus) on {len(idx)} of the groups, {a.threads} host threads; "
@@ -149,7 +167,7 @@ def main():
             d = os.path.join(a.trace_dir, f"alg{alg}")
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
                    sys.executable, os.path.abspath(__file__), "--child", str(alg), "--groups", str(a.groups), "--len", str(a.len),
-                   "--depth", str(a.depth)]
+                   "--depth", str(a.depth), "--gaps", a.gaps]
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
             if p.returncode != 0:
                 emit(f"  {NAMES[alg]}: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")

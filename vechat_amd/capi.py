@@ -62,6 +62,15 @@ class VcPoaParams(C.Structure):
     ]
 
 
+class VcPoaGapParams(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("algorithm", C.c_int32),
+        ("match", C.c_int32), ("mismatch", C.c_int32),
+        ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("gap_open2", C.c_int32), ("gap_extend2", C.c_int32),
+    ]
+
+
 class VcStats(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64), ("alignments", C.c_uint64), ("dp_rows", C.c_uint64),
@@ -323,6 +332,8 @@ def load_hip():
         lib.vc_set_window_type.argtypes = [vp, C.c_int]; lib.vc_set_window_type.restype = C.c_int
         lib.vc_poa_run.argtypes = [C.POINTER(VcPoaParams), C.POINTER(VcBatch), C.POINTER(VcResult)]; lib.vc_poa_run.restype = C.c_int
         lib.vc_poa_last_error.argtypes = []; lib.vc_poa_last_error.restype = C.c_char_p
+        lib.vc_poa_run_gaps.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult)]
+        lib.vc_poa_run_gaps.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

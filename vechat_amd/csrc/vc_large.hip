@@ -14,7 +14,9 @@
 //     aligned against the WHOLE graph (sequence 0 against the empty graph: an empty alignment), AddAlignment with the quality
 //     overload where a sequence has one (weights vc_weight_lut, graph.cpp:160-171) and weight 1 otherwise, GenerateConsensus at
 //     the end (graph.cpp:450-459, the heaviest bundle with branch completion).  One engine for every alignment of the batch,
-//     kSW / kNW / kOV with the caller's linear scores.  None of the window rules apply: no rank sort, spans, subgraph,
+//     kSW / kNW / kOV with the caller's scores: linear gaps (vc_poa_run), or linear, affine or convex ones as spoa's
+//     Create(type, m, n, g, e, q, c) chooses (vc_poa_run_gaps; LArgs::gaps, k_lg_fwd / k_lg_back <1> and <2> with 3 and 5 int32
+//     planes per matrix cell).  None of the window rules apply: no rank sort, spans, subgraph,
 //     UpdateAlignment, "< 3 sequences", prune, trim, window type or FASTA-backbone quirk; seq_begin / seq_end / win_fasta are
 //     never uploaded.  An empty sequence adds nothing (graph.cpp:187-190); a group of none, or of empty ones only, has the
 //     empty consensus (graph.cpp:534-537).
@@ -49,7 +51,7 @@
 //   VC_LARGE_CAPS=n:4,a:6   a table starts at max(1, size >> shift): n nodes, e edges, a aligned cells, l labels, s stack, p pairs
 //                           (the stack then also grows from (nodes + edges + aligned) >> shift, not from the unshifted sum);
 //   VC_LARGE_ARENA_MB=x     arena budget (window tables per group; a window above twice the budget is refused) in MiB, fractions allowed;
-//   VC_LARGE_MAT_MB=x       matrix budget (int32 matrices per forward launch) in MiB;
+//   VC_LARGE_MAT_MB=x       matrix budget (int32 matrices, every plane, per forward launch) in MiB;
 //   VC_LARGE_LOG=1          one stderr line per event: "vc_large: regrow window=W flags=nodes,... caps n=.. e=.. a=.. l=.. s=.. p=..",
 //                           "vc_large: group windows=N bytes=B ids=W,.. need=B,..", "vc_large: step launches=K over=O" (steps of more than one
 //                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B",
@@ -97,7 +99,7 @@ struct LWin {
     uint32_t num_codes;
     double total, avg;
     uint32_t rows, qlen, qs, type;                     // the current alignment: graph rows, query length, query (sequence index), 0 SW / 1 NW / 2 OV
-    int32_t m, x, g;
+    int32_t m, x, g, e, q, c;                          // scores; e, q, c: the affine / convex ones (mode 2), g elsewhere
     uint32_t max_i, max_j, npairs, cons_n;
     LGraph gr[2];
     int32_t *coder, *decoder;                          // [256]
@@ -124,6 +126,8 @@ struct LArgs {
     double min_conf, min_sup;
     uint32_t num_prune, mode, trim, window_type;       // mode 0 haplotype, 1 racon-linear, 2 POA group
     uint32_t algorithm;                                // mode 2: spoa::AlignmentType of every alignment (0 kSW, 1 kNW, 2 kOV)
+    uint32_t gaps;                                     // mode 2: spoa::AlignmentSubtype (0 linear, 1 affine, 2 convex); 0 elsewhere
+    int32_t gap_e, gap_q, gap_c;                       // mode 2: spoa's e, q, c after Create's subtype rule
     // k_lg_fwd / k_lg_back: windows of this launch and their matrices
     const uint32_t* list;
     const uint64_t* hoff;
@@ -570,13 +574,15 @@ __device__ bool prune_and_keep_largest(const LArgs& a, LWin& W) {
     return true;
 }
 
-// AlignmentEngine::WorstCaseAlignmentScore with e = q = c = g
-__device__ int64_t worst_case(int64_t m, int64_t gp, int64_t i, int64_t j) {
+// AlignmentEngine::WorstCaseAlignmentScore (alignment_engine.cpp:101-110); e = q = c = g gives the linear engine's
+__device__ int64_t worst_case(int64_t m, int64_t gp, int64_t ge, int64_t gq, int64_t gc, int64_t i, int64_t j) {
+    auto gap_score = [&](int64_t len) -> int64_t {
+        if (len == 0) return 0;
+        const int64_t a = gp + (len - 1) * ge, b = gq + (len - 1) * gc;
+        return a < b ? a : b;
+    };
     const int64_t d = i > j ? i - j : j - i, mn = i < j ? i : j;
-    const int64_t gs_d = d == 0 ? 0 : gp + (d - 1) * gp;
-    const int64_t gs_i = i == 0 ? 0 : gp + (i - 1) * gp;
-    const int64_t gs_j = j == 0 ? 0 : gp + (j - 1) * gp;
-    const int64_t x = -1 * (m * mn + gs_d), y = gs_i + gs_j;
+    const int64_t x = -1 * (m * mn + gap_score(d)), y = gap_score(i) + gap_score(j);
     return x < y ? x : y;
 }
 
@@ -622,7 +628,7 @@ __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
     uint32_t gi = W.cur;
     if (a.mode == 2) {                                                     // POA group: the next sequence against the whole graph
         W.qs = W.s0 + W.j;
-        W.type = a.algorithm; W.m = a.match; W.x = a.mismatch; W.g = a.gap;
+        W.type = a.algorithm; W.m = a.match; W.x = a.mismatch; W.g = a.gap; W.e = a.gap_e; W.q = a.gap_q; W.c = a.gap_c;
     } else {
         bool nw = true;
         if (W.phase == PH_BUILD) {
@@ -639,11 +645,12 @@ __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
         }
         W.type = nw ? 1 : 0;
         W.m = nw ? a.match : a.sw_match; W.x = nw ? a.mismatch : a.sw_mismatch; W.g = nw ? a.gap : a.sw_gap;
+        W.e = W.q = W.c = W.g;
     }
     const LGraph& g = W.gr[gi];
     const uint32_t N = g.n_nodes, len = (uint32_t)(a.seq_off[W.qs + 1] - a.seq_off[W.qs]);
     if (N == 0 || len == 0) return;                                       // an empty alignment
-    if (worst_case(W.m, W.g, (int64_t)len + 8, N) < (int64_t)KNEG) { fail_window(W, VC_WIN_INVALID); return; }
+    if (worst_case(W.m, W.g, W.e, W.q, W.c, (int64_t)len + 8, N) < (int64_t)KNEG) { fail_window(W, VC_WIN_INVALID); return; }
     if (g.n_rank != N) { fail_window(W, VC_WIN_INVALID); return; }      // the rows below read rank[0 .. N)
     for (uint32_t r = 0; r < N; ++r) W.node_rank[g.rank[r]] = r;
     uint32_t cnt = 0;
@@ -662,13 +669,165 @@ __device__ __forceinline__ bool better(int32_t s, uint32_t i, uint32_t j, int32_
     return s > bs || (s == bs && (i < bi || (i == bi && j < bj)));
 }
 
+// The horizontal gap of an affine / convex row as a wave scan: out[q] = max over the columns k < j of v[k] - k d, where column j =
+// j0 + q, v holds this lane's kCols columns (columns beyond len take no part) and carry the maximum over the chunks before (it
+// starts at column 0's term and is updated here).  Every lane calls it: it shuffles.
+__device__ __forceinline__ void gap_scan(const int32_t (&v)[kCols], uint32_t j0, uint32_t len, int32_t d, int64_t& carry,
+                                         int64_t (&out)[kCols]) {
+    const uint32_t lane = threadIdx.x;
+    int64_t run = TNEG;
+#pragma unroll
+    for (uint32_t q = 0; q < kCols; ++q) {
+        out[q] = run;
+        const uint32_t j = j0 + q;
+        if (j <= len) {
+            const int64_t t = (int64_t)v[q] - (int64_t)j * d;
+            if (t > run) run = t;
+        }
+    }
+    int64_t T = run;                                                   // inclusive scan of the lanes' maxima
+    for (uint32_t s = 1; s < 64; s <<= 1) {
+        const int64_t o = __shfl_up(T, s, 64);
+        if (lane >= s && o > T) T = o;
+    }
+    int64_t before = __shfl_up(T, 1, 64);
+    if (lane == 0 || carry > before) before = carry;
+    const int64_t last = __shfl(T, 63, 64);
+    if (last > carry) carry = last;
+#pragma unroll
+    for (uint32_t q = 0; q < kCols; ++q) if (before > out[q]) out[q] = before;
+}
+
+// g_align's forward pass with affine (GM 1) or convex (GM 2) gaps, sisd_alignment_engine.cpp:462-540 / :678-770 with Initialize
+// (:120-246).  The planes H, F, E (and O, Q) follow each other, (rows + 1) x (len + 1) int32 each, and hold spoa's values cell
+// for cell, the kNegativeInfinity borders and column 0's F / O chains included: the backtrack compares them for equality.
+// Per row: x[j] = max(diagonal, F[j] (, O[j]) (, 0 for kSW)) over every predecessor row, as the linear pass does; then the
+// horizontal gaps.  Since g <= e, E[j] = max(max_k<j (H[k] + g + (j - 1 - k) e), kNegativeInfinity + j e) equals the same
+// maximum over x[k] with x[0] = H[i][0]: one exclusive prefix maximum of x[k] - k e gives E and H = max(x, E).  Convex: H comes
+// out of the two scans over x, (g, e) and (q, c), but E and Q do not (E may extend a gap opened in Q and vice versa), so they
+// are scanned a second time over the final H.
+template <uint32_t GM>
+__device__ void fwd_gaps(const LArgs& a) {
+    LWin& W = a.win[a.list[blockIdx.x]];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t N = W.rows, len = W.qlen;
+    const uint64_t w = (uint64_t)len + 1, P = ((uint64_t)N + 1) * w;
+    int32_t* H = a.H + a.hoff[blockIdx.x];
+    int32_t* F = H + P;
+    int32_t* E = F + P;
+    int32_t* O = GM == 2 ? E + P : nullptr;
+    int32_t* Q = GM == 2 ? O + P : nullptr;
+    const bool sw = W.type == 0, ov = W.type == 2;
+    const int32_t m = W.m, x = W.x, gp = W.g, ge = W.e, gq = W.q, gc = W.c;
+    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    for (uint32_t j = lane; j <= len; j += 64) {                       // row 0
+        const int32_t ej = j == 0 ? 0 : gp + (int32_t)(j - 1) * ge;
+        int32_t h = ej;
+        F[j] = j == 0 ? 0 : KNEG;
+        E[j] = ej;
+        if constexpr (GM == 2) {
+            const int32_t qj = j == 0 ? 0 : gq + (int32_t)(j - 1) * gc;
+            O[j] = j == 0 ? 0 : KNEG;
+            Q[j] = qj;
+            h = max(ej, qj);
+        }
+        H[j] = (sw || j == 0) ? 0 : h;
+    }
+    __syncthreads();
+    int32_t bs = sw ? 0 : KNEG;
+    uint32_t bi = 0, bj = 0;
+    for (uint32_t r = 0; r < N; ++r) {
+        const uint64_t i = (uint64_t)r + 1;
+        const uint32_t po = W.poff[r], pe = W.poff[r + 1];
+        const uint8_t ch = W.rchar[r];
+        const bool sink = W.sink[r] != 0;
+        int32_t f0 = pe == po ? gp - ge : KNEG, o0 = pe == po ? gq - gc : KNEG;
+        for (uint32_t k = po; k < pe; ++k) {
+            f0 = max(f0, F[(uint64_t)W.prank[k] * w]);
+            if constexpr (GM == 2) o0 = max(o0, O[(uint64_t)W.prank[k] * w]);
+        }
+        f0 += ge; o0 += gc;
+        const int32_t h0 = (sw || ov) ? 0 : (GM == 2 ? max(o0, f0) : f0);
+        int32_t *Hr = H + i * w, *Fr = F + i * w, *Er = E + i * w;
+        if (lane == 0) {
+            Hr[0] = h0; Fr[0] = f0; Er[0] = KNEG;
+            if constexpr (GM == 2) { O[i * w] = o0; Q[i * w] = KNEG; }
+        }
+        // column 0's terms of the scans, kNegativeInfinity's chain (E[i][0] + j e) beside H[i][0]
+        int64_t cxe = max((int64_t)h0, (int64_t)KNEG - gp + ge), cxq = max((int64_t)h0, (int64_t)KNEG - gq + gc);
+        int64_t che = cxe, chq = cxq;
+        for (uint32_t cb = 0; cb < len; cb += 64 * kCols) {
+            const uint32_t j0 = cb + lane * kCols + 1;
+            int32_t xv[kCols];
+#pragma unroll
+            for (uint32_t q = 0; q < kCols; ++q) {
+                const uint32_t j = j0 + q;
+                xv[q] = KNEG;
+                if (j > len) continue;
+                const int32_t s = seq[j - 1] == ch ? m : x;
+                uint64_t p = pe == po ? 0 : (uint64_t)W.prank[po] * w;
+                int32_t d = H[p + j - 1] + s, f = max(H[p + j] + gp, F[p + j] + ge), o = KNEG;
+                if constexpr (GM == 2) o = max(H[p + j] + gq, O[p + j] + gc);
+                for (uint32_t k = po + 1; k < pe; ++k) {
+                    p = (uint64_t)W.prank[k] * w;
+                    d = max(d, H[p + j - 1] + s);
+                    f = max(f, max(H[p + j] + gp, F[p + j] + ge));
+                    if constexpr (GM == 2) o = max(o, max(H[p + j] + gq, O[p + j] + gc));
+                }
+                Fr[j] = f;
+                int32_t v = max(d, f);
+                if constexpr (GM == 2) { O[i * w + j] = o; v = max(v, o); }
+                if (sw) v = max(v, 0);
+                xv[q] = v;
+            }
+            int64_t se[kCols], sq[kCols];
+            int32_t hv[kCols];
+            gap_scan(xv, j0, len, ge, cxe, se);
+            if constexpr (GM == 2) gap_scan(xv, j0, len, gc, cxq, sq);
+#pragma unroll
+            for (uint32_t q = 0; q < kCols; ++q) {
+                const int64_t j = (int64_t)(j0 + q);
+                int64_t h = max((int64_t)xv[q], se[q] + (gp - ge) + j * ge);
+                if constexpr (GM == 2) h = max(h, sq[q] + (gq - gc) + j * gc);
+                hv[q] = (int32_t)h;
+            }
+            if constexpr (GM == 2) {                                   // E and Q over the final H
+                gap_scan(hv, j0, len, ge, che, se);
+                gap_scan(hv, j0, len, gc, chq, sq);
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < kCols; ++q) {
+                const uint32_t j = j0 + q;
+                if (j > len) break;
+                const int32_t h = hv[q];
+                Hr[j] = h;
+                Er[j] = (int32_t)(se[q] + (gp - ge) + (int64_t)j * ge);
+                if constexpr (GM == 2) Q[i * w + j] = (int32_t)(sq[q] + (gq - gc) + (int64_t)j * gc);
+                if (sw ? h > bs : (sink && (ov || j == len) && h > bs)) { bs = h; bi = (uint32_t)i; bj = j; }
+            }
+        }
+        __syncthreads();
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int32_t os = __shfl_xor(bs, d, 64);
+        const uint32_t oi = __shfl_xor(bi, d, 64), oj = __shfl_xor(bj, d, 64);
+        if (better(os, oi, oj, bs, bi, bj)) { bs = os; bi = oi; bj = oj; }
+    }
+    if (lane == 0) { W.max_i = bi; W.max_j = bj; }
+}
+
 // One wave per alignment (g_align's forward pass).  Row i = rank i - 1; lane l holds columns 512 c + 8 l + 1 .. + 8 of chunk c.
 // Diagonal / vertical moves from every predecessor row give x[j]; SW clamps it at 0 first (C[j] = max(0, x[j], C[j-1] + g) is the
 // plain recurrence on max(0, x)); the horizontal move H[j] = max_k<=j (x[k] + (j - k) g) is a prefix maximum of the tilted
 // T[k] = x[k] - k g, carried from chunk to chunk.  The matrix row is stored and the next row may read it after the barrier.
 // kOV: column 0 of a graph row is 0 instead of the vertical chain (so the horizontal move starts from 0), and every cell of a
-// sink row is an end-cell candidate, not only the last column.
+// sink row is an end-cell candidate, not only the last column.  GM 1 / 2: fwd_gaps.
+template <uint32_t GM>
 __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
+    if constexpr (GM != 0) {
+        fwd_gaps<GM>(a);
+        return;
+    }
     LWin& W = a.win[a.list[blockIdx.x]];
     const uint32_t lane = threadIdx.x;
     int32_t* H = a.H + a.hoff[blockIdx.x];
@@ -744,8 +903,125 @@ __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
     if (lane == 0) { W.max_i = bi; W.max_j = bj; }
 }
 
-// g_align's backtrack, one lane per alignment: diagonal from each predecessor (in in-edge order), vertical likewise, then horizontal
+// The backtrack of Affine (GM 1, sisd_alignment_engine.cpp:542-676) and Convex (GM 2, :780-925), literally: the diagonal over
+// the in-edges; then vertical (extend_up when H == F + e / O + c of a predecessor, an opening when H == H + g / + q); then
+// horizontal (extend_left from E / Q likewise); then the inner loops that emit a whole gap run.  Affine's vertical run stops on
+// F == H + g; convex's tries the extensions over every in-edge first, then the openings (prev_i = 0 when none is found).
+template <uint32_t GM>
+__device__ void back_gaps(const LArgs& a, uint32_t n) {
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    LWin& W = a.win[a.list[b]];
+    const uint64_t w = (uint64_t)W.qlen + 1, P = ((uint64_t)W.rows + 1) * w;
+    const int32_t* H = a.H + a.hoff[b];
+    const int32_t* F = H + P;
+    const int32_t* E = F + P;
+    const int32_t* O = E + P;                                          // O, Q: convex only
+    const int32_t* Q = O + P;
+    const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
+    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    const bool sw = W.type == 0, ov = W.type == 2;
+    const int32_t gp = W.g, ge = W.e, gq = W.q, gc = W.c;
+    W.npairs = 0;
+    uint32_t i = W.max_i, j = W.max_j, np = 0;
+    if (i == 0 && j == 0) return;                                          // an empty alignment
+    auto emit = [&](int32_t node, int32_t pos) -> bool {
+        if (np >= W.PC) { W.grow |= G_PAIRS; return false; }
+        W.pairs[2 * np] = node; W.pairs[2 * np + 1] = pos;
+        ++np;
+        return true;
+    };
+    for (;;) {
+        if (sw) { if (H[(uint64_t)i * w + j] == 0) break; }
+        else if (ov) { if (i == 0 || j == 0) break; }
+        else if (i == 0 && j == 0) break;
+        const int32_t Hij = H[(uint64_t)i * w + j];
+        uint32_t pi = 0, pj = 0;
+        bool found = false, up = false, left = false;
+        const uint32_t po = i ? W.poff[i - 1] : 0, pe = i ? W.poff[i] : 0;
+        const uint32_t ncand = pe > po ? pe - po : 1;
+        if (i != 0 && j != 0) {
+            const int32_t s = seq[j - 1] == W.rchar[i - 1] ? W.m : W.x;
+            for (uint32_t k = 0; k < ncand; ++k) {
+                const uint32_t p = pe > po ? W.prank[po + k] : 0;
+                if (Hij == H[(uint64_t)p * w + (j - 1)] + s) { pi = p; pj = j - 1; found = true; break; }
+            }
+        }
+        if (!found && i != 0) {
+            for (uint32_t k = 0; k < ncand; ++k) {
+                const uint64_t c = (uint64_t)(pe > po ? W.prank[po + k] : 0) * w + j;
+                if constexpr (GM == 1) found = (up = Hij == F[c] + ge) || Hij == H[c] + gp;
+                else found = (up = Hij == F[c] + ge) || Hij == H[c] + gp || (up = Hij == O[c] + gc) || Hij == H[c] + gq;
+                if (found) { pi = (uint32_t)(c / w); pj = j; break; }
+            }
+        }
+        if (!found && j != 0) {
+            const uint64_t c = (uint64_t)i * w + j - 1;
+            if constexpr (GM == 1) found = (left = Hij == E[c] + ge) || Hij == H[c] + gp;
+            else found = (left = Hij == E[c] + ge) || Hij == H[c] + gp || (left = Hij == Q[c] + gc) || Hij == H[c] + gq;
+            if (found) { pi = i; pj = j - 1; }
+        }
+        if (!found) { fail_window(W, VC_WIN_INVALID); return; }             // cannot happen on a DAG
+        if (!emit(i == pi ? -1 : (int32_t)g.rank[i - 1], j == pj ? -1 : (int32_t)j - 1)) return;
+        i = pi; j = pj;
+        if (left) {
+            for (;;) {
+                if (j == 0) { fail_window(W, VC_WIN_INVALID); return; }     // E[i][0] is kNegativeInfinity: cannot happen
+                if (!emit(-1, (int32_t)j - 1)) return;
+                --j;
+                const uint64_t c = (uint64_t)i * w + j;
+                if constexpr (GM == 1) { if (E[c] + ge != E[c + 1]) break; }
+                else { if (E[c] + ge != E[c + 1] && Q[c] + gc != Q[c + 1]) break; }
+            }
+        } else if (up) {
+            for (;;) {
+                if (i == 0) { fail_window(W, VC_WIN_INVALID); return; }     // F[0][j] is kNegativeInfinity: cannot happen
+                const uint64_t c = (uint64_t)i * w + j;
+                const uint32_t qo = W.poff[i - 1], qe = W.poff[i];
+                bool stop;
+                uint32_t prev = 0;
+                if constexpr (GM == 1) {
+                    stop = false;
+                    for (uint32_t k = qo; k < qe; ++k) {
+                        const uint64_t pc = (uint64_t)W.prank[k] * w + j;
+                        if ((stop = F[c] == H[pc] + gp) || F[c] == F[pc] + ge) { prev = W.prank[k]; break; }
+                    }
+                } else {
+                    stop = true;
+                    for (uint32_t k = qo; k < qe; ++k) {
+                        const uint64_t pc = (uint64_t)W.prank[k] * w + j;
+                        if (F[c] == F[pc] + ge || O[c] == O[pc] + gc) { prev = W.prank[k]; stop = false; break; }
+                    }
+                    if (stop) {
+                        for (uint32_t k = qo; k < qe; ++k) {
+                            const uint64_t pc = (uint64_t)W.prank[k] * w + j;
+                            if (F[c] == H[pc] + gp || O[c] == H[pc] + gq) { prev = W.prank[k]; break; }
+                        }
+                    }
+                }
+                if (!emit((int32_t)g.rank[i - 1], -1)) return;
+                i = prev;
+                if (stop || i == 0) break;
+            }
+        }
+    }
+    for (uint32_t x = 0; x < np / 2; ++x) {
+        const uint32_t y = np - 1 - x;
+        const int32_t t0 = W.pairs[2 * x], t1 = W.pairs[2 * x + 1];
+        W.pairs[2 * x] = W.pairs[2 * y]; W.pairs[2 * x + 1] = W.pairs[2 * y + 1];
+        W.pairs[2 * y] = t0; W.pairs[2 * y + 1] = t1;
+    }
+    W.npairs = np;
+}
+
+// g_align's backtrack, one lane per alignment: diagonal from each predecessor (in in-edge order), vertical likewise, then horizontal.
+// GM 1 / 2: back_gaps.
+template <uint32_t GM>
 __global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
+    if constexpr (GM != 0) {
+        back_gaps<GM>(a, n);
+        return;
+    }
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= n) return;
     LWin& W = a.win[a.list[b]];
@@ -970,6 +1246,42 @@ int check_device(int32_t device) {
 
 int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r);
 
+// vc_poa_run / vc_poa_run_gaps after their score checks: the knobs, the batch (still without the device), the device, the run.
+// `a` holds the scores.
+int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r) {
+    Knobs kn;
+    if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
+    const uint32_t nw = b->n_windows;
+    std::vector<Caps> caps(nw);
+    if (nw) {
+        if (!b->win_seq_off || !b->seq_off || !b->seq_has_qual) return fail(VC_ERR_ARG, "null array in batch");
+        if (b->win_seq_off[0] != 0) return fail(VC_ERR_ARG, "win_seq_off[0] must be 0");
+        for (uint32_t w = 0; w < nw; ++w)
+            if (b->win_seq_off[w + 1] < b->win_seq_off[w]) return fail(VC_ERR_ARG, "win_seq_off decreases");
+        const uint32_t nseq_all = b->win_seq_off[nw];
+        if (b->seq_off[0] != 0) return fail(VC_ERR_ARG, "seq_off[0] must be 0");
+        bool any_qual = false;
+        for (uint32_t s = 0; s < nseq_all; ++s) {
+            if (b->seq_off[s + 1] < b->seq_off[s]) return fail(VC_ERR_ARG, "seq_off decreases");
+            if (b->seq_off[s + 1] - b->seq_off[s] >= 65535) return fail(VC_ERR_ARG, "sequence length unsupported (at most 65 534 bases)");
+            any_qual |= b->seq_has_qual[s] != 0;
+        }
+        if (b->seq_off[nseq_all] && !b->bases) return fail(VC_ERR_ARG, "null bases");
+        if (b->seq_off[nseq_all] && any_qual && !b->quals) return fail(VC_ERR_ARG, "null quals beside seq_has_qual");
+        for (uint32_t w = 0; w < nw; ++w) {
+            const uint32_t s0 = b->win_seq_off[w], s1 = b->win_seq_off[w + 1];
+            uint64_t mx = 0;
+            for (uint32_t s = s0; s < s1; ++s) mx = std::max<uint64_t>(mx, b->seq_off[s + 1] - b->seq_off[s]);
+            caps[w] = initial_caps(b->seq_off[s1] - b->seq_off[s0], mx, s1 - s0, kn);
+        }
+    }
+    if (const int rc = check_device(device)) return rc;
+    r->cons_off[0] = 0;
+    if (nw == 0) return VC_OK;
+    a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)algorithm;
+    return run_windows(device, a, b, caps, false, false, kn, r);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1023,38 +1335,27 @@ int vc_poa_run(const vc_poa_params* p, const vc_batch* b, vc_result* r) {
     if (p->gap > 0) return fail(VC_ERR_ARG, "gap must be <= 0 (linear gaps: spoa's gap opening penalty must be non-positive)");
     for (const int32_t s : {p->match, p->mismatch, p->gap})
         if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
-    Knobs kn;
-    if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
-    const uint32_t nw = b->n_windows;
-    std::vector<Caps> caps(nw);
-    if (nw) {
-        if (!b->win_seq_off || !b->seq_off || !b->seq_has_qual) return fail(VC_ERR_ARG, "null array in batch");
-        if (b->win_seq_off[0] != 0) return fail(VC_ERR_ARG, "win_seq_off[0] must be 0");
-        for (uint32_t w = 0; w < nw; ++w)
-            if (b->win_seq_off[w + 1] < b->win_seq_off[w]) return fail(VC_ERR_ARG, "win_seq_off decreases");
-        const uint32_t nseq_all = b->win_seq_off[nw];
-        if (b->seq_off[0] != 0) return fail(VC_ERR_ARG, "seq_off[0] must be 0");
-        bool any_qual = false;
-        for (uint32_t s = 0; s < nseq_all; ++s) {
-            if (b->seq_off[s + 1] < b->seq_off[s]) return fail(VC_ERR_ARG, "seq_off decreases");
-            if (b->seq_off[s + 1] - b->seq_off[s] >= 65535) return fail(VC_ERR_ARG, "sequence length unsupported (at most 65 534 bases)");
-            any_qual |= b->seq_has_qual[s] != 0;
-        }
-        if (b->seq_off[nseq_all] && !b->bases) return fail(VC_ERR_ARG, "null bases");
-        if (b->seq_off[nseq_all] && any_qual && !b->quals) return fail(VC_ERR_ARG, "null quals beside seq_has_qual");
-        for (uint32_t w = 0; w < nw; ++w) {
-            const uint32_t s0 = b->win_seq_off[w], s1 = b->win_seq_off[w + 1];
-            uint64_t mx = 0;
-            for (uint32_t s = s0; s < s1; ++s) mx = std::max<uint64_t>(mx, b->seq_off[s + 1] - b->seq_off[s]);
-            caps[w] = initial_caps(b->seq_off[s1] - b->seq_off[s0], mx, s1 - s0, kn);
-        }
-    }
-    if (const int rc = check_device(p->device)) return rc;
-    r->cons_off[0] = 0;
-    if (nw == 0) return VC_OK;
     LArgs a{};
-    a.match = p->match; a.mismatch = p->mismatch; a.gap = p->gap; a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)p->algorithm;
-    return run_windows(p->device, a, b, caps, false, false, kn, r);
+    a.match = p->match; a.mismatch = p->mismatch; a.gap = p->gap; a.gap_e = a.gap_q = a.gap_c = p->gap; a.gaps = 0;
+    return run_groups(p->device, p->algorithm, a, b, r);
+}
+
+int vc_poa_run_gaps(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r) {
+    // the arguments first, in AlignmentEngine::Create's order (alignment_engine.cpp:39-57; spoa takes the scores as int8_t)
+    if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+    if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
+    if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
+    if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
+    for (const int32_t s : {p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_open2, p->gap_extend2})
+        if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
+    // the subtype and its scores (alignment_engine.cpp:59-69)
+    int32_t g = p->gap_open, e = p->gap_extend, q = p->gap_open2, c = p->gap_extend2;
+    const uint32_t gaps = g >= e ? 0 : (g <= q || e >= c ? 1 : 2);
+    if (gaps == 0) e = g;
+    else if (gaps == 1) { q = g; c = e; }
+    LArgs a{};
+    a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
+    return run_groups(p->device, p->algorithm, a, b, r);
 }
 
 }  // extern "C"
@@ -1099,6 +1400,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
     for (uint32_t w = 0; w < nw; ++w) pending[w] = w;
     uint32_t *d_list = nullptr; uint64_t* d_hoff = nullptr; LWin* d_win = nullptr;
     uint64_t n_align = 0, n_cells = 0;                                     // forward passes run (VC_LARGE_LOG's "done" line)
+    const uint64_t planes = a.gaps == 0 ? 1 : a.gaps == 1 ? 3 : 5;         // int32 planes per matrix cell: H (, F, E (, O, Q))
     while (!pending.empty()) {
         // windows in flight: as many as the arena budget holds, in order (at least one)
         std::vector<uint32_t> grp;
@@ -1163,6 +1465,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
             }
             if (!live) break;
             // matrices of this step, in launches that fit the budget; a matrix the device cannot hold takes its window out
+            // (cells counts int32 cells of every plane)
             uint32_t launches = 0, over = 0;
             for (size_t k0 = 0; k0 < act.size() && ok;) {
                 std::vector<uint32_t> list;
@@ -1171,7 +1474,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
                 size_t k1 = k0;
                 for (; k1 < act.size(); ++k1) {
                     const LWin& W = hw[act[k1]];
-                    const uint64_t need = ((uint64_t)W.rows + 1) * ((uint64_t)W.qlen + 1);
+                    const uint64_t need = ((uint64_t)W.rows + 1) * ((uint64_t)W.qlen + 1) * planes;
                     if (!list.empty() && (cells + need) * 4 > mat_budget) break;
                     list.push_back(act[k1]); hoff.push_back(cells); cells += need;
                 }
@@ -1190,8 +1493,17 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
                 if (!ok) break;
                 LArgs f = a;
                 f.list = d_list; f.hoff = d_hoff; f.H = H;
-                hipLaunchKernelGGL(k_lg_fwd, dim3(nl), dim3(64), 0, 0, f);
-                hipLaunchKernelGGL(k_lg_back, dim3((nl + 63) / 64), dim3(64), 0, 0, f, nl);
+                const dim3 fb(nl), bb((nl + 63) / 64);
+                if (a.gaps == 0) {
+                    hipLaunchKernelGGL(k_lg_fwd<0>, fb, dim3(64), 0, 0, f);
+                    hipLaunchKernelGGL(k_lg_back<0>, bb, dim3(64), 0, 0, f, nl);
+                } else if (a.gaps == 1) {
+                    hipLaunchKernelGGL(k_lg_fwd<1>, fb, dim3(64), 0, 0, f);
+                    hipLaunchKernelGGL(k_lg_back<1>, bb, dim3(64), 0, 0, f, nl);
+                } else {
+                    hipLaunchKernelGGL(k_lg_fwd<2>, fb, dim3(64), 0, 0, f);
+                    hipLaunchKernelGGL(k_lg_back<2>, bb, dim3(64), 0, 0, f, nl);
+                }
                 ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
                 for (const uint32_t k : list) n_cells += (uint64_t)hw[k].rows * hw[k].qlen;
                 n_align += nl;

@@ -1,15 +1,19 @@
 """Consensus of read groups on the device: spoa's public flow (AlignmentEngine::Create, Align + Graph::AddAlignment per
-sequence in the order given, GenerateConsensus) for every group of a batch, over the C ABI `vc_poa_run` (schedule 2 of
-vechat_amd/csrc/vc_large.hip; include/vechat_hip.h has the semantics).  Local (kSW), global (kNW) and semi-global (kOV)
-alignment with linear gaps; no window rules.  No CPU path: without a device the calls raise.
+sequence in the order given, GenerateConsensus) for every group of a batch, over the C ABI `vc_poa_run` / `vc_poa_run_gaps`
+(schedule 2 of vechat_amd/csrc/vc_large.hip; include/vechat_hip.h has the semantics).  Local (kSW), global (kNW) and
+semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chosen from the gap scores as spoa chooses it
+(gap_model); no window rules.  No CPU path: without a device the calls raise.
 
-    python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [-l 0|1|2] [--device D] FILE [FILE ...]
+    python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [--device D]
+                             FILE [FILE ...]
 
 prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`.
 The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
 as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
 non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
-consensus sequences.  poa_consensus() takes sequences and qualities as given.
+consensus sequences.  poa_consensus() takes sequences and qualities as given.  spoa's -e / -q / -c are spelt --gap-extend /
+--gap-open2 / --gap-extend2 here, and the gaps stay linear unless they are given (spoa's own command line defaults to convex gaps,
+-g -8 -e -6 -q -10 -c -4).
 """
 import argparse
 import ctypes as C
@@ -42,6 +46,19 @@ def algorithm_code(algorithm):
     if isinstance(algorithm, (int, np.integer)) and not isinstance(algorithm, bool) and int(algorithm) in (0, 1, 2):
         return int(algorithm)
     raise ValueError(f"algorithm must be 0, 1, 2 or one of {sorted(ALGORITHMS)}, not {algorithm!r}")
+
+
+def gap_model(g, e=None, q=None, c=None):
+    """spoa's subtype rule (AlignmentEngine::Create, alignment_engine.cpp:15-69) -> ("linear" | "affine" | "convex", g, e, q, c)
+    with the scores the engine then uses.  Left out, e = g, q = g and c = e, as in spoa's shorter overloads."""
+    e = g if e is None else e
+    q = g if q is None else q
+    c = e if c is None else c
+    if g >= e:
+        return "linear", g, g, q, c
+    if g <= q or e >= c:
+        return "affine", g, e, g, e
+    return "convex", g, e, q, c
 
 
 def _bytes(x, what):
@@ -90,8 +107,8 @@ def group_batch(groups):
 
 
 def run_batch(batch, params, lib=None):
-    """vc_poa_run on a capi.Batch (its seq_begin / seq_end / win_fasta are passed as NULL) -> (consensus bytes per group, status
-    array).  Raises PoaError on a library error."""
+    """vc_poa_run (params: capi.VcPoaParams) or vc_poa_run_gaps (capi.VcPoaGapParams) on a capi.Batch (its seq_begin / seq_end /
+    win_fasta are passed as NULL) -> (consensus bytes per group, status array).  Raises PoaError on a library error."""
     lib = lib or capi.load_hip()
     n = batch.n_windows
     cons = np.zeros(max(int(batch.bases.size), 1), np.uint8)       # a group's consensus is never longer than its sequences
@@ -101,18 +118,29 @@ def run_batch(batch, params, lib=None):
                       status.ctypes.data_as(C.POINTER(C.c_uint8)))
     vb = batch.as_struct()
     vb.seq_begin = vb.seq_end = vb.win_fasta = None
-    rc = lib.vc_poa_run(C.byref(params), C.byref(vb), C.byref(r))
+    name = "vc_poa_run_gaps" if isinstance(params, capi.VcPoaGapParams) else "vc_poa_run"
+    rc = getattr(lib, name)(C.byref(params), C.byref(vb), C.byref(r))
     if rc != 0:
-        raise PoaError(f"vc_poa_run failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+        raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     return [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n]
 
 
-def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None):
+def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+                  gap_extend=None, gap_open2=None, gap_extend2=None):
     """Consensus of every group -> list of bytes.  The defaults are spoa's -m / -n / -g.  A group the device could not compute
     (VC_WIN_INVALID: the reference throws on it; VC_WIN_OVERFLOW: too large for the device memory) raises PoaError with the
-    indices, or with strict=False comes back as None."""
+    indices, or with strict=False comes back as None.
+    gap_extend / gap_open2 / gap_extend2 are spoa's e / q / c: all None runs linear gaps through vc_poa_run; otherwise
+    vc_poa_run_gaps with spoa's overload defaults (gap_extend = gap, gap_open2 = gap, gap_extend2 = gap_extend), whose subtype
+    follows gap_model()."""
     batch = group_batch(groups)
-    p = capi.VcPoaParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap=gap)
+    if gap_extend is None and gap_open2 is None and gap_extend2 is None:
+        p = capi.VcPoaParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap=gap)
+    else:
+        e = gap if gap_extend is None else gap_extend
+        p = capi.VcPoaGapParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap_open=gap,
+                                gap_extend=e, gap_open2=gap if gap_open2 is None else gap_open2,
+                                gap_extend2=e if gap_extend2 is None else gap_extend2)
     cons, status = run_batch(batch, p, lib)
     bad = {w: int(s) for w, s in enumerate(status) if int(s) != capi.VC_WIN_OK}
     if bad and strict:
@@ -126,11 +154,18 @@ def parse_args(argv=None):
         prog="python -m vechat_amd.poa",
         description="Partial-order consensus of each FASTA/FASTQ(.gz) file on the device, as spoa computes it (one file = one group; "
                     "records in file order, quality strings as weights; read as the polisher reads them: upper-cased, an all-'!' quality "
-                    "string counts as none). Gaps are linear only: spoa's -e / -q / -c (affine and convex "
-                    "gaps) are not accepted.")
+                    "string counts as none). Gaps are linear unless --gap-extend / --gap-open2 / --gap-extend2 are given (spoa's -e / -q / "
+                    "-c, which this command does not take as such); spoa's own defaults are -g -8 --gap-extend -6 --gap-open2 -10 "
+                    "--gap-extend2 -4 (convex gaps).")
     ap.add_argument("-m", type=int, default=5, help="score for matching bases (default 5)")
     ap.add_argument("-n", type=int, default=-4, help="score for mismatching bases (default -4)")
-    ap.add_argument("-g", type=int, default=-8, help="linear gap penalty, <= 0 (default -8)")
+    ap.add_argument("-g", type=int, default=-8, help="gap opening penalty, <= 0 (default -8)")
+    ap.add_argument("--gap-extend", type=int, default=None, metavar="E",
+                    help="gap extension penalty, <= 0 (spoa's -e; default: -g, linear gaps)")
+    ap.add_argument("--gap-open2", type=int, default=None, metavar="Q",
+                    help="gap opening penalty of the second affine model, <= 0 (spoa's -q; default: -g)")
+    ap.add_argument("--gap-extend2", type=int, default=None, metavar="C",
+                    help="gap extension penalty of the second affine model, <= 0 (spoa's -c; default: --gap-extend)")
     ap.add_argument("-l", type=int, default=0, choices=(0, 1, 2), help="alignment mode: 0 local (SW), 1 global (NW), 2 semi-global (OV); default 0")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="+", metavar="FILE")
@@ -142,7 +177,8 @@ def main(argv=None):
     from . import seqio
     try:
         groups = [[(data, qual) for _, data, qual in seqio.read_sequences(f)] for f in a.files]
-        cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device)
+        cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device, gap_extend=a.gap_extend, gap_open2=a.gap_open2,
+                             gap_extend2=a.gap_extend2)
     except (PoaError, ValueError, OSError) as e:
         print(f"vechat_amd.poa: {e}", file=sys.stderr)
         return 1
