@@ -407,6 +407,45 @@ typedef struct vc_poa_gap_params {
 } vc_poa_gap_params;
 int         vc_poa_run_gaps(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r);
 
+/* The multiple sequence alignment and the per-base coverage of every group: beside the consensus, what
+ *     graph.GenerateMultipleSequenceAlignment(include_consensus)                         graph.cpp:393-448 (spoa -r 1 / -r 2)
+ *     graph.GenerateConsensus(&summary, false)                                           graph.cpp:461-485
+ * return for the graph of the same flow.  p, b and r as vc_poa_run_gaps (a parameter set that selects linear gaps gives
+ * vc_poa_run's bytes); o->flags selects the outputs and is the only field read:
+ *     VC_POA_MSA            one row per sequence that was added, in the order given: '-' or the sequence's base per column
+ *     VC_POA_MSA_CONSENSUS  (with VC_POA_MSA) one more row, the last, with the consensus
+ *     VC_POA_COVERAGE       per consensus base, the number of sequences through its node and the nodes aligned to it
+ * With flags == 0 the call is vc_poa_run_gaps: no labels kept, no extra kernel, every pointer of o NULL.
+ * An empty sequence is never added (graph.cpp:187-190) and has no row, so row_member names the group member of every row
+ * (index within the group; VC_POA_ROW_CONSENSUS for the consensus row).  A group that is VC_WIN_INVALID or VC_WIN_OVERFLOW has
+ * n_rows = 0; a group without a non-empty sequence is VC_WIN_OK with row_size 0 and no row, or with VC_POA_MSA_CONSENSUS the one
+ * consensus row of length 0, as the reference returns it.
+ * Row i of group w is the row_size[w] bytes at rows + row_off[w] + i * row_size[w] (not NUL-terminated; blocks follow no
+ * order and other bytes lie between them); its member is row_member[member_off[w] + i]; the coverage of consensus base k of
+ * group w is coverage[r->cons_off[w] + k].
+ * Lifetime: the library owns every array o points to.  They stay valid until the next vc_poa_* or vc_large_* call or
+ * vc_large_release, whichever comes first (one set per process; like the buffer cache it is not thread-safe); copy what
+ * must live longer.  A failed call leaves every pointer NULL.
+ * Checked before the device, in this order: as vc_poa_run_gaps up to the scores, then flag bits other than the three above or
+ * VC_POA_MSA_CONSENSUS without VC_POA_MSA, then the batch: VC_ERR_ARG. */
+#define VC_POA_MSA            1u
+#define VC_POA_MSA_CONSENSUS  2u
+#define VC_POA_COVERAGE       4u
+#define VC_POA_ROW_CONSENSUS  0xFFFFFFFFu
+typedef struct vc_poa_msa_out {
+    uint32_t flags;                 /* in: VC_POA_* bits                                                            */
+    uint32_t n_groups;              /* out: b->n_windows                                                            */
+    const uint32_t* n_rows;         /* [n_groups]                                                                   */
+    const uint32_t* row_size;       /* [n_groups] columns of the group's alignment                                  */
+    const uint64_t* row_off;        /* [n_groups] offset of the group's row block in rows                           */
+    const uint64_t* member_off;     /* [n_groups + 1] first entry of the group in row_member (prefix sums of n_rows) */
+    const uint32_t* row_member;     /* [member_off[n_groups]]                                                       */
+    const uint8_t*  rows;
+    uint64_t        rows_bytes;     /* bytes behind rows                                                            */
+    const uint32_t* coverage;       /* [r->cons_off[n_groups]], or NULL without VC_POA_COVERAGE                     */
+} vc_poa_msa_out;
+int         vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o);
+
 #ifdef __cplusplus
 }
 #endif

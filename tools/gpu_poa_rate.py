@@ -10,7 +10,13 @@ libvcref_sse41.so, vcref_spoa_consensus) on a sample of the same groups on 16 ho
 compared with the device's.
 
   python tools/gpu_poa_rate.py [--groups 4096] [--len 1000] [--depth 32] [--cpu-sample 256] [--out profiles/poa_rate.txt]
-                               [--gaps linear|affine|convex]
+                               [--gaps linear|affine|convex] [--msa]
+
+--msa measures the multiple sequence alignment instead (vc_poa_run_msa with the consensus row and the coverage, global
+alignment) and writes profiles/poa_msa_rate.txt: after one warm-up call on all groups, three consensus-only calls and three
+MSA calls in the same process, then each kind once under `rocprofv3 --kernel-trace --stats` (kernel trace only) for k_lg_apply's
+and k_lg_msa's kernel time -- the label bookkeeping shows as the difference of k_lg_apply between the two traces, and what the
+MSA call's wall time exceeds the consensus-only one's beyond the kernels is the copy-out and the host's assembly.
 
 --gaps affine / convex runs vc_poa_run_gaps with spoa's affine known-answer scores (5 -4 -8 -6) or its command-line defaults
 (5 -4 -8 -6 -10 -4, convex); the cells are still rows x columns (not x planes).  The reference in oracle/_ref only takes linear
@@ -89,8 +95,98 @@ def kernel_shares(trace_dir):
     return dict(ms)
 
 
+def timed_msa(batch, flags):
+    """-> (seconds, rows_bytes, alignments, cells) of one vc_poa_run_msa (global, 5/-4/-8 linear) on the batch"""
+    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
+    import ctypes as C
+    import tempfile
+    import numpy as np
+    lib = capi.load_hip()
+    n = batch.n_windows
+    cons, off, status = np.zeros(int(batch.bases.size), np.uint8), np.zeros(n + 1, np.uint64), np.zeros(n, np.uint8)
+    r = capi.VcResult(off.ctypes.data_as(C.POINTER(C.c_uint64)), cons.ctypes.data_as(C.POINTER(C.c_uint8)), cons.size,
+                      status.ctypes.data_as(C.POINTER(C.c_uint8)))
+    vb = batch.as_struct()
+    o = capi.VcPoaMsaOut(flags=flags)
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            rc = lib.vc_poa_run_msa(C.byref(p), C.byref(vb), C.byref(r), C.byref(o))
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read().decode()
+    if rc != 0 or int((status != 0).sum()):
+        raise RuntimeError(f"vc_poa_run_msa: rc {rc}, {int((status != 0).sum())} groups not computed")
+    done = [l for l in err.splitlines() if l.startswith("vc_large: done")][-1]
+    kv = dict(t.split("=") for t in done.split()[2:])
+    return dt, int(o.rows_bytes), int(kv["alignments"]), int(kv["cells"])
+
+
+def main_msa(a):
+    batch = synth_groups(a)
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_msa_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    emit(f"POA groups with the MSA: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100, PacBio-like errors, frac_partial=0, FASTQ), "
+         f"{int(batch.seq_off[-1])} bases; 5/-4/-8, global (kNW); one MI355X; vc_poa_run_msa, synchronous; host clock around one call; "
+         f"one untimed call on all groups first, then three calls of each kind in the same process")
+    timed_msa(batch, 0)
+    plain = [timed_msa(batch, 0) for _ in range(3)]
+    full = [timed_msa(batch, 7) for _ in range(3)]
+    for name, runs in (("consensus only (flags 0)", plain), ("MSA + consensus row + coverage (flags 7)", full)):
+        emit(f"{name:42s} " + "  ".join(f"{a.groups / r[0]:7.1f}" for r in runs) + f" groups/s  ({'  '.join(f'{r[0]:.2f}' for r in runs)} s; "
+             f"{runs[0][2]} alignments, {runs[0][3] / 1e9:.2f} G cells, output blocks {runs[0][1] / 1e6:.1f} MB)")
+    mp, mf = min(r[0] for r in plain), min(r[0] for r in full)
+    emit(f"MSA / consensus-only rate (best of three each): {mp / mf:.3f}; the MSA call takes {mf - mp:.2f} s longer")
+    large.release()
+    if a.no_trace:
+        return
+    emit("kernel times, each kind's call in a run of its own under rocprofv3 --kernel-trace --stats (a fresh process: 64 groups first, then all):")
+    traced = {}
+    for kind, flags in (("consensus only", 0), ("MSA", 7)):
+        d = os.path.join(a.trace_dir, f"msa{flags}")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+               sys.executable, os.path.abspath(__file__), "--child", str(flags), "--msa", "--groups", str(a.groups), "--len", str(a.len),
+               "--depth", str(a.depth)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"  {kind}: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return
+        ms = kernel_shares(d)
+        traced[flags] = ms
+        wall = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+        emit(f"  {kind:15s} kernels {sum(ms.values()) / 1e3:.2f} s of {wall:.2f} s wall: " +
+             ", ".join(f"{k} {v / 1e3:.3f} s" for k, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+    ap0 = sum(v for k, v in traced[0].items() if k.startswith("k_lg_apply"))
+    ap7 = sum(v for k, v in traced[7].items() if k.startswith("k_lg_apply"))
+    km = sum(v for k, v in traced[7].items() if k.startswith("k_lg_msa"))
+    emit(f"(i) label bookkeeping: k_lg_apply {ap0 / 1e3:.3f} s without, {ap7 / 1e3:.3f} s with labels (+{(ap7 - ap0) / 1e3:.3f} s, the 64-group "
+         f"warm-up included in both); (ii) k_lg_msa, both phases: {km / 1e3:.3f} s = {km / ap7 * 100:.2f} % of k_lg_apply's time in the same trace; "
+         f"(iii) copy-out and host assembly: what remains of the {mf - mp:.2f} s above, about {mf - mp - (ap7 - ap0 + km) / 1e3:.2f} s "
+         f"for {full[0][1] / 1e6:.1f} MB")
+    print("wrote", out)
+
+
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    if a.msa:
+        batch = synth_groups(a)
+        timed_msa(batch.slice(0, min(64, batch.n_windows)), a.child)
+        dt, nbytes, n_al, cells = timed_msa(batch, a.child)
+        print(json.dumps(dict(seconds=dt, alignments=n_al, cells=cells, bytes=nbytes)))
+        return
     batch = synth_groups(a)
     dt, _, status, n_al, cells = timed(batch, a.child, "small", a.gaps)
     print(json.dumps(dict(seconds=dt, alignments=n_al, cells=cells, ok=int((status == 0).sum()))))
@@ -121,10 +217,13 @@ def main():
     ap.add_argument("--trace-dir", default="/tmp/poa_rate_trace")
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--gaps", choices=sorted(GAPS), default="linear")
+    ap.add_argument("--msa", action="store_true", help="measure vc_poa_run_msa beside the consensus-only call (profiles/poa_msa_rate.txt)")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
         return child(a)
+    if a.msa:
+        return main_msa(a)
     batch = synth_groups(a)
     bases = int(batch.seq_off[-1])
     scores, entry = ("5/-4/-8", "vc_poa_run") if GAPS[a.gaps] is None else \

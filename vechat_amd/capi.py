@@ -71,6 +71,22 @@ class VcPoaGapParams(C.Structure):
     ]
 
 
+VC_POA_MSA, VC_POA_MSA_CONSENSUS, VC_POA_COVERAGE = 1, 2, 4
+VC_POA_ROW_CONSENSUS = 0xFFFFFFFF
+
+
+class VcPoaMsaOut(C.Structure):
+    """vc_poa_msa_out: flags in, the rest out and owned by the library until its next vc_poa_* / vc_large_* call"""
+    _fields_ = [
+        ("flags", C.c_uint32), ("n_groups", C.c_uint32),
+        ("n_rows", C.POINTER(C.c_uint32)), ("row_size", C.POINTER(C.c_uint32)),
+        ("row_off", C.POINTER(C.c_uint64)), ("member_off", C.POINTER(C.c_uint64)),
+        ("row_member", C.POINTER(C.c_uint32)),
+        ("rows", C.POINTER(C.c_uint8)), ("rows_bytes", C.c_uint64),
+        ("coverage", C.POINTER(C.c_uint32)),
+    ]
+
+
 class VcStats(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64), ("alignments", C.c_uint64), ("dp_rows", C.c_uint64),
@@ -334,6 +350,8 @@ def load_hip():
         lib.vc_poa_last_error.argtypes = []; lib.vc_poa_last_error.restype = C.c_char_p
         lib.vc_poa_run_gaps.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult)]
         lib.vc_poa_run_gaps.restype = C.c_int
+        lib.vc_poa_run_msa.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut)]
+        lib.vc_poa_run_msa.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

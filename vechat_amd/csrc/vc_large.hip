@@ -41,6 +41,8 @@
 //   k_lg_apply  one lane per window: add-alignment + topological sort, or add-weights; prune + largest component at the end of
 //               the build and of every round; the corrected sequence (mode 0), heaviest bundle + coverage + trim (mode 1) or the
 //               heaviest bundle alone (mode 2).
+//   k_lg_msa    vc_poa_run_msa only, one wave per finished group: <0> node -> column by a wave prefix sum over the topological
+//               order, <1> the rows ('-' fill, then a scatter over the edge labels), the consensus row and the coverage.
 //
 // Limits, every schedule: a sequence is shorter than 65 535 bases; beyond that only the device memory bounds a window or group,
 // and one whose tables or matrix it cannot hold at all comes back VC_WIN_OVERFLOW.  Where the reference throws (an invalid
@@ -55,6 +57,7 @@
 //   VC_LARGE_LOG=1          one stderr line per event: "vc_large: regrow window=W flags=nodes,... caps n=.. e=.. a=.. l=.. s=.. p=..",
 //                           "vc_large: group windows=N bytes=B ids=W,.. need=B,..", "vc_large: step launches=K over=O" (steps of more than one
 //                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B",
+//                           "vc_large: msa launches=K bytes=B" (vc_poa_run_msa with flags: k_lg_msa<1> launches, bytes copied out),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes run, their rows x columns
 //                           summed; a regrown window's are counted again).
 #include <hip/hip_runtime.h>
@@ -82,7 +85,7 @@ enum : uint32_t { G_NODES = 1, G_EDGES = 2, G_ALIGNED = 4, G_LABELS = 8, G_STACK
 
 struct LGraph {
     uint32_t n_nodes, n_edges, n_al, n_lb, n_rank, nseq;
-    uint32_t labels;                                   // 1: edges keep sequence labels (only the racon-linear overload's coverage reads them)
+    uint32_t labels;                                   // 1: edges keep sequence labels (the racon-linear overload's coverage and k_lg_msa read them)
     uint8_t* code;                                     // [NC]
     uint32_t *in_h, *in_t, *in_n, *out_h, *out_t, *out_n, *al_h, *al_t, *al_n, *rank;   // [NC]
     uint32_t *tail, *head, *nx_in, *nx_out, *lb_h, *lb_t;                               // [EC]
@@ -112,6 +115,9 @@ struct LWin {
     uint32_t *poff, *prank;                            // [NC + 1], [EC]
     int32_t* pairs;                                    // [2 PC]
     uint8_t* cons;                                     // [NC]
+    // vc_poa_run_msa only (nullptr otherwise): spoa's sequences_, one entry per sequence that was added (label = index)
+    uint32_t *sq_begin, *sq_member;                    // [nseq] begin node; index of the group member
+    uint32_t msa_rows, row_size;                       // k_lg_msa<0>: rows and columns of the group's alignment
 };
 
 struct LArgs {
@@ -128,10 +134,12 @@ struct LArgs {
     uint32_t algorithm;                                // mode 2: spoa::AlignmentType of every alignment (0 kSW, 1 kNW, 2 kOV)
     uint32_t gaps;                                     // mode 2: spoa::AlignmentSubtype (0 linear, 1 affine, 2 convex); 0 elsewhere
     int32_t gap_e, gap_q, gap_c;                       // mode 2: spoa's e, q, c after Create's subtype rule
-    // k_lg_fwd / k_lg_back: windows of this launch and their matrices
+    uint32_t msa;                                      // mode 2: VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE, 0 elsewhere
+    // k_lg_fwd / k_lg_back: windows of this launch and their matrices (k_lg_msa<1>: groups and the byte offsets of their blocks)
     const uint32_t* list;
     const uint64_t* hoff;
     int32_t* H;
+    uint8_t* msa_out;
 };
 
 // ------------------------------------------------------------------ graph tables
@@ -271,6 +279,7 @@ __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* 
     uint32_t first;
     if (np == 0) {
         if (!add_chain(a, W, g, s, uq, 0, len, &first)) return -2;
+        if (W.sq_begin) { W.sq_begin[g.nseq] = first; W.sq_member[g.nseq] = s - W.s0; }
         g.nseq++;
         return toposort(W, g) ? 0 : -2;
     }
@@ -320,6 +329,7 @@ __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* 
         prev = curr;
     }
     if (last != NONE && !add_edge(W, g, prev, last, weight_of(a, s, vback, uq) + weight_of(a, s, vback + 1, uq))) return -2;
+    if (W.sq_begin) { W.sq_begin[g.nseq] = begin; W.sq_member[g.nseq] = s - W.s0; }   // sequences_.emplace_back(begin), graph.cpp:296
     g.nseq++;
     return toposort(W, g) ? 0 : -2;
 }
@@ -594,8 +604,9 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     for (int c = 0; c < 256; ++c) { W.coder[c] = -1; W.decoder[c] = -1; }
     W.num_codes = 0;
     reset_graph(W.gr[0]); reset_graph(W.gr[1]);
-    W.gr[0].labels = a.mode == 1; W.gr[1].labels = 0;
+    W.gr[0].labels = a.mode == 1 || a.msa != 0; W.gr[1].labels = 0;
     W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
+    W.msa_rows = 0; W.row_size = 0;
     if (a.mode == 2) {                                                     // POA group: sequence 0 meets the empty graph in k_lg_prep
         W.phase = PH_BUILD; W.j = 0; W.k = 0;
         if (W.nseq == 0) finish_poa(W);                                    // no sequence: the empty consensus
@@ -1117,6 +1128,98 @@ __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
     }
 }
 
+// Graph::GenerateMultipleSequenceAlignment (graph.cpp:393-448) and the summary of GenerateConsensus(&summary, false)
+// (graph.cpp:476-484) of a finished POA group: one wave per group, no lane-serial stage.
+//   PH 0, every group in flight: node -> column (InitializeMultipleSequenceAlignment) into W.map, W.row_size, W.msa_rows.  The
+//     topological sort emits an aligned group as one block, the leader followed by its aligned list, and the reference gives a
+//     block one column.  Aligned nodes are mutually aligned (add_alignment joins a new node to the whole group), so position i
+//     opens a block exactly when rank[i - 1] is not an aligned node of rank[i]: a flag per position, a wave prefix sum over
+//     tiles of 64 positions with a carried total, column = prefix - 1.
+//   PH 1, the groups of a.list, block at a.msa_out + a.hoff[blockIdx.x]: msa_rows x row_size bytes, then (16-byte aligned)
+//     msa_rows uint32, the group member of every row, then (16-byte aligned, VC_POA_COVERAGE) cons_n uint32.  The rows are filled with '-' by 16-byte stores, then the bases are scattered: the
+//     reference walks Successor(i) from sequences_[i], which visits the begin node and the head of every edge that carries label
+//     i -- a sequence's path has, at each of its nodes, exactly one out-edge with its label, and meets a node once -- so
+//     row[label][column[head]] = decoder[code[head]] over all label cells writes the same bytes without the dependent chain.
+//     Coverage: Node::Coverage() counts the distinct labels of a node's in- and out-edges.  A sequence enters and leaves a
+//     node once, so no label repeats among the in-edges nor among the out-edges, and a label on an out-edge is missing from the
+//     in-edges exactly when the sequence begins at the node: the count is the in-edge label cells plus the out-edge cells
+//     whose sequence begins here.  Lanes take consensus positions.
+template <uint32_t PH>
+__global__ __launch_bounds__(64) void k_lg_msa(LArgs a) {
+    const uint32_t lane = threadIdx.x;
+    if constexpr (PH == 0) {
+        LWin& W = a.win[blockIdx.x];
+        if (W.phase != PH_DONE || W.grow || W.status != VC_WIN_OK) return;
+        const LGraph& g = W.gr[W.cur];
+        if (!(a.msa & VC_POA_MSA)) return;
+        const uint32_t N = g.n_rank;
+        uint32_t carry = 0;
+        for (uint32_t base = 0; base < N; base += 64) {
+            const uint32_t i = base + lane;
+            uint32_t v = NONE, x = 0;
+            if (i < N) {
+                v = g.rank[i];
+                x = 1;
+                if (i > 0) {
+                    const uint32_t p = g.rank[i - 1];
+                    for (uint32_t q = g.al_h[v]; q != NONE; q = g.al_nx[q]) if (g.al_v[q] == p) { x = 0; break; }
+                }
+            }
+            for (uint32_t d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(x, d, 64);
+                if (lane >= d) x += o;
+            }
+            if (i < N) W.map[v] = carry + x - 1;
+            carry += __shfl(x, 63, 64);
+        }
+        if (lane == 0) { W.row_size = carry; W.msa_rows = g.nseq + ((a.msa & VC_POA_MSA_CONSENSUS) ? 1u : 0u); }
+    } else {
+        LWin& W = a.win[a.list[blockIdx.x]];
+        const LGraph& g = W.gr[W.cur];
+        uint8_t* out = a.msa_out + a.hoff[blockIdx.x];                     // 16-byte aligned
+        const uint64_t rs = W.row_size, total = (uint64_t)W.msa_rows * rs;
+        const uint32_t fill = 0x2D2D2D2Du;                                 // '-'
+        uint4* o4 = (uint4*)out;
+        for (uint64_t k = lane; k < total / 16; k += 64) o4[k] = make_uint4(fill, fill, fill, fill);
+        for (uint64_t k = (total & ~15ull) + lane; k < total; k += 64) out[k] = '-';
+        __syncthreads();
+        if (total) {
+            for (uint32_t s = lane; s < g.nseq; s += 64) {
+                const uint32_t v = W.sq_begin[s];
+                out[(uint64_t)s * rs + W.map[v]] = (uint8_t)W.decoder[g.code[v]];
+            }
+            for (uint32_t e = lane; e < g.n_edges; e += 64) {
+                const uint32_t h = g.head[e];
+                const uint64_t col = W.map[h];
+                const uint8_t ch = (uint8_t)W.decoder[g.code[h]];
+                for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) out[(uint64_t)g.lb_v[c] * rs + col] = ch;
+            }
+            if (a.msa & VC_POA_MSA_CONSENSUS) {
+                uint8_t* row = out + (uint64_t)g.nseq * rs;
+                for (uint32_t i = lane; i < W.cons_n; i += 64) row[W.map[W.comp[i]]] = W.cons[i];
+            }
+        }
+        uint32_t* mem = (uint32_t*)(out + ((total + 15) & ~15ull));
+        for (uint32_t s = lane; s < W.msa_rows; s += 64) mem[s] = s < g.nseq ? W.sq_member[s] : VC_POA_ROW_CONSENSUS;
+        if (a.msa & VC_POA_COVERAGE) {
+            uint32_t* cov = mem + ((W.msa_rows + 3) & ~3u);
+            for (uint32_t i = lane; i < W.cons_n; i += 64) {
+                const uint32_t v = W.comp[i];
+                uint32_t cnt = 0, u = v;
+                for (uint32_t q = g.al_h[v];; q = g.al_nx[q]) {           // the node, then its aligned nodes
+                    for (uint32_t e = g.in_h[u]; e != NONE; e = g.nx_in[e])
+                        for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) cnt++;
+                    for (uint32_t e = g.out_h[u]; e != NONE; e = g.nx_out[e])
+                        for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) cnt += W.sq_begin[g.lb_v[c]] == u;
+                    if (q == NONE) break;
+                    u = g.al_v[q];
+                }
+                cov[i] = cnt;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host
 thread_local std::string g_err;
 int fail(int rc, const char* m) { g_err = m; return rc; }
@@ -1124,7 +1227,7 @@ int fail(int rc, const char* m) { g_err = m; return rc; }
 struct Caps { uint64_t NC, EC, AC, LC, SC, PC, nseq; };
 
 // bytes of a window's tables, and (base != nullptr) the pointers into them
-uint64_t layout(LWin* W, uint8_t* base, const Caps& c, bool labels) {
+uint64_t layout(LWin* W, uint8_t* base, const Caps& c, bool labels, bool msa) {
     uint64_t off = 0;
     auto take = [&](auto** p, uint64_t n) {
         using T = std::remove_pointer_t<std::remove_reference_t<decltype(p)>>;
@@ -1156,6 +1259,7 @@ uint64_t layout(LWin* W, uint8_t* base, const Caps& c, bool labels) {
     take(&x->poff, c.NC + 1); take(&x->prank, c.EC);
     take(&x->pairs, 2 * c.PC);
     take(&x->cons, c.NC);
+    if (msa) { take(&x->sq_begin, c.nseq); take(&x->sq_member, c.nseq); }
     return (off + 255) & ~255ull;
 }
 
@@ -1244,11 +1348,20 @@ int check_device(int32_t device) {
     return VC_OK;
 }
 
-int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r);
+// what vc_poa_run_msa hands out: owned here, valid until the next vc_poa_* / vc_large_* call or vc_large_release
+struct MsaStore {
+    std::vector<uint32_t> n_rows, row_size, row_member, coverage;
+    std::vector<uint64_t> row_off, member_off;
+    std::vector<uint8_t> rows;
+    void clear() { *this = MsaStore{}; }
+} g_msa;
+
+int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r,
+                MsaStore* msa = nullptr);
 
 // vc_poa_run / vc_poa_run_gaps after their score checks: the knobs, the batch (still without the device), the device, the run.
 // `a` holds the scores.
-int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r) {
+int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa = nullptr) {
     Knobs kn;
     if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
     const uint32_t nw = b->n_windows;
@@ -1279,7 +1392,7 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
     r->cons_off[0] = 0;
     if (nw == 0) return VC_OK;
     a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)algorithm;
-    return run_windows(device, a, b, caps, false, false, kn, r);
+    return run_windows(device, a, b, caps, msa != nullptr, false, kn, r, msa);
 }
 
 }  // namespace
@@ -1288,7 +1401,7 @@ extern "C" {
 
 const char* vc_large_last_error(void) { return g_err.c_str(); }
 
-void vc_large_release(void) { release_cache(); }
+void vc_large_release(void) { release_cache(); g_msa.clear(); }
 
 int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
@@ -1358,6 +1471,38 @@ int vc_poa_run_gaps(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r)
     return run_groups(p->device, p->algorithm, a, b, r);
 }
 
+int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o) {
+    if (!p || !b || !r || !o || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+    if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
+    if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
+    if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
+    for (const int32_t s : {p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_open2, p->gap_extend2})
+        if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
+    const uint32_t flags = o->flags;
+    if (flags & ~(uint32_t)(VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE)) return fail(VC_ERR_ARG, "unknown flag bits");
+    if ((flags & VC_POA_MSA_CONSENSUS) && !(flags & VC_POA_MSA)) return fail(VC_ERR_ARG, "VC_POA_MSA_CONSENSUS needs VC_POA_MSA");
+    int32_t g = p->gap_open, e = p->gap_extend, q = p->gap_open2, c = p->gap_extend2;
+    const uint32_t gaps = g >= e ? 0 : (g <= q || e >= c ? 1 : 2);
+    if (gaps == 0) e = g;
+    else if (gaps == 1) { q = g; c = e; }
+    LArgs a{};
+    a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
+    a.msa = flags;
+    *o = vc_poa_msa_out{};
+    o->flags = flags;
+    g_msa.clear();
+    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr);
+    if (rc != VC_OK) { g_msa.clear(); return rc; }
+    o->n_groups = b->n_windows;
+    if (flags && b->n_windows) {
+        o->n_rows = g_msa.n_rows.data(); o->row_size = g_msa.row_size.data(); o->row_off = g_msa.row_off.data();
+        o->member_off = g_msa.member_off.data(); o->row_member = g_msa.row_member.data();
+        o->rows = g_msa.rows.data(); o->rows_bytes = g_msa.rows.size();
+        if (flags & VC_POA_COVERAGE) o->coverage = g_msa.coverage.data();
+    }
+    return VC_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1365,7 +1510,7 @@ namespace {
 // The host schedule of vc_large_run and vc_poa_run: the batch on the device (seq_begin / seq_end only with spans), windows in
 // flight in groups that fit the arena budget, one alignment of each per lock-step step with the forward passes in launches that
 // fit the matrix budget, and a window whose table filled run again with larger tables.  `a` holds the scores and the schedule.
-int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r) {
+int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r, MsaStore* msa) {
     const uint32_t nw = b->n_windows;
     const uint64_t nseq_all = b->win_seq_off[nw], nbytes = b->seq_off[nseq_all];
     if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
@@ -1396,6 +1541,12 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
 
     std::vector<std::vector<uint8_t>> out(nw);
     std::vector<uint8_t> status(nw, VC_WIN_OVERFLOW);
+    std::vector<std::vector<uint32_t>> mem_of(msa ? nw : 0), cov_of(msa ? nw : 0);   // vc_poa_run_msa: row members, coverage
+    uint32_t msa_launches = 0;
+    if (msa) {
+        msa->clear();
+        msa->n_rows.assign(nw, 0); msa->row_size.assign(nw, 0); msa->row_off.assign(nw, 0); msa->member_off.assign(nw + 1, 0);
+    }
     std::vector<uint32_t> pending(nw);
     for (uint32_t w = 0; w < nw; ++w) pending[w] = w;
     uint32_t *d_list = nullptr; uint64_t* d_hoff = nullptr; LWin* d_win = nullptr;
@@ -1408,7 +1559,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
         uint64_t abytes = 0;
         std::vector<uint32_t> rest;
         for (uint32_t w : pending) {
-            const uint64_t need = layout(nullptr, nullptr, caps[w], labels);
+            const uint64_t need = layout(nullptr, nullptr, caps[w], labels, msa != nullptr);
             if (grp.empty() && need > arena_budget * 2) {                  // the device cannot hold its tables
                 status[w] = VC_WIN_OVERFLOW;
                 if (kn.log) std::fprintf(stderr, "vc_large: refuse window=%u bytes=%llu budget=%llu\n", w, (unsigned long long)need, (unsigned long long)arena_budget);
@@ -1442,7 +1593,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
             const uint32_t w = grp[k];
             LWin& W = hw[k];
             W = LWin{};
-            layout(&W, arena + aoff[k], caps[w], labels);
+            layout(&W, arena + aoff[k], caps[w], labels, msa != nullptr);
             const Caps& c = caps[w];
             W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
             W.L = W.nseq ? (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]) : 0;     // (POA groups: unused, and may be empty)
@@ -1515,6 +1666,10 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
             hipLaunchKernelGGL(k_lg_apply, lanes, dim3(64), 0, 0, a);
             ok = hipGetLastError() == hipSuccess;
         }
+        if (ok && msa) {                                                   // columns, row_size and rows of every finished group
+            hipLaunchKernelGGL(k_lg_msa<0>, dim3(n), dim3(64), 0, 0, a);
+            ok = hipGetLastError() == hipSuccess;
+        }
         ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(hw.data(), d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) == hipSuccess;
         if (!ok) { done_tmp(); cleanup(); return fail(VC_ERR_HIP, "a large-graph kernel failed"); }
         for (uint32_t k = 0; k < n; ++k) {
@@ -1548,9 +1703,77 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
                 done_tmp(); cleanup(); return fail(VC_ERR_HIP, "copy of a consensus failed");
             }
         }
+        // the alignments and coverage of the groups that finished, while their tables are resident: blocks laid out in the matrix
+        // buffer (free after the last step), in launches that fit the matrix budget, each copied out at once
+        std::vector<uint32_t> fin;
+        for (uint32_t k = 0; msa && k < n; ++k) if (!hw[k].grow && hw[k].status == VC_WIN_OK) fin.push_back(k);
+        auto block = [&](const LWin& W, uint64_t* mem_at, uint64_t* cov_at) {
+            const uint64_t rows = ((uint64_t)W.msa_rows * W.row_size + 15) & ~15ull;
+            *mem_at = rows;
+            *cov_at = rows + 4 * (((uint64_t)W.msa_rows + 3) & ~3ull);
+            return *cov_at + ((a.msa & VC_POA_COVERAGE) ? 4 * (((uint64_t)W.cons_n + 3) & ~3ull) : 0);
+        };
+        for (size_t k0 = 0; k0 < fin.size();) {
+            std::vector<uint32_t> list;
+            std::vector<uint64_t> hoff;
+            uint64_t bytes = 0, mem_at, cov_at;
+            size_t k1 = k0;
+            for (; k1 < fin.size(); ++k1) {
+                const uint64_t need = block(hw[fin[k1]], &mem_at, &cov_at);
+                if (!list.empty() && bytes + need > mat_budget) break;
+                list.push_back(fin[k1]); hoff.push_back(bytes); bytes += need;
+            }
+            k0 = k1;
+            uint8_t* dout = (uint8_t*)cached(g_cache.mat, bytes);
+            if (!dout) {
+                if (list.size() > 1) { done_tmp(); cleanup(); return fail(VC_ERR_HIP, "device allocation of the alignment rows failed"); }
+                status[grp[list[0]]] = VC_WIN_OVERFLOW; out[grp[list[0]]].clear();
+                continue;
+            }
+            const uint32_t nl = (uint32_t)list.size();
+            const uint64_t at = msa->rows.size();
+            LArgs f = a;
+            f.list = d_list; f.hoff = d_hoff; f.msa_out = dout;
+            ok = hipMemcpy(d_list, list.data(), nl * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                 hipMemcpy(d_hoff, hoff.data(), nl * 8, hipMemcpyHostToDevice) == hipSuccess;
+            if (ok) {
+                hipLaunchKernelGGL(k_lg_msa<1>, dim3(nl), dim3(64), 0, 0, f);
+                ok = hipGetLastError() == hipSuccess;
+                msa->rows.resize(at + bytes);
+                ok = ok && hipMemcpy(msa->rows.data() + at, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+            }
+            if (!ok) { done_tmp(); cleanup(); return fail(VC_ERR_HIP, "the alignment-row kernel or its copy failed"); }
+            for (uint32_t q = 0; q < nl; ++q) {
+                const LWin& W = hw[list[q]];
+                const uint32_t w = grp[list[q]];
+                (void)block(W, &mem_at, &cov_at);
+                const uint8_t* blk = msa->rows.data() + at + hoff[q];
+                msa->n_rows[w] = W.msa_rows; msa->row_size[w] = W.row_size; msa->row_off[w] = at + hoff[q];
+                mem_of[w].resize(W.msa_rows);
+                if (W.msa_rows) std::memcpy(mem_of[w].data(), blk + mem_at, 4ull * W.msa_rows);
+                if (a.msa & VC_POA_COVERAGE) {
+                    cov_of[w].resize(W.cons_n);
+                    if (W.cons_n) std::memcpy(cov_of[w].data(), blk + cov_at, 4ull * W.cons_n);
+                }
+            }
+            msa_launches++;
+        }
         done_tmp();
     }
     cleanup();
+    if (msa) {                                                             // per-row and per-base tables in group order
+        msa->member_off[0] = 0;
+        for (uint32_t w = 0; w < nw; ++w) {
+            if (status[w] != VC_WIN_OK) { msa->n_rows[w] = 0; msa->row_size[w] = 0; mem_of[w].clear(); cov_of[w].clear(); }
+            msa->row_member.insert(msa->row_member.end(), mem_of[w].begin(), mem_of[w].end());
+            msa->member_off[w + 1] = msa->row_member.size();
+            if (a.msa & VC_POA_COVERAGE) {
+                cov_of[w].resize(out[w].size());
+                msa->coverage.insert(msa->coverage.end(), cov_of[w].begin(), cov_of[w].end());
+            }
+        }
+        if (kn.log) std::fprintf(stderr, "vc_large: msa launches=%u bytes=%llu\n", msa_launches, (unsigned long long)msa->rows.size());
+    }
     if (kn.log) std::fprintf(stderr, "vc_large: done alignments=%llu cells=%llu\n", (unsigned long long)n_align, (unsigned long long)n_cells);
     uint64_t o = 0;
     for (uint32_t w = 0; w < nw; ++w) {

@@ -4,10 +4,15 @@ sequence in the order given, GenerateConsensus) for every group of a batch, over
 semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chosen from the gap scores as spoa chooses it
 (gap_model); no window rules.  No CPU path: without a device the calls raise.
 
-    python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [--device D]
-                             FILE [FILE ...]
+    python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [-r 0|1|2]
+                             [--coverage] [--device D] FILE [FILE ...]
 
-prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`.
+prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`,
+or with -r 1 / -r 2 the multiple sequence alignment of its records as FASTA (`>name` / row, with -r 2 a last row `>Consensus`;
+spoa's src/main.cpp:326-335).  -r is given once (spoa's may be repeated).  --coverage adds the tag `CV:B:I,c1,c2,...` to the
+`-r 0` header: per consensus base the number of records through its node and the nodes aligned to it (spoa's
+GenerateConsensus(&summary, false)).  spoa's GFA output (-r 3 / -r 4), --dot and --strand-ambiguous are not offered.
+poa_msa() is the same over groups in memory (vc_poa_run_msa).
 The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
 as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
 non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
@@ -149,6 +154,74 @@ def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, devi
     return [None if w in bad else c for w, c in enumerate(cons)]
 
 
+class Msa:
+    """One group's result of poa_msa: rows (bytes, all of one length; '-' is a gap), members (for every row the index of the group
+    member it belongs to -- an empty member has no row --, CONSENSUS_ROW for the consensus row of include_consensus), consensus
+    and coverage (numpy uint32 per consensus base, or None)."""
+    __slots__ = ("rows", "members", "consensus", "coverage")
+
+    def __init__(self, rows, members, consensus, coverage):
+        self.rows, self.members, self.consensus, self.coverage = rows, members, consensus, coverage
+
+    def __iter__(self):
+        return iter((self.rows, self.members, self.consensus, self.coverage))
+
+
+CONSENSUS_ROW = capi.VC_POA_ROW_CONSENSUS
+
+
+def run_batch_msa(batch, params, flags, lib=None):
+    """vc_poa_run_msa (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits) on a capi.Batch -> (list of Msa, status array).
+    Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error."""
+    lib = lib or capi.load_hip()
+    n = batch.n_windows
+    cons = np.zeros(max(int(batch.bases.size), 1), np.uint8)
+    off = np.zeros(n + 1, np.uint64)
+    status = np.zeros(max(n, 1), np.uint8)
+    r = capi.VcResult(off.ctypes.data_as(C.POINTER(C.c_uint64)), cons.ctypes.data_as(C.POINTER(C.c_uint8)), cons.size,
+                      status.ctypes.data_as(C.POINTER(C.c_uint8)))
+    vb = batch.as_struct()
+    vb.seq_begin = vb.seq_end = vb.win_fasta = None
+    o = capi.VcPoaMsaOut(flags=flags)
+    rc = lib.vc_poa_run_msa(C.byref(params), C.byref(vb), C.byref(r), C.byref(o))
+    if rc != 0:
+        raise PoaError(f"vc_poa_run_msa failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    res = []
+    rows_base = C.addressof(o.rows.contents) if o.rows else 0
+    for w in range(n):
+        c0, c1 = int(off[w]), int(off[w + 1])
+        rows, members, cov = [], [], None
+        if o.n_rows and o.n_rows[w]:
+            k, rs, at, m0 = o.n_rows[w], o.row_size[w], o.row_off[w], o.member_off[w]
+            block = C.string_at(rows_base + at, k * rs)
+            rows = [block[i * rs:(i + 1) * rs] for i in range(k)]
+            members = [int(o.row_member[m0 + i]) for i in range(k)]
+        if flags & capi.VC_POA_COVERAGE:
+            cov = np.array(o.coverage[c0:c1], np.uint32) if o.coverage and c1 > c0 else np.zeros(0, np.uint32)
+        res.append(Msa(rows, members, cons[c0:c1].tobytes(), cov))
+    return res, status[:n]
+
+
+def poa_msa(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+            gap_extend=None, gap_open2=None, gap_extend2=None, include_consensus=False, coverage=False):
+    """The multiple sequence alignment of every group (spoa's GenerateMultipleSequenceAlignment(include_consensus)) -> list of
+    Msa; with coverage=True also the coverage of every consensus base (GenerateConsensus(&summary, false)).  Parameters,
+    PoaError and strict as poa_consensus (a group that was not computed comes back as None with strict=False); the gap scores
+    left out are spoa's overload defaults, so the default call runs linear gaps and its consensus is poa_consensus's."""
+    batch = group_batch(groups)
+    e = gap if gap_extend is None else gap_extend
+    p = capi.VcPoaGapParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap_open=gap,
+                            gap_extend=e, gap_open2=gap if gap_open2 is None else gap_open2,
+                            gap_extend2=e if gap_extend2 is None else gap_extend2)
+    flags = capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if include_consensus else 0) | (capi.VC_POA_COVERAGE if coverage else 0)
+    res, status = run_batch_msa(batch, p, flags, lib)
+    bad = {w: int(s) for w, s in enumerate(status) if int(s) != capi.VC_WIN_OK}
+    if bad and strict:
+        what = ", ".join(f"{w}: {_STATUS.get(s, s)}" for w, s in list(bad.items())[:8])
+        raise PoaError(f"{len(bad)} group(s) not computed: {what}{' ...' if len(bad) > 8 else ''}", groups=bad)
+    return [None if w in bad else m for w, m in enumerate(res)]
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(
         prog="python -m vechat_amd.poa",
@@ -167,6 +240,11 @@ def parse_args(argv=None):
     ap.add_argument("--gap-extend2", type=int, default=None, metavar="C",
                     help="gap extension penalty of the second affine model, <= 0 (spoa's -c; default: --gap-extend)")
     ap.add_argument("-l", type=int, default=0, choices=(0, 1, 2), help="alignment mode: 0 local (SW), 1 global (NW), 2 semi-global (OV); default 0")
+    ap.add_argument("-r", type=int, default=0, choices=(0, 1, 2),
+                    help="result: 0 consensus (FASTA), 1 multiple sequence alignment (FASTA), 2 both, the consensus as the last row "
+                         "'Consensus' (spoa's -r; given once here, and without spoa's GFA modes 3 and 4); default 0")
+    ap.add_argument("--coverage", action="store_true",
+                    help="with -r 0: add the tag CV:B:I,c1,c2,... to the header, the coverage of every consensus base")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="+", metavar="FILE")
     return ap.parse_args(argv)
@@ -175,16 +253,34 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     from . import seqio
+    if a.coverage and a.r != 0:
+        print("vechat_amd.poa: --coverage goes with -r 0", file=sys.stderr)
+        return 1
+    msa = cons = None
     try:
-        groups = [[(data, qual) for _, data, qual in seqio.read_sequences(f)] for f in a.files]
-        cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device, gap_extend=a.gap_extend, gap_open2=a.gap_open2,
-                             gap_extend2=a.gap_extend2)
+        records = [list(seqio.read_sequences(f)) for f in a.files]
+        groups = [[(data, qual) for _, data, qual in recs] for recs in records]
+        gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
+        if a.r == 0 and not a.coverage:
+            cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)
+        else:
+            msa = poa_msa(groups, a.l, a.m, a.n, a.g, device=a.device, include_consensus=a.r == 2, coverage=a.coverage, **gaps)
     except (PoaError, ValueError, OSError) as e:
         print(f"vechat_amd.poa: {e}", file=sys.stderr)
         return 1
     out = sys.stdout.buffer
-    for c in cons:
-        out.write(b">Consensus LN:i:%d\n%s\n" % (len(c), c))
+    if cons is not None:
+        for c in cons:
+            out.write(b">Consensus LN:i:%d\n%s\n" % (len(c), c))
+    elif a.r == 0:
+        for m in msa:
+            cv = b"".join(b",%d" % x for x in m.coverage)
+            out.write(b">Consensus LN:i:%d CV:B:I%s\n%s\n" % (len(m.consensus), cv, m.consensus))
+    else:
+        for recs, m in zip(records, msa):
+            for row, mb in zip(m.rows, m.members):
+                name = b"Consensus" if mb == CONSENSUS_ROW else _bytes(recs[mb][0], "record name")
+                out.write(b">%s\n%s\n" % (name, row))
     out.flush()
     return 0
 
