@@ -446,6 +446,33 @@ typedef struct vc_poa_msa_out {
 } vc_poa_msa_out;
 int         vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o);
 
+/* Strand-ambiguous groups: spoa's `-s` (src/main.cpp:287-304).  Every sequence, sequence 0 and empty ones included, is aligned
+ * to the graph twice, as given and reverse-complemented, and the better strand is added:
+ *     score = 0;     alignment     = Align(data, graph, &score);
+ *     ReverseAndComplement();                                             biosoup/sequence.hpp:55-77
+ *     score_rev = 0; alignment_rev = Align(data, graph, &score_rev);
+ *     score >= score_rev ? ReverseAndComplement() again, keep `alignment` : keep `alignment_rev`
+ * A score is the value of the end cell; it stays 0 where the engine does not write it: against the empty graph, for an empty
+ * sequence, and where a local alignment finds no positive cell.
+ * The tie rule: score == score_rev keeps the forward strand, so a sequence meeting the empty graph, an empty one and a
+ * reverse-palindromic one are never reported reversed.
+ * The complement is chosen on the upper-cased byte and is upper case: A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H; S, W, N
+ * and every other byte stay as they are, in their own case.  The round-trip rule: a kept forward strand has been complemented
+ * twice, which is not the identity -- u / U become T, lower-case a c g t r y k m b d h v become upper case (s, w, n keep their
+ * case).  Its alignment was computed on the bytes as given; the nodes it adds, the consensus and the rows carry the
+ * round-tripped bytes.  A kept reverse strand is added with its quality string reversed.  Rows show the kept bytes.
+ * p, b, r and o as vc_poa_run_msa (o may be NULL: the consensus only); s is caller-owned, one entry per sequence of the batch
+ * (b->win_seq_off[n_windows]), in batch order.  Groups that are not VC_WIN_OK have zeros in s.  Both strands' forward passes run
+ * in one launch, each with a matrix of its own, so a step needs twice vc_poa_run_msa's matrix memory; the graph stages run once.
+ * Checked before the device, in this order: as vc_poa_run_msa up to the flags, then s and s->reversed, then the batch:
+ * VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these. */
+typedef struct vc_poa_strand_out {
+    uint8_t* reversed;              /* 1: the reverse complement was kept (required)                                */
+    int32_t* score;                 /* spoa's *score of the forward strand (may be NULL)                            */
+    int32_t* score_rev;             /* and of the reverse strand (may be NULL)                                      */
+} vc_poa_strand_out;
+int         vc_poa_run_strand(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s);
+
 #ifdef __cplusplus
 }
 #endif

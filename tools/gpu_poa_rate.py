@@ -10,13 +10,21 @@ libvcref_sse41.so, vcref_spoa_consensus) on a sample of the same groups on 16 ho
 compared with the device's.
 
   python tools/gpu_poa_rate.py [--groups 4096] [--len 1000] [--depth 32] [--cpu-sample 256] [--out profiles/poa_rate.txt]
-                               [--gaps linear|affine|convex] [--msa]
+                               [--gaps linear|affine|convex] [--msa] [--strand]
 
 --msa measures the multiple sequence alignment instead (vc_poa_run_msa with the consensus row and the coverage, global
 alignment) and writes profiles/poa_msa_rate.txt: after one warm-up call on all groups, three consensus-only calls and three
 MSA calls in the same process, then each kind once under `rocprofv3 --kernel-trace --stats` (kernel trace only) for k_lg_apply's
 and k_lg_msa's kernel time -- the label bookkeeping shows as the difference of k_lg_apply between the two traces, and what the
 MSA call's wall time exceeds the consensus-only one's beyond the kernels is the copy-out and the host's assembly.
+
+--strand measures the strand-ambiguous call (vc_poa_run_strand, consensus only, global alignment, the gap model of --gaps) and
+writes profiles/poa_strand_rate.txt: every second member of every group, never member 0, is reverse-complemented (its quality
+string reversed); after one warm-up call, three plain calls (vc_poa_run_msa without flags, which is vc_poa_run_gaps) on the
+unflipped groups and three strand calls on the flipped ones in the same process, the number of groups whose consensus differs
+between the two (the synthetic reads are upper-case ACGT, so 0 is expected), the members reported reversed, and then each kind
+once under `rocprofv3 --kernel-trace --stats` for the k_lg_* shares.  Exits 1 if the strand call takes 2x the plain call's time
+or more: two whole flows would cost that, so it would mean the graph stages or the launches were duplicated.
 
 --gaps affine / convex runs vc_poa_run_gaps with spoa's affine known-answer scores (5 -4 -8 -6) or its command-line defaults
 (5 -4 -8 -6 -10 -4, convex); the cells are still rows x columns (not x planes).  The reference in oracle/_ref only takes linear
@@ -129,6 +137,123 @@ def timed_msa(batch, flags):
     return dt, int(o.rows_bytes), int(kv["alignments"]), int(kv["cells"])
 
 
+def flip_members(batch):
+    """every second member of every group, never member 0, reverse-complemented in place of itself (quality reversed)"""
+    import numpy as np
+    comp = np.arange(256, dtype=np.uint8)
+    for x, y in ("AT", "CG", "RY", "KM", "BV", "DH"):
+        for u, v in ((x, y), (y, x)):
+            comp[ord(u)] = comp[ord(u.lower())] = ord(v)
+    comp[ord("U")] = comp[ord("u")] = ord("A")
+    bases, quals = batch.bases.copy(), batch.quals.copy()
+    flips = np.zeros(batch.n_seqs, bool)
+    for w in range(batch.n_windows):
+        s0, s1 = int(batch.win_seq_off[w]), int(batch.win_seq_off[w + 1])
+        for s in range(s0 + 1, s1, 2):
+            o0, o1 = int(batch.seq_off[s]), int(batch.seq_off[s + 1])
+            bases[o0:o1] = comp[batch.bases[o0:o1]][::-1]
+            quals[o0:o1] = batch.quals[o0:o1][::-1]
+            flips[s] = True
+    return capi.Batch(batch.win_seq_off, batch.seq_off, batch.seq_begin, batch.seq_end, batch.seq_has_qual, bases, quals,
+                      batch.win_fasta), flips
+
+
+def gap_params(gaps):
+    g, e, q, c = GAPS[gaps] or (-8, -8, -8, -8)
+    return capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=g, gap_extend=e, gap_open2=q, gap_extend2=c)
+
+
+def timed_strand(batch, gaps, strand):
+    """-> (seconds, consensus per group, reversed per sequence or None, alignments, cells) of one vc_poa_run_strand (strand) or
+    vc_poa_run_msa without flags (plain) on the batch, global alignment"""
+    import ctypes as C
+    import tempfile
+    import numpy as np
+    lib = capi.load_hip()
+    p = gap_params(gaps)
+    n = batch.n_windows
+    cons, off, status = np.zeros(int(batch.bases.size), np.uint8), np.zeros(n + 1, np.uint64), np.zeros(n, np.uint8)
+    r = capi.VcResult(off.ctypes.data_as(C.POINTER(C.c_uint64)), cons.ctypes.data_as(C.POINTER(C.c_uint8)), cons.size,
+                      status.ctypes.data_as(C.POINTER(C.c_uint8)))
+    vb = batch.as_struct()
+    o = capi.VcPoaMsaOut(flags=0)
+    rev = np.zeros(max(batch.n_seqs, 1), np.uint8)
+    so = capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)), None, None)
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            if strand:
+                rc = lib.vc_poa_run_strand(C.byref(p), C.byref(vb), C.byref(r), C.byref(o), C.byref(so))
+            else:
+                rc = lib.vc_poa_run_msa(C.byref(p), C.byref(vb), C.byref(r), C.byref(o))
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read().decode()
+    if rc != 0 or int((status != 0).sum()):
+        raise RuntimeError(f"rc {rc}, {int((status != 0).sum())} groups not computed")
+    done = [l for l in err.splitlines() if l.startswith("vc_large: done")][-1]
+    kv = dict(t.split("=") for t in done.split()[2:])
+    return (dt, [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], rev[:batch.n_seqs].astype(bool) if strand else None,
+            int(kv["alignments"]), int(kv["cells"]))
+
+
+def main_strand(a):
+    batch = synth_groups(a)
+    fbatch, flips = flip_members(batch)
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_strand_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = open(out).read().splitlines() if a.append and os.path.exists(out) else []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    g = GAPS[a.gaps] or (-8,)
+    emit(f"POA groups with both strands ({a.gaps} gaps, 5/-4/{'/'.join(map(str, g))}): {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed "
+         f"4100, PacBio-like errors, frac_partial=0, FASTQ), {int(batch.seq_off[-1])} bases; global (kNW), consensus only; one MI355X; "
+         f"host clock around one synchronous call; one untimed strand call on all groups first, then three plain calls "
+         f"(vc_poa_run_msa, flags 0) on the groups as synthesised and three strand calls (vc_poa_run_strand) on the groups with "
+         f"every second member, never member 0, reverse-complemented ({int(flips.sum())} of {batch.n_seqs} members), in the same process")
+    timed_strand(fbatch, a.gaps, True)
+    plain = [timed_strand(batch, a.gaps, False) for _ in range(3)]
+    both = [timed_strand(fbatch, a.gaps, True) for _ in range(3)]
+    for name, runs in (("plain, unflipped groups", plain), ("both strands, flipped groups", both)):
+        emit(f"{name:30s} " + "  ".join(f"{a.groups / r[0]:7.1f}" for r in runs) + f" groups/s  ({'  '.join(f'{r[0]:.2f}' for r in runs)} s; "
+             f"{runs[0][3]} alignments, {runs[0][4] / 1e9:.2f} G cells)")
+    differ = sum(1 for x, y in zip(plain[0][1], both[0][1]) if x != y)
+    wrong = int((both[0][2] != flips).sum())
+    mp, mb = min(r[0] for r in plain), min(r[0] for r in both)
+    emit(f"groups whose consensus differs between the two: {differ} of {a.groups} (expected 0); members whose reported strand is not "
+         f"the flip that was applied: {wrong} of {batch.n_seqs}")
+    emit(f"strand / plain time (best of three each): {mb / mp:.3f} (must stay below 2; the forward pass alone doubles)")
+    large.release()
+    if not a.no_trace:
+        emit("kernel time shares, each kind's call in a run of its own under rocprofv3 --kernel-trace --stats (a fresh process: 64 groups first, then all):")
+        for kind, flag in (("plain", 0), ("both strands", 1)):
+            d = os.path.join(a.trace_dir, f"strand{flag}_{a.gaps}")
+            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+                   sys.executable, os.path.abspath(__file__), "--child", str(flag), "--strand", "--groups", str(a.groups), "--len", str(a.len),
+                   "--depth", str(a.depth), "--gaps", a.gaps]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"  {kind}: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                break
+            ms = kernel_shares(d)
+            tot = sum(ms.values())
+            shares = ", ".join(f"{k} {v / tot * 100:.1f} % ({v / 1e3:.2f} s)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1]))
+            wall = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            emit(f"  {kind:13s} kernels {tot / 1e3:.2f} s of {wall:.2f} s wall: {shares}")
+    print("wrote", out)
+    return 1 if mb >= 2 * mp else 0
+
+
 def main_msa(a):
     batch = synth_groups(a)
     out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_msa_rate.txt")
@@ -181,6 +306,14 @@ def main_msa(a):
 
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    if a.strand:
+        batch = synth_groups(a)
+        if a.child:
+            batch = flip_members(batch)[0]
+        timed_strand(batch.slice(0, min(64, batch.n_windows)), a.gaps, bool(a.child))
+        dt, _, _, n_al, cells = timed_strand(batch, a.gaps, bool(a.child))
+        print(json.dumps(dict(seconds=dt, alignments=n_al, cells=cells)))
+        return
     if a.msa:
         batch = synth_groups(a)
         timed_msa(batch.slice(0, min(64, batch.n_windows)), a.child)
@@ -218,10 +351,14 @@ def main():
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--gaps", choices=sorted(GAPS), default="linear")
     ap.add_argument("--msa", action="store_true", help="measure vc_poa_run_msa beside the consensus-only call (profiles/poa_msa_rate.txt)")
+    ap.add_argument("--strand", action="store_true", help="measure vc_poa_run_strand beside the plain call (profiles/poa_strand_rate.txt)")
+    ap.add_argument("--append", action="store_true", help="--strand: keep what the output file holds and write below it")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
         return child(a)
+    if a.strand:
+        return main_strand(a)
     if a.msa:
         return main_msa(a)
     batch = synth_groups(a)
@@ -280,4 +417,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

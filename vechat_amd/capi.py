@@ -87,6 +87,11 @@ class VcPoaMsaOut(C.Structure):
     ]
 
 
+class VcPoaStrandOut(C.Structure):
+    """vc_poa_strand_out: caller-owned arrays, one entry per sequence of the batch; score / score_rev may be NULL"""
+    _fields_ = [("reversed", C.POINTER(C.c_uint8)), ("score", C.POINTER(C.c_int32)), ("score_rev", C.POINTER(C.c_int32))]
+
+
 class VcStats(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64), ("alignments", C.c_uint64), ("dp_rows", C.c_uint64),
@@ -352,6 +357,9 @@ def load_hip():
         lib.vc_poa_run_gaps.restype = C.c_int
         lib.vc_poa_run_msa.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut)]
         lib.vc_poa_run_msa.restype = C.c_int
+        lib.vc_poa_run_strand.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut),
+                                          C.POINTER(VcPoaStrandOut)]
+        lib.vc_poa_run_strand.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

@@ -41,6 +41,10 @@
 //   k_lg_apply  one lane per window: add-alignment + topological sort, or add-weights; prune + largest component at the end of
 //               the build and of every round; the corrected sequence (mode 0), heaviest bundle + coverage + trim (mode 1) or the
 //               heaviest bundle alone (mode 2).
+//   k_lg_views  vc_poa_run_strand only, once per call, one lane per byte of the batch: the strand views (reverse complement, reversed
+//               quality, the bytes complemented twice).  With them k_lg_fwd runs on a grid of (alignments, 2) -- one wave per
+//               alignment and strand, the second strand's matrix behind the first's --, k_lg_back picks the strand by score and
+//               walks the winner's matrix only, and k_lg_apply adds the kept view and records the choice (spoa's -s, main.cpp:287-304);
 //   k_lg_msa    vc_poa_run_msa only, one wave per finished group: <0> node -> column by a wave prefix sum over the topological
 //               order, <1> the rows ('-' fill, then a scatter over the edge labels), the consensus row and the coverage.
 //
@@ -53,13 +57,13 @@
 //   VC_LARGE_CAPS=n:4,a:6   a table starts at max(1, size >> shift): n nodes, e edges, a aligned cells, l labels, s stack, p pairs
 //                           (the stack then also grows from (nodes + edges + aligned) >> shift, not from the unshifted sum);
 //   VC_LARGE_ARENA_MB=x     arena budget (window tables per group; a window above twice the budget is refused) in MiB, fractions allowed;
-//   VC_LARGE_MAT_MB=x       matrix budget (int32 matrices, every plane, per forward launch) in MiB;
+//   VC_LARGE_MAT_MB=x       matrix budget (int32 matrices, every plane and both strands, per forward launch) in MiB;
 //   VC_LARGE_LOG=1          one stderr line per event: "vc_large: regrow window=W flags=nodes,... caps n=.. e=.. a=.. l=.. s=.. p=..",
 //                           "vc_large: group windows=N bytes=B ids=W,.. need=B,..", "vc_large: step launches=K over=O" (steps of more than one
 //                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B",
 //                           "vc_large: msa launches=K bytes=B" (vc_poa_run_msa with flags: k_lg_msa<1> launches, bytes copied out),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes run, their rows x columns
-//                           summed; a regrown window's are counted again).
+//                           summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,7 +107,9 @@ struct LWin {
     double total, avg;
     uint32_t rows, qlen, qs, type;                     // the current alignment: graph rows, query length, query (sequence index), 0 SW / 1 NW / 2 OV
     int32_t m, x, g, e, q, c;                          // scores; e, q, c: the affine / convex ones (mode 2), g elsewhere
-    uint32_t max_i, max_j, npairs, cons_n;
+    uint32_t max_i[2], max_j[2], npairs, cons_n;       // end cell per strand ([1]: vc_poa_run_strand's reverse complement)
+    int32_t score[2];                                  // spoa's *score per strand: the end cell's value, 0 where spoa does not write it
+    uint32_t rev;                                      // the strand the backtrack kept (1: the reverse complement), 0 without strands
     LGraph gr[2];
     int32_t *coder, *decoder;                          // [256]
     uint8_t *mark, *ign;                               // [NC]
@@ -135,6 +141,13 @@ struct LArgs {
     uint32_t gaps;                                     // mode 2: spoa::AlignmentSubtype (0 linear, 1 affine, 2 convex); 0 elsewhere
     int32_t gap_e, gap_q, gap_c;                       // mode 2: spoa's e, q, c after Create's subtype rule
     uint32_t msa;                                      // mode 2: VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE, 0 elsewhere
+    // mode 2, vc_poa_run_strand (strand = 1; nullptr / 0 elsewhere): the strand views of the batch, k_lg_views, laid out as bases /
+    // quals are, and the choice per sequence of the batch
+    uint32_t strand;
+    uint8_t *rc_bases, *rv_quals, *rt_bases;           // reverse complement, reversed quality, the bytes complemented twice
+    uint8_t* s_rev;                                    // [sequences] 1: the reverse complement was kept
+    int32_t *s_score, *s_score_rev;                    // [sequences] both strands' scores
+    uint64_t nbytes;                                   // k_lg_views: bytes of the batch
     // k_lg_fwd / k_lg_back: windows of this launch and their matrices (k_lg_msa<1>: groups and the byte offsets of their blocks)
     const uint32_t* list;
     const uint64_t* hoff;
@@ -197,20 +210,30 @@ __device__ bool add_edge(LWin& W, LGraph& g, uint32_t tail, uint32_t head, uint3
     return new_edge(W, g, tail, head, g.nseq, w);
 }
 
-__device__ __forceinline__ uint32_t weight_of(const LArgs& a, uint32_t s, uint32_t i, bool use_qual) {
-    return use_qual ? a.lut_w[a.quals[a.seq_off[s] + i]] : 1u;
+// The bytes a step reads of sequence s.  Without strands: the batch's.  vc_poa_run_strand: strand 1 aligns the reverse complement;
+// what is added to the graph is the kept view -- the reverse complement with the reversed quality, or the forward strand
+// complemented twice (main.cpp:297-299; its alignment was computed on the batch's own bytes).
+__device__ __forceinline__ const uint8_t* aligned_bases(const LArgs& a, uint32_t s, uint32_t strand) {
+    return (strand ? a.rc_bases : a.bases) + a.seq_off[s];
+}
+__device__ __forceinline__ const uint8_t* kept_bases(const LArgs& a, const LWin& W, uint32_t s) {
+    return (a.strand ? (W.rev ? a.rc_bases : a.rt_bases) : a.bases) + a.seq_off[s];
+}
+
+__device__ __forceinline__ uint32_t weight_of(const LArgs& a, const LWin& W, uint32_t s, uint32_t i, bool use_qual) {
+    return use_qual ? a.lut_w[(a.strand && W.rev ? a.rv_quals : a.quals)[a.seq_off[s] + i]] : 1u;
 }
 
 // g_add_chain: fresh chain for seq[begin, end); *first = first node or NONE
 __device__ bool add_chain(const LArgs& a, LWin& W, LGraph& g, uint32_t s, bool uq, uint32_t begin, uint32_t end, uint32_t* first) {
     *first = NONE;
-    const uint8_t* seq = a.bases + a.seq_off[s];
+    const uint8_t* seq = kept_bases(a, W, s);
     uint32_t prev = NONE;
     for (uint32_t i = begin; i < end; ++i) {
         const uint32_t curr = add_node(W, g, (uint32_t)W.coder[seq[i]]);
         if (curr == NONE) return false;
         if (*first == NONE) *first = curr;
-        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, s, i - 1, uq) + weight_of(a, s, i, uq))) return false;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, W, s, i - 1, uq) + weight_of(a, W, s, i, uq))) return false;
         prev = curr;
     }
     return true;
@@ -268,7 +291,7 @@ __device__ bool toposort(LWin& W, LGraph& g) {
 // g_add_alignment.  Returns 0, -1 where the reference throws, -2 when a table filled.
 __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* A, uint32_t np, uint32_t s, bool uq) {
     const uint32_t len = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
-    const uint8_t* seq = a.bases + a.seq_off[s];
+    const uint8_t* seq = kept_bases(a, W, s);
     if (len == 0) return 0;
     for (uint32_t i = 0; i < len; ++i) {
         if (W.coder[seq[i]] == -1) {
@@ -325,10 +348,10 @@ __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* 
             }
         }
         if (begin == NONE) begin = curr;
-        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, s, q - 1, uq) + weight_of(a, s, q, uq))) return -2;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, W, s, q - 1, uq) + weight_of(a, W, s, q, uq))) return -2;
         prev = curr;
     }
-    if (last != NONE && !add_edge(W, g, prev, last, weight_of(a, s, vback, uq) + weight_of(a, s, vback + 1, uq))) return -2;
+    if (last != NONE && !add_edge(W, g, prev, last, weight_of(a, W, s, vback, uq) + weight_of(a, W, s, vback + 1, uq))) return -2;
     if (W.sq_begin) { W.sq_begin[g.nseq] = begin; W.sq_member[g.nseq] = s - W.s0; }   // sequences_.emplace_back(begin), graph.cpp:296
     g.nseq++;
     return toposort(W, g) ? 0 : -2;
@@ -456,7 +479,7 @@ __device__ bool add_weights(const LArgs& a, LWin& W, LGraph& g, const int32_t* A
         const int32_t n = A[2 * k], q = A[2 * k + 1];
         if (n == -1 || q == -1) { prev = NONE; continue; }
         const uint32_t curr = (uint32_t)n;
-        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, s, q - 1, uq) + weight_of(a, s, q, uq))) return false;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, W, s, q - 1, uq) + weight_of(a, W, s, q, uq))) return false;
         prev = curr;
     }
     return true;
@@ -597,6 +620,44 @@ __device__ int64_t worst_case(int64_t m, int64_t gp, int64_t ge, int64_t gq, int
 }
 
 // ------------------------------------------------------------------ kernels
+// biosoup::Sequence::ReverseAndComplement's byte rule (sequence.hpp:55-77): the complement is chosen on the upper-cased byte and is
+// upper case; S, W, N and every byte without a complement stay as they are, in their own case.
+__device__ __forceinline__ uint8_t complement(uint8_t c) {
+    switch (c >= 'a' && c <= 'z' ? c - 32 : c) {
+        case 'A': return 'T';
+        case 'C': return 'G';
+        case 'G': return 'C';
+        case 'T': case 'U': return 'A';
+        case 'R': return 'Y';
+        case 'Y': return 'R';
+        case 'K': return 'M';
+        case 'M': return 'K';
+        case 'B': return 'V';
+        case 'D': return 'H';
+        case 'H': return 'D';
+        case 'V': return 'B';
+        default: return c;
+    }
+}
+
+// The strand views of vc_poa_run_strand, once per call, one lane per byte of the batch: byte x of sequence s (found by bisection
+// of seq_off) goes, complemented, to the mirrored place of s in rc_bases, its quality to the same place of rv_quals, and,
+// complemented twice, to its own place in rt_bases.
+__global__ __launch_bounds__(256) void k_lg_views(LArgs a, uint32_t nseq) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= a.nbytes) return;
+    uint32_t lo = 0, hi = nseq;                                            // the last s with seq_off[s] <= x
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.seq_off[mid] <= x) lo = mid; else hi = mid;
+    }
+    const uint64_t y = a.seq_off[lo] + (a.seq_off[lo + 1] - 1 - x);
+    const uint8_t c = complement(a.bases[x]);
+    a.rc_bases[y] = c;
+    a.rv_quals[y] = a.quals[x];
+    a.rt_bases[x] = complement(c);
+}
+
 __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     const uint32_t w = blockIdx.x * 64 + threadIdx.x;
     if (w >= a.n) return;
@@ -606,7 +667,7 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     reset_graph(W.gr[0]); reset_graph(W.gr[1]);
     W.gr[0].labels = a.mode == 1 || a.msa != 0; W.gr[1].labels = 0;
     W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
-    W.msa_rows = 0; W.row_size = 0;
+    W.msa_rows = 0; W.row_size = 0; W.rev = 0;
     if (a.mode == 2) {                                                     // POA group: sequence 0 meets the empty graph in k_lg_prep
         W.phase = PH_BUILD; W.j = 0; W.k = 0;
         if (W.nseq == 0) finish_poa(W);                                    // no sequence: the empty consensus
@@ -634,7 +695,8 @@ __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
     const uint32_t w = blockIdx.x * 64 + threadIdx.x;
     if (w >= a.n) return;
     LWin& W = a.win[w];
-    W.rows = 0; W.npairs = 0; W.max_i = W.max_j = 0; W.sub = 0;
+    W.rows = 0; W.npairs = 0; W.max_i[0] = W.max_j[0] = W.max_i[1] = W.max_j[1] = 0; W.sub = 0;
+    W.score[0] = W.score[1] = 0; W.rev = 0;                                // no forward pass: spoa leaves both scores at 0, forward is kept
     if (W.phase == PH_DONE || W.grow) return;
     uint32_t gi = W.cur;
     if (a.mode == 2) {                                                     // POA group: the next sequence against the whole graph
@@ -723,14 +785,15 @@ __device__ void fwd_gaps(const LArgs& a) {
     const uint32_t lane = threadIdx.x;
     const uint32_t N = W.rows, len = W.qlen;
     const uint64_t w = (uint64_t)len + 1, P = ((uint64_t)N + 1) * w;
-    int32_t* H = a.H + a.hoff[blockIdx.x];
+    const uint32_t st = blockIdx.y;                                    // the strand; its planes follow the forward strand's
+    int32_t* H = a.H + a.hoff[blockIdx.x] + st * (GM == 2 ? 5 : 3) * P;
     int32_t* F = H + P;
     int32_t* E = F + P;
     int32_t* O = GM == 2 ? E + P : nullptr;
     int32_t* Q = GM == 2 ? O + P : nullptr;
     const bool sw = W.type == 0, ov = W.type == 2;
     const int32_t m = W.m, x = W.x, gp = W.g, ge = W.e, gq = W.q, gc = W.c;
-    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    const uint8_t* seq = aligned_bases(a, W.qs, st);
     for (uint32_t j = lane; j <= len; j += 64) {                       // row 0
         const int32_t ej = j == 0 ? 0 : gp + (int32_t)(j - 1) * ge;
         int32_t h = ej;
@@ -824,7 +887,7 @@ __device__ void fwd_gaps(const LArgs& a) {
         const uint32_t oi = __shfl_xor(bi, d, 64), oj = __shfl_xor(bj, d, 64);
         if (better(os, oi, oj, bs, bi, bj)) { bs = os; bi = oi; bj = oj; }
     }
-    if (lane == 0) { W.max_i = bi; W.max_j = bj; }
+    if (lane == 0) { W.max_i[st] = bi; W.max_j[st] = bj; W.score[st] = bs; }
 }
 
 // One wave per alignment (g_align's forward pass).  Row i = rank i - 1; lane l holds columns 512 c + 8 l + 1 .. + 8 of chunk c.
@@ -841,12 +904,13 @@ __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
     }
     LWin& W = a.win[a.list[blockIdx.x]];
     const uint32_t lane = threadIdx.x;
-    int32_t* H = a.H + a.hoff[blockIdx.x];
     const uint32_t N = W.rows, len = W.qlen;
     const uint64_t w = (uint64_t)len + 1;
+    const uint32_t st = blockIdx.y;                                        // the strand; its matrix follows the forward strand's
+    int32_t* H = a.H + a.hoff[blockIdx.x] + st * ((uint64_t)N + 1) * w;
     const bool sw = W.type == 0, ov = W.type == 2;
     const int32_t m = W.m, x = W.x, gp = W.g;
-    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    const uint8_t* seq = aligned_bases(a, W.qs, st);
     for (uint32_t j = lane; j <= len; j += 64) H[j] = (sw || j == 0) ? 0 : (int32_t)j * gp;
     __syncthreads();
     int32_t bs = sw ? 0 : KNEG;
@@ -911,7 +975,7 @@ __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
         const uint32_t oi = __shfl_xor(bi, d, 64), oj = __shfl_xor(bj, d, 64);
         if (better(os, oi, oj, bs, bi, bj)) { bs = os; bi = oi; bj = oj; }
     }
-    if (lane == 0) { W.max_i = bi; W.max_j = bj; }
+    if (lane == 0) { W.max_i[st] = bi; W.max_j[st] = bj; W.score[st] = bs; }
 }
 
 // The backtrack of Affine (GM 1, sisd_alignment_engine.cpp:542-676) and Convex (GM 2, :780-925), literally: the diagonal over
@@ -924,17 +988,20 @@ __device__ void back_gaps(const LArgs& a, uint32_t n) {
     if (b >= n) return;
     LWin& W = a.win[a.list[b]];
     const uint64_t w = (uint64_t)W.qlen + 1, P = ((uint64_t)W.rows + 1) * w;
-    const int32_t* H = a.H + a.hoff[b];
+    // the strand: spoa keeps the forward one unless the reverse complement scores higher (main.cpp:297), and walks that matrix
+    const uint32_t st = a.strand && W.score[0] < W.score[1];
+    W.rev = st;
+    const int32_t* H = a.H + a.hoff[b] + st * (GM == 2 ? 5 : 3) * P;
     const int32_t* F = H + P;
     const int32_t* E = F + P;
     const int32_t* O = E + P;                                          // O, Q: convex only
     const int32_t* Q = O + P;
     const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
-    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    const uint8_t* seq = aligned_bases(a, W.qs, st);
     const bool sw = W.type == 0, ov = W.type == 2;
     const int32_t gp = W.g, ge = W.e, gq = W.q, gc = W.c;
     W.npairs = 0;
-    uint32_t i = W.max_i, j = W.max_j, np = 0;
+    uint32_t i = W.max_i[st], j = W.max_j[st], np = 0;
     if (i == 0 && j == 0) return;                                          // an empty alignment
     auto emit = [&](int32_t node, int32_t pos) -> bool {
         if (np >= W.PC) { W.grow |= G_PAIRS; return false; }
@@ -1036,13 +1103,15 @@ __global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= n) return;
     LWin& W = a.win[a.list[b]];
-    const int32_t* H = a.H + a.hoff[b];
     const uint64_t w = (uint64_t)W.qlen + 1;
+    const uint32_t st = a.strand && W.score[0] < W.score[1];              // main.cpp:297: ties keep the forward strand
+    W.rev = st;
+    const int32_t* H = a.H + a.hoff[b] + st * ((uint64_t)W.rows + 1) * w;
     const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
-    const uint8_t* seq = a.bases + a.seq_off[W.qs];
+    const uint8_t* seq = aligned_bases(a, W.qs, st);
     const bool sw = W.type == 0, ov = W.type == 2;
     W.npairs = 0;
-    uint32_t i = W.max_i, j = W.max_j, np = 0;
+    uint32_t i = W.max_i[st], j = W.max_j[st], np = 0;
     if (i == 0 && j == 0) return;                                          // an empty alignment
     for (;;) {                                                             // sisd_alignment_engine.cpp:374-389
         if (sw) { if (H[(uint64_t)i * w + j] == 0) break; }
@@ -1096,6 +1165,7 @@ __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
         const int rc = add_alignment(a, W, W.gr[W.cur], W.pairs, np, s, hq);
         if (rc == -2) return;
         if (rc) { fail_window(W, VC_WIN_INVALID); return; }
+        if (a.strand) { a.s_rev[s] = (uint8_t)W.rev; a.s_score[s] = W.score[0]; a.s_score_rev[s] = W.score[1]; }
         if (a.mode == 0) {
             const uint32_t len = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
             if (!hq) W.total += (double)len;
@@ -1357,11 +1427,12 @@ struct MsaStore {
 } g_msa;
 
 int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r,
-                MsaStore* msa = nullptr);
+                MsaStore* msa = nullptr, const vc_poa_strand_out* so = nullptr);
 
 // vc_poa_run / vc_poa_run_gaps after their score checks: the knobs, the batch (still without the device), the device, the run.
 // `a` holds the scores.
-int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa = nullptr) {
+int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa = nullptr,
+               const vc_poa_strand_out* so = nullptr) {
     Knobs kn;
     if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
     const uint32_t nw = b->n_windows;
@@ -1392,7 +1463,7 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
     r->cons_off[0] = 0;
     if (nw == 0) return VC_OK;
     a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)algorithm;
-    return run_windows(device, a, b, caps, msa != nullptr, false, kn, r, msa);
+    return run_windows(device, a, b, caps, msa != nullptr, false, kn, r, msa, so);
 }
 
 }  // namespace
@@ -1471,16 +1542,18 @@ int vc_poa_run_gaps(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r)
     return run_groups(p->device, p->algorithm, a, b, r);
 }
 
-int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o) {
-    if (!p || !b || !r || !o || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+// vc_poa_run_msa, and vc_poa_run_strand (strand: `o` may be NULL, `so` is checked after the flags and before the batch)
+static int poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, bool strand, vc_poa_strand_out* so) {
+    if (!p || !b || !r || (!o && !strand) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
     if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
     for (const int32_t s : {p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_open2, p->gap_extend2})
         if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
-    const uint32_t flags = o->flags;
+    const uint32_t flags = o ? o->flags : 0;
     if (flags & ~(uint32_t)(VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE)) return fail(VC_ERR_ARG, "unknown flag bits");
     if ((flags & VC_POA_MSA_CONSENSUS) && !(flags & VC_POA_MSA)) return fail(VC_ERR_ARG, "VC_POA_MSA_CONSENSUS needs VC_POA_MSA");
+    if (strand && (!so || !so->reversed)) return fail(VC_ERR_ARG, "null strand output (reversed is required)");
     int32_t g = p->gap_open, e = p->gap_extend, q = p->gap_open2, c = p->gap_extend2;
     const uint32_t gaps = g >= e ? 0 : (g <= q || e >= c ? 1 : 2);
     if (gaps == 0) e = g;
@@ -1488,12 +1561,12 @@ int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, 
     LArgs a{};
     a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
     a.msa = flags;
-    *o = vc_poa_msa_out{};
-    o->flags = flags;
+    a.strand = strand ? 1 : 0;
+    if (o) { *o = vc_poa_msa_out{}; o->flags = flags; }
     g_msa.clear();
-    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr);
+    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr, strand ? so : nullptr);
     if (rc != VC_OK) { g_msa.clear(); return rc; }
-    o->n_groups = b->n_windows;
+    if (o) o->n_groups = b->n_windows;
     if (flags && b->n_windows) {
         o->n_rows = g_msa.n_rows.data(); o->row_size = g_msa.row_size.data(); o->row_off = g_msa.row_off.data();
         o->member_off = g_msa.member_off.data(); o->row_member = g_msa.row_member.data();
@@ -1503,6 +1576,14 @@ int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, 
     return VC_OK;
 }
 
+int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o) {
+    return poa_run_msa(p, b, r, o, false, nullptr);
+}
+
+int vc_poa_run_strand(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s) {
+    return poa_run_msa(p, b, r, o, true, s);
+}
+
 }  // extern "C"
 
 namespace {
@@ -1510,7 +1591,8 @@ namespace {
 // The host schedule of vc_large_run and vc_poa_run: the batch on the device (seq_begin / seq_end only with spans), windows in
 // flight in groups that fit the arena budget, one alignment of each per lock-step step with the forward passes in launches that
 // fit the matrix budget, and a window whose table filled run again with larger tables.  `a` holds the scores and the schedule.
-int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r, MsaStore* msa) {
+int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r, MsaStore* msa,
+                const vc_poa_strand_out* so) {
     const uint32_t nw = b->n_windows;
     const uint64_t nseq_all = b->win_seq_off[nw], nbytes = b->seq_off[nseq_all];
     if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
@@ -1531,6 +1613,19 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
         cleanup(); return fail(VC_ERR_HIP, "device allocation or copy of the batch failed");
     }
     a.seq_off = d_so; a.seq_begin = d_sb; a.seq_end = d_se; a.has_qual = d_hq; a.bases = d_b; a.quals = d_q; a.lut_w = d_lw; a.lut_d = d_ld;
+    if (so) {                                                              // the strand views, once per call, and the zeroed choices
+        a.nbytes = nbytes;
+        bool ok = dalloc(fixed, &a.rc_bases, nbytes) && dalloc(fixed, &a.rv_quals, nbytes) && dalloc(fixed, &a.rt_bases, nbytes) &&
+                  dalloc(fixed, &a.s_rev, nseq_all) && dalloc(fixed, &a.s_score, nseq_all) && dalloc(fixed, &a.s_score_rev, nseq_all) &&
+                  hipMemset(a.s_rev, 0, std::max<size_t>(nseq_all, 1)) == hipSuccess &&
+                  hipMemset(a.s_score, 0, std::max<size_t>(nseq_all, 1) * 4) == hipSuccess &&
+                  hipMemset(a.s_score_rev, 0, std::max<size_t>(nseq_all, 1) * 4) == hipSuccess;
+        if (ok && nbytes) {
+            hipLaunchKernelGGL(k_lg_views, dim3((uint32_t)((nbytes + 255) / 256)), dim3(256), 0, 0, a, (uint32_t)nseq_all);
+            ok = hipGetLastError() == hipSuccess;
+        }
+        if (!ok) { cleanup(); return fail(VC_ERR_HIP, "device allocation or launch of the strand views failed"); }
+    }
 
     // budgets from free device memory (what this library keeps cached counts as free)
     size_t free_b = 0, total_b = 0;
@@ -1552,6 +1647,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
     uint32_t *d_list = nullptr; uint64_t* d_hoff = nullptr; LWin* d_win = nullptr;
     uint64_t n_align = 0, n_cells = 0;                                     // forward passes run (VC_LARGE_LOG's "done" line)
     const uint64_t planes = a.gaps == 0 ? 1 : a.gaps == 1 ? 3 : 5;         // int32 planes per matrix cell: H (, F, E (, O, Q))
+    const uint32_t ns = so ? 2 : 1;                                        // forward passes, and matrices, per alignment: one per strand
     while (!pending.empty()) {
         // windows in flight: as many as the arena budget holds, in order (at least one)
         std::vector<uint32_t> grp;
@@ -1625,7 +1721,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
                 size_t k1 = k0;
                 for (; k1 < act.size(); ++k1) {
                     const LWin& W = hw[act[k1]];
-                    const uint64_t need = ((uint64_t)W.rows + 1) * ((uint64_t)W.qlen + 1) * planes;
+                    const uint64_t need = ((uint64_t)W.rows + 1) * ((uint64_t)W.qlen + 1) * planes * ns;
                     if (!list.empty() && (cells + need) * 4 > mat_budget) break;
                     list.push_back(act[k1]); hoff.push_back(cells); cells += need;
                 }
@@ -1644,7 +1740,7 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
                 if (!ok) break;
                 LArgs f = a;
                 f.list = d_list; f.hoff = d_hoff; f.H = H;
-                const dim3 fb(nl), bb((nl + 63) / 64);
+                const dim3 fb(nl, ns), bb((nl + 63) / 64);
                 if (a.gaps == 0) {
                     hipLaunchKernelGGL(k_lg_fwd<0>, fb, dim3(64), 0, 0, f);
                     hipLaunchKernelGGL(k_lg_back<0>, bb, dim3(64), 0, 0, f, nl);
@@ -1656,8 +1752,8 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
                     hipLaunchKernelGGL(k_lg_back<2>, bb, dim3(64), 0, 0, f, nl);
                 }
                 ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-                for (const uint32_t k : list) n_cells += (uint64_t)hw[k].rows * hw[k].qlen;
-                n_align += nl;
+                for (const uint32_t k : list) n_cells += (uint64_t)hw[k].rows * hw[k].qlen * ns;
+                n_align += (uint64_t)nl * ns;
                 launches++;
                 if (cells * 4 > mat_budget) over++;
             }
@@ -1759,6 +1855,20 @@ int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& c
             msa_launches++;
         }
         done_tmp();
+    }
+    if (so) {                                                              // the choices; zeros for the groups that were not computed
+        bool ok = hipMemcpy(so->reversed, a.s_rev, nseq_all, hipMemcpyDeviceToHost) == hipSuccess;
+        if (so->score) ok = ok && hipMemcpy(so->score, a.s_score, nseq_all * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (so->score_rev) ok = ok && hipMemcpy(so->score_rev, a.s_score_rev, nseq_all * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (!ok) { cleanup(); return fail(VC_ERR_HIP, "copy of the strand choices failed"); }
+        for (uint32_t w = 0; w < nw; ++w) {
+            if (status[w] == VC_WIN_OK) continue;
+            for (uint32_t s = b->win_seq_off[w]; s < b->win_seq_off[w + 1]; ++s) {
+                so->reversed[s] = 0;
+                if (so->score) so->score[s] = 0;
+                if (so->score_rev) so->score_rev[s] = 0;
+            }
+        }
     }
     cleanup();
     if (msa) {                                                             // per-row and per-base tables in group order

@@ -5,18 +5,24 @@ semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chos
 (gap_model); no window rules.  No CPU path: without a device the calls raise.
 
     python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [-r 0|1|2]
-                             [--coverage] [--device D] FILE [FILE ...]
+                             [--coverage] [--both-strands] [--device D] FILE [FILE ...]
 
 prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`,
 or with -r 1 / -r 2 the multiple sequence alignment of its records as FASTA (`>name` / row, with -r 2 a last row `>Consensus`;
 spoa's src/main.cpp:326-335).  -r is given once (spoa's may be repeated).  --coverage adds the tag `CV:B:I,c1,c2,...` to the
 `-r 0` header: per consensus base the number of records through its node and the nodes aligned to it (spoa's
-GenerateConsensus(&summary, false)).  spoa's GFA output (-r 3 / -r 4), --dot and --strand-ambiguous are not offered.
+GenerateConsensus(&summary, false)).  spoa's GFA output (-r 3 / -r 4) and --dot are not offered.  spoa's -s /
+--strand-ambiguous is spelt --both-strands here (those two spellings stay refused): every record is aligned as given and
+reverse-complemented, and the better strand is added, ties going forward (spoa's src/main.cpp:287-304; vc_poa_run_strand,
+poa_consensus_strands(), poa_msa(strand_ambiguous=True)).  It goes with every -r and with --coverage and changes no output
+format: spoa prints nothing about strands there either, and a row shows the bytes that were kept.
 poa_msa() is the same over groups in memory (vc_poa_run_msa).
 The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
 as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
 non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
-consensus sequences.  poa_consensus() takes sequences and qualities as given.  spoa's -e / -q / -c are spelt --gap-extend /
+consensus sequences.  poa_consensus() takes sequences and qualities as given.  With both strands spoa complements a kept forward
+record twice, which turns u / U into T and lower-case IUPAC letters into upper case (include/vechat_hip.h); since the reader
+upper-cases, on the command line only U is affected by that round trip.  spoa's -e / -q / -c are spelt --gap-extend /
 --gap-open2 / --gap-extend2 here, and the gaps stay linear unless they are given (spoa's own command line defaults to convex gaps,
 -g -8 -e -6 -q -10 -c -4).
 """
@@ -158,10 +164,11 @@ class Msa:
     """One group's result of poa_msa: rows (bytes, all of one length; '-' is a gap), members (for every row the index of the group
     member it belongs to -- an empty member has no row --, CONSENSUS_ROW for the consensus row of include_consensus), consensus
     and coverage (numpy uint32 per consensus base, or None)."""
-    __slots__ = ("rows", "members", "consensus", "coverage")
+    __slots__ = ("rows", "members", "consensus", "coverage", "reversed")
 
-    def __init__(self, rows, members, consensus, coverage):
+    def __init__(self, rows, members, consensus, coverage, reversed=None):
         self.rows, self.members, self.consensus, self.coverage = rows, members, consensus, coverage
+        self.reversed = reversed                 # poa_msa(strand_ambiguous=True): numpy bool per group member, else None
 
     def __iter__(self):
         return iter((self.rows, self.members, self.consensus, self.coverage))
@@ -170,9 +177,11 @@ class Msa:
 CONSENSUS_ROW = capi.VC_POA_ROW_CONSENSUS
 
 
-def run_batch_msa(batch, params, flags, lib=None):
+def run_batch_msa(batch, params, flags, lib=None, strands=False):
     """vc_poa_run_msa (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits) on a capi.Batch -> (list of Msa, status array).
-    Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error."""
+    Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error.
+    strands=True: vc_poa_run_strand instead -> (list of Msa with .reversed, status array, forward scores, reverse scores), the
+    scores as one int32 array per group."""
     lib = lib or capi.load_hip()
     n = batch.n_windows
     cons = np.zeros(max(int(batch.bases.size), 1), np.uint8)
@@ -183,9 +192,17 @@ def run_batch_msa(batch, params, flags, lib=None):
     vb = batch.as_struct()
     vb.seq_begin = vb.seq_end = vb.win_fasta = None
     o = capi.VcPoaMsaOut(flags=flags)
-    rc = lib.vc_poa_run_msa(C.byref(params), C.byref(vb), C.byref(r), C.byref(o))
+    wso = [int(x) for x in batch.win_seq_off]
+    if strands:
+        nseq = max(wso[-1], 1)
+        rev, sc, scr = np.zeros(nseq, np.uint8), np.zeros(nseq, np.int32), np.zeros(nseq, np.int32)
+        so = capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)), sc.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 scr.ctypes.data_as(C.POINTER(C.c_int32)))
+        name, rc = "vc_poa_run_strand", lib.vc_poa_run_strand(C.byref(params), C.byref(vb), C.byref(r), C.byref(o), C.byref(so))
+    else:
+        name, rc = "vc_poa_run_msa", lib.vc_poa_run_msa(C.byref(params), C.byref(vb), C.byref(r), C.byref(o))
     if rc != 0:
-        raise PoaError(f"vc_poa_run_msa failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+        raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     res = []
     rows_base = C.addressof(o.rows.contents) if o.rows else 0
     for w in range(n):
@@ -198,27 +215,58 @@ def run_batch_msa(batch, params, flags, lib=None):
             members = [int(o.row_member[m0 + i]) for i in range(k)]
         if flags & capi.VC_POA_COVERAGE:
             cov = np.array(o.coverage[c0:c1], np.uint32) if o.coverage and c1 > c0 else np.zeros(0, np.uint32)
-        res.append(Msa(rows, members, cons[c0:c1].tobytes(), cov))
+        res.append(Msa(rows, members, cons[c0:c1].tobytes(), cov, rev[wso[w]:wso[w + 1]].astype(bool) if strands else None))
+    if strands:
+        return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
     return res, status[:n]
 
 
-def poa_msa(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-            gap_extend=None, gap_open2=None, gap_extend2=None, include_consensus=False, coverage=False):
-    """The multiple sequence alignment of every group (spoa's GenerateMultipleSequenceAlignment(include_consensus)) -> list of
-    Msa; with coverage=True also the coverage of every consensus base (GenerateConsensus(&summary, false)).  Parameters,
-    PoaError and strict as poa_consensus (a group that was not computed comes back as None with strict=False); the gap scores
-    left out are spoa's overload defaults, so the default call runs linear gaps and its consensus is poa_consensus's."""
-    batch = group_batch(groups)
+def _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2):
     e = gap if gap_extend is None else gap_extend
-    p = capi.VcPoaGapParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap_open=gap,
-                            gap_extend=e, gap_open2=gap if gap_open2 is None else gap_open2,
-                            gap_extend2=e if gap_extend2 is None else gap_extend2)
-    flags = capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if include_consensus else 0) | (capi.VC_POA_COVERAGE if coverage else 0)
-    res, status = run_batch_msa(batch, p, flags, lib)
+    return capi.VcPoaGapParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap_open=gap,
+                               gap_extend=e, gap_open2=gap if gap_open2 is None else gap_open2,
+                               gap_extend2=e if gap_extend2 is None else gap_extend2)
+
+
+def _not_computed(status, strict):
     bad = {w: int(s) for w, s in enumerate(status) if int(s) != capi.VC_WIN_OK}
     if bad and strict:
         what = ", ".join(f"{w}: {_STATUS.get(s, s)}" for w, s in list(bad.items())[:8])
         raise PoaError(f"{len(bad)} group(s) not computed: {what}{' ...' if len(bad) > 8 else ''}", groups=bad)
+    return bad
+
+
+def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+                          gap_extend=None, gap_open2=None, gap_extend2=None, scores=False):
+    """Consensus of every group whose members may come from either strand (spoa's -s, vc_poa_run_strand): every member is
+    aligned as given and reverse-complemented and the better strand is added, ties going forward -> (list of consensus bytes,
+    list of numpy bool arrays: per group, per member -- empty members included -- True where the reverse complement was kept).
+    With scores=True also the forward and the reverse score of every member, two lists of int32 arrays.  The consensus is on the
+    strand of the group's first non-empty member.  A kept forward member has been complemented twice: u / U count as T and
+    lower-case IUPAC letters as upper case (include/vechat_hip.h).  Parameters, PoaError and strict as poa_consensus; the gap
+    scores left out are spoa's overload defaults."""
+    batch = group_batch(groups)
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    res, status, sc, scr = run_batch_msa(batch, p, 0, lib, strands=True)
+    bad = _not_computed(status, strict)
+    cons = [None if w in bad else m.consensus for w, m in enumerate(res)]
+    rev = [m.reversed for m in res]
+    return (cons, rev, sc, scr) if scores else (cons, rev)
+
+
+def poa_msa(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+            gap_extend=None, gap_open2=None, gap_extend2=None, include_consensus=False, coverage=False, strand_ambiguous=False):
+    """The multiple sequence alignment of every group (spoa's GenerateMultipleSequenceAlignment(include_consensus)) -> list of
+    Msa; with coverage=True also the coverage of every consensus base (GenerateConsensus(&summary, false)).  Parameters,
+    PoaError and strict as poa_consensus (a group that was not computed comes back as None with strict=False); the gap scores
+    left out are spoa's overload defaults, so the default call runs linear gaps and its consensus is poa_consensus's.
+    strand_ambiguous=True is spoa's -s (vc_poa_run_strand, see poa_consensus_strands): Msa.reversed then tells, per group
+    member, whether the reverse complement was kept, and a row shows the kept bytes."""
+    batch = group_batch(groups)
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    flags = capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if include_consensus else 0) | (capi.VC_POA_COVERAGE if coverage else 0)
+    res, status = run_batch_msa(batch, p, flags, lib, strands=True)[:2] if strand_ambiguous else run_batch_msa(batch, p, flags, lib)
+    bad = _not_computed(status, strict)
     return [None if w in bad else m for w, m in enumerate(res)]
 
 
@@ -245,6 +293,9 @@ def parse_args(argv=None):
                          "'Consensus' (spoa's -r; given once here, and without spoa's GFA modes 3 and 4); default 0")
     ap.add_argument("--coverage", action="store_true",
                     help="with -r 0: add the tag CV:B:I,c1,c2,... to the header, the coverage of every consensus base")
+    ap.add_argument("--both-strands", action="store_true",
+                    help="align every record as given and reverse-complemented and add the better strand (spoa's -s / "
+                         "--strand-ambiguous); the output formats are unchanged")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="+", metavar="FILE")
     return ap.parse_args(argv)
@@ -262,9 +313,13 @@ def main(argv=None):
         groups = [[(data, qual) for _, data, qual in recs] for recs in records]
         gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
         if a.r == 0 and not a.coverage:
-            cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)
+            if a.both_strands:
+                cons = poa_consensus_strands(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)[0]
+            else:
+                cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)
         else:
-            msa = poa_msa(groups, a.l, a.m, a.n, a.g, device=a.device, include_consensus=a.r == 2, coverage=a.coverage, **gaps)
+            strands = dict(strand_ambiguous=True) if a.both_strands else {}
+            msa = poa_msa(groups, a.l, a.m, a.n, a.g, device=a.device, include_consensus=a.r == 2, coverage=a.coverage, **gaps, **strands)
     except (PoaError, ValueError, OSError) as e:
         print(f"vechat_amd.poa: {e}", file=sys.stderr)
         return 1
