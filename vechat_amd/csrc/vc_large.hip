@@ -15,8 +15,8 @@
 //     overload where a sequence has one (weights vc_weight_lut, graph.cpp:160-171) and weight 1 otherwise, GenerateConsensus at
 //     the end (graph.cpp:450-459, the heaviest bundle with branch completion).  One engine for every alignment of the batch,
 //     kSW / kNW / kOV with the caller's scores: linear gaps (vc_poa_run), or linear, affine or convex ones as spoa's
-//     Create(type, m, n, g, e, q, c) chooses (vc_poa_run_gaps; LArgs::gaps, k_lg_fwd / k_lg_back <1> and <2> with 3 and 5 int32
-//     planes per matrix cell).  None of the window rules apply: no rank sort, spans, subgraph,
+//     Create(type, m, n, g, e, q, c) chooses (vc_poa_run_gaps; LArgs::gaps = GM of k_lg_fwd / k_lg_back <GM>: 0, 1, 2 with 1, 3
+//     and 5 int32 planes per matrix cell, one body each).  None of the window rules apply: no rank sort, spans, subgraph,
 //     UpdateAlignment, "< 3 sequences", prune, trim, window type or FASTA-backbone quirk; seq_begin / seq_end / win_fasta are
 //     never uploaded.  An empty sequence adds nothing (graph.cpp:187-190); a group of none, or of empty ones only, has the
 //     empty consensus (graph.cpp:534-537).
@@ -35,9 +35,10 @@
 //               empty graph, or at once the empty consensus of an empty group);
 //   k_lg_prep   one lane per window: the next alignment of the window's schedule (subgraph of a partial-span layer when the
 //               build needs one), its rank-ordered predecessor lists (CSR of row indices), row bytes and sink flags;
-//   k_lg_fwd    one wave per alignment: rows in rank order, columns over the 64 lanes; predecessor rows are read back from the
-//               int32 matrix (rows + 1) x (len + 1) in HBM; the horizontal move is a wave prefix maximum on tilted scores;
-//   k_lg_back   one lane per alignment: walks the stored matrix in the oracle's order of candidates;
+//   k_lg_fwd    <GM>, one wave per alignment: rows in rank order, columns over the 64 lanes; predecessor rows are read back from
+//               the int32 planes (rows + 1) x (len + 1) in HBM; the horizontal move is a wave prefix maximum on tilted scores
+//               (gap_scan), for every gap model;
+//   k_lg_back   <GM>, one lane per alignment: walks the stored planes in the reference's order of candidates;
 //   k_lg_apply  one lane per window: add-alignment + topological sort, or add-weights; prune + largest component at the end of
 //               the build and of every round; the corrected sequence (mode 0), heaviest bundle + coverage + trim (mode 1) or the
 //               heaviest bundle alone (mode 2).
@@ -557,6 +558,14 @@ __device__ uint32_t coverage(LWin& W, const LGraph& g, uint32_t v, uint32_t tick
     return cnt;
 }
 
+// the bases of the bundle's nodes W.comp[begin .. end] are the consensus, and the window or group is done
+__device__ void write_consensus(LWin& W, const LGraph& G, int32_t begin, int32_t end) {
+    W.cons_n = 0;
+    for (int32_t i = begin; i <= end; ++i) W.cons[W.cons_n++] = (uint8_t)W.decoder[G.code[W.comp[i]]];
+    W.status = VC_WIN_OK;
+    W.phase = PH_DONE;
+}
+
 // window_linear after build_graph: heaviest bundle, coverage, TGS trim
 __device__ void finish_linear(const LArgs& a, LWin& W) {
     const LGraph& G = W.gr[W.cur];
@@ -576,20 +585,13 @@ __device__ void finish_linear(const LArgs& a, LWin& W) {
         for (; end >= 0; --end) if (cov[end] >= avgc) break;
         if (begin >= end) { begin = 0; end = (int32_t)n - 1; }
     }
-    W.cons_n = 0;
-    for (int32_t i = begin; i <= end; ++i) W.cons[W.cons_n++] = (uint8_t)W.decoder[G.code[W.comp[i]]];
-    W.status = VC_WIN_OK;
-    W.phase = PH_DONE;
+    write_consensus(W, G, begin, end);
 }
 
 // Graph::GenerateConsensus of a POA group (graph.cpp:450-459): the heaviest bundle, no coverage, no trim
 __device__ void finish_poa(LWin& W) {
     const LGraph& G = W.gr[W.cur];
-    const uint32_t n = heaviest_bundle(W, G);
-    W.cons_n = 0;
-    for (uint32_t i = 0; i < n; ++i) W.cons[W.cons_n++] = (uint8_t)W.decoder[G.code[W.comp[i]]];
-    W.status = VC_WIN_OK;
-    W.phase = PH_DONE;
+    write_consensus(W, G, 0, (int32_t)heaviest_bundle(W, G) - 1);
 }
 
 __device__ __forceinline__ bool full_span(const LArgs& a, const LWin& W, uint32_t s) {
@@ -742,28 +744,26 @@ __device__ __forceinline__ bool better(int32_t s, uint32_t i, uint32_t j, int32_
     return s > bs || (s == bs && (i < bi || (i == bi && j < bj)));
 }
 
-// The horizontal gap of an affine / convex row as a wave scan: out[q] = max over the columns k < j of v[k] - k d, where column j =
-// j0 + q, v holds this lane's kCols columns (columns beyond len take no part) and carry the maximum over the chunks before (it
-// starts at column 0's term and is updated here).  Every lane calls it: it shuffles.
-__device__ __forceinline__ void gap_scan(const int32_t (&v)[kCols], uint32_t j0, uint32_t len, int32_t d, int64_t& carry,
-                                         int64_t (&out)[kCols]) {
+// The horizontal gap of a row as a wave scan: out[q] = max over the columns k < j of v[k] - k d, where column j = j0 + q, v holds
+// this lane's kCols columns and carry the maximum over the chunks before (it starts at column 0's term and is updated here).
+// Columns beyond the sequence need no test: they lie behind every real column, only in the last chunk, and a prefix maximum
+// carries nothing backwards, so whatever v holds there reaches no real column (and the carry is not read again).
+// Every lane calls it: it shuffles.
+__device__ __forceinline__ void gap_scan(const int32_t (&v)[kCols], uint32_t j0, int32_t d, int64_t& carry, int64_t (&out)[kCols]) {
     const uint32_t lane = threadIdx.x;
     int64_t run = TNEG;
 #pragma unroll
     for (uint32_t q = 0; q < kCols; ++q) {
         out[q] = run;
-        const uint32_t j = j0 + q;
-        if (j <= len) {
-            const int64_t t = (int64_t)v[q] - (int64_t)j * d;
-            if (t > run) run = t;
-        }
+        const int64_t t = (int64_t)v[q] - (int64_t)(j0 + q) * d;
+        if (t > run) run = t;
     }
     int64_t T = run;                                                   // inclusive scan of the lanes' maxima
     for (uint32_t s = 1; s < 64; s <<= 1) {
-        const int64_t o = __shfl_up(T, s, 64);
-        if (lane >= s && o > T) T = o;
+        const int64_t o = __shfl_up(T, s, 64);                         // (a lane below s gets its own T back)
+        if (o > T) T = o;
     }
-    int64_t before = __shfl_up(T, 1, 64);
+    int64_t before = __shfl_up(T, 1, 64);                              // what the lanes in front (and the chunks before) reached
     if (lane == 0 || carry > before) before = carry;
     const int64_t last = __shfl(T, 63, 64);
     if (last > carry) carry = last;
@@ -771,34 +771,59 @@ __device__ __forceinline__ void gap_scan(const int32_t (&v)[kCols], uint32_t j0,
     for (uint32_t q = 0; q < kCols; ++q) if (before > out[q]) out[q] = before;
 }
 
-// g_align's forward pass with affine (GM 1) or convex (GM 2) gaps, sisd_alignment_engine.cpp:462-540 / :678-770 with Initialize
-// (:120-246).  The planes H, F, E (and O, Q) follow each other, (rows + 1) x (len + 1) int32 each, and hold spoa's values cell
-// for cell, the kNegativeInfinity borders and column 0's F / O chains included: the backtrack compares them for equality.
-// Per row: x[j] = max(diagonal, F[j] (, O[j]) (, 0 for kSW)) over every predecessor row, as the linear pass does; then the
-// horizontal gaps.  Since g <= e, E[j] = max(max_k<j (H[k] + g + (j - 1 - k) e), kNegativeInfinity + j e) equals the same
-// maximum over x[k] with x[0] = H[i][0]: one exclusive prefix maximum of x[k] - k e gives E and H = max(x, E).  Convex: H comes
-// out of the two scans over x, (g, e) and (q, c), but E and Q do not (E may extend a gap opened in Q and vice versa), so they
-// are scanned a second time over the final H.
+// int32 planes per matrix cell under gap model gm (LArgs::gaps, the kernels' GM): H (, F, E (, O, Q))
+__host__ __device__ constexpr uint32_t plane_count(uint32_t gm) { return gm == 0 ? 1 : gm == 1 ? 3 : 5; }
+
+// The matrix of the alignment in slot `slot` of a launch, strand st: plane_count(GM) planes of (rows + 1) x (len + 1) int32 each,
+// one behind the other, strand 1's behind strand 0's.  w: cells per row.  A plane GM does not have is nullptr.
+struct Mat { uint64_t w; int32_t *H, *F, *E, *O, *Q; };
+
 template <uint32_t GM>
-__device__ void fwd_gaps(const LArgs& a) {
+__device__ __forceinline__ Mat matrix_of(const LArgs& a, uint32_t slot, const LWin& W, uint32_t st) {
+    Mat M{};
+    M.w = (uint64_t)W.qlen + 1;
+    const uint64_t P = ((uint64_t)W.rows + 1) * M.w;
+    M.H = a.H + a.hoff[slot] + st * plane_count(GM) * P;
+    if constexpr (GM >= 1) { M.F = M.H + P; M.E = M.F + P; }
+    if constexpr (GM == 2) { M.O = M.E + P; M.Q = M.O + P; }
+    return M;
+}
+
+// g_align's forward pass with linear (GM 0, sisd_alignment_engine.cpp:292-367), affine (GM 1, :462-540) or convex (GM 2,
+// :678-770) gaps and Initialize (:120-246): one wave per alignment and strand.  Row i = rank i - 1; lane l holds columns
+// 512 c + 8 l + 1 .. + 8 of chunk c.  The planes hold spoa's values cell for cell, the kNegativeInfinity borders and column 0's
+// F / O chains included: the backtrack compares them for equality.  A row is stored and the next may read it after the barrier.
+// Per row: x[j] = max(diagonal, F[j] (, O[j]) (, 0 for kSW)) over every predecessor row -- SW clamps first, C[j] = max(0, x[j],
+// C[j-1] + g) being the plain recurrence on max(0, x) --; then the horizontal gaps.  Since g <= e, E[j] = max(max_k<j (H[k] + g +
+// (j - 1 - k) e), kNegativeInfinity + j e) equals the same maximum over x[k] with x[0] = H[i][0]: one exclusive prefix maximum of
+// the tilted x[k] - k e (gap_scan, carried from chunk to chunk) gives E and H = max(x, E).
+// GM 0 is that recurrence with e = g and H alone: the vertical term is H + g, column 0's chain lives in H itself, nothing but H
+// is stored, and column 0's scan term max(H[i][0], kNegativeInfinity - g + e) is H[i][0] (k_lg_prep's worst-case check keeps
+// every score above kNegativeInfinity).
+// Convex: H comes out of the two scans over x, (g, e) and (q, c), but E and Q do not (E may extend a gap opened in Q and vice
+// versa), so they are scanned a second time over the final H.
+// kOV: column 0 of a graph row is 0 instead of the vertical chain (so the horizontal move starts from 0), and every cell of a
+// sink row is an end-cell candidate, not only the last column.
+template <uint32_t GM>
+__global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
     LWin& W = a.win[a.list[blockIdx.x]];
     const uint32_t lane = threadIdx.x;
     const uint32_t N = W.rows, len = W.qlen;
-    const uint64_t w = (uint64_t)len + 1, P = ((uint64_t)N + 1) * w;
-    const uint32_t st = blockIdx.y;                                    // the strand; its planes follow the forward strand's
-    int32_t* H = a.H + a.hoff[blockIdx.x] + st * (GM == 2 ? 5 : 3) * P;
-    int32_t* F = H + P;
-    int32_t* E = F + P;
-    int32_t* O = GM == 2 ? E + P : nullptr;
-    int32_t* Q = GM == 2 ? O + P : nullptr;
+    const uint32_t st = blockIdx.y;                                    // the strand
+    const Mat M = matrix_of<GM>(a, blockIdx.x, W, st);
+    const uint64_t w = M.w;
+    int32_t *const H = M.H, *const F = M.F, *const E = M.E, *const O = M.O, *const Q = M.Q;
     const bool sw = W.type == 0, ov = W.type == 2;
-    const int32_t m = W.m, x = W.x, gp = W.g, ge = W.e, gq = W.q, gc = W.c;
+    const int32_t m = W.m, x = W.x, gp = W.g, ge = GM == 0 ? gp : W.e, gq = W.q, gc = W.c;
     const uint8_t* seq = aligned_bases(a, W.qs, st);
+    auto vertical = [&](uint64_t c) -> int32_t {                       // F's term from cell c of a predecessor row
+        if constexpr (GM == 0) return H[c] + gp;
+        else return max(H[c] + gp, F[c] + ge);
+    };
     for (uint32_t j = lane; j <= len; j += 64) {                       // row 0
         const int32_t ej = j == 0 ? 0 : gp + (int32_t)(j - 1) * ge;
         int32_t h = ej;
-        F[j] = j == 0 ? 0 : KNEG;
-        E[j] = ej;
+        if constexpr (GM >= 1) { F[j] = j == 0 ? 0 : KNEG; E[j] = ej; }
         if constexpr (GM == 2) {
             const int32_t qj = j == 0 ? 0 : gq + (int32_t)(j - 1) * gc;
             O[j] = j == 0 ? 0 : KNEG;
@@ -811,25 +836,27 @@ __device__ void fwd_gaps(const LArgs& a) {
     int32_t bs = sw ? 0 : KNEG;
     uint32_t bi = 0, bj = 0;
     for (uint32_t r = 0; r < N; ++r) {
-        const uint64_t i = (uint64_t)r + 1;
+        const uint64_t i = (uint64_t)r + 1, ro = i * w;
         const uint32_t po = W.poff[r], pe = W.poff[r + 1];
         const uint8_t ch = W.rchar[r];
         const bool sink = W.sink[r] != 0;
+        const int32_t* F0 = GM == 0 ? H : F;                           // column 0's vertical chain
         int32_t f0 = pe == po ? gp - ge : KNEG, o0 = pe == po ? gq - gc : KNEG;
         for (uint32_t k = po; k < pe; ++k) {
-            f0 = max(f0, F[(uint64_t)W.prank[k] * w]);
+            f0 = max(f0, F0[(uint64_t)W.prank[k] * w]);
             if constexpr (GM == 2) o0 = max(o0, O[(uint64_t)W.prank[k] * w]);
         }
         f0 += ge; o0 += gc;
         const int32_t h0 = (sw || ov) ? 0 : (GM == 2 ? max(o0, f0) : f0);
-        int32_t *Hr = H + i * w, *Fr = F + i * w, *Er = E + i * w;
         if (lane == 0) {
-            Hr[0] = h0; Fr[0] = f0; Er[0] = KNEG;
-            if constexpr (GM == 2) { O[i * w] = o0; Q[i * w] = KNEG; }
+            H[ro] = h0;
+            if constexpr (GM >= 1) { F[ro] = f0; E[ro] = KNEG; }
+            if constexpr (GM == 2) { O[ro] = o0; Q[ro] = KNEG; }
         }
         // column 0's terms of the scans, kNegativeInfinity's chain (E[i][0] + j e) beside H[i][0]
         int64_t cxe = max((int64_t)h0, (int64_t)KNEG - gp + ge), cxq = max((int64_t)h0, (int64_t)KNEG - gq + gc);
         int64_t che = cxe, chq = cxq;
+        // a chunk is 64 lanes x kCols consecutive columns: the prefix maximum runs inside a lane first, then once across the lanes
         for (uint32_t cb = 0; cb < len; cb += 64 * kCols) {
             const uint32_t j0 = cb + lane * kCols + 1;
             int32_t xv[kCols];
@@ -840,24 +867,24 @@ __device__ void fwd_gaps(const LArgs& a) {
                 if (j > len) continue;
                 const int32_t s = seq[j - 1] == ch ? m : x;
                 uint64_t p = pe == po ? 0 : (uint64_t)W.prank[po] * w;
-                int32_t d = H[p + j - 1] + s, f = max(H[p + j] + gp, F[p + j] + ge), o = KNEG;
+                int32_t d = H[p + j - 1] + s, f = vertical(p + j), o = KNEG;
                 if constexpr (GM == 2) o = max(H[p + j] + gq, O[p + j] + gc);
                 for (uint32_t k = po + 1; k < pe; ++k) {
                     p = (uint64_t)W.prank[k] * w;
                     d = max(d, H[p + j - 1] + s);
-                    f = max(f, max(H[p + j] + gp, F[p + j] + ge));
+                    f = max(f, vertical(p + j));
                     if constexpr (GM == 2) o = max(o, max(H[p + j] + gq, O[p + j] + gc));
                 }
-                Fr[j] = f;
                 int32_t v = max(d, f);
-                if constexpr (GM == 2) { O[i * w + j] = o; v = max(v, o); }
+                if constexpr (GM >= 1) F[ro + j] = f;
+                if constexpr (GM == 2) { O[ro + j] = o; v = max(v, o); }
                 if (sw) v = max(v, 0);
                 xv[q] = v;
             }
             int64_t se[kCols], sq[kCols];
             int32_t hv[kCols];
-            gap_scan(xv, j0, len, ge, cxe, se);
-            if constexpr (GM == 2) gap_scan(xv, j0, len, gc, cxq, sq);
+            gap_scan(xv, j0, ge, cxe, se);
+            if constexpr (GM == 2) gap_scan(xv, j0, gc, cxq, sq);
 #pragma unroll
             for (uint32_t q = 0; q < kCols; ++q) {
                 const int64_t j = (int64_t)(j0 + q);
@@ -866,17 +893,17 @@ __device__ void fwd_gaps(const LArgs& a) {
                 hv[q] = (int32_t)h;
             }
             if constexpr (GM == 2) {                                   // E and Q over the final H
-                gap_scan(hv, j0, len, ge, che, se);
-                gap_scan(hv, j0, len, gc, chq, sq);
+                gap_scan(hv, j0, ge, che, se);
+                gap_scan(hv, j0, gc, chq, sq);
             }
 #pragma unroll
             for (uint32_t q = 0; q < kCols; ++q) {
                 const uint32_t j = j0 + q;
                 if (j > len) break;
                 const int32_t h = hv[q];
-                Hr[j] = h;
-                Er[j] = (int32_t)(se[q] + (gp - ge) + (int64_t)j * ge);
-                if constexpr (GM == 2) Q[i * w + j] = (int32_t)(sq[q] + (gq - gc) + (int64_t)j * gc);
+                H[ro + j] = h;
+                if constexpr (GM >= 1) E[ro + j] = (int32_t)(se[q] + (gp - ge) + (int64_t)j * ge);
+                if constexpr (GM == 2) Q[ro + j] = (int32_t)(sq[q] + (gq - gc) + (int64_t)j * gc);
                 if (sw ? h > bs : (sink && (ov || j == len) && h > bs)) { bs = h; bi = (uint32_t)i; bj = j; }
             }
         }
@@ -890,112 +917,24 @@ __device__ void fwd_gaps(const LArgs& a) {
     if (lane == 0) { W.max_i[st] = bi; W.max_j[st] = bj; W.score[st] = bs; }
 }
 
-// One wave per alignment (g_align's forward pass).  Row i = rank i - 1; lane l holds columns 512 c + 8 l + 1 .. + 8 of chunk c.
-// Diagonal / vertical moves from every predecessor row give x[j]; SW clamps it at 0 first (C[j] = max(0, x[j], C[j-1] + g) is the
-// plain recurrence on max(0, x)); the horizontal move H[j] = max_k<=j (x[k] + (j - k) g) is a prefix maximum of the tilted
-// T[k] = x[k] - k g, carried from chunk to chunk.  The matrix row is stored and the next row may read it after the barrier.
-// kOV: column 0 of a graph row is 0 instead of the vertical chain (so the horizontal move starts from 0), and every cell of a
-// sink row is an end-cell candidate, not only the last column.  GM 1 / 2: fwd_gaps.
+// g_align's backtrack, one lane per alignment, in the reference's order of candidates, literally.
+// GM 0 (Linear, sisd_alignment_engine.cpp:369-460): the diagonal from each predecessor (in in-edge order), vertical likewise, then
+// horizontal; one pair per step.
+// GM 1 (Affine, :542-676) and GM 2 (Convex, :780-925): the diagonal over the in-edges; then vertical (extend_up when H == F + e /
+// O + c of a predecessor, an opening when H == H + g / + q); then horizontal (extend_left from E / Q likewise); then the inner
+// loops that emit a whole gap run.  Affine's vertical run stops on F == H + g; convex's tries the extensions over every in-edge
+// first, then the openings (prev_i = 0 when none is found).
 template <uint32_t GM>
-__global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
-    if constexpr (GM != 0) {
-        fwd_gaps<GM>(a);
-        return;
-    }
-    LWin& W = a.win[a.list[blockIdx.x]];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t N = W.rows, len = W.qlen;
-    const uint64_t w = (uint64_t)len + 1;
-    const uint32_t st = blockIdx.y;                                        // the strand; its matrix follows the forward strand's
-    int32_t* H = a.H + a.hoff[blockIdx.x] + st * ((uint64_t)N + 1) * w;
-    const bool sw = W.type == 0, ov = W.type == 2;
-    const int32_t m = W.m, x = W.x, gp = W.g;
-    const uint8_t* seq = aligned_bases(a, W.qs, st);
-    for (uint32_t j = lane; j <= len; j += 64) H[j] = (sw || j == 0) ? 0 : (int32_t)j * gp;
-    __syncthreads();
-    int32_t bs = sw ? 0 : KNEG;
-    uint32_t bi = 0, bj = 0;
-    for (uint32_t r = 0; r < N; ++r) {
-        const uint64_t i = (uint64_t)r + 1;
-        const uint32_t po = W.poff[r], pe = W.poff[r + 1];
-        const uint8_t c = W.rchar[r];
-        const bool sink = W.sink[r] != 0;
-        int32_t h0 = 0;                                                    // SW and OV (sisd_alignment_engine.cpp:182-190, 227-247)
-        if (!sw && !ov) {
-            int32_t pen = pe == po ? 0 : KNEG;
-            for (uint32_t k = po; k < pe; ++k) pen = max(pen, H[(uint64_t)W.prank[k] * w]);
-            h0 = pen + gp;
-        }
-        int32_t* Hr = H + i * w;
-        if (lane == 0) Hr[0] = h0;
-        int64_t carry = h0;
-        // a chunk is 64 lanes x kCols consecutive columns: the prefix maximum runs inside a lane first, then once across the lanes
-        for (uint32_t cb = 0; cb < len; cb += 64 * kCols) {
-            const uint32_t j0 = cb + lane * kCols + 1;
-            int64_t t[kCols];
-#pragma unroll
-            for (uint32_t q = 0; q < kCols; ++q) {
-                const uint32_t j = j0 + q;
-                t[q] = TNEG;
-                if (j <= len) {
-                    const int32_t s = seq[j - 1] == c ? m : x;
-                    const int32_t* Hp = H + (pe == po ? 0 : (uint64_t)W.prank[po] * w);
-                    int32_t v = max(Hp[j - 1] + s, Hp[j] + gp);
-                    for (uint32_t k = po + 1; k < pe; ++k) {
-                        Hp = H + (uint64_t)W.prank[k] * w;
-                        v = max(v, max(Hp[j - 1] + s, Hp[j] + gp));
-                    }
-                    if (sw) v = max(v, 0);
-                    t[q] = (int64_t)v - (int64_t)j * gp;
-                }
-                if (q > 0 && t[q - 1] > t[q]) t[q] = t[q - 1];
-            }
-            int64_t T = t[kCols - 1];                                      // inclusive scan of the lanes' maxima
-            for (uint32_t d = 1; d < 64; d <<= 1) {
-                const int64_t o = __shfl_up(T, d, 64);
-                if (lane >= d && o > T) T = o;
-            }
-            int64_t before = __shfl_up(T, 1, 64);                          // what the lanes in front (and the chunks before) reached
-            if (lane == 0 || carry > before) before = carry;
-            const int64_t last = __shfl(T, 63, 64);
-            if (last > carry) carry = last;
-#pragma unroll
-            for (uint32_t q = 0; q < kCols; ++q) {
-                const uint32_t j = j0 + q;
-                if (j > len) break;
-                const int32_t h = (int32_t)((t[q] > before ? t[q] : before) + (int64_t)j * gp);
-                Hr[j] = h;
-                if (sw ? h > bs : (sink && (ov || j == len) && h > bs)) { bs = h; bi = (uint32_t)i; bj = j; }
-            }
-        }
-        __syncthreads();
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int32_t os = __shfl_xor(bs, d, 64);
-        const uint32_t oi = __shfl_xor(bi, d, 64), oj = __shfl_xor(bj, d, 64);
-        if (better(os, oi, oj, bs, bi, bj)) { bs = os; bi = oi; bj = oj; }
-    }
-    if (lane == 0) { W.max_i[st] = bi; W.max_j[st] = bj; W.score[st] = bs; }
-}
-
-// The backtrack of Affine (GM 1, sisd_alignment_engine.cpp:542-676) and Convex (GM 2, :780-925), literally: the diagonal over
-// the in-edges; then vertical (extend_up when H == F + e / O + c of a predecessor, an opening when H == H + g / + q); then
-// horizontal (extend_left from E / Q likewise); then the inner loops that emit a whole gap run.  Affine's vertical run stops on
-// F == H + g; convex's tries the extensions over every in-edge first, then the openings (prev_i = 0 when none is found).
-template <uint32_t GM>
-__device__ void back_gaps(const LArgs& a, uint32_t n) {
+__global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= n) return;
     LWin& W = a.win[a.list[b]];
-    const uint64_t w = (uint64_t)W.qlen + 1, P = ((uint64_t)W.rows + 1) * w;
     // the strand: spoa keeps the forward one unless the reverse complement scores higher (main.cpp:297), and walks that matrix
     const uint32_t st = a.strand && W.score[0] < W.score[1];
     W.rev = st;
-    const int32_t* H = a.H + a.hoff[b] + st * (GM == 2 ? 5 : 3) * P;
-    const int32_t* F = H + P;
-    const int32_t* E = F + P;
-    const int32_t* O = E + P;                                          // O, Q: convex only
-    const int32_t* Q = O + P;
+    const Mat M = matrix_of<GM>(a, b, W, st);
+    const uint64_t w = M.w;
+    const int32_t *const H = M.H, *const F = M.F, *const E = M.E, *const O = M.O, *const Q = M.Q;
     const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
     const uint8_t* seq = aligned_bases(a, W.qs, st);
     const bool sw = W.type == 0, ov = W.type == 2;
@@ -1017,7 +956,7 @@ __device__ void back_gaps(const LArgs& a, uint32_t n) {
         uint32_t pi = 0, pj = 0;
         bool found = false, up = false, left = false;
         const uint32_t po = i ? W.poff[i - 1] : 0, pe = i ? W.poff[i] : 0;
-        const uint32_t ncand = pe > po ? pe - po : 1;
+        const uint32_t ncand = pe > po ? pe - po : 1;                      // a row without predecessors follows row 0
         if (i != 0 && j != 0) {
             const int32_t s = seq[j - 1] == W.rchar[i - 1] ? W.m : W.x;
             for (uint32_t k = 0; k < ncand; ++k) {
@@ -1028,120 +967,64 @@ __device__ void back_gaps(const LArgs& a, uint32_t n) {
         if (!found && i != 0) {
             for (uint32_t k = 0; k < ncand; ++k) {
                 const uint64_t c = (uint64_t)(pe > po ? W.prank[po + k] : 0) * w + j;
-                if constexpr (GM == 1) found = (up = Hij == F[c] + ge) || Hij == H[c] + gp;
+                if constexpr (GM == 0) found = Hij == H[c] + gp;
+                else if constexpr (GM == 1) found = (up = Hij == F[c] + ge) || Hij == H[c] + gp;
                 else found = (up = Hij == F[c] + ge) || Hij == H[c] + gp || (up = Hij == O[c] + gc) || Hij == H[c] + gq;
                 if (found) { pi = (uint32_t)(c / w); pj = j; break; }
             }
         }
         if (!found && j != 0) {
             const uint64_t c = (uint64_t)i * w + j - 1;
-            if constexpr (GM == 1) found = (left = Hij == E[c] + ge) || Hij == H[c] + gp;
+            if constexpr (GM == 0) found = Hij == H[c] + gp;
+            else if constexpr (GM == 1) found = (left = Hij == E[c] + ge) || Hij == H[c] + gp;
             else found = (left = Hij == E[c] + ge) || Hij == H[c] + gp || (left = Hij == Q[c] + gc) || Hij == H[c] + gq;
             if (found) { pi = i; pj = j - 1; }
         }
         if (!found) { fail_window(W, VC_WIN_INVALID); return; }             // cannot happen on a DAG
         if (!emit(i == pi ? -1 : (int32_t)g.rank[i - 1], j == pj ? -1 : (int32_t)j - 1)) return;
         i = pi; j = pj;
-        if (left) {
-            for (;;) {
-                if (j == 0) { fail_window(W, VC_WIN_INVALID); return; }     // E[i][0] is kNegativeInfinity: cannot happen
-                if (!emit(-1, (int32_t)j - 1)) return;
-                --j;
-                const uint64_t c = (uint64_t)i * w + j;
-                if constexpr (GM == 1) { if (E[c] + ge != E[c + 1]) break; }
-                else { if (E[c] + ge != E[c + 1] && Q[c] + gc != Q[c + 1]) break; }
-            }
-        } else if (up) {
-            for (;;) {
-                if (i == 0) { fail_window(W, VC_WIN_INVALID); return; }     // F[0][j] is kNegativeInfinity: cannot happen
-                const uint64_t c = (uint64_t)i * w + j;
-                const uint32_t qo = W.poff[i - 1], qe = W.poff[i];
-                bool stop;
-                uint32_t prev = 0;
-                if constexpr (GM == 1) {
-                    stop = false;
-                    for (uint32_t k = qo; k < qe; ++k) {
-                        const uint64_t pc = (uint64_t)W.prank[k] * w + j;
-                        if ((stop = F[c] == H[pc] + gp) || F[c] == F[pc] + ge) { prev = W.prank[k]; break; }
-                    }
-                } else {
-                    stop = true;
-                    for (uint32_t k = qo; k < qe; ++k) {
-                        const uint64_t pc = (uint64_t)W.prank[k] * w + j;
-                        if (F[c] == F[pc] + ge || O[c] == O[pc] + gc) { prev = W.prank[k]; stop = false; break; }
-                    }
-                    if (stop) {
+        if constexpr (GM != 0) {
+            if (left) {
+                for (;;) {
+                    if (j == 0) { fail_window(W, VC_WIN_INVALID); return; } // E[i][0] is kNegativeInfinity: cannot happen
+                    if (!emit(-1, (int32_t)j - 1)) return;
+                    --j;
+                    const uint64_t c = (uint64_t)i * w + j;
+                    if constexpr (GM == 1) { if (E[c] + ge != E[c + 1]) break; }
+                    else { if (E[c] + ge != E[c + 1] && Q[c] + gc != Q[c + 1]) break; }
+                }
+            } else if (up) {
+                for (;;) {
+                    if (i == 0) { fail_window(W, VC_WIN_INVALID); return; } // F[0][j] is kNegativeInfinity: cannot happen
+                    const uint64_t c = (uint64_t)i * w + j;
+                    const uint32_t qo = W.poff[i - 1], qe = W.poff[i];
+                    bool stop;
+                    uint32_t prev = 0;
+                    if constexpr (GM == 1) {
+                        stop = false;
                         for (uint32_t k = qo; k < qe; ++k) {
                             const uint64_t pc = (uint64_t)W.prank[k] * w + j;
-                            if (F[c] == H[pc] + gp || O[c] == H[pc] + gq) { prev = W.prank[k]; break; }
+                            if ((stop = F[c] == H[pc] + gp) || F[c] == F[pc] + ge) { prev = W.prank[k]; break; }
+                        }
+                    } else {
+                        stop = true;
+                        for (uint32_t k = qo; k < qe; ++k) {
+                            const uint64_t pc = (uint64_t)W.prank[k] * w + j;
+                            if (F[c] == F[pc] + ge || O[c] == O[pc] + gc) { prev = W.prank[k]; stop = false; break; }
+                        }
+                        if (stop) {
+                            for (uint32_t k = qo; k < qe; ++k) {
+                                const uint64_t pc = (uint64_t)W.prank[k] * w + j;
+                                if (F[c] == H[pc] + gp || O[c] == H[pc] + gq) { prev = W.prank[k]; break; }
+                            }
                         }
                     }
+                    if (!emit((int32_t)g.rank[i - 1], -1)) return;
+                    i = prev;
+                    if (stop || i == 0) break;
                 }
-                if (!emit((int32_t)g.rank[i - 1], -1)) return;
-                i = prev;
-                if (stop || i == 0) break;
             }
         }
-    }
-    for (uint32_t x = 0; x < np / 2; ++x) {
-        const uint32_t y = np - 1 - x;
-        const int32_t t0 = W.pairs[2 * x], t1 = W.pairs[2 * x + 1];
-        W.pairs[2 * x] = W.pairs[2 * y]; W.pairs[2 * x + 1] = W.pairs[2 * y + 1];
-        W.pairs[2 * y] = t0; W.pairs[2 * y + 1] = t1;
-    }
-    W.npairs = np;
-}
-
-// g_align's backtrack, one lane per alignment: diagonal from each predecessor (in in-edge order), vertical likewise, then horizontal.
-// GM 1 / 2: back_gaps.
-template <uint32_t GM>
-__global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
-    if constexpr (GM != 0) {
-        back_gaps<GM>(a, n);
-        return;
-    }
-    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= n) return;
-    LWin& W = a.win[a.list[b]];
-    const uint64_t w = (uint64_t)W.qlen + 1;
-    const uint32_t st = a.strand && W.score[0] < W.score[1];              // main.cpp:297: ties keep the forward strand
-    W.rev = st;
-    const int32_t* H = a.H + a.hoff[b] + st * ((uint64_t)W.rows + 1) * w;
-    const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
-    const uint8_t* seq = aligned_bases(a, W.qs, st);
-    const bool sw = W.type == 0, ov = W.type == 2;
-    W.npairs = 0;
-    uint32_t i = W.max_i[st], j = W.max_j[st], np = 0;
-    if (i == 0 && j == 0) return;                                          // an empty alignment
-    for (;;) {                                                             // sisd_alignment_engine.cpp:374-389
-        if (sw) { if (H[(uint64_t)i * w + j] == 0) break; }
-        else if (ov) { if (i == 0 || j == 0) break; }
-        else if (i == 0 && j == 0) break;
-        const int32_t Hij = H[(uint64_t)i * w + j];
-        uint32_t pi = 0, pj = 0;
-        bool found = false;
-        const uint32_t po = i ? W.poff[i - 1] : 0, pe = i ? W.poff[i] : 0;
-        const uint32_t ncand = pe > po ? pe - po : 1;
-        if (i != 0 && j != 0) {
-            const int32_t s = seq[j - 1] == W.rchar[i - 1] ? W.m : W.x;
-            for (uint32_t k = 0; k < ncand; ++k) {
-                const uint32_t p = pe > po ? W.prank[po + k] : 0;
-                if (Hij == H[(uint64_t)p * w + (j - 1)] + s) { pi = p; pj = j - 1; found = true; break; }
-            }
-        }
-        if (!found && i != 0) {
-            for (uint32_t k = 0; k < ncand; ++k) {
-                const uint32_t p = pe > po ? W.prank[po + k] : 0;
-                if (Hij == H[(uint64_t)p * w + j] + W.g) { pi = p; pj = j; found = true; break; }
-            }
-        }
-        if (!found && j != 0 && Hij == H[(uint64_t)i * w + j - 1] + W.g) { pi = i; pj = j - 1; found = true; }
-        if (!found) { fail_window(W, VC_WIN_INVALID); return; }             // cannot happen on a DAG
-        if (np >= W.PC) { W.grow |= G_PAIRS; return; }
-        W.pairs[2 * np] = i == pi ? -1 : (int32_t)g.rank[i - 1];
-        W.pairs[2 * np + 1] = j == pj ? -1 : (int32_t)j - 1;
-        ++np;
-        i = pi; j = pj;
     }
     for (uint32_t x = 0; x < np / 2; ++x) {
         const uint32_t y = np - 1 - x;
@@ -1352,13 +1235,22 @@ void release_cache() {
     g_cache = Cache{};
 }
 
-template <class T> bool dalloc(std::vector<void*>& l, T** p, size_t n, const void* src = nullptr) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    l.push_back(q);
-    *p = (T*)q;
-    return !src || n == 0 || hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
-}
+// the device allocations of one scope, freed when it ends
+struct DevMem {
+    std::vector<void*> held;
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { for (void* q : held) (void)hipFree(q); }
+    // n elements (at least one), filled from src where there is one
+    template <class T> bool alloc(T** p, size_t n, const void* src = nullptr) {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        held.push_back(q);
+        *p = (T*)q;
+        return !src || n == 0 || hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+    }
+};
 
 // the development knobs of the header comment; false: VC_LARGE_CAPS does not parse
 constexpr char kTables[] = "nealsp";                   // Knobs::shift order
@@ -1426,13 +1318,404 @@ struct MsaStore {
     void clear() { *this = MsaStore{}; }
 } g_msa;
 
-int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r,
-                MsaStore* msa = nullptr, const vc_poa_strand_out* so = nullptr);
+// ------------------------------------------------------------------ the host schedule
+// One call of vc_large_run / vc_poa_run*: the batch on the device (seq_begin / seq_end only with spans), windows in flight in
+// groups that fit the arena budget, one alignment of each per lock-step step with the forward passes in launches that fit the
+// matrix budget, and a window whose table filled run again with larger tables.  `a` holds the scores and the schedule.
+struct Run {
+    LArgs a;
+    const vc_batch* b;
+    std::vector<Caps>& caps;
+    bool labels;
+    const Knobs& kn;
+    MsaStore* msa;                                     // vc_poa_run_msa with flags, else nullptr
+    const vc_poa_strand_out* so;                       // vc_poa_run_strand, else nullptr
+    uint32_t nw;
+    uint64_t nseq_all, nbytes;
+    uint64_t arena_budget = 0, mat_budget = 0;
+    uint64_t planes = 1;                               // int32 planes per matrix cell
+    uint32_t ns = 1;                                   // forward passes, and matrices, per alignment: one per strand
+    std::vector<uint32_t> pending;                     // windows still to run, in order
+    std::vector<std::vector<uint8_t>> out;             // per window: the consensus, ...
+    std::vector<uint8_t> status;
+    std::vector<std::vector<uint32_t>> mem_of, cov_of; // ... and (msa) row members and coverage
+    uint32_t msa_launches = 0;
+    uint64_t n_align = 0, n_cells = 0;                 // forward passes run (VC_LARGE_LOG's "done" line)
+};
 
-// vc_poa_run / vc_poa_run_gaps after their score checks: the knobs, the batch (still without the device), the device, the run.
+// the windows in flight together: their ids, their tables in the arena, their LWin here and on the device
+struct Group {
+    std::vector<uint32_t> ids;
+    std::vector<uint64_t> aoff;
+    uint64_t abytes = 0;
+    std::vector<LWin> hw;
+    LWin* d_win = nullptr;
+    uint32_t* d_list = nullptr;                        // the windows of one launch (k_lg_fwd / k_lg_back / k_lg_msa<1>) ...
+    uint64_t* d_hoff = nullptr;                        // ... and where their matrices or blocks begin
+};
+
+int upload_batch(Run& R, DevMem& mem, bool spans) {
+    const vc_batch* b = R.b;
+    uint32_t lut_w[256];
+    double lut_d[256];
+    vc_weight_lut(lut_w);
+    for (int c = 0; c < 256; ++c) lut_d[c] = 1 - pow(10, (33 - (int)(signed char)c) / 10.0);
+    uint64_t* d_so = nullptr; uint32_t *d_sb = nullptr, *d_se = nullptr, *d_lw = nullptr; uint8_t *d_hq = nullptr, *d_b = nullptr, *d_q = nullptr;
+    double* d_ld = nullptr;
+    if (!mem.alloc(&d_so, R.nseq_all + 1, b->seq_off) ||
+        (spans && (!mem.alloc(&d_sb, R.nseq_all, b->seq_begin) || !mem.alloc(&d_se, R.nseq_all, b->seq_end))) ||
+        !mem.alloc(&d_hq, R.nseq_all, b->seq_has_qual) || !mem.alloc(&d_b, R.nbytes, b->bases) || !mem.alloc(&d_q, R.nbytes, b->quals) ||
+        !mem.alloc(&d_lw, 256, lut_w) || !mem.alloc(&d_ld, 256, lut_d))
+        return fail(VC_ERR_HIP, "device allocation or copy of the batch failed");
+    LArgs& a = R.a;
+    a.seq_off = d_so; a.seq_begin = d_sb; a.seq_end = d_se; a.has_qual = d_hq; a.bases = d_b; a.quals = d_q; a.lut_w = d_lw; a.lut_d = d_ld;
+    return VC_OK;
+}
+
+// vc_poa_run_strand: the strand views, once per call, and the zeroed choices
+int strand_views(Run& R, DevMem& mem) {
+    LArgs& a = R.a;
+    const uint64_t nseq_all = R.nseq_all, nbytes = R.nbytes;
+    a.nbytes = nbytes;
+    bool ok = mem.alloc(&a.rc_bases, nbytes) && mem.alloc(&a.rv_quals, nbytes) && mem.alloc(&a.rt_bases, nbytes) &&
+              mem.alloc(&a.s_rev, nseq_all) && mem.alloc(&a.s_score, nseq_all) && mem.alloc(&a.s_score_rev, nseq_all) &&
+              hipMemset(a.s_rev, 0, std::max<size_t>(nseq_all, 1)) == hipSuccess &&
+              hipMemset(a.s_score, 0, std::max<size_t>(nseq_all, 1) * 4) == hipSuccess &&
+              hipMemset(a.s_score_rev, 0, std::max<size_t>(nseq_all, 1) * 4) == hipSuccess;
+    if (ok && nbytes) {
+        hipLaunchKernelGGL(k_lg_views, dim3((uint32_t)((nbytes + 255) / 256)), dim3(256), 0, 0, a, (uint32_t)nseq_all);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    return ok ? VC_OK : fail(VC_ERR_HIP, "device allocation or launch of the strand views failed");
+}
+
+// The windows in flight next: as many of the pending ones as the arena budget holds, in order (at least one; a window the device
+// cannot hold at all is refused).  G.ids is empty when every pending window was refused.
+void next_group(Run& R, Group& G) {
+    std::vector<uint32_t> rest;
+    for (uint32_t w : R.pending) {
+        const uint64_t need = layout(nullptr, nullptr, R.caps[w], R.labels, R.msa != nullptr);
+        if (G.ids.empty() && need > R.arena_budget * 2) {                  // the device cannot hold its tables
+            R.status[w] = VC_WIN_OVERFLOW;
+            if (R.kn.log) std::fprintf(stderr, "vc_large: refuse window=%u bytes=%llu budget=%llu\n", w, (unsigned long long)need, (unsigned long long)R.arena_budget);
+            continue;
+        }
+        if (!G.ids.empty() && G.abytes + need > R.arena_budget) { rest.push_back(w); continue; }
+        G.ids.push_back(w); G.aoff.push_back(G.abytes); G.abytes += need;
+    }
+    R.pending.swap(rest);
+    const uint32_t n = (uint32_t)G.ids.size();
+    if (!R.kn.log || n == 0) return;
+    std::string ids, needs;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint64_t end = k + 1 < n ? G.aoff[k + 1] : G.abytes;
+        ids += (k ? "," : "") + std::to_string(G.ids[k]);
+        needs += (k ? "," : "") + std::to_string(end - G.aoff[k]);
+    }
+    std::fprintf(stderr, "vc_large: group windows=%u bytes=%llu ids=%s need=%s\n", n, (unsigned long long)G.abytes, ids.c_str(), needs.c_str());
+}
+
+// the group's LWin on the host: tables in the arena, the window's sequences and capacities
+void place_windows(const Run& R, Group& G, uint8_t* arena) {
+    const vc_batch* b = R.b;
+    G.hw.resize(G.ids.size());
+    for (size_t k = 0; k < G.ids.size(); ++k) {
+        const uint32_t w = G.ids[k];
+        LWin& W = G.hw[k];
+        W = LWin{};
+        layout(&W, arena + G.aoff[k], R.caps[w], R.labels, R.msa != nullptr);
+        const Caps& c = R.caps[w];
+        W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
+        W.L = W.nseq ? (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]) : 0;     // (POA groups: unused, and may be empty)
+        W.fasta = b->win_fasta && b->win_fasta[w] ? 1 : 0;
+        W.NC = (uint32_t)c.NC; W.EC = (uint32_t)c.EC; W.AC = (uint32_t)c.AC; W.LC = (uint32_t)c.LC; W.SC = (uint32_t)c.SC; W.PC = (uint32_t)c.PC;
+    }
+}
+
+// The next launch over items[k0 ..): consecutive items while their sizes fit the budget -- at least one, however large.  list and
+// off (where each item begins) describe it, total is its size; returns the first item left for the launch after.
+template <class Size>
+size_t pack_launch(const std::vector<uint32_t>& items, size_t k0, uint64_t budget, Size size, std::vector<uint32_t>& list,
+                   std::vector<uint64_t>& off, uint64_t& total) {
+    list.clear(); off.clear(); total = 0;
+    for (; k0 < items.size(); ++k0) {
+        const uint64_t need = size(items[k0]);
+        if (!list.empty() && total + need > budget) break;
+        list.push_back(items[k0]); off.push_back(total); total += need;
+    }
+    return k0;
+}
+
+bool upload_launch(const Group& G, const std::vector<uint32_t>& list, const std::vector<uint64_t>& off) {
+    return hipMemcpy(G.d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(G.d_hoff, off.data(), off.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+template <uint32_t GM>
+void launch_align(const LArgs& f, uint32_t nl, uint32_t ns) {
+    hipLaunchKernelGGL(k_lg_fwd<GM>, dim3(nl, ns), dim3(64), 0, 0, f);
+    hipLaunchKernelGGL(k_lg_back<GM>, dim3((nl + 63) / 64), dim3(64), 0, 0, f, nl);
+}
+
+// The forward passes and backtracks of one step, over the windows `act` that have an alignment: their matrices in launches that
+// fit the budget (in int32 cells of every plane and strand); a matrix the device cannot hold takes its window out.
+bool align_step(Run& R, Group& G, const std::vector<uint32_t>& act) {
+    uint32_t launches = 0, over = 0;
+    std::vector<uint32_t> list;
+    std::vector<uint64_t> hoff;
+    auto matrix_cells = [&](uint32_t k) { return ((uint64_t)G.hw[k].rows + 1) * ((uint64_t)G.hw[k].qlen + 1) * R.planes * R.ns; };
+    for (size_t k0 = 0; k0 < act.size();) {
+        uint64_t cells;
+        k0 = pack_launch(act, k0, R.mat_budget / 4, matrix_cells, list, hoff, cells);
+        int32_t* H = (int32_t*)cached(g_cache.mat, cells * 4);
+        if (!H) {
+            if (list.size() > 1) return false;
+            LWin& W = G.hw[list[0]];
+            W.phase = PH_DONE; W.status = VC_WIN_OVERFLOW; W.rows = 0;
+            if (hipMemcpy(G.d_win + list[0], &W, sizeof(LWin), hipMemcpyHostToDevice) != hipSuccess) return false;
+            continue;
+        }
+        if (!upload_launch(G, list, hoff)) return false;
+        const uint32_t nl = (uint32_t)list.size();
+        LArgs f = R.a;
+        f.list = G.d_list; f.hoff = G.d_hoff; f.H = H;
+        if (f.gaps == 0) launch_align<0>(f, nl, R.ns);
+        else if (f.gaps == 1) launch_align<1>(f, nl, R.ns);
+        else launch_align<2>(f, nl, R.ns);
+        const bool ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        for (const uint32_t k : list) R.n_cells += (uint64_t)G.hw[k].rows * G.hw[k].qlen * R.ns;
+        R.n_align += (uint64_t)nl * R.ns;
+        launches++;
+        if (cells * 4 > R.mat_budget) over++;
+        if (!ok) return false;
+    }
+    if (R.kn.log && launches > 1) std::fprintf(stderr, "vc_large: step launches=%u over=%u\n", launches, over);
+    return true;
+}
+
+// The lock-step schedule of one group: one alignment of every window in flight per step, until none is live; then (msa) columns,
+// row_size and rows of every finished group.  G.hw holds the windows' final state.
+bool lock_step(Run& R, Group& G) {
+    const LArgs& a = R.a;
+    const uint32_t n = (uint32_t)G.ids.size();
+    const dim3 lanes((n + 63) / 64);
+    bool ok = hipMemcpy(G.d_win, G.hw.data(), n * sizeof(LWin), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) { hipLaunchKernelGGL(k_lg_init, lanes, dim3(64), 0, 0, a); ok = hipGetLastError() == hipSuccess; }
+    while (ok) {
+        hipLaunchKernelGGL(k_lg_prep, lanes, dim3(64), 0, 0, a);
+        if (hipMemcpy(G.hw.data(), G.d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) != hipSuccess) return false;
+        bool live = false;
+        std::vector<uint32_t> act;
+        for (uint32_t k = 0; k < n; ++k) {
+            if (G.hw[k].phase != PH_DONE && !G.hw[k].grow) live = true;
+            if (G.hw[k].rows) act.push_back(k);
+        }
+        if (!live) break;
+        if (!align_step(R, G, act)) return false;
+        hipLaunchKernelGGL(k_lg_apply, lanes, dim3(64), 0, 0, a);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (ok && R.msa) {
+        hipLaunchKernelGGL(k_lg_msa<0>, dim3(n), dim3(64), 0, 0, a);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    return ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(G.hw.data(), G.d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// a table of window w filled (W.grow): larger tables, and the window runs again unless they outgrow the 32-bit ids
+void regrow(Run& R, uint32_t w, const LWin& W) {
+    Caps& c = R.caps[w];
+    if (W.grow & G_NODES) c.NC *= 2;
+    if (W.grow & G_EDGES) c.EC *= 2;
+    if (W.grow & G_ALIGNED) c.AC *= 2;
+    if (W.grow & G_LABELS) c.LC *= 2;
+    if (W.grow & G_PAIRS) c.PC *= 2;
+    c.SC = std::max<uint64_t>(c.SC * ((W.grow & G_STACK) ? 2 : 1), (c.NC + c.EC + c.AC) >> R.kn.shift[4]);
+    if (R.kn.log) {
+        std::string fl;
+        static const char* const names[] = {"nodes", "edges", "aligned", "labels", "stack", "pairs"};
+        for (int t = 0; t < 6; ++t) if (W.grow & (1u << t)) { if (!fl.empty()) fl += ','; fl += names[t]; }
+        std::fprintf(stderr, "vc_large: regrow window=%u flags=%s caps n=%llu e=%llu a=%llu l=%llu s=%llu p=%llu\n", w, fl.c_str(),
+                     (unsigned long long)c.NC, (unsigned long long)c.EC, (unsigned long long)c.AC, (unsigned long long)c.LC,
+                     (unsigned long long)c.SC, (unsigned long long)c.PC);
+    }
+    if (c.NC >= (1ull << 31) || c.EC >= (1ull << 31) || c.AC >= (1ull << 31) || c.SC >= (1ull << 31) || c.PC >= (1ull << 30))
+        R.status[w] = VC_WIN_OVERFLOW;
+    else
+        R.pending.push_back(w);
+}
+
+// A finished group's block of k_lg_msa<1>: msa_rows x row_size bytes, then (16-byte aligned) the row members at mem_at, then
+// (16-byte aligned, VC_POA_COVERAGE) the coverage at cov_at.
+struct MsaBlock { uint64_t mem_at, cov_at, bytes; };
+MsaBlock msa_block(const LWin& W, uint32_t flags) {
+    MsaBlock B;
+    B.mem_at = ((uint64_t)W.msa_rows * W.row_size + 15) & ~15ull;
+    B.cov_at = B.mem_at + 4 * (((uint64_t)W.msa_rows + 3) & ~3ull);
+    B.bytes = B.cov_at + ((flags & VC_POA_COVERAGE) ? 4 * (((uint64_t)W.cons_n + 3) & ~3ull) : 0);
+    return B;
+}
+
+// The alignments and coverage of the groups that finished, while their tables are resident: blocks laid out in the matrix buffer
+// (free after the last step), in launches that fit the matrix budget, each copied out at once.
+int collect_msa(Run& R, Group& G) {
+    const LArgs& a = R.a;
+    MsaStore* msa = R.msa;
+    std::vector<uint32_t> fin, list;
+    std::vector<uint64_t> hoff;
+    for (uint32_t k = 0; k < G.ids.size(); ++k) if (!G.hw[k].grow && G.hw[k].status == VC_WIN_OK) fin.push_back(k);
+    auto block_bytes = [&](uint32_t k) { return msa_block(G.hw[k], a.msa).bytes; };
+    for (size_t k0 = 0; k0 < fin.size();) {
+        uint64_t bytes;
+        k0 = pack_launch(fin, k0, R.mat_budget, block_bytes, list, hoff, bytes);
+        uint8_t* dout = (uint8_t*)cached(g_cache.mat, bytes);
+        if (!dout) {
+            if (list.size() > 1) return fail(VC_ERR_HIP, "device allocation of the alignment rows failed");
+            R.status[G.ids[list[0]]] = VC_WIN_OVERFLOW; R.out[G.ids[list[0]]].clear();
+            continue;
+        }
+        const uint32_t nl = (uint32_t)list.size();
+        const uint64_t at = msa->rows.size();
+        LArgs f = a;
+        f.list = G.d_list; f.hoff = G.d_hoff; f.msa_out = dout;
+        bool ok = upload_launch(G, list, hoff);
+        if (ok) {
+            hipLaunchKernelGGL(k_lg_msa<1>, dim3(nl), dim3(64), 0, 0, f);
+            ok = hipGetLastError() == hipSuccess;
+            msa->rows.resize(at + bytes);
+            ok = ok && hipMemcpy(msa->rows.data() + at, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        if (!ok) return fail(VC_ERR_HIP, "the alignment-row kernel or its copy failed");
+        for (uint32_t q = 0; q < nl; ++q) {
+            const LWin& W = G.hw[list[q]];
+            const uint32_t w = G.ids[list[q]];
+            const MsaBlock B = msa_block(W, a.msa);
+            const uint8_t* blk = msa->rows.data() + at + hoff[q];
+            msa->n_rows[w] = W.msa_rows; msa->row_size[w] = W.row_size; msa->row_off[w] = at + hoff[q];
+            R.mem_of[w].resize(W.msa_rows);
+            if (W.msa_rows) std::memcpy(R.mem_of[w].data(), blk + B.mem_at, 4ull * W.msa_rows);
+            if (a.msa & VC_POA_COVERAGE) {
+                R.cov_of[w].resize(W.cons_n);
+                if (W.cons_n) std::memcpy(R.cov_of[w].data(), blk + B.cov_at, 4ull * W.cons_n);
+            }
+        }
+        R.msa_launches++;
+    }
+    return VC_OK;
+}
+
+// One group from its tables to its results: a window whose table filled goes back to pending, the others leave their status,
+// consensus and (msa) alignment.  A single window the device has no room for is VC_WIN_OVERFLOW; more than one is an error.
+int run_group(Run& R, Group& G) {
+    const uint32_t n = (uint32_t)G.ids.size();
+    uint8_t* arena = (uint8_t*)cached(g_cache.arena, G.abytes);
+    DevMem mem;
+    if (!arena || !mem.alloc(&G.d_win, n) || !mem.alloc(&G.d_list, n) || !mem.alloc(&G.d_hoff, n)) {
+        if (n == 1) { R.status[G.ids[0]] = VC_WIN_OVERFLOW; return VC_OK; }
+        return fail(VC_ERR_HIP, "device allocation of the window tables failed");
+    }
+    place_windows(R, G, arena);
+    R.a.win = G.d_win; R.a.n = n;
+    if (!lock_step(R, G)) return fail(VC_ERR_HIP, "a large-graph kernel failed");
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t w = G.ids[k];
+        const LWin& W = G.hw[k];
+        if (W.grow) { regrow(R, w, W); continue; }
+        R.status[w] = (uint8_t)W.status;
+        R.out[w].resize(W.cons_n);
+        if (W.cons_n && hipMemcpy(R.out[w].data(), W.cons, W.cons_n, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(VC_ERR_HIP, "copy of a consensus failed");
+    }
+    return R.msa ? collect_msa(R, G) : VC_OK;
+}
+
+// vc_poa_run_strand: the choices; zeros for the groups that were not computed
+int copy_strands(const Run& R) {
+    const vc_batch* b = R.b;
+    const vc_poa_strand_out* so = R.so;
+    bool ok = hipMemcpy(so->reversed, R.a.s_rev, R.nseq_all, hipMemcpyDeviceToHost) == hipSuccess;
+    if (so->score) ok = ok && hipMemcpy(so->score, R.a.s_score, R.nseq_all * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (so->score_rev) ok = ok && hipMemcpy(so->score_rev, R.a.s_score_rev, R.nseq_all * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail(VC_ERR_HIP, "copy of the strand choices failed");
+    for (uint32_t w = 0; w < R.nw; ++w) {
+        if (R.status[w] == VC_WIN_OK) continue;
+        for (uint32_t s = b->win_seq_off[w]; s < b->win_seq_off[w + 1]; ++s) {
+            so->reversed[s] = 0;
+            if (so->score) so->score[s] = 0;
+            if (so->score_rev) so->score_rev[s] = 0;
+        }
+    }
+    return VC_OK;
+}
+
+// the results in window order: (msa) the per-row and per-base tables, the closing log lines, consensus and status
+int assemble(Run& R, vc_result* r) {
+    if (MsaStore* msa = R.msa) {
+        msa->member_off[0] = 0;
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            if (R.status[w] != VC_WIN_OK) { msa->n_rows[w] = 0; msa->row_size[w] = 0; R.mem_of[w].clear(); R.cov_of[w].clear(); }
+            msa->row_member.insert(msa->row_member.end(), R.mem_of[w].begin(), R.mem_of[w].end());
+            msa->member_off[w + 1] = msa->row_member.size();
+            if (R.a.msa & VC_POA_COVERAGE) {
+                R.cov_of[w].resize(R.out[w].size());
+                msa->coverage.insert(msa->coverage.end(), R.cov_of[w].begin(), R.cov_of[w].end());
+            }
+        }
+        if (R.kn.log) std::fprintf(stderr, "vc_large: msa launches=%u bytes=%llu\n", R.msa_launches, (unsigned long long)msa->rows.size());
+    }
+    if (R.kn.log) std::fprintf(stderr, "vc_large: done alignments=%llu cells=%llu\n", (unsigned long long)R.n_align, (unsigned long long)R.n_cells);
+    uint64_t o = 0;
+    for (uint32_t w = 0; w < R.nw; ++w) {
+        if (o + R.out[w].size() > r->cons_cap) return fail(VC_ERR_CAPACITY, "consensus buffer too small");
+        if (!R.out[w].empty()) std::memcpy(r->cons + o, R.out[w].data(), R.out[w].size());
+        o += R.out[w].size();
+        r->cons_off[w + 1] = o;
+        r->status[w] = R.status[w];
+    }
+    return VC_OK;
+}
+
+int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r,
+                MsaStore* msa = nullptr, const vc_poa_strand_out* so = nullptr) {
+    const uint32_t nw = b->n_windows;
+    if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
+    if (g_cache.device != device) { release_cache(); g_cache.device = device; }
+    Run R{a, b, caps, labels, kn, msa, so, nw, b->win_seq_off[nw], b->seq_off[b->win_seq_off[nw]]};
+    DevMem mem;                                                            // the batch and the strand views: held until the call ends
+    if (const int rc = upload_batch(R, mem, spans)) return rc;
+    if (so) if (const int rc = strand_views(R, mem)) return rc;
+
+    // budgets from free device memory (what this library keeps cached counts as free)
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const uint64_t avail = free_b + g_cache.arena.bytes + g_cache.mat.bytes;
+    R.arena_budget = kn.arena ? kn.arena : std::min<uint64_t>(avail / 4, 16ull << 30);
+    R.mat_budget = kn.mat ? kn.mat : std::min<uint64_t>(avail / 2, 48ull << 30);
+    R.planes = plane_count(a.gaps);
+    R.ns = so ? 2 : 1;
+
+    R.out.resize(nw);
+    R.status.assign(nw, VC_WIN_OVERFLOW);
+    if (msa) {
+        R.mem_of.resize(nw); R.cov_of.resize(nw);
+        msa->clear();
+        msa->n_rows.assign(nw, 0); msa->row_size.assign(nw, 0); msa->row_off.assign(nw, 0); msa->member_off.assign(nw + 1, 0);
+    }
+    R.pending.resize(nw);
+    for (uint32_t w = 0; w < nw; ++w) R.pending[w] = w;
+    while (!R.pending.empty()) {
+        Group G;
+        next_group(R, G);
+        if (G.ids.empty()) continue;
+        if (const int rc = run_group(R, G)) return rc;
+    }
+    if (so) if (const int rc = copy_strands(R)) return rc;
+    return assemble(R, r);
+}
+
+// The four vc_poa_* entries after their score checks: the knobs, the batch (still without the device), the device, the run.
 // `a` holds the scores.
-int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa = nullptr,
-               const vc_poa_strand_out* so = nullptr) {
+int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa, const vc_poa_strand_out* so) {
     Knobs kn;
     if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
     const uint32_t nw = b->n_windows;
@@ -1464,6 +1747,48 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
     if (nw == 0) return VC_OK;
     a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)algorithm;
     return run_windows(device, a, b, caps, msa != nullptr, false, kn, r, msa, so);
+}
+
+// vc_poa_run_gaps, vc_poa_run_msa (o is required) and vc_poa_run_strand (so is required, o may be NULL); vc_poa_run after its
+// own checks comes in as POA_GAPS.  The arguments first, without the device, in AlignmentEngine::Create's order
+// (alignment_engine.cpp:39-57; spoa takes the scores as int8_t); then the flags, then the strand output; the batch in run_groups.
+enum PoaCall { POA_GAPS, POA_MSA, POA_STRAND };
+
+int poa_run(PoaCall call, const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* so) {
+    if (!p || !b || !r || (call == POA_MSA && !o) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+    if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
+    if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
+    if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
+    for (const int32_t s : {p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_open2, p->gap_extend2})
+        if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
+    const uint32_t flags = o ? o->flags : 0;
+    if (flags & ~(uint32_t)(VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE)) return fail(VC_ERR_ARG, "unknown flag bits");
+    if ((flags & VC_POA_MSA_CONSENSUS) && !(flags & VC_POA_MSA)) return fail(VC_ERR_ARG, "VC_POA_MSA_CONSENSUS needs VC_POA_MSA");
+    if (call == POA_STRAND && (!so || !so->reversed)) return fail(VC_ERR_ARG, "null strand output (reversed is required)");
+    // the subtype and its scores (alignment_engine.cpp:59-69)
+    int32_t g = p->gap_open, e = p->gap_extend, q = p->gap_open2, c = p->gap_extend2;
+    const uint32_t gaps = g >= e ? 0 : (g <= q || e >= c ? 1 : 2);
+    if (gaps == 0) e = g;
+    else if (gaps == 1) { q = g; c = e; }
+    LArgs a{};
+    a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
+    a.msa = flags;
+    a.strand = call == POA_STRAND ? 1 : 0;
+    if (o) { *o = vc_poa_msa_out{}; o->flags = flags; }
+    if (call != POA_GAPS) g_msa.clear();                                   // what an earlier call handed out ends here
+    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr, call == POA_STRAND ? so : nullptr);
+    if (rc != VC_OK) {
+        if (call != POA_GAPS) g_msa.clear();
+        return rc;
+    }
+    if (o) o->n_groups = b->n_windows;
+    if (flags && b->n_windows) {
+        o->n_rows = g_msa.n_rows.data(); o->row_size = g_msa.row_size.data(); o->row_off = g_msa.row_off.data();
+        o->member_off = g_msa.member_off.data(); o->row_member = g_msa.row_member.data();
+        o->rows = g_msa.rows.data(); o->rows_bytes = g_msa.rows.size();
+        if (flags & VC_POA_COVERAGE) o->coverage = g_msa.coverage.data();
+    }
+    return VC_OK;
 }
 
 }  // namespace
@@ -1513,387 +1838,23 @@ int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
 const char* vc_poa_last_error(void) { return g_err.c_str(); }
 
 int vc_poa_run(const vc_poa_params* p, const vc_batch* b, vc_result* r) {
-    // the arguments first, without the device (alignment_engine.cpp:39-57; spoa takes the scores as int8_t)
+    // its own struct and messages; the rest is vc_poa_run_gaps with e = q = c = g, which selects linear gaps
     if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap > 0) return fail(VC_ERR_ARG, "gap must be <= 0 (linear gaps: spoa's gap opening penalty must be non-positive)");
     for (const int32_t s : {p->match, p->mismatch, p->gap})
         if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
-    LArgs a{};
-    a.match = p->match; a.mismatch = p->mismatch; a.gap = p->gap; a.gap_e = a.gap_q = a.gap_c = p->gap; a.gaps = 0;
-    return run_groups(p->device, p->algorithm, a, b, r);
+    // poa_run repeats these checks on gp; after the ones above none of them can fire
+    const vc_poa_gap_params gp{p->device, p->algorithm, p->match, p->mismatch, p->gap, p->gap, p->gap, p->gap};
+    return poa_run(POA_GAPS, &gp, b, r, nullptr, nullptr);
 }
 
-int vc_poa_run_gaps(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r) {
-    // the arguments first, in AlignmentEngine::Create's order (alignment_engine.cpp:39-57; spoa takes the scores as int8_t)
-    if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
-    if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
-    if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
-    if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
-    for (const int32_t s : {p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_open2, p->gap_extend2})
-        if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
-    // the subtype and its scores (alignment_engine.cpp:59-69)
-    int32_t g = p->gap_open, e = p->gap_extend, q = p->gap_open2, c = p->gap_extend2;
-    const uint32_t gaps = g >= e ? 0 : (g <= q || e >= c ? 1 : 2);
-    if (gaps == 0) e = g;
-    else if (gaps == 1) { q = g; c = e; }
-    LArgs a{};
-    a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
-    return run_groups(p->device, p->algorithm, a, b, r);
-}
+int vc_poa_run_gaps(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r) { return poa_run(POA_GAPS, p, b, r, nullptr, nullptr); }
 
-// vc_poa_run_msa, and vc_poa_run_strand (strand: `o` may be NULL, `so` is checked after the flags and before the batch)
-static int poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, bool strand, vc_poa_strand_out* so) {
-    if (!p || !b || !r || (!o && !strand) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
-    if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
-    if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
-    if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
-    for (const int32_t s : {p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_open2, p->gap_extend2})
-        if (s < -128 || s > 127) return fail(VC_ERR_ARG, "scores must lie in -128..127 (spoa's int8_t parameters)");
-    const uint32_t flags = o ? o->flags : 0;
-    if (flags & ~(uint32_t)(VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE)) return fail(VC_ERR_ARG, "unknown flag bits");
-    if ((flags & VC_POA_MSA_CONSENSUS) && !(flags & VC_POA_MSA)) return fail(VC_ERR_ARG, "VC_POA_MSA_CONSENSUS needs VC_POA_MSA");
-    if (strand && (!so || !so->reversed)) return fail(VC_ERR_ARG, "null strand output (reversed is required)");
-    int32_t g = p->gap_open, e = p->gap_extend, q = p->gap_open2, c = p->gap_extend2;
-    const uint32_t gaps = g >= e ? 0 : (g <= q || e >= c ? 1 : 2);
-    if (gaps == 0) e = g;
-    else if (gaps == 1) { q = g; c = e; }
-    LArgs a{};
-    a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
-    a.msa = flags;
-    a.strand = strand ? 1 : 0;
-    if (o) { *o = vc_poa_msa_out{}; o->flags = flags; }
-    g_msa.clear();
-    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr, strand ? so : nullptr);
-    if (rc != VC_OK) { g_msa.clear(); return rc; }
-    if (o) o->n_groups = b->n_windows;
-    if (flags && b->n_windows) {
-        o->n_rows = g_msa.n_rows.data(); o->row_size = g_msa.row_size.data(); o->row_off = g_msa.row_off.data();
-        o->member_off = g_msa.member_off.data(); o->row_member = g_msa.row_member.data();
-        o->rows = g_msa.rows.data(); o->rows_bytes = g_msa.rows.size();
-        if (flags & VC_POA_COVERAGE) o->coverage = g_msa.coverage.data();
-    }
-    return VC_OK;
-}
-
-int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o) {
-    return poa_run_msa(p, b, r, o, false, nullptr);
-}
+int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o) { return poa_run(POA_MSA, p, b, r, o, nullptr); }
 
 int vc_poa_run_strand(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s) {
-    return poa_run_msa(p, b, r, o, true, s);
+    return poa_run(POA_STRAND, p, b, r, o, s);
 }
 
 }  // extern "C"
-
-namespace {
-
-// The host schedule of vc_large_run and vc_poa_run: the batch on the device (seq_begin / seq_end only with spans), windows in
-// flight in groups that fit the arena budget, one alignment of each per lock-step step with the forward passes in launches that
-// fit the matrix budget, and a window whose table filled run again with larger tables.  `a` holds the scores and the schedule.
-int run_windows(int32_t device, LArgs a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r, MsaStore* msa,
-                const vc_poa_strand_out* so) {
-    const uint32_t nw = b->n_windows;
-    const uint64_t nseq_all = b->win_seq_off[nw], nbytes = b->seq_off[nseq_all];
-    if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
-    if (g_cache.device != device) { release_cache(); g_cache.device = device; }
-
-    std::vector<void*> fixed;
-    auto cleanup = [&]() { for (void* q : fixed) (void)hipFree(q); fixed.clear(); };
-    uint32_t lut_w[256];
-    double lut_d[256];
-    vc_weight_lut(lut_w);
-    for (int c = 0; c < 256; ++c) lut_d[c] = 1 - pow(10, (33 - (int)(signed char)c) / 10.0);
-    uint64_t* d_so = nullptr; uint32_t *d_sb = nullptr, *d_se = nullptr, *d_lw = nullptr; uint8_t *d_hq = nullptr, *d_b = nullptr, *d_q = nullptr;
-    double* d_ld = nullptr;
-    if (!dalloc(fixed, &d_so, nseq_all + 1, b->seq_off) ||
-        (spans && (!dalloc(fixed, &d_sb, nseq_all, b->seq_begin) || !dalloc(fixed, &d_se, nseq_all, b->seq_end))) ||
-        !dalloc(fixed, &d_hq, nseq_all, b->seq_has_qual) || !dalloc(fixed, &d_b, nbytes, b->bases) || !dalloc(fixed, &d_q, nbytes, b->quals) ||
-        !dalloc(fixed, &d_lw, 256, lut_w) || !dalloc(fixed, &d_ld, 256, lut_d)) {
-        cleanup(); return fail(VC_ERR_HIP, "device allocation or copy of the batch failed");
-    }
-    a.seq_off = d_so; a.seq_begin = d_sb; a.seq_end = d_se; a.has_qual = d_hq; a.bases = d_b; a.quals = d_q; a.lut_w = d_lw; a.lut_d = d_ld;
-    if (so) {                                                              // the strand views, once per call, and the zeroed choices
-        a.nbytes = nbytes;
-        bool ok = dalloc(fixed, &a.rc_bases, nbytes) && dalloc(fixed, &a.rv_quals, nbytes) && dalloc(fixed, &a.rt_bases, nbytes) &&
-                  dalloc(fixed, &a.s_rev, nseq_all) && dalloc(fixed, &a.s_score, nseq_all) && dalloc(fixed, &a.s_score_rev, nseq_all) &&
-                  hipMemset(a.s_rev, 0, std::max<size_t>(nseq_all, 1)) == hipSuccess &&
-                  hipMemset(a.s_score, 0, std::max<size_t>(nseq_all, 1) * 4) == hipSuccess &&
-                  hipMemset(a.s_score_rev, 0, std::max<size_t>(nseq_all, 1) * 4) == hipSuccess;
-        if (ok && nbytes) {
-            hipLaunchKernelGGL(k_lg_views, dim3((uint32_t)((nbytes + 255) / 256)), dim3(256), 0, 0, a, (uint32_t)nseq_all);
-            ok = hipGetLastError() == hipSuccess;
-        }
-        if (!ok) { cleanup(); return fail(VC_ERR_HIP, "device allocation or launch of the strand views failed"); }
-    }
-
-    // budgets from free device memory (what this library keeps cached counts as free)
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    const uint64_t avail = free_b + g_cache.arena.bytes + g_cache.mat.bytes;
-    const uint64_t arena_budget = kn.arena ? kn.arena : std::min<uint64_t>(avail / 4, 16ull << 30);
-    const uint64_t mat_budget = kn.mat ? kn.mat : std::min<uint64_t>(avail / 2, 48ull << 30);
-
-    std::vector<std::vector<uint8_t>> out(nw);
-    std::vector<uint8_t> status(nw, VC_WIN_OVERFLOW);
-    std::vector<std::vector<uint32_t>> mem_of(msa ? nw : 0), cov_of(msa ? nw : 0);   // vc_poa_run_msa: row members, coverage
-    uint32_t msa_launches = 0;
-    if (msa) {
-        msa->clear();
-        msa->n_rows.assign(nw, 0); msa->row_size.assign(nw, 0); msa->row_off.assign(nw, 0); msa->member_off.assign(nw + 1, 0);
-    }
-    std::vector<uint32_t> pending(nw);
-    for (uint32_t w = 0; w < nw; ++w) pending[w] = w;
-    uint32_t *d_list = nullptr; uint64_t* d_hoff = nullptr; LWin* d_win = nullptr;
-    uint64_t n_align = 0, n_cells = 0;                                     // forward passes run (VC_LARGE_LOG's "done" line)
-    const uint64_t planes = a.gaps == 0 ? 1 : a.gaps == 1 ? 3 : 5;         // int32 planes per matrix cell: H (, F, E (, O, Q))
-    const uint32_t ns = so ? 2 : 1;                                        // forward passes, and matrices, per alignment: one per strand
-    while (!pending.empty()) {
-        // windows in flight: as many as the arena budget holds, in order (at least one)
-        std::vector<uint32_t> grp;
-        std::vector<uint64_t> aoff;
-        uint64_t abytes = 0;
-        std::vector<uint32_t> rest;
-        for (uint32_t w : pending) {
-            const uint64_t need = layout(nullptr, nullptr, caps[w], labels, msa != nullptr);
-            if (grp.empty() && need > arena_budget * 2) {                  // the device cannot hold its tables
-                status[w] = VC_WIN_OVERFLOW;
-                if (kn.log) std::fprintf(stderr, "vc_large: refuse window=%u bytes=%llu budget=%llu\n", w, (unsigned long long)need, (unsigned long long)arena_budget);
-                continue;
-            }
-            if (!grp.empty() && abytes + need > arena_budget) { rest.push_back(w); continue; }
-            grp.push_back(w); aoff.push_back(abytes); abytes += need;
-        }
-        pending.swap(rest);
-        if (grp.empty()) continue;
-        const uint32_t n = (uint32_t)grp.size();
-        if (kn.log) {
-            std::string ids, needs;
-            for (uint32_t k = 0; k < n; ++k) {
-                const uint64_t end = k + 1 < n ? aoff[k + 1] : abytes;
-                ids += (k ? "," : "") + std::to_string(grp[k]);
-                needs += (k ? "," : "") + std::to_string(end - aoff[k]);
-            }
-            std::fprintf(stderr, "vc_large: group windows=%u bytes=%llu ids=%s need=%s\n", n, (unsigned long long)abytes, ids.c_str(), needs.c_str());
-        }
-        uint8_t* arena = (uint8_t*)cached(g_cache.arena, abytes);
-        std::vector<void*> tmp;
-        auto done_tmp = [&]() { for (void* q : tmp) (void)hipFree(q); tmp.clear(); };
-        if (!arena || !dalloc(tmp, &d_win, n) || !dalloc(tmp, &d_list, n) || !dalloc(tmp, &d_hoff, n)) {
-            done_tmp();
-            if (n == 1) { status[grp[0]] = VC_WIN_OVERFLOW; continue; }
-            cleanup(); return fail(VC_ERR_HIP, "device allocation of the window tables failed");
-        }
-        std::vector<LWin> hw(n);
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t w = grp[k];
-            LWin& W = hw[k];
-            W = LWin{};
-            layout(&W, arena + aoff[k], caps[w], labels, msa != nullptr);
-            const Caps& c = caps[w];
-            W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
-            W.L = W.nseq ? (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]) : 0;     // (POA groups: unused, and may be empty)
-            W.fasta = b->win_fasta && b->win_fasta[w] ? 1 : 0;
-            W.NC = (uint32_t)c.NC; W.EC = (uint32_t)c.EC; W.AC = (uint32_t)c.AC; W.LC = (uint32_t)c.LC; W.SC = (uint32_t)c.SC; W.PC = (uint32_t)c.PC;
-        }
-        a.win = d_win; a.n = n;
-        const dim3 lanes((n + 63) / 64);
-        bool ok = hipMemcpy(d_win, hw.data(), n * sizeof(LWin), hipMemcpyHostToDevice) == hipSuccess;
-        if (ok) { hipLaunchKernelGGL(k_lg_init, lanes, dim3(64), 0, 0, a); ok = hipGetLastError() == hipSuccess; }
-        // the lock-step schedule: one alignment of every window in flight per step
-        while (ok) {
-            hipLaunchKernelGGL(k_lg_prep, lanes, dim3(64), 0, 0, a);
-            if (hipMemcpy(hw.data(), d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
-            bool live = false;
-            std::vector<uint32_t> act;
-            for (uint32_t k = 0; k < n; ++k) {
-                if (hw[k].phase != PH_DONE && !hw[k].grow) live = true;
-                if (hw[k].rows) act.push_back(k);
-            }
-            if (!live) break;
-            // matrices of this step, in launches that fit the budget; a matrix the device cannot hold takes its window out
-            // (cells counts int32 cells of every plane)
-            uint32_t launches = 0, over = 0;
-            for (size_t k0 = 0; k0 < act.size() && ok;) {
-                std::vector<uint32_t> list;
-                std::vector<uint64_t> hoff;
-                uint64_t cells = 0;
-                size_t k1 = k0;
-                for (; k1 < act.size(); ++k1) {
-                    const LWin& W = hw[act[k1]];
-                    const uint64_t need = ((uint64_t)W.rows + 1) * ((uint64_t)W.qlen + 1) * planes * ns;
-                    if (!list.empty() && (cells + need) * 4 > mat_budget) break;
-                    list.push_back(act[k1]); hoff.push_back(cells); cells += need;
-                }
-                k0 = k1;
-                int32_t* H = (int32_t*)cached(g_cache.mat, cells * 4);
-                if (!H) {
-                    if (list.size() > 1) { ok = false; break; }
-                    LWin& W = hw[list[0]];
-                    W.phase = PH_DONE; W.status = VC_WIN_OVERFLOW; W.rows = 0;
-                    ok = hipMemcpy(d_win + list[0], &W, sizeof(LWin), hipMemcpyHostToDevice) == hipSuccess;
-                    continue;
-                }
-                const uint32_t nl = (uint32_t)list.size();
-                ok = hipMemcpy(d_list, list.data(), nl * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                     hipMemcpy(d_hoff, hoff.data(), nl * 8, hipMemcpyHostToDevice) == hipSuccess;
-                if (!ok) break;
-                LArgs f = a;
-                f.list = d_list; f.hoff = d_hoff; f.H = H;
-                const dim3 fb(nl, ns), bb((nl + 63) / 64);
-                if (a.gaps == 0) {
-                    hipLaunchKernelGGL(k_lg_fwd<0>, fb, dim3(64), 0, 0, f);
-                    hipLaunchKernelGGL(k_lg_back<0>, bb, dim3(64), 0, 0, f, nl);
-                } else if (a.gaps == 1) {
-                    hipLaunchKernelGGL(k_lg_fwd<1>, fb, dim3(64), 0, 0, f);
-                    hipLaunchKernelGGL(k_lg_back<1>, bb, dim3(64), 0, 0, f, nl);
-                } else {
-                    hipLaunchKernelGGL(k_lg_fwd<2>, fb, dim3(64), 0, 0, f);
-                    hipLaunchKernelGGL(k_lg_back<2>, bb, dim3(64), 0, 0, f, nl);
-                }
-                ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-                for (const uint32_t k : list) n_cells += (uint64_t)hw[k].rows * hw[k].qlen * ns;
-                n_align += (uint64_t)nl * ns;
-                launches++;
-                if (cells * 4 > mat_budget) over++;
-            }
-            if (!ok) break;
-            if (kn.log && launches > 1) std::fprintf(stderr, "vc_large: step launches=%u over=%u\n", launches, over);
-            hipLaunchKernelGGL(k_lg_apply, lanes, dim3(64), 0, 0, a);
-            ok = hipGetLastError() == hipSuccess;
-        }
-        if (ok && msa) {                                                   // columns, row_size and rows of every finished group
-            hipLaunchKernelGGL(k_lg_msa<0>, dim3(n), dim3(64), 0, 0, a);
-            ok = hipGetLastError() == hipSuccess;
-        }
-        ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(hw.data(), d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) == hipSuccess;
-        if (!ok) { done_tmp(); cleanup(); return fail(VC_ERR_HIP, "a large-graph kernel failed"); }
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t w = grp[k];
-            const LWin& W = hw[k];
-            if (W.grow) {                                                  // a table filled: larger tables, the window runs again
-                Caps& c = caps[w];
-                if (W.grow & G_NODES) c.NC *= 2;
-                if (W.grow & G_EDGES) c.EC *= 2;
-                if (W.grow & G_ALIGNED) c.AC *= 2;
-                if (W.grow & G_LABELS) c.LC *= 2;
-                if (W.grow & G_PAIRS) c.PC *= 2;
-                c.SC = std::max<uint64_t>(c.SC * ((W.grow & G_STACK) ? 2 : 1), (c.NC + c.EC + c.AC) >> kn.shift[4]);
-                if (kn.log) {
-                    std::string fl;
-                    static const char* const names[] = {"nodes", "edges", "aligned", "labels", "stack", "pairs"};
-                    for (int t = 0; t < 6; ++t) if (W.grow & (1u << t)) { if (!fl.empty()) fl += ','; fl += names[t]; }
-                    std::fprintf(stderr, "vc_large: regrow window=%u flags=%s caps n=%llu e=%llu a=%llu l=%llu s=%llu p=%llu\n", w, fl.c_str(),
-                                 (unsigned long long)c.NC, (unsigned long long)c.EC, (unsigned long long)c.AC, (unsigned long long)c.LC,
-                                 (unsigned long long)c.SC, (unsigned long long)c.PC);
-                }
-                if (c.NC >= (1ull << 31) || c.EC >= (1ull << 31) || c.AC >= (1ull << 31) || c.SC >= (1ull << 31) || c.PC >= (1ull << 30))
-                    status[w] = VC_WIN_OVERFLOW;
-                else
-                    pending.push_back(w);
-                continue;
-            }
-            status[w] = (uint8_t)W.status;
-            out[w].resize(W.cons_n);
-            if (W.cons_n && hipMemcpy(out[w].data(), W.cons, W.cons_n, hipMemcpyDeviceToHost) != hipSuccess) {
-                done_tmp(); cleanup(); return fail(VC_ERR_HIP, "copy of a consensus failed");
-            }
-        }
-        // the alignments and coverage of the groups that finished, while their tables are resident: blocks laid out in the matrix
-        // buffer (free after the last step), in launches that fit the matrix budget, each copied out at once
-        std::vector<uint32_t> fin;
-        for (uint32_t k = 0; msa && k < n; ++k) if (!hw[k].grow && hw[k].status == VC_WIN_OK) fin.push_back(k);
-        auto block = [&](const LWin& W, uint64_t* mem_at, uint64_t* cov_at) {
-            const uint64_t rows = ((uint64_t)W.msa_rows * W.row_size + 15) & ~15ull;
-            *mem_at = rows;
-            *cov_at = rows + 4 * (((uint64_t)W.msa_rows + 3) & ~3ull);
-            return *cov_at + ((a.msa & VC_POA_COVERAGE) ? 4 * (((uint64_t)W.cons_n + 3) & ~3ull) : 0);
-        };
-        for (size_t k0 = 0; k0 < fin.size();) {
-            std::vector<uint32_t> list;
-            std::vector<uint64_t> hoff;
-            uint64_t bytes = 0, mem_at, cov_at;
-            size_t k1 = k0;
-            for (; k1 < fin.size(); ++k1) {
-                const uint64_t need = block(hw[fin[k1]], &mem_at, &cov_at);
-                if (!list.empty() && bytes + need > mat_budget) break;
-                list.push_back(fin[k1]); hoff.push_back(bytes); bytes += need;
-            }
-            k0 = k1;
-            uint8_t* dout = (uint8_t*)cached(g_cache.mat, bytes);
-            if (!dout) {
-                if (list.size() > 1) { done_tmp(); cleanup(); return fail(VC_ERR_HIP, "device allocation of the alignment rows failed"); }
-                status[grp[list[0]]] = VC_WIN_OVERFLOW; out[grp[list[0]]].clear();
-                continue;
-            }
-            const uint32_t nl = (uint32_t)list.size();
-            const uint64_t at = msa->rows.size();
-            LArgs f = a;
-            f.list = d_list; f.hoff = d_hoff; f.msa_out = dout;
-            ok = hipMemcpy(d_list, list.data(), nl * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(d_hoff, hoff.data(), nl * 8, hipMemcpyHostToDevice) == hipSuccess;
-            if (ok) {
-                hipLaunchKernelGGL(k_lg_msa<1>, dim3(nl), dim3(64), 0, 0, f);
-                ok = hipGetLastError() == hipSuccess;
-                msa->rows.resize(at + bytes);
-                ok = ok && hipMemcpy(msa->rows.data() + at, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-            }
-            if (!ok) { done_tmp(); cleanup(); return fail(VC_ERR_HIP, "the alignment-row kernel or its copy failed"); }
-            for (uint32_t q = 0; q < nl; ++q) {
-                const LWin& W = hw[list[q]];
-                const uint32_t w = grp[list[q]];
-                (void)block(W, &mem_at, &cov_at);
-                const uint8_t* blk = msa->rows.data() + at + hoff[q];
-                msa->n_rows[w] = W.msa_rows; msa->row_size[w] = W.row_size; msa->row_off[w] = at + hoff[q];
-                mem_of[w].resize(W.msa_rows);
-                if (W.msa_rows) std::memcpy(mem_of[w].data(), blk + mem_at, 4ull * W.msa_rows);
-                if (a.msa & VC_POA_COVERAGE) {
-                    cov_of[w].resize(W.cons_n);
-                    if (W.cons_n) std::memcpy(cov_of[w].data(), blk + cov_at, 4ull * W.cons_n);
-                }
-            }
-            msa_launches++;
-        }
-        done_tmp();
-    }
-    if (so) {                                                              // the choices; zeros for the groups that were not computed
-        bool ok = hipMemcpy(so->reversed, a.s_rev, nseq_all, hipMemcpyDeviceToHost) == hipSuccess;
-        if (so->score) ok = ok && hipMemcpy(so->score, a.s_score, nseq_all * 4, hipMemcpyDeviceToHost) == hipSuccess;
-        if (so->score_rev) ok = ok && hipMemcpy(so->score_rev, a.s_score_rev, nseq_all * 4, hipMemcpyDeviceToHost) == hipSuccess;
-        if (!ok) { cleanup(); return fail(VC_ERR_HIP, "copy of the strand choices failed"); }
-        for (uint32_t w = 0; w < nw; ++w) {
-            if (status[w] == VC_WIN_OK) continue;
-            for (uint32_t s = b->win_seq_off[w]; s < b->win_seq_off[w + 1]; ++s) {
-                so->reversed[s] = 0;
-                if (so->score) so->score[s] = 0;
-                if (so->score_rev) so->score_rev[s] = 0;
-            }
-        }
-    }
-    cleanup();
-    if (msa) {                                                             // per-row and per-base tables in group order
-        msa->member_off[0] = 0;
-        for (uint32_t w = 0; w < nw; ++w) {
-            if (status[w] != VC_WIN_OK) { msa->n_rows[w] = 0; msa->row_size[w] = 0; mem_of[w].clear(); cov_of[w].clear(); }
-            msa->row_member.insert(msa->row_member.end(), mem_of[w].begin(), mem_of[w].end());
-            msa->member_off[w + 1] = msa->row_member.size();
-            if (a.msa & VC_POA_COVERAGE) {
-                cov_of[w].resize(out[w].size());
-                msa->coverage.insert(msa->coverage.end(), cov_of[w].begin(), cov_of[w].end());
-            }
-        }
-        if (kn.log) std::fprintf(stderr, "vc_large: msa launches=%u bytes=%llu\n", msa_launches, (unsigned long long)msa->rows.size());
-    }
-    if (kn.log) std::fprintf(stderr, "vc_large: done alignments=%llu cells=%llu\n", (unsigned long long)n_align, (unsigned long long)n_cells);
-    uint64_t o = 0;
-    for (uint32_t w = 0; w < nw; ++w) {
-        if (o + out[w].size() > r->cons_cap) return fail(VC_ERR_CAPACITY, "consensus buffer too small");
-        if (!out[w].empty()) std::memcpy(r->cons + o, out[w].data(), out[w].size());
-        o += out[w].size();
-        r->cons_off[w + 1] = o;
-        r->status[w] = status[w];
-    }
-    return VC_OK;
-}
-
-}  // namespace

@@ -117,10 +117,8 @@ def group_batch(groups):
                       np.zeros(len(groups), np.uint8))
 
 
-def run_batch(batch, params, lib=None):
-    """vc_poa_run (params: capi.VcPoaParams) or vc_poa_run_gaps (capi.VcPoaGapParams) on a capi.Batch (its seq_begin / seq_end /
-    win_fasta are passed as NULL) -> (consensus bytes per group, status array).  Raises PoaError on a library error."""
-    lib = lib or capi.load_hip()
+def _result_buffers(batch):
+    """-> (consensus bytes, offsets, status, VcResult over them, the batch as a struct whose seq_begin / seq_end / win_fasta are NULL)"""
     n = batch.n_windows
     cons = np.zeros(max(int(batch.bases.size), 1), np.uint8)       # a group's consensus is never longer than its sequences
     off = np.zeros(n + 1, np.uint64)
@@ -129,11 +127,35 @@ def run_batch(batch, params, lib=None):
                       status.ctypes.data_as(C.POINTER(C.c_uint8)))
     vb = batch.as_struct()
     vb.seq_begin = vb.seq_end = vb.win_fasta = None
+    return cons, off, status, r, vb
+
+
+def run_batch(batch, params, lib=None):
+    """vc_poa_run (params: capi.VcPoaParams) or vc_poa_run_gaps (capi.VcPoaGapParams) on a capi.Batch (its seq_begin / seq_end /
+    win_fasta are passed as NULL) -> (consensus bytes per group, status array).  Raises PoaError on a library error."""
+    lib = lib or capi.load_hip()
+    n = batch.n_windows
+    cons, off, status, r, vb = _result_buffers(batch)
     name = "vc_poa_run_gaps" if isinstance(params, capi.VcPoaGapParams) else "vc_poa_run"
     rc = getattr(lib, name)(C.byref(params), C.byref(vb), C.byref(r))
     if rc != 0:
         raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     return [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n]
+
+
+def _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2):
+    e = gap if gap_extend is None else gap_extend
+    return capi.VcPoaGapParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap_open=gap,
+                               gap_extend=e, gap_open2=gap if gap_open2 is None else gap_open2,
+                               gap_extend2=e if gap_extend2 is None else gap_extend2)
+
+
+def _not_computed(status, strict):
+    bad = {w: int(s) for w, s in enumerate(status) if int(s) != capi.VC_WIN_OK}
+    if bad and strict:
+        what = ", ".join(f"{w}: {_STATUS.get(s, s)}" for w, s in list(bad.items())[:8])
+        raise PoaError(f"{len(bad)} group(s) not computed: {what}{' ...' if len(bad) > 8 else ''}", groups=bad)
+    return bad
 
 
 def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
@@ -148,15 +170,9 @@ def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, devi
     if gap_extend is None and gap_open2 is None and gap_extend2 is None:
         p = capi.VcPoaParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap=gap)
     else:
-        e = gap if gap_extend is None else gap_extend
-        p = capi.VcPoaGapParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap_open=gap,
-                                gap_extend=e, gap_open2=gap if gap_open2 is None else gap_open2,
-                                gap_extend2=e if gap_extend2 is None else gap_extend2)
+        p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
     cons, status = run_batch(batch, p, lib)
-    bad = {w: int(s) for w, s in enumerate(status) if int(s) != capi.VC_WIN_OK}
-    if bad and strict:
-        what = ", ".join(f"{w}: {_STATUS.get(s, s)}" for w, s in list(bad.items())[:8])
-        raise PoaError(f"{len(bad)} group(s) not computed: {what}{' ...' if len(bad) > 8 else ''}", groups=bad)
+    bad = _not_computed(status, strict)
     return [None if w in bad else c for w, c in enumerate(cons)]
 
 
@@ -184,13 +200,7 @@ def run_batch_msa(batch, params, flags, lib=None, strands=False):
     scores as one int32 array per group."""
     lib = lib or capi.load_hip()
     n = batch.n_windows
-    cons = np.zeros(max(int(batch.bases.size), 1), np.uint8)
-    off = np.zeros(n + 1, np.uint64)
-    status = np.zeros(max(n, 1), np.uint8)
-    r = capi.VcResult(off.ctypes.data_as(C.POINTER(C.c_uint64)), cons.ctypes.data_as(C.POINTER(C.c_uint8)), cons.size,
-                      status.ctypes.data_as(C.POINTER(C.c_uint8)))
-    vb = batch.as_struct()
-    vb.seq_begin = vb.seq_end = vb.win_fasta = None
+    cons, off, status, r, vb = _result_buffers(batch)
     o = capi.VcPoaMsaOut(flags=flags)
     wso = [int(x) for x in batch.win_seq_off]
     if strands:
@@ -219,21 +229,6 @@ def run_batch_msa(batch, params, flags, lib=None, strands=False):
     if strands:
         return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
     return res, status[:n]
-
-
-def _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2):
-    e = gap if gap_extend is None else gap_extend
-    return capi.VcPoaGapParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap_open=gap,
-                               gap_extend=e, gap_open2=gap if gap_open2 is None else gap_open2,
-                               gap_extend2=e if gap_extend2 is None else gap_extend2)
-
-
-def _not_computed(status, strict):
-    bad = {w: int(s) for w, s in enumerate(status) if int(s) != capi.VC_WIN_OK}
-    if bad and strict:
-        what = ", ".join(f"{w}: {_STATUS.get(s, s)}" for w, s in list(bad.items())[:8])
-        raise PoaError(f"{len(bad)} group(s) not computed: {what}{' ...' if len(bad) > 8 else ''}", groups=bad)
-    return bad
 
 
 def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
