@@ -473,6 +473,59 @@ typedef struct vc_poa_strand_out {
 } vc_poa_strand_out;
 int         vc_poa_run_strand(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s);
 
+/* The partial order graph of every group: beside the consensus, what spoa's command line prints with -r 3 / -r 4 (PrintGfa,
+ * src/main.cpp:120-200) and with -d (Graph::PrintDot, src/graph.cpp:746-803) -- nodes, weighted edges, aligned nodes, the path of
+ * every sequence and the consensus path -- as tables, compacted on the device (k_lg_graph in vc_large.hip).
+ * p, b and r as vc_poa_run_gaps.  o may be NULL; otherwise it is vc_poa_run_msa's and the alignment of the same graph comes with
+ * it.  s NULL is the plain flow; otherwise it is vc_poa_run_strand's and the groups are built with spoa's -s.
+ * The id rule: a node id is spoa's Node::id -- 0-based, in creation order (graph.cpp:73-76), local to its group.  GFA prints id + 1.
+ * The layout, per batch, group w of n = n_groups:
+ *   nodes    n_nodes[w] of them; node i of group w is entry node_off[w] + i of node_base (the decoded byte, graph.decoder(code)),
+ *            of node_cons_pos (k: the node is consensus_[k]; -1: it is not on the consensus -- GFA's ic:Z:true, main.cpp:135-138,
+ *            and dot's colours, graph.cpp:755-760,777) and of rank_to_node (the topological order, Graph::rank_to_node()).
+ *   edges    out_off holds n_nodes[w] + 1 entries per group, node i's at out_off[node_off[w] + w + i]: its out-edges are
+ *            edge_head[k] / edge_weight[k] (int64, Edge::weight) for k from that entry up to the next one.  Every edge of the graph
+ *            appears once, ordered by tail id and then by position in the tail's out-list: the order in which PrintGfa and
+ *            PrintDot print them (main.cpp:141-164, graph.cpp:764-783).  The group's edges are the k from out_off[node_off[w] + w]
+ *            up to out_off[node_off[w + 1] + w].
+ *   aligned  the pairs k in aligned_off[w] .. aligned_off[w + 1]: nodes aligned_a[k] < aligned_b[k] are aligned to each other; ordered
+ *            by a and then by a's aligned-node list, dot's order (graph.cpp:784-800).
+ *   paths    the paths k in path_first[w] .. path_first[w + 1], one per sequence that was added, in the order added (sequences_):
+ *            path_member[k] is the index of the group member (as row_member: an empty member is never added, graph.cpp:187-190,
+ *            and has no path); its nodes are path_node[path_off[k] .. path_off[k + 1]), one per base, from sequences_[k] along
+ *            Node::Successor(k) (main.cpp:166-176).  path_reversed[k] is 1 where the strand flow kept the reverse complement: the
+ *            nodes are in graph order and spell the kept bytes; PrintGfa prints such a path backwards with '-' (main.cpp:178-187).
+ *   cons_node[r->cons_off[w] + k] is the node of consensus base k (Graph::consensus()).
+ * A group that is not VC_WIN_OK has no node and no path; so has a group without a non-empty sequence.
+ * Lifetime: as vc_poa_msa_out -- the library owns every array, they stay valid until the next vc_poa_* or vc_large_* call or
+ * vc_large_release, and a failed call leaves every pointer NULL.
+ * Calls that do not ask for the graph are unchanged: this entry alone launches k_lg_graph and keeps what it needs.
+ * Checked before the device, in this order: as vc_poa_run_msa up to the flags (o == NULL counts as flags 0), then g, then
+ * s->reversed when s is given, then the batch: VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these. */
+typedef struct vc_poa_graph_out {
+    uint32_t n_groups;              /* out: b->n_windows                                                            */
+    const uint32_t* n_nodes;        /* [n_groups]                                                                   */
+    const uint64_t* node_off;       /* [n_groups + 1] prefix sums of n_nodes                                        */
+    const uint8_t*  node_base;      /* [node_off[n_groups]]                                                         */
+    const int32_t*  node_cons_pos;  /* [node_off[n_groups]]                                                         */
+    const uint32_t* rank_to_node;   /* [node_off[n_groups]]                                                         */
+    const uint64_t* out_off;        /* [node_off[n_groups] + n_groups] into edge_head / edge_weight                 */
+    const uint32_t* edge_head;
+    const int64_t*  edge_weight;
+    const uint64_t* aligned_off;    /* [n_groups + 1] into aligned_a / aligned_b                                    */
+    const uint32_t* aligned_a;
+    const uint32_t* aligned_b;
+    const uint64_t* path_first;     /* [n_groups + 1] first path of the group                                       */
+    const uint32_t* path_member;    /* [path_first[n_groups]]                                                       */
+    const uint8_t*  path_reversed;  /* [path_first[n_groups]]                                                       */
+    const uint64_t* path_off;       /* [path_first[n_groups] + 1] into path_node                                    */
+    const uint32_t* path_node;
+    const uint32_t* cons_node;      /* [r->cons_off[n_groups]]                                                      */
+    uint64_t        bytes;          /* copied out of the device for this call                                       */
+} vc_poa_graph_out;
+int         vc_poa_run_graph(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o /* may be NULL */,
+                             vc_poa_strand_out* s /* NULL: the plain flow; else spoa's -s */, vc_poa_graph_out* g);
+
 #ifdef __cplusplus
 }
 #endif

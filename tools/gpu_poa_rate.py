@@ -10,7 +10,7 @@ libvcref_sse41.so, vcref_spoa_consensus) on a sample of the same groups on 16 ho
 compared with the device's.
 
   python tools/gpu_poa_rate.py [--groups 4096] [--len 1000] [--depth 32] [--cpu-sample 256] [--out profiles/poa_rate.txt]
-                               [--gaps linear|affine|convex] [--msa] [--strand]
+                               [--gaps linear|affine|convex] [--msa] [--strand] [--graph [--parent-lib LIB]]
 
 --msa measures the multiple sequence alignment instead (vc_poa_run_msa with the consensus row and the coverage, global
 alignment) and writes profiles/poa_msa_rate.txt: after one warm-up call on all groups, three consensus-only calls and three
@@ -25,6 +25,14 @@ unflipped groups and three strand calls on the flipped ones in the same process,
 between the two (the synthetic reads are upper-case ACGT, so 0 is expected), the members reported reversed, and then each kind
 once under `rocprofv3 --kernel-trace --stats` for the k_lg_* shares.  Exits 1 if the strand call takes 2x the plain call's time
 or more: two whole flows would cost that, so it would mean the graph stages or the launches were duplicated.
+
+--graph measures the graph output (vc_poa_run_graph, global alignment, 5/-4/-8; profiles/poa_graph_rate.txt): in one process
+three consensus-only calls and three graph calls with the bytes copied out; with --parent-lib (a library built from the parent
+commit) the consensus-only calls of that library and of this one in alternating processes of their own (parent, this, parent,
+this; a warm-up and three timed calls each), for the comparison against the spread of the parent's own runs; then the
+graph call under `rocprofv3 --kernel-trace --stats` once per path route (scatter and compaction, and the literal walk of
+VC_LARGE_GRAPH_WALK=1) for k_lg_graph's time beside k_lg_msa<1>'s on the same groups.  Exits 1 if the GFA of a sampled group
+differs from the one of the CPU restatement tests/poa_graph_ref.py (--check groups, the smallest ones of the batch).
 
 --gaps affine / convex runs vc_poa_run_gaps with spoa's affine known-answer scores (5 -4 -8 -6) or its command-line defaults
 (5 -4 -8 -6 -10 -4, convex); the cells are still rows x columns (not x planes).  The reference in oracle/_ref only takes linear
@@ -304,8 +312,154 @@ def main_msa(a):
     print("wrote", out)
 
 
+def timed_graph(batch, flags=0, graph=True, lib=None):
+    """-> (seconds, bytes copied out, graphs or None) of one vc_poa_run_graph (global, 5/-4/-8 linear; flags: the MSA beside it) on
+    the batch, or with graph=False of the consensus-only vc_poa_run_gaps (lib: another library's handle, see parent_handle)"""
+    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
+    import re
+    import tempfile
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            res, status = poa.run_batch_graph(batch, p, flags) if graph else poa.run_batch(batch, p, lib)
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read().decode()
+    if int((status != 0).sum()):
+        raise RuntimeError(f"{int((status != 0).sum())} groups not computed")
+    m = re.search(r"vc_large: graph launches=(\d+) bytes=(\d+)", err)
+    return dt, int(m.group(2)) if m else 0, res if graph else None
+
+
+def parent_handle(path):
+    """The two entry points the consensus-only call needs, from a library that may lack the newer ones (capi.load_hip binds them all
+    and so refuses a library of the parent commit)."""
+    import ctypes as C
+    lib = C.CDLL(path)
+    lib.vc_poa_run_gaps.argtypes = [C.POINTER(capi.VcPoaGapParams), C.POINTER(capi.VcBatch), C.POINTER(capi.VcResult)]
+    lib.vc_poa_run_gaps.restype = C.c_int
+    lib.vc_poa_last_error.argtypes = []
+    lib.vc_poa_last_error.restype = C.c_char_p
+    return lib
+
+
+def _gfa_job(args):
+    import poa_graph_ref as G
+    mem, names = args
+    return G.to_poa_graph(G.graph(mem, 1, 5, -4, -8)).to_gfa(names, include_consensus=True)
+
+
+def main_graph(a):
+    batch = synth_groups(a)
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_graph_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    emit(f"POA groups with the graph output: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100, PacBio-like errors, frac_partial=0, "
+         f"FASTQ), {int(batch.seq_off[-1])} bases; 5/-4/-8, global (kNW); one MI355X; synchronous; host clock around one call; one untimed "
+         f"call on all groups first, then three calls of each kind in the same process")
+    timed_graph(batch, graph=False)
+    plain = [timed_graph(batch, graph=False)[0] for _ in range(3)]
+    emit(f"{'consensus only (vc_poa_run_gaps)':44s} " + "  ".join(f"{a.groups / t:7.1f}" for t in plain) + f" groups/s  ({'  '.join(f'{t:.2f}' for t in plain)} s)")
+    runs = [timed_graph(batch) for _ in range(3)]
+    emit(f"{'graph (vc_poa_run_graph, Python copies incl.)':44s} " + "  ".join(f"{a.groups / r[0]:7.1f}" for r in runs) +
+         f" groups/s  ({'  '.join(f'{r[0]:.2f}' for r in runs)} s; {runs[0][1] / 1e6:.1f} MB copied out of the device)")
+    graphs = runs[-1][2]
+    large.release()
+    ok = True
+    if a.check:
+        sizes = [int(batch.seq_off[batch.win_seq_off[w + 1]] - batch.seq_off[batch.win_seq_off[w]]) for w in range(batch.n_windows)]
+        idx = sorted(range(batch.n_windows), key=lambda w: sizes[w])[:a.check]
+        jobs = []
+        for w in idx:
+            seqs, quals, _, _ = batch.window(w)
+            jobs.append((list(zip(seqs, quals)), [f"r{i}" for i in range(len(seqs))]))
+        from concurrent.futures import ProcessPoolExecutor
+        with ProcessPoolExecutor(min(a.threads, len(jobs))) as ex:
+            want = list(ex.map(_gfa_job, jobs))
+        bad = [w for w, (mem, names), t in zip(idx, jobs, want) if graphs[w].to_gfa(names, include_consensus=True) != t]
+        ok = not bad
+        emit(f"GFA of {len(idx)} sampled groups (the smallest of the batch: {idx}) against the CPU restatement: " +
+             ("identical" if ok else f"DIFFERENT for {bad}"))
+    del graphs, runs
+    if a.parent_lib:
+        # the two libraries alternate, each run a process of its own (a warm-up call, then three timed ones): parent, this, parent, this
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "0", "--graph", "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth)]
+        secs = {"parent": [], "this": []}
+        for which in ("parent", "this", "parent", "this"):
+            p = subprocess.run(cmd + (["--parent-lib", os.path.abspath(a.parent_lib)] if which == "parent" else []),
+                               capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"{which} library: run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1                          # nothing more is started on the device after a failed run
+            t = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            secs[which] += t
+            name = "library of the parent commit" if which == "parent" else "this library"
+            emit(f"{'consensus only, ' + name:44s} " + "  ".join(f"{a.groups / x:7.1f}" for x in t) +
+                 f" groups/s  ({'  '.join(f'{x:.3f}' for x in t)} s; a process of its own)")
+        par, cur = sorted(secs["parent"]), sorted(secs["this"])
+        lo, hi = par[0], par[-1]
+        med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2
+        emit(f"consensus-only time over the two alternated processes each: the parent's {lo:.3f} .. {hi:.3f} s (its own spread "
+             f"{(hi - lo) / lo * 100:.2f} %, median {med(par):.3f}), this library's {cur[0]:.3f} .. {cur[-1]:.3f} s (median {med(cur):.3f}): "
+             f"best against best {(cur[0] / lo - 1) * 100:+.2f} %, median against median {(med(cur) / med(par) - 1) * 100:+.2f} %; this "
+             f"library's median lies {'inside (or below)' if med(cur) <= hi else 'ABOVE'} the range of the parent's own runs")
+    if not a.no_trace:
+        emit("kernel times of the graph call (with the MSA beside it, flags 7), a run of its own per path route under rocprofv3 --kernel-trace "
+             "--stats (a fresh process: 64 groups first, then all):")
+        digests = []
+        for route, child_id in (("scatter + compaction", 1), ("literal walk", 2)):
+            d = os.path.join(a.trace_dir, f"graph{child_id}")
+            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+                   sys.executable, os.path.abspath(__file__), "--child", str(child_id), "--graph", "--groups", str(a.groups), "--len", str(a.len),
+                   "--depth", str(a.depth)]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"  {route}: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1
+            ms = kernel_shares(d)
+            tot = sum(ms.values())
+            kg = {k: v for k, v in ms.items() if k.startswith("k_lg_graph") or k.startswith("k_lg_msa")}
+            emit(f"  {route:21s} kernels {tot / 1e3:.2f} s: " + ", ".join(f"{k} {v:.1f} ms ({v / tot * 100:.2f} %)" for k, v in sorted(kg.items())))
+            digests.append([json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["paths"])
+        if len(digests) == 2:
+            same = digests[0] == digests[1]
+            ok = ok and same
+            emit(f"  the paths of all {a.groups} groups by the two routes: " + ("identical" if same else "DIFFERENT"))
+    print("wrote", out)
+    return 0 if ok else 1
+
+
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    if a.graph:
+        batch = synth_groups(a)
+        if a.child == 0:                          # consensus only, three calls after a full warm-up (the parent library's run)
+            lib = parent_handle(a.parent_lib) if a.parent_lib else None
+            timed_graph(batch, graph=False, lib=lib)
+            print(json.dumps(dict(seconds=[timed_graph(batch, graph=False, lib=lib)[0] for _ in range(3)])))
+            return
+        if a.child == 2:
+            os.environ["VC_LARGE_GRAPH_WALK"] = "1"
+        timed_graph(batch.slice(0, min(64, batch.n_windows)), 7)
+        dt, nbytes, graphs = timed_graph(batch, 7)
+        import hashlib
+        h = hashlib.sha256()
+        for g in graphs:                          # the two routes must write the same paths
+            h.update(g.path_off.tobytes() + g.path_node.tobytes())
+        print(json.dumps(dict(seconds=dt, bytes=nbytes, paths=h.hexdigest())))
+        return
     if a.strand:
         batch = synth_groups(a)
         if a.child:
@@ -352,11 +506,16 @@ def main():
     ap.add_argument("--gaps", choices=sorted(GAPS), default="linear")
     ap.add_argument("--msa", action="store_true", help="measure vc_poa_run_msa beside the consensus-only call (profiles/poa_msa_rate.txt)")
     ap.add_argument("--strand", action="store_true", help="measure vc_poa_run_strand beside the plain call (profiles/poa_strand_rate.txt)")
+    ap.add_argument("--graph", action="store_true", help="measure vc_poa_run_graph beside the consensus-only call (profiles/poa_graph_rate.txt)")
+    ap.add_argument("--parent-lib", default=None, help="--graph: a libvechat_hip.so of the parent commit, for its consensus-only rate")
+    ap.add_argument("--check", type=int, default=2, help="--graph: groups whose GFA is compared with the CPU restatement's")
     ap.add_argument("--append", action="store_true", help="--strand: keep what the output file holds and write below it")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
         return child(a)
+    if a.graph:
+        return main_graph(a)
     if a.strand:
         return main_strand(a)
     if a.msa:

@@ -92,6 +92,21 @@ class VcPoaStrandOut(C.Structure):
     _fields_ = [("reversed", C.POINTER(C.c_uint8)), ("score", C.POINTER(C.c_int32)), ("score_rev", C.POINTER(C.c_int32))]
 
 
+class VcPoaGraphOut(C.Structure):
+    """vc_poa_graph_out: everything out and owned by the library until its next vc_poa_* / vc_large_* call"""
+    _fields_ = [
+        ("n_groups", C.c_uint32),
+        ("n_nodes", C.POINTER(C.c_uint32)), ("node_off", C.POINTER(C.c_uint64)), ("node_base", C.POINTER(C.c_uint8)),
+        ("node_cons_pos", C.POINTER(C.c_int32)), ("rank_to_node", C.POINTER(C.c_uint32)),
+        ("out_off", C.POINTER(C.c_uint64)), ("edge_head", C.POINTER(C.c_uint32)), ("edge_weight", C.POINTER(C.c_int64)),
+        ("aligned_off", C.POINTER(C.c_uint64)), ("aligned_a", C.POINTER(C.c_uint32)), ("aligned_b", C.POINTER(C.c_uint32)),
+        ("path_first", C.POINTER(C.c_uint64)), ("path_member", C.POINTER(C.c_uint32)), ("path_reversed", C.POINTER(C.c_uint8)),
+        ("path_off", C.POINTER(C.c_uint64)), ("path_node", C.POINTER(C.c_uint32)),
+        ("cons_node", C.POINTER(C.c_uint32)),
+        ("bytes", C.c_uint64),
+    ]
+
+
 class VcStats(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64), ("alignments", C.c_uint64), ("dp_rows", C.c_uint64),
@@ -360,6 +375,9 @@ def load_hip():
         lib.vc_poa_run_strand.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut),
                                           C.POINTER(VcPoaStrandOut)]
         lib.vc_poa_run_strand.restype = C.c_int
+        lib.vc_poa_run_graph.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut),
+                                         C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut)]
+        lib.vc_poa_run_graph.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

@@ -47,7 +47,9 @@
 //               alignment and strand, the second strand's matrix behind the first's --, k_lg_back picks the strand by score and
 //               walks the winner's matrix only, and k_lg_apply adds the kept view and records the choice (spoa's -s, main.cpp:287-304);
 //   k_lg_msa    vc_poa_run_msa only, one wave per finished group: <0> node -> column by a wave prefix sum over the topological
-//               order, <1> the rows ('-' fill, then a scatter over the edge labels), the consensus row and the coverage.
+//               order, <1> the rows ('-' fill, then a scatter over the edge labels), the consensus row and the coverage;
+//   k_lg_graph  vc_poa_run_graph only, one wave per finished group: <0> the counts of the group's graph tables, <1> the tables --
+//               nodes, out-edges as CSR, aligned pairs, a path per sequence, the consensus path (spoa's GFA and dot output).
 //
 // Limits, every schedule: a sequence is shorter than 65 535 bases; beyond that only the device memory bounds a window or group,
 // and one whose tables or matrix it cannot hold at all comes back VC_WIN_OVERFLOW.  Where the reference throws (an invalid
@@ -59,10 +61,12 @@
 //                           (the stack then also grows from (nodes + edges + aligned) >> shift, not from the unshifted sum);
 //   VC_LARGE_ARENA_MB=x     arena budget (window tables per group; a window above twice the budget is refused) in MiB, fractions allowed;
 //   VC_LARGE_MAT_MB=x       matrix budget (int32 matrices, every plane and both strands, per forward launch) in MiB;
+//   VC_LARGE_GRAPH_WALK=1   vc_poa_run_graph walks every path node by node (Node::Successor) instead of scattering and compacting it;
 //   VC_LARGE_LOG=1          one stderr line per event: "vc_large: regrow window=W flags=nodes,... caps n=.. e=.. a=.. l=.. s=.. p=..",
 //                           "vc_large: group windows=N bytes=B ids=W,.. need=B,..", "vc_large: step launches=K over=O" (steps of more than one
 //                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B",
 //                           "vc_large: msa launches=K bytes=B" (vc_poa_run_msa with flags: k_lg_msa<1> launches, bytes copied out),
+//                           "vc_large: graph launches=K bytes=B" (vc_poa_run_graph: k_lg_graph<1> launches, bytes copied out),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes run, their rows x columns
 //                           summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes).
 #include <hip/hip_runtime.h>
@@ -125,6 +129,7 @@ struct LWin {
     // vc_poa_run_msa only (nullptr otherwise): spoa's sequences_, one entry per sequence that was added (label = index)
     uint32_t *sq_begin, *sq_member;                    // [nseq] begin node; index of the group member
     uint32_t msa_rows, row_size;                       // k_lg_msa<0>: rows and columns of the group's alignment
+    uint32_t gr_cols, gr_path;                         // k_lg_graph<0>: columns of the alignment, path entries (bases of the added sequences)
 };
 
 struct LArgs {
@@ -142,6 +147,7 @@ struct LArgs {
     uint32_t gaps;                                     // mode 2: spoa::AlignmentSubtype (0 linear, 1 affine, 2 convex); 0 elsewhere
     int32_t gap_e, gap_q, gap_c;                       // mode 2: spoa's e, q, c after Create's subtype rule
     uint32_t msa;                                      // mode 2: VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE, 0 elsewhere
+    uint32_t graph;                                    // mode 2, vc_poa_run_graph: 1 paths by scatter and compaction, 2 by the literal walk; 0 elsewhere
     // mode 2, vc_poa_run_strand (strand = 1; nullptr / 0 elsewhere): the strand views of the batch, k_lg_views, laid out as bases /
     // quals are, and the choice per sequence of the batch
     uint32_t strand;
@@ -149,7 +155,8 @@ struct LArgs {
     uint8_t* s_rev;                                    // [sequences] 1: the reverse complement was kept
     int32_t *s_score, *s_score_rev;                    // [sequences] both strands' scores
     uint64_t nbytes;                                   // k_lg_views: bytes of the batch
-    // k_lg_fwd / k_lg_back: windows of this launch and their matrices (k_lg_msa<1>: groups and the byte offsets of their blocks)
+    // k_lg_fwd / k_lg_back: windows of this launch and their matrices (k_lg_msa<1>, k_lg_graph<1>: groups and the byte offsets of
+    // their blocks in msa_out; k_lg_graph<1> has the offsets of the groups' scratch behind them, at hoff[groups + k])
     const uint32_t* list;
     const uint64_t* hoff;
     int32_t* H;
@@ -667,9 +674,9 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     for (int c = 0; c < 256; ++c) { W.coder[c] = -1; W.decoder[c] = -1; }
     W.num_codes = 0;
     reset_graph(W.gr[0]); reset_graph(W.gr[1]);
-    W.gr[0].labels = a.mode == 1 || a.msa != 0; W.gr[1].labels = 0;
+    W.gr[0].labels = a.mode == 1 || a.msa != 0 || a.graph != 0; W.gr[1].labels = 0;
     W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
-    W.msa_rows = 0; W.row_size = 0; W.rev = 0;
+    W.msa_rows = 0; W.row_size = 0; W.rev = 0; W.gr_cols = 0; W.gr_path = 0;
     if (a.mode == 2) {                                                     // POA group: sequence 0 meets the empty graph in k_lg_prep
         W.phase = PH_BUILD; W.j = 0; W.k = 0;
         if (W.nseq == 0) finish_poa(W);                                    // no sequence: the empty consensus
@@ -1097,6 +1104,37 @@ __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
 //     node once, so no label repeats among the in-edges nor among the out-edges, and a label on an out-edge is missing from the
 //     in-edges exactly when the sequence begins at the node: the count is the in-edge label cells plus the out-edge cells
 //     whose sequence begins here.  Lanes take consensus positions.
+// inclusive prefix sum over the wave
+__device__ __forceinline__ uint32_t wave_scan(uint32_t x, uint32_t lane) {
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(x, d, 64);
+        if (lane >= d) x += o;
+    }
+    return x;
+}
+
+// PH 0 of k_lg_msa and of k_lg_graph: node -> column into W.map; returns the number of columns.  Every lane calls it.
+__device__ uint32_t msa_columns(LWin& W, const LGraph& g, uint32_t lane) {
+    const uint32_t N = g.n_rank;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < N; base += 64) {
+        const uint32_t i = base + lane;
+        uint32_t v = NONE, x = 0;
+        if (i < N) {
+            v = g.rank[i];
+            x = 1;
+            if (i > 0) {
+                const uint32_t p = g.rank[i - 1];
+                for (uint32_t q = g.al_h[v]; q != NONE; q = g.al_nx[q]) if (g.al_v[q] == p) { x = 0; break; }
+            }
+        }
+        x = wave_scan(x, lane);
+        if (i < N) W.map[v] = carry + x - 1;
+        carry += __shfl(x, 63, 64);
+    }
+    return carry;
+}
+
 template <uint32_t PH>
 __global__ __launch_bounds__(64) void k_lg_msa(LArgs a) {
     const uint32_t lane = threadIdx.x;
@@ -1105,27 +1143,8 @@ __global__ __launch_bounds__(64) void k_lg_msa(LArgs a) {
         if (W.phase != PH_DONE || W.grow || W.status != VC_WIN_OK) return;
         const LGraph& g = W.gr[W.cur];
         if (!(a.msa & VC_POA_MSA)) return;
-        const uint32_t N = g.n_rank;
-        uint32_t carry = 0;
-        for (uint32_t base = 0; base < N; base += 64) {
-            const uint32_t i = base + lane;
-            uint32_t v = NONE, x = 0;
-            if (i < N) {
-                v = g.rank[i];
-                x = 1;
-                if (i > 0) {
-                    const uint32_t p = g.rank[i - 1];
-                    for (uint32_t q = g.al_h[v]; q != NONE; q = g.al_nx[q]) if (g.al_v[q] == p) { x = 0; break; }
-                }
-            }
-            for (uint32_t d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(x, d, 64);
-                if (lane >= d) x += o;
-            }
-            if (i < N) W.map[v] = carry + x - 1;
-            carry += __shfl(x, 63, 64);
-        }
-        if (lane == 0) { W.row_size = carry; W.msa_rows = g.nseq + ((a.msa & VC_POA_MSA_CONSENSUS) ? 1u : 0u); }
+        const uint32_t cols = msa_columns(W, g, lane);
+        if (lane == 0) { W.row_size = cols; W.msa_rows = g.nseq + ((a.msa & VC_POA_MSA_CONSENSUS) ? 1u : 0u); }
     } else {
         LWin& W = a.win[a.list[blockIdx.x]];
         const LGraph& g = W.gr[W.cur];
@@ -1168,6 +1187,156 @@ __global__ __launch_bounds__(64) void k_lg_msa(LArgs a) {
                     u = g.al_v[q];
                 }
                 cov[i] = cnt;
+            }
+        }
+    }
+}
+
+// A finished group's block of k_lg_graph<1>: the byte offset of every table in it, each 16-byte aligned and padded to 16 bytes
+// (the fills store whole uint4).  N nodes, E edges, P aligned pairs, S added sequences, T path entries, C consensus nodes.
+struct GraphBlock {
+    uint64_t base, cons_pos, rank, out_off, head, weight, al_a, al_b, member, rev, p_off, p_node, cons_node, bytes;
+};
+__host__ __device__ inline GraphBlock graph_block(uint64_t N, uint64_t E, uint64_t P, uint64_t S, uint64_t T, uint64_t Cn) {
+    GraphBlock B;
+    uint64_t off = 0;
+    auto take = [&](uint64_t bytes) { const uint64_t at = off; off += (bytes + 15) & ~15ull; return at; };
+    B.base = take(N); B.cons_pos = take(4 * N); B.rank = take(4 * N); B.out_off = take(4 * (N + 1));
+    B.head = take(4 * E); B.weight = take(8 * E);
+    B.al_a = take(4 * P); B.al_b = take(4 * P);
+    B.member = take(4 * S); B.rev = take(S); B.p_off = take(4 * (S + 1)); B.p_node = take(4 * T);
+    B.cons_node = take(4 * Cn);
+    B.bytes = off;
+    return B;
+}
+// the (sequence, column) scratch of the path stage beside it
+__host__ __device__ inline uint64_t graph_scratch_bytes(uint64_t S, uint64_t cols) { return (4 * S * cols + 15) & ~15ull; }
+
+// The partial order graph of a finished POA group, as spoa's PrintGfa (main.cpp:120-200) and Graph::PrintDot (graph.cpp:746-803)
+// read it: one wave per group, no lane-serial stage.  Node ids are the table index, which is spoa's id: add_node numbers the
+// nodes in creation order and schedule 2 never rebuilds its graph.
+//   PH 0, every group in flight: what PH 1 writes, for the host to size and place the block.  Nodes n_nodes; edges n_edges (every
+//     edge lies in exactly one out-list and schedule 2 removes none); aligned pairs n_al / 2 (push_aligned always stores a pair
+//     both ways); the columns of the alignment (msa_columns) into W.gr_cols; the path entries -- a path has a node per base, so
+//     the lengths of the added sequences, summed over the wave -- into W.gr_path.
+//   PH 1, the groups of a.list, block at a.msa_out + a.hoff[blockIdx.x] (graph_block), scratch at a.hoff[groups + blockIdx.x]:
+//     per node its base, its consensus position (filled with -1, then scattered from the bundle W.comp) and rank_to_node;
+//     out-edges as CSR by tail id and out-list position: a wave prefix sum of out_n over tiles of 64 nodes with a carried
+//     total, then every lane walks its own node's list into its slots; the aligned pairs (a, b), a < b, the same way on the
+//     count of larger ids in a's aligned list; a path per added sequence.  PrintGfa walks Successor(i) from sequences_[i]; as in
+//     k_lg_msa<1> the nodes of sequence i are its begin node and the head of every edge that carries label i, each met once, and
+//     an edge goes from a column to a later one, so the path is those nodes in column order: they are scattered into row i of
+//     the scratch (S x columns of NONE) and every row is compacted with a wave prefix sum behind the sequence's offset (a
+//     prefix sum of the lengths).  a.graph == 2 takes the literal walk instead, a lane per sequence: the dependent chain, kept
+//     to be measured against.  A kept reverse strand's path stays in graph order and is flagged (main.cpp:178-187 reverses it
+//     while printing).
+template <uint32_t PH>
+__global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
+    const uint32_t lane = threadIdx.x;
+    if constexpr (PH == 0) {
+        LWin& W = a.win[blockIdx.x];
+        if (W.phase != PH_DONE || W.grow || W.status != VC_WIN_OK) return;
+        const LGraph& g = W.gr[W.cur];
+        const uint32_t cols = msa_columns(W, g, lane);
+        uint32_t t = 0;
+        for (uint32_t s = lane; s < g.nseq; s += 64) {
+            const uint32_t q = W.s0 + W.sq_member[s];
+            t += (uint32_t)(a.seq_off[q + 1] - a.seq_off[q]);
+        }
+        for (uint32_t d = 32; d; d >>= 1) t += __shfl_xor(t, d, 64);
+        if (lane == 0) { W.gr_cols = cols; W.gr_path = t; }
+    } else {
+        LWin& W = a.win[a.list[blockIdx.x]];
+        const LGraph& g = W.gr[W.cur];
+        const uint32_t N = g.n_nodes, E = g.n_edges, P = g.n_al / 2, S = g.nseq, T = W.gr_path, Cn = W.cons_n, cols = W.gr_cols;
+        const GraphBlock B = graph_block(N, E, P, S, T, Cn);
+        uint8_t* out = a.msa_out + a.hoff[blockIdx.x];                     // 16-byte aligned, and so is every table
+        uint8_t* base = out + B.base;
+        int32_t* cons_pos = (int32_t*)(out + B.cons_pos);
+        uint32_t *rank = (uint32_t*)(out + B.rank), *out_off = (uint32_t*)(out + B.out_off), *head = (uint32_t*)(out + B.head);
+        int64_t* weight = (int64_t*)(out + B.weight);
+        uint32_t *al_a = (uint32_t*)(out + B.al_a), *al_b = (uint32_t*)(out + B.al_b), *member = (uint32_t*)(out + B.member);
+        uint8_t* rev = out + B.rev;
+        uint32_t *p_off = (uint32_t*)(out + B.p_off), *p_node = (uint32_t*)(out + B.p_node), *cons_node = (uint32_t*)(out + B.cons_node);
+        uint32_t* scr = (uint32_t*)(a.msa_out + a.hoff[gridDim.x + blockIdx.x]);
+        const uint64_t cells = a.graph == 1 ? (uint64_t)S * cols : 0;
+        const uint4 none4 = make_uint4(NONE, NONE, NONE, NONE);
+        for (uint64_t k = lane; k < ((uint64_t)N + 3) / 4; k += 64) ((uint4*)cons_pos)[k] = none4;      // -1
+        for (uint64_t k = lane; k < (cells + 3) / 4; k += 64) ((uint4*)scr)[k] = none4;
+        for (uint32_t v = lane; v < N; v += 64) { base[v] = (uint8_t)W.decoder[g.code[v]]; rank[v] = g.rank[v]; }
+        // the sequences: member, strand, offset of the path
+        uint32_t carry = 0;
+        for (uint32_t s0 = 0; s0 < S; s0 += 64) {
+            const uint32_t s = s0 + lane;
+            uint32_t len = 0;
+            if (s < S) {
+                const uint32_t q = W.s0 + W.sq_member[s];
+                len = (uint32_t)(a.seq_off[q + 1] - a.seq_off[q]);
+                member[s] = W.sq_member[s];
+                rev[s] = a.strand ? a.s_rev[q] : 0;
+            }
+            const uint32_t x = wave_scan(len, lane);
+            if (s < S) p_off[s] = carry + x - len;
+            carry += __shfl(x, 63, 64);
+        }
+        if (lane == 0) p_off[S] = carry;
+        __syncthreads();
+        for (uint32_t i = lane; i < Cn; i += 64) { cons_pos[W.comp[i]] = (int32_t)i; cons_node[i] = W.comp[i]; }
+        // out-edges and aligned pairs
+        uint32_t ce = 0, cp = 0;
+        for (uint32_t v0 = 0; v0 < N; v0 += 64) {
+            const uint32_t v = v0 + lane;
+            uint32_t ne = 0, np = 0;
+            if (v < N) {
+                ne = g.out_n[v];
+                for (uint32_t q = g.al_h[v]; q != NONE; q = g.al_nx[q]) np += g.al_v[q] > v;
+            }
+            const uint32_t xe = wave_scan(ne, lane), xp = wave_scan(np, lane);
+            if (v < N) {
+                uint32_t k = ce + xe - ne;
+                out_off[v] = k;
+                for (uint32_t e = g.out_h[v]; e != NONE && k < E; e = g.nx_out[e], ++k) { head[k] = g.head[e]; weight[k] = g.weight[e]; }
+                k = cp + xp - np;
+                for (uint32_t q = g.al_h[v]; q != NONE; q = g.al_nx[q])
+                    if (g.al_v[q] > v && k < P) { al_a[k] = v; al_b[k] = g.al_v[q]; ++k; }
+            }
+            ce += __shfl(xe, 63, 64); cp += __shfl(xp, 63, 64);
+        }
+        if (lane == 0) out_off[N] = ce;
+        // the paths
+        if (a.graph == 2) {
+            for (uint32_t s = lane; s < S; s += 64) {
+                uint32_t k = p_off[s];
+                const uint32_t end = p_off[s + 1];
+                for (uint32_t v = W.sq_begin[s]; v != NONE && k < end;) {
+                    p_node[k++] = v;
+                    uint32_t nx = NONE;                                    // Node::Successor, graph.cpp:28-39
+                    for (uint32_t e = g.out_h[v]; e != NONE && nx == NONE; e = g.nx_out[e])
+                        for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) if (g.lb_v[c] == s) { nx = g.head[e]; break; }
+                    v = nx;
+                }
+            }
+            return;
+        }
+        for (uint32_t s = lane; s < S; s += 64) {
+            const uint32_t v = W.sq_begin[s];
+            scr[(uint64_t)s * cols + W.map[v]] = v;
+        }
+        for (uint32_t e = lane; e < E; e += 64) {
+            const uint32_t h = g.head[e];
+            const uint64_t col = W.map[h];
+            for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) scr[(uint64_t)g.lb_v[c] * cols + col] = h;
+        }
+        __syncthreads();
+        for (uint32_t s = 0; s < S; ++s) {
+            const uint32_t* row = scr + (uint64_t)s * cols;
+            const uint32_t end = p_off[s + 1];
+            uint32_t at = p_off[s];
+            for (uint32_t c0 = 0; c0 < cols; c0 += 64) {
+                const uint32_t v = c0 + lane < cols ? row[c0 + lane] : NONE;
+                const uint32_t x = wave_scan(v != NONE, lane);
+                if (v != NONE && at + x - 1 < end) p_node[at + x - 1] = v;
+                at += __shfl(x, 63, 64);
             }
         }
     }
@@ -1283,6 +1452,12 @@ bool read_knobs(Knobs& k) {
     return true;
 }
 
+// LArgs::graph of vc_poa_run_graph: 1, or 2 with VC_LARGE_GRAPH_WALK=1 (the paths by the literal walk: only to be measured)
+uint32_t graph_route() {
+    const char* v = getenv("VC_LARGE_GRAPH_WALK");
+    return v && std::atoi(v) != 0 ? 2 : 1;
+}
+
 uint64_t shrunk(uint64_t v, uint32_t s) { return std::max<uint64_t>(v >> s, 1); }
 
 // initial tables of a window or group from its sum of sequence lengths and its longest sequence.  Nodes: every node is made from
@@ -1318,6 +1493,20 @@ struct MsaStore {
     void clear() { *this = MsaStore{}; }
 } g_msa;
 
+// what vc_poa_run_graph hands out, with the same lifetime: the tables of vc_poa_graph_out
+struct GraphStore {
+    std::vector<uint32_t> n_nodes, rank_to_node, edge_head, aligned_a, aligned_b, path_member, path_node, cons_node;
+    std::vector<uint64_t> node_off, out_off, aligned_off, path_first, path_off;
+    std::vector<uint8_t> node_base, path_reversed;
+    std::vector<int32_t> node_cons_pos;
+    std::vector<int64_t> edge_weight;
+    uint64_t bytes = 0;                                // copied out of the device
+    void clear() { *this = GraphStore{}; }
+} g_graph;
+
+// a group's block of k_lg_graph<1> on the host, and the counts that lay it out
+struct GraphPart { uint32_t N = 0, E = 0, P = 0, S = 0, T = 0, Cn = 0; std::vector<uint8_t> blk; };
+
 // ------------------------------------------------------------------ the host schedule
 // One call of vc_large_run / vc_poa_run*: the batch on the device (seq_begin / seq_end only with spans), windows in flight in
 // groups that fit the arena budget, one alignment of each per lock-step step with the forward passes in launches that fit the
@@ -1341,6 +1530,10 @@ struct Run {
     std::vector<std::vector<uint32_t>> mem_of, cov_of; // ... and (msa) row members and coverage
     uint32_t msa_launches = 0;
     uint64_t n_align = 0, n_cells = 0;                 // forward passes run (VC_LARGE_LOG's "done" line)
+    GraphStore* gs = nullptr;                          // vc_poa_run_graph, else nullptr
+    std::vector<GraphPart> part;                       // ... per window: its block
+    uint32_t graph_launches = 0;
+    bool seqs() const { return msa != nullptr || gs != nullptr; }   // the windows keep sq_begin / sq_member
 };
 
 // the windows in flight together: their ids, their tables in the arena, their LWin here and on the device
@@ -1394,7 +1587,7 @@ int strand_views(Run& R, DevMem& mem) {
 void next_group(Run& R, Group& G) {
     std::vector<uint32_t> rest;
     for (uint32_t w : R.pending) {
-        const uint64_t need = layout(nullptr, nullptr, R.caps[w], R.labels, R.msa != nullptr);
+        const uint64_t need = layout(nullptr, nullptr, R.caps[w], R.labels, R.seqs());
         if (G.ids.empty() && need > R.arena_budget * 2) {                  // the device cannot hold its tables
             R.status[w] = VC_WIN_OVERFLOW;
             if (R.kn.log) std::fprintf(stderr, "vc_large: refuse window=%u bytes=%llu budget=%llu\n", w, (unsigned long long)need, (unsigned long long)R.arena_budget);
@@ -1423,7 +1616,7 @@ void place_windows(const Run& R, Group& G, uint8_t* arena) {
         const uint32_t w = G.ids[k];
         LWin& W = G.hw[k];
         W = LWin{};
-        layout(&W, arena + G.aoff[k], R.caps[w], R.labels, R.msa != nullptr);
+        layout(&W, arena + G.aoff[k], R.caps[w], R.labels, R.seqs());
         const Caps& c = R.caps[w];
         W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
         W.L = W.nseq ? (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]) : 0;     // (POA groups: unused, and may be empty)
@@ -1519,6 +1712,10 @@ bool lock_step(Run& R, Group& G) {
         hipLaunchKernelGGL(k_lg_msa<0>, dim3(n), dim3(64), 0, 0, a);
         ok = hipGetLastError() == hipSuccess;
     }
+    if (ok && R.gs) {
+        hipLaunchKernelGGL(k_lg_graph<0>, dim3(n), dim3(64), 0, 0, a);
+        ok = hipGetLastError() == hipSuccess;
+    }
     return ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(G.hw.data(), G.d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) == hipSuccess;
 }
 
@@ -1604,13 +1801,67 @@ int collect_msa(Run& R, Group& G) {
     return VC_OK;
 }
 
+// The graphs of the groups that finished, as collect_msa: a block and a scratch per group in the matrix buffer, the blocks in
+// front so that one copy takes them out and leaves the scratch behind.
+int collect_graph(Run& R, Group& G) {
+    const LArgs& a = R.a;
+    std::vector<uint32_t> fin, list;
+    std::vector<uint64_t> hoff;
+    for (uint32_t k = 0; k < G.ids.size(); ++k) if (!G.hw[k].grow && G.hw[k].status == VC_WIN_OK && R.status[G.ids[k]] == VC_WIN_OK) fin.push_back(k);
+    auto part_of = [&](uint32_t k) {
+        const LWin& W = G.hw[k];
+        const LGraph& g = W.gr[W.cur];
+        GraphPart p;
+        p.N = g.n_nodes; p.E = g.n_edges; p.P = g.n_al / 2; p.S = g.nseq; p.T = W.gr_path; p.Cn = W.cons_n;
+        return p;
+    };
+    auto block_of = [&](uint32_t k) { const GraphPart p = part_of(k); return graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn).bytes; };
+    auto scratch_of = [&](uint32_t k) { return a.graph == 1 ? graph_scratch_bytes(G.hw[k].gr[G.hw[k].cur].nseq, G.hw[k].gr_cols) : 0; };
+    auto need = [&](uint32_t k) { return block_of(k) + scratch_of(k); };
+    std::vector<uint8_t> host;
+    for (size_t k0 = 0; k0 < fin.size();) {
+        uint64_t bytes;
+        k0 = pack_launch(fin, k0, R.mat_budget, need, list, hoff, bytes);
+        const uint32_t nl = (uint32_t)list.size();
+        uint64_t blocks = 0;                                               // every block, then every scratch
+        hoff.assign(2 * (size_t)nl, 0);
+        for (uint32_t q = 0; q < nl; ++q) { hoff[q] = blocks; blocks += block_of(list[q]); }
+        uint64_t at = blocks;
+        for (uint32_t q = 0; q < nl; ++q) { hoff[nl + q] = at; at += scratch_of(list[q]); }
+        uint8_t* dout = (uint8_t*)cached(g_cache.mat, bytes);
+        if (!dout) {
+            if (nl > 1) return fail(VC_ERR_HIP, "device allocation of the graph tables failed");
+            R.status[G.ids[list[0]]] = VC_WIN_OVERFLOW; R.out[G.ids[list[0]]].clear();
+            continue;
+        }
+        LArgs f = a;
+        f.list = G.d_list; f.hoff = G.d_hoff; f.msa_out = dout;
+        bool ok = upload_launch(G, list, hoff);
+        if (ok) {
+            hipLaunchKernelGGL(k_lg_graph<1>, dim3(nl), dim3(64), 0, 0, f);
+            ok = hipGetLastError() == hipSuccess;
+            host.resize(blocks);
+            ok = ok && hipMemcpy(host.data(), dout, blocks, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        if (!ok) return fail(VC_ERR_HIP, "the graph kernel or its copy failed");
+        for (uint32_t q = 0; q < nl; ++q) {
+            GraphPart& p = R.part[G.ids[list[q]]];
+            p = part_of(list[q]);
+            p.blk.assign(host.begin() + hoff[q], host.begin() + (q + 1 < nl ? hoff[q + 1] : blocks));
+        }
+        R.gs->bytes += blocks;
+        R.graph_launches++;
+    }
+    return VC_OK;
+}
+
 // One group from its tables to its results: a window whose table filled goes back to pending, the others leave their status,
 // consensus and (msa) alignment.  A single window the device has no room for is VC_WIN_OVERFLOW; more than one is an error.
 int run_group(Run& R, Group& G) {
     const uint32_t n = (uint32_t)G.ids.size();
     uint8_t* arena = (uint8_t*)cached(g_cache.arena, G.abytes);
     DevMem mem;
-    if (!arena || !mem.alloc(&G.d_win, n) || !mem.alloc(&G.d_list, n) || !mem.alloc(&G.d_hoff, n)) {
+    if (!arena || !mem.alloc(&G.d_win, n) || !mem.alloc(&G.d_list, n) || !mem.alloc(&G.d_hoff, R.gs ? 2 * (size_t)n : n)) {
         if (n == 1) { R.status[G.ids[0]] = VC_WIN_OVERFLOW; return VC_OK; }
         return fail(VC_ERR_HIP, "device allocation of the window tables failed");
     }
@@ -1626,7 +1877,8 @@ int run_group(Run& R, Group& G) {
         if (W.cons_n && hipMemcpy(R.out[w].data(), W.cons, W.cons_n, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(VC_ERR_HIP, "copy of a consensus failed");
     }
-    return R.msa ? collect_msa(R, G) : VC_OK;
+    if (R.msa) if (const int rc = collect_msa(R, G)) return rc;
+    return R.gs ? collect_graph(R, G) : VC_OK;
 }
 
 // vc_poa_run_strand: the choices; zeros for the groups that were not computed
@@ -1663,6 +1915,39 @@ int assemble(Run& R, vc_result* r) {
         }
         if (R.kn.log) std::fprintf(stderr, "vc_large: msa launches=%u bytes=%llu\n", R.msa_launches, (unsigned long long)msa->rows.size());
     }
+    if (GraphStore* gs = R.gs) {
+        auto put = [](auto& dst, const GraphPart& p, uint64_t at, uint64_t n) {
+            using T = typename std::remove_reference_t<decltype(dst)>::value_type;
+            const T* src = (const T*)(p.blk.data() + at);
+            dst.insert(dst.end(), src, src + n);
+        };
+        gs->node_off.assign(1, 0); gs->aligned_off.assign(1, 0); gs->path_first.assign(1, 0); gs->path_off.assign(1, 0);
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            if (R.status[w] != VC_WIN_OK) R.part[w] = GraphPart{};
+            const GraphPart& p = R.part[w];
+            const GraphBlock B = graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn);
+            const uint64_t e0 = gs->edge_head.size(), t0 = gs->path_node.size();
+            gs->n_nodes.push_back(p.N);
+            if (!p.blk.empty()) {
+                put(gs->node_base, p, B.base, p.N); put(gs->node_cons_pos, p, B.cons_pos, p.N); put(gs->rank_to_node, p, B.rank, p.N);
+                put(gs->edge_head, p, B.head, p.E); put(gs->edge_weight, p, B.weight, p.E);
+                put(gs->aligned_a, p, B.al_a, p.P); put(gs->aligned_b, p, B.al_b, p.P);
+                put(gs->path_member, p, B.member, p.S); put(gs->path_reversed, p, B.rev, p.S); put(gs->path_node, p, B.p_node, p.T);
+                put(gs->cons_node, p, B.cons_node, p.Cn);
+                const uint32_t* oo = (const uint32_t*)(p.blk.data() + B.out_off);
+                for (uint32_t v = 0; v <= p.N; ++v) gs->out_off.push_back(e0 + oo[v]);
+                const uint32_t* po = (const uint32_t*)(p.blk.data() + B.p_off);
+                for (uint32_t k = 1; k <= p.S; ++k) gs->path_off.push_back(t0 + po[k]);
+            } else {
+                gs->out_off.push_back(e0);      // a group without a block has no node and no path: its one out_off entry
+            }
+            gs->node_off.push_back(gs->node_base.size());
+            gs->aligned_off.push_back(gs->aligned_a.size());
+            gs->path_first.push_back(gs->path_member.size());
+            R.part[w] = GraphPart{};
+        }
+        if (R.kn.log) std::fprintf(stderr, "vc_large: graph launches=%u bytes=%llu\n", R.graph_launches, (unsigned long long)gs->bytes);
+    }
     if (R.kn.log) std::fprintf(stderr, "vc_large: done alignments=%llu cells=%llu\n", (unsigned long long)R.n_align, (unsigned long long)R.n_cells);
     uint64_t o = 0;
     for (uint32_t w = 0; w < R.nw; ++w) {
@@ -1676,7 +1961,7 @@ int assemble(Run& R, vc_result* r) {
 }
 
 int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r,
-                MsaStore* msa = nullptr, const vc_poa_strand_out* so = nullptr) {
+                MsaStore* msa = nullptr, const vc_poa_strand_out* so = nullptr, GraphStore* gs = nullptr) {
     const uint32_t nw = b->n_windows;
     if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
     if (g_cache.device != device) { release_cache(); g_cache.device = device; }
@@ -1691,6 +1976,8 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     const uint64_t avail = free_b + g_cache.arena.bytes + g_cache.mat.bytes;
     R.arena_budget = kn.arena ? kn.arena : std::min<uint64_t>(avail / 4, 16ull << 30);
     R.mat_budget = kn.mat ? kn.mat : std::min<uint64_t>(avail / 2, 48ull << 30);
+    R.gs = gs;
+    if (gs) { gs->clear(); R.part.resize(nw); }
     R.planes = plane_count(a.gaps);
     R.ns = so ? 2 : 1;
 
@@ -1715,7 +2002,8 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
 
 // The four vc_poa_* entries after their score checks: the knobs, the batch (still without the device), the device, the run.
 // `a` holds the scores.
-int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa, const vc_poa_strand_out* so) {
+int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa, const vc_poa_strand_out* so,
+               GraphStore* gs) {
     Knobs kn;
     if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
     const uint32_t nw = b->n_windows;
@@ -1746,15 +2034,18 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
     r->cons_off[0] = 0;
     if (nw == 0) return VC_OK;
     a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)algorithm;
-    return run_windows(device, a, b, caps, msa != nullptr, false, kn, r, msa, so);
+    return run_windows(device, a, b, caps, msa != nullptr || gs != nullptr, false, kn, r, msa, so, gs);
 }
 
 // vc_poa_run_gaps, vc_poa_run_msa (o is required) and vc_poa_run_strand (so is required, o may be NULL); vc_poa_run after its
-// own checks comes in as POA_GAPS.  The arguments first, without the device, in AlignmentEngine::Create's order
-// (alignment_engine.cpp:39-57; spoa takes the scores as int8_t); then the flags, then the strand output; the batch in run_groups.
-enum PoaCall { POA_GAPS, POA_MSA, POA_STRAND };
+// own checks comes in as POA_GAPS; vc_poa_run_graph (go is required, o and so may be NULL: so chooses the strand flow).  The
+// arguments first, without the device, in AlignmentEngine::Create's order (alignment_engine.cpp:39-57; spoa takes the scores as
+// int8_t); then the flags, then the graph output, then the strand output; the batch in run_groups.
+enum PoaCall { POA_GAPS, POA_MSA, POA_STRAND, POA_GRAPH };
 
-int poa_run(PoaCall call, const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* so) {
+int poa_run(PoaCall call, const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* so,
+            vc_poa_graph_out* go = nullptr) {
+    if (go) *go = vc_poa_graph_out{};                                      // a failed call leaves every pointer NULL
     if (!p || !b || !r || (call == POA_MSA && !o) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
@@ -1764,7 +2055,8 @@ int poa_run(PoaCall call, const vc_poa_gap_params* p, const vc_batch* b, vc_resu
     const uint32_t flags = o ? o->flags : 0;
     if (flags & ~(uint32_t)(VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE)) return fail(VC_ERR_ARG, "unknown flag bits");
     if ((flags & VC_POA_MSA_CONSENSUS) && !(flags & VC_POA_MSA)) return fail(VC_ERR_ARG, "VC_POA_MSA_CONSENSUS needs VC_POA_MSA");
-    if (call == POA_STRAND && (!so || !so->reversed)) return fail(VC_ERR_ARG, "null strand output (reversed is required)");
+    if (call == POA_GRAPH && !go) return fail(VC_ERR_ARG, "null graph output");
+    if ((call == POA_STRAND && !so) || (so && !so->reversed)) return fail(VC_ERR_ARG, "null strand output (reversed is required)");
     // the subtype and its scores (alignment_engine.cpp:59-69)
     int32_t g = p->gap_open, e = p->gap_extend, q = p->gap_open2, c = p->gap_extend2;
     const uint32_t gaps = g >= e ? 0 : (g <= q || e >= c ? 1 : 2);
@@ -1773,13 +2065,31 @@ int poa_run(PoaCall call, const vc_poa_gap_params* p, const vc_batch* b, vc_resu
     LArgs a{};
     a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
     a.msa = flags;
-    a.strand = call == POA_STRAND ? 1 : 0;
+    a.strand = so ? 1 : 0;
+    a.graph = call == POA_GRAPH ? graph_route() : 0;
     if (o) { *o = vc_poa_msa_out{}; o->flags = flags; }
-    if (call != POA_GAPS) g_msa.clear();                                   // what an earlier call handed out ends here
-    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr, call == POA_STRAND ? so : nullptr);
+    if (call != POA_GAPS) { g_msa.clear(); g_graph.clear(); }              // what an earlier call handed out ends here
+    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr, so, go ? &g_graph : nullptr);
     if (rc != VC_OK) {
-        if (call != POA_GAPS) g_msa.clear();
+        if (call != POA_GAPS) { g_msa.clear(); g_graph.clear(); }
         return rc;
+    }
+    if (go) {
+        go->n_groups = b->n_windows;
+        if (b->n_windows) {
+            GraphStore& G = g_graph;
+            for (auto* v : {&G.n_nodes, &G.rank_to_node, &G.edge_head, &G.aligned_a, &G.aligned_b, &G.path_member, &G.path_node, &G.cons_node})
+                v->reserve(1);                                             // an empty table is still a pointer
+            G.node_base.reserve(1); G.path_reversed.reserve(1); G.node_cons_pos.reserve(1); G.edge_weight.reserve(1);
+            go->n_nodes = G.n_nodes.data(); go->node_off = G.node_off.data(); go->node_base = G.node_base.data();
+            go->node_cons_pos = G.node_cons_pos.data(); go->rank_to_node = G.rank_to_node.data();
+            go->out_off = G.out_off.data(); go->edge_head = G.edge_head.data(); go->edge_weight = G.edge_weight.data();
+            go->aligned_off = G.aligned_off.data(); go->aligned_a = G.aligned_a.data(); go->aligned_b = G.aligned_b.data();
+            go->path_first = G.path_first.data(); go->path_member = G.path_member.data(); go->path_reversed = G.path_reversed.data();
+            go->path_off = G.path_off.data(); go->path_node = G.path_node.data();
+            go->cons_node = G.cons_node.data();
+            go->bytes = G.bytes;
+        }
     }
     if (o) o->n_groups = b->n_windows;
     if (flags && b->n_windows) {
@@ -1797,7 +2107,7 @@ extern "C" {
 
 const char* vc_large_last_error(void) { return g_err.c_str(); }
 
-void vc_large_release(void) { release_cache(); g_msa.clear(); }
+void vc_large_release(void) { release_cache(); g_msa.clear(); g_graph.clear(); }
 
 int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
@@ -1855,6 +2165,11 @@ int vc_poa_run_msa(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, 
 
 int vc_poa_run_strand(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s) {
     return poa_run(POA_STRAND, p, b, r, o, s);
+}
+
+int vc_poa_run_graph(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s,
+                     vc_poa_graph_out* g) {
+    return poa_run(POA_GRAPH, p, b, r, o, s, g);
 }
 
 }  // extern "C"

@@ -5,13 +5,18 @@ semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chos
 (gap_model); no window rules.  No CPU path: without a device the calls raise.
 
     python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [-r 0|1|2]
-                             [--coverage] [--both-strands] [--device D] FILE [FILE ...]
+                             [--coverage] [--both-strands] [--gfa | --gfa-consensus] [--graphviz FILE] [--device D] FILE [FILE ...]
 
 prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`,
 or with -r 1 / -r 2 the multiple sequence alignment of its records as FASTA (`>name` / row, with -r 2 a last row `>Consensus`;
 spoa's src/main.cpp:326-335).  -r is given once (spoa's may be repeated).  --coverage adds the tag `CV:B:I,c1,c2,...` to the
 `-r 0` header: per consensus base the number of records through its node and the nodes aligned to it (spoa's
-GenerateConsensus(&summary, false)).  spoa's GFA output (-r 3 / -r 4) and --dot are not offered.  spoa's -s /
+GenerateConsensus(&summary, false)).  spoa's GFA output is spelt --gfa (its -r 3) and --gfa-consensus (its -r 4, with the
+consensus path) here, and its -d / --dot is spelt --graphviz FILE (the spellings -r 3, -r 4, -d and --dot stay refused): the
+partial order graph itself, from vc_poa_run_graph (poa_graph(), PoaGraph.to_gfa / to_dot), byte for byte what spoa's PrintGfa
+(src/main.cpp:120-200) and Graph::PrintDot (src/graph.cpp:746-803) write.  --gfa / --gfa-consensus replace the -r 0 output and
+exclude -r 1 / -r 2 / --coverage; --graphviz goes with every output and writes FILE for the first input file and FILE.2,
+FILE.3, ... for the others.  spoa's -s /
 --strand-ambiguous is spelt --both-strands here (those two spellings stay refused): every record is aligned as given and
 reverse-complemented, and the better strand is added, ties going forward (spoa's src/main.cpp:287-304; vc_poa_run_strand,
 poa_consensus_strands(), poa_msa(strand_ambiguous=True)).  It goes with every -r and with --coverage and changes no output
@@ -193,6 +198,24 @@ class Msa:
 CONSENSUS_ROW = capi.VC_POA_ROW_CONSENSUS
 
 
+def _msa_results(o, flags, n, cons, off, wso, rev):
+    """the Msa of every group out of a filled capi.VcPoaMsaOut (rev: the batch's strand choices, or None)"""
+    res = []
+    rows_base = C.addressof(o.rows.contents) if o.rows else 0
+    for w in range(n):
+        c0, c1 = int(off[w]), int(off[w + 1])
+        rows, members, cov = [], [], None
+        if o.n_rows and o.n_rows[w]:
+            k, rs, at, m0 = o.n_rows[w], o.row_size[w], o.row_off[w], o.member_off[w]
+            block = C.string_at(rows_base + at, k * rs)
+            rows = [block[i * rs:(i + 1) * rs] for i in range(k)]
+            members = [int(o.row_member[m0 + i]) for i in range(k)]
+        if flags & capi.VC_POA_COVERAGE:
+            cov = np.array(o.coverage[c0:c1], np.uint32) if o.coverage and c1 > c0 else np.zeros(0, np.uint32)
+        res.append(Msa(rows, members, cons[c0:c1].tobytes(), cov, rev[wso[w]:wso[w + 1]].astype(bool) if rev is not None else None))
+    return res
+
+
 def run_batch_msa(batch, params, flags, lib=None, strands=False):
     """vc_poa_run_msa (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits) on a capi.Batch -> (list of Msa, status array).
     Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error.
@@ -213,19 +236,7 @@ def run_batch_msa(batch, params, flags, lib=None, strands=False):
         name, rc = "vc_poa_run_msa", lib.vc_poa_run_msa(C.byref(params), C.byref(vb), C.byref(r), C.byref(o))
     if rc != 0:
         raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
-    res = []
-    rows_base = C.addressof(o.rows.contents) if o.rows else 0
-    for w in range(n):
-        c0, c1 = int(off[w]), int(off[w + 1])
-        rows, members, cov = [], [], None
-        if o.n_rows and o.n_rows[w]:
-            k, rs, at, m0 = o.n_rows[w], o.row_size[w], o.row_off[w], o.member_off[w]
-            block = C.string_at(rows_base + at, k * rs)
-            rows = [block[i * rs:(i + 1) * rs] for i in range(k)]
-            members = [int(o.row_member[m0 + i]) for i in range(k)]
-        if flags & capi.VC_POA_COVERAGE:
-            cov = np.array(o.coverage[c0:c1], np.uint32) if o.coverage and c1 > c0 else np.zeros(0, np.uint32)
-        res.append(Msa(rows, members, cons[c0:c1].tobytes(), cov, rev[wso[w]:wso[w + 1]].astype(bool) if strands else None))
+    res = _msa_results(o, flags, n, cons, off, wso, rev if strands else None)
     if strands:
         return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
     return res, status[:n]
@@ -265,6 +276,156 @@ def poa_msa(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, 
     return [None if w in bad else m for w, m in enumerate(res)]
 
 
+class PoaGraph:
+    """One group's partial order graph (poa_graph): numpy copies of the tables of vc_poa_graph_out (include/vechat_hip.h), with
+    the offsets local to the group.  Node ids are spoa's: 0-based, in creation order.
+      node_base (uint8), node_cons_pos (int32; k: the node is consensus base k, -1: not on the consensus), rank_to_node (uint32)
+      out_off (int64, nodes + 1), edge_head (uint32), edge_weight (int64): node v's out-edges are out_off[v] .. out_off[v + 1]
+      aligned_a, aligned_b (uint32): pairs of aligned nodes, a < b
+      path_member (uint32), path_reversed (bool), path_off (int64, paths + 1), path_node (uint32): one path per member that was
+        added -- an empty member has none --, in graph order; a reversed path belongs to a member whose reverse complement was kept
+      cons_node (uint32), consensus (bytes); msa (an Msa, with poa_graph(msa=True), else None)"""
+    __slots__ = ("node_base", "node_cons_pos", "rank_to_node", "out_off", "edge_head", "edge_weight", "aligned_a", "aligned_b",
+                 "path_member", "path_reversed", "path_off", "path_node", "cons_node", "consensus", "msa")
+
+    def __init__(self, **kw):
+        self.msa = None
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    @property
+    def n_nodes(self):
+        return int(self.node_base.size)
+
+    def edges(self):
+        """-> [(tail, head, weight)] by tail id, then by position in the tail's out-list (spoa's printing order)"""
+        tails = np.repeat(np.arange(self.n_nodes), np.diff(self.out_off))
+        return list(zip(tails.tolist(), self.edge_head.tolist(), self.edge_weight.tolist()))
+
+    def aligned_pairs(self):
+        """-> [(a, b)], a < b"""
+        return list(zip(self.aligned_a.tolist(), self.aligned_b.tolist()))
+
+    def paths(self):
+        """-> [(member, reversed, [node ids in graph order])]"""
+        po, pn = self.path_off.tolist(), self.path_node.tolist()
+        return [(int(m), bool(r), pn[po[k]:po[k + 1]]) for k, (m, r) in enumerate(zip(self.path_member, self.path_reversed))]
+
+    def to_gfa(self, names, include_consensus=False):
+        """The bytes of spoa's PrintGfa (src/main.cpp:120-200; its -r 3, or with include_consensus its -r 4).  names: the name of
+        every group member (str or bytes), empty members included.  Tab-separated; node ids are printed + 1; a weight is printed
+        as the integer it is (`ew:f:<int64>`); `ic:Z:true` marks consensus nodes and the links between two of them; a reversed
+        path is printed backwards with `-` on every node.
+        One deliberate difference: spoa indexes its headers and reversal flags by the i-th ADDED sequence, so after an empty
+        record it prints the name of the wrong record; here a path is named by its own member."""
+        on = (self.node_cons_pos >= 0).tolist()
+        base, off, head, weight = self.node_base.tolist(), self.out_off.tolist(), self.edge_head.tolist(), self.edge_weight.tolist()
+        out = [b"H\tVN:Z:1.0\n"]
+        for v in range(self.n_nodes):
+            out.append(b"S\t%d\t%c%s\n" % (v + 1, base[v], b"\tic:Z:true" if on[v] else b""))
+            for k in range(off[v], off[v + 1]):
+                out.append(b"L\t%d\t+\t%d\t+\tOM\tew:f:%d%s\n" % (v + 1, head[k] + 1, weight[k], b"\tic:Z:true" if on[v] and on[head[k]] else b""))
+        for member, rev, path in self.paths():
+            name = names[member]
+            sign = b"-" if rev else b"+"
+            out.append(b"P\t%s\t%s\t*\n" % (name.encode() if isinstance(name, str) else bytes(name),
+                                             b",".join(b"%d%s" % (v + 1, sign) for v in (path[::-1] if rev else path))))
+        if include_consensus:
+            out.append(b"P\tConsensus\t%s\t*\n" % b",".join(b"%d+" % (v + 1) for v in self.cons_node.tolist()))
+        return b"".join(out)
+
+    def to_dot(self):
+        """The bytes of spoa's Graph::PrintDot (src/graph.cpp:746-803; its -d FILE beside -r 0, i.e. after GenerateConsensus):
+        consensus nodes filled, an edge coloured where its head follows its tail on the consensus (spoa's test is
+        rank[tail] + 1 == rank[head] with -1 for a node off the consensus, kept as it is), aligned pairs dotted."""
+        pos, base = self.node_cons_pos.tolist(), self.node_base.tolist()
+        off, head, weight = self.out_off.tolist(), self.edge_head.tolist(), self.edge_weight.tolist()
+        al = {}
+        for a, b in self.aligned_pairs():
+            al.setdefault(a, []).append(b)
+        out = [b"digraph %d {\n  graph [rankdir = LR]\n" % self.path_member.size]
+        for v in range(self.n_nodes):
+            out.append(b'  %d[label = "%d - %c"%s]\n' % (v, v, base[v], b", style = filled, fillcolor = goldenrod1" if pos[v] != -1 else b""))
+            for k in range(off[v], off[v + 1]):
+                out.append(b'  %d -> %d [label = "%d"%s]\n' % (v, head[k], weight[k],
+                                                               b", color = goldenrod1" if pos[v] + 1 == pos[head[k]] else b""))
+            for b in al.get(v, ()):
+                out.append(b"  %d -> %d [style = dotted, arrowhead = none]\n" % (v, b))
+        out.append(b"}\n")
+        return b"".join(out)
+
+
+def run_batch_graph(batch, params, flags=0, lib=None, strands=False):
+    """vc_poa_run_graph (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits for the alignment beside it, 0: none) on a
+    capi.Batch -> (list of PoaGraph, status array); strands=True builds the groups with spoa's -s and also returns the forward and
+    reverse scores per group, as run_batch_msa.  PoaGraph.msa is the group's Msa (its .reversed set with strands).  Everything is
+    copied out of the library's buffers before returning.  Raises PoaError on a library error."""
+    lib = lib or capi.load_hip()
+    n = batch.n_windows
+    cons, off, status, r, vb = _result_buffers(batch)
+    o, g = capi.VcPoaMsaOut(flags=flags), capi.VcPoaGraphOut()
+    wso = [int(x) for x in batch.win_seq_off]
+    so = None
+    if strands:
+        nseq = max(wso[-1], 1)
+        rev, sc, scr = np.zeros(nseq, np.uint8), np.zeros(nseq, np.int32), np.zeros(nseq, np.int32)
+        so = C.byref(capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)), sc.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         scr.ctypes.data_as(C.POINTER(C.c_int32))))
+    rc = lib.vc_poa_run_graph(C.byref(params), C.byref(vb), C.byref(r), C.byref(o), so, C.byref(g))
+    if rc != 0:
+        raise PoaError(f"vc_poa_run_graph failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    msas = _msa_results(o, flags, n, cons, off, wso, rev if strands else None)
+
+    def table(ptr, count):
+        """a copy of a whole library-owned table (one view over it, no Python list between)"""
+        return np.ctypeslib.as_array(ptr, shape=(count,)).copy() if count else np.zeros(0, ptr._type_)
+    node_off = table(g.node_off, n + 1).astype(np.int64)
+    nn = int(node_off[-1])
+    out_off = table(g.out_off, nn + n).astype(np.int64)
+    aligned_off, path_first = table(g.aligned_off, n + 1).astype(np.int64), table(g.path_first, n + 1).astype(np.int64)
+    ne, na, npath = int(out_off[-1]) if n else 0, int(aligned_off[-1]), int(path_first[-1])
+    path_off = table(g.path_off, npath + 1).astype(np.int64)
+    node_base, node_cons_pos, rank_to_node = table(g.node_base, nn), table(g.node_cons_pos, nn), table(g.rank_to_node, nn)
+    edge_head, edge_weight = table(g.edge_head, ne), table(g.edge_weight, ne)
+    aligned_a, aligned_b = table(g.aligned_a, na), table(g.aligned_b, na)
+    path_member, path_reversed = table(g.path_member, npath), table(g.path_reversed, npath).astype(bool)
+    path_node, cons_node = table(g.path_node, int(path_off[-1])), table(g.cons_node, int(off[n]))
+    res = []
+    for w in range(n):
+        n0, n1 = int(node_off[w]), int(node_off[w + 1])
+        oo = out_off[n0 + w:n1 + w + 1]
+        e0, e1 = int(oo[0]), int(oo[-1])
+        a0, a1, p0, p1 = int(aligned_off[w]), int(aligned_off[w + 1]), int(path_first[w]), int(path_first[w + 1])
+        po = path_off[p0:p1 + 1]
+        c0, c1 = int(off[w]), int(off[w + 1])
+        res.append(PoaGraph(node_base=node_base[n0:n1].copy(), node_cons_pos=node_cons_pos[n0:n1].copy(),
+                            rank_to_node=rank_to_node[n0:n1].copy(), out_off=oo - e0,
+                            edge_head=edge_head[e0:e1].copy(), edge_weight=edge_weight[e0:e1].copy(),
+                            aligned_a=aligned_a[a0:a1].copy(), aligned_b=aligned_b[a0:a1].copy(),
+                            path_member=path_member[p0:p1].copy(), path_reversed=path_reversed[p0:p1].copy(),
+                            path_off=po - po[0], path_node=path_node[int(po[0]):int(po[-1])].copy(),
+                            cons_node=cons_node[c0:c1].copy(), consensus=cons[c0:c1].tobytes(),
+                            msa=msas[w] if flags or strands else None))
+    if strands:
+        return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
+    return res, status[:n]
+
+
+def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+              gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False):
+    """The partial order graph of every group (vc_poa_run_graph) -> list of PoaGraph: nodes, weighted edges, aligned nodes, the
+    path of every member and the consensus path, as spoa's GFA (-r 3 / -r 4) and dot (-d) output hold them; PoaGraph.to_gfa and
+    to_dot give those bytes.  Parameters, PoaError and strict as poa_consensus (a group that was not computed comes back as None
+    with strict=False); the gap scores left out are spoa's overload defaults.  strand_ambiguous=True builds the graph with spoa's
+    -s (poa_consensus_strands): a member whose reverse complement was kept has a path with reversed=True.  msa=True also asks
+    for the multiple sequence alignment of the same graph in the same call: PoaGraph.msa, as poa_msa() returns it."""
+    batch = group_batch(groups)
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous)[:2]
+    bad = _not_computed(status, strict)
+    return [None if w in bad else m for w, m in enumerate(res)]
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(
         prog="python -m vechat_amd.poa",
@@ -291,6 +452,12 @@ def parse_args(argv=None):
     ap.add_argument("--both-strands", action="store_true",
                     help="align every record as given and reverse-complemented and add the better strand (spoa's -s / "
                          "--strand-ambiguous); the output formats are unchanged")
+    ap.add_argument("--gfa", action="store_true",
+                    help="print the partial order graph as GFA instead of the consensus (spoa's -r 3); not with -r 1 / -r 2 / --coverage")
+    ap.add_argument("--gfa-consensus", action="store_true", help="--gfa with the consensus as a last path (spoa's -r 4)")
+    ap.add_argument("--graphviz", metavar="FILE", default=None,
+                    help="also write the graph in Graphviz dot format to FILE (spoa's -d); with several input files FILE is the "
+                         "first one's and FILE.2, FILE.3, ... the others'")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="+", metavar="FILE")
     return ap.parse_args(argv)
@@ -302,12 +469,30 @@ def main(argv=None):
     if a.coverage and a.r != 0:
         print("vechat_amd.poa: --coverage goes with -r 0", file=sys.stderr)
         return 1
-    msa = cons = None
+    gfa = a.gfa or a.gfa_consensus
+    if gfa and (a.r != 0 or a.coverage):
+        print("vechat_amd.poa: --gfa / --gfa-consensus do not go with -r 1 / -r 2 / --coverage", file=sys.stderr)
+        return 1
+    msa = cons = graphs = None
     try:
         records = [list(seqio.read_sequences(f)) for f in a.files]
         groups = [[(data, qual) for _, data, qual in recs] for recs in records]
         gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
-        if a.r == 0 and not a.coverage:
+        if gfa or a.graphviz is not None:
+            # one call for everything: the graph carries the consensus, and with -r 1 / -r 2 / --coverage the alignment beside it
+            flags = 0 if a.r == 0 and not a.coverage else \
+                capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if a.r == 2 else 0) | (capi.VC_POA_COVERAGE if a.coverage else 0)
+            p = _gap_params(a.l, a.m, a.n, a.g, a.device, a.gap_extend, a.gap_open2, a.gap_extend2)
+            graphs, status = run_batch_graph(group_batch(groups), p, flags, strands=a.both_strands)[:2]
+            _not_computed(status, True)
+            if flags:
+                msa = [g.msa for g in graphs]
+            elif not gfa:
+                cons = [g.consensus for g in graphs]
+            for k, g in enumerate(graphs if a.graphviz is not None else ()):
+                with open(a.graphviz if k == 0 else f"{a.graphviz}.{k + 1}", "wb") as f:
+                    f.write(g.to_dot())
+        elif a.r == 0 and not a.coverage:
             if a.both_strands:
                 cons = poa_consensus_strands(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)[0]
             else:
@@ -319,7 +504,10 @@ def main(argv=None):
         print(f"vechat_amd.poa: {e}", file=sys.stderr)
         return 1
     out = sys.stdout.buffer
-    if cons is not None:
+    if gfa:
+        for recs, g in zip(records, graphs):
+            out.write(g.to_gfa([name for name, _, _ in recs], include_consensus=a.gfa_consensus))
+    elif cons is not None:
         for c in cons:
             out.write(b">Consensus LN:i:%d\n%s\n" % (len(c), c))
     elif a.r == 0:
