@@ -39,7 +39,8 @@
  *   VC_IO_TIMING           set: phase times of the file readers on stderr (tools/gpu_files_host.sh)
  *   VC_HOSTBUF=0|1|2       host buffers: malloc / mmap + huge pages (default) / mmap; read once per process (tools/gpu_files_host.sh)
  * Read on every vc_large_run and vc_poa_run call (vc_large.hip, whose header describes them; tests/test_large_schedule.py):
- *   VC_LARGE_CAPS, VC_LARGE_ARENA_MB, VC_LARGE_MAT_MB, VC_LARGE_LOG
+ *   VC_LARGE_CAPS, VC_LARGE_ARENA_MB, VC_LARGE_MAT_MB, VC_LARGE_LOG (its lines: regrow, group, step, refuse, msa, graph, and for
+ *   vc_poa_run_align with queries "vc_large: align jobs=J launches=K cells=C bytes=B"; done), VC_LARGE_GRAPH_WALK
  */
 #ifndef VECHAT_HIP_H_
 #define VECHAT_HIP_H_
@@ -525,6 +526,49 @@ typedef struct vc_poa_graph_out {
 } vc_poa_graph_out;
 int         vc_poa_run_graph(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o /* may be NULL */,
                              vc_poa_strand_out* s /* NULL: the plain flow; else spoa's -s */, vc_poa_graph_out* g);
+
+/* Queries against finished groups: spoa's other public result, `engine->Align(sequence, graph, &score)` for a sequence that is
+ * NOT added -- the score and the (node id, position) alignment of a query against the graph of its group, for assigning reads to
+ * families by score, genotyping held-out reads, or asking which strand a read fits.
+ * p, b, r, s and g as vc_poa_run_graph (g may be NULL here: no graph tables): the groups are built exactly as that call builds
+ * them and the consensus comes back as always.  q holds the queries: q->n_windows == b->n_windows, and window w of q lists the
+ * queries of group w (it may be empty); only n_windows, win_seq_off, seq_off and bases of q are read.  Every query is aligned
+ * against the finished graph of its group with the call's engine -- the type, scores and subtype rule of the build -- and nothing
+ * is added, so a group's consensus, graph and other queries do not depend on it.  a->flags selects:
+ *     VC_POA_ALIGN_PAIRS    the alignments (pair_off, pair_node, pair_pos), not only the scores: without it no backtrack runs
+ *     VC_POA_ALIGN_STRANDS  every query as given and reverse-complemented (the byte rule of vc_poa_run_strand), the better kept:
+ *                           score >= score_rev keeps the query as given (main.cpp:297), so ties, palindromes and empty
+ *                           alignments are never reported reversed.  A query is never added, so no byte makes a round trip.
+ * Semantics, from the scalar engine (sisd_alignment_engine.cpp): an empty query, or a group with an empty graph, has an empty
+ * alignment and score 0 (VC_WIN_OK); so has a local alignment without a positive cell; where WorstCaseAlignmentScore makes spoa
+ * throw for the query's length, that query alone is VC_WIN_INVALID; a query whose matrix the device cannot hold is
+ * VC_WIN_OVERFLOW; a query of a group that is not VC_WIN_OK carries the group's status, score 0 and no pairs.
+ * Query k of the batch (queries in q's order) has pairs pair_off[k] .. pair_off[k + 1]: pair_node is the node id as in
+ * vc_poa_graph_out or -1 (the base is inserted), pair_pos the position in the query -- in the kept strand's bytes when
+ * reversed[k] -- or -1 (the node is skipped); spoa's Alignment, in sequence order.
+ * The stage runs per batch of resident groups after their build (k_lg_rows, k_lg_qfwd, k_lg_qback, k_lg_qpack in vc_large.hip):
+ * every (group, query) pair is independent, so the forward passes fill as few launches as the matrix budget allows.
+ * Lifetime: as vc_poa_msa_out -- the library owns every array of a, they stay valid until the next vc_poa_* or vc_large_* call
+ * or vc_large_release, and a failed call leaves every pointer NULL.  A call whose query batch holds no sequence runs no stage.
+ * Checked before the device, in this order: as vc_poa_run_graph with g == NULL allowed, the batch included; then a, then flag
+ * bits other than the two above; then q, its arrays and its window count against b; then the query lengths (below 65 535):
+ * VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these. */
+#define VC_POA_ALIGN_PAIRS    1u
+#define VC_POA_ALIGN_STRANDS  2u
+typedef struct vc_poa_align_out {
+    uint32_t flags;                 /* in: VC_POA_ALIGN_* bits                                                      */
+    uint64_t n_queries;             /* out: sequences of the query batch                                            */
+    const uint8_t*  status;         /* [n_queries]                                                                  */
+    const int32_t*  score;          /* [n_queries] spoa's *score: 0 where spoa does not write it                    */
+    const int32_t*  score_rev;      /* [n_queries], NULL without VC_POA_ALIGN_STRANDS                               */
+    const uint8_t*  reversed;       /* [n_queries], NULL without VC_POA_ALIGN_STRANDS                               */
+    const uint64_t* pair_off;       /* [n_queries + 1], NULL without VC_POA_ALIGN_PAIRS                             */
+    const int32_t*  pair_node;      /* spoa's Alignment: node id as in vc_poa_graph_out, or -1                      */
+    const int32_t*  pair_pos;       /* position in the query (in the kept strand's bytes when reversed), or -1      */
+    uint64_t        bytes;          /* copied out of the device for this stage                                      */
+} vc_poa_align_out;
+int         vc_poa_run_align(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_strand_out* s /* may be NULL */,
+                             vc_poa_graph_out* g /* may be NULL */, const vc_batch* q, vc_poa_align_out* a);
 
 #ifdef __cplusplus
 }

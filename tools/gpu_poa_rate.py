@@ -37,6 +37,12 @@ differs from the one of the CPU restatement tests/poa_graph_ref.py (--check grou
 --gaps affine / convex runs vc_poa_run_gaps with spoa's affine known-answer scores (5 -4 -8 -6) or its command-line defaults
 (5 -4 -8 -6 -10 -4, convex); the cells are still rows x columns (not x planes).  The reference in oracle/_ref only takes linear
 gaps, so those runs have no host comparison.
+--align [--queries-per-group 32] [--parent-lib LIB]: the query stage of vc_poa_run_align (profiles/poa_align_rate.txt).  The groups
+are built from all members but the last; the last and --queries-per-group mutated members are each group's queries.  Three calls
+of each kind after a warm-up in one process: the stage's own time is the call minus the plain call, its GCUPS the rows x length
+of the align log line over that time; then the consensus-only rate beside the parent commit's library in alternating processes,
+for every gap model of --parent-gaps (the shared row body, a template over the gap model, changes how k_lg_fwd is compiled); then one rocprofv3 --kernel-trace --stats run of its own for the shares of
+the query kernels and the cells per forward-kernel second of k_lg_qfwd beside k_lg_fwd.
 """
 import argparse
 import csv
@@ -441,8 +447,143 @@ def main_graph(a):
     return 0 if ok else 1
 
 
+def align_batches(a, batch):
+    """the groups without their last member, and per group that member plus --queries-per-group mutated members as queries"""
+    import random
+    rng = random.Random(4101)
+    groups, queries = [], []
+    for w in range(batch.n_windows):
+        seqs, quals, _, _ = batch.window(w)
+        groups.append(list(zip(seqs[:-1], quals[:-1])))
+        qs = [seqs[-1]]
+        for _ in range(a.queries_per_group):
+            s = bytearray(rng.choice(seqs[:-1]))
+            for _ in range(max(1, len(s) // 20)):                      # 5 % substitutions
+                s[rng.randrange(len(s))] = rng.choice(b"ACGT")
+            qs.append(bytes(s))
+        queries.append(qs)
+    return poa.group_batch(groups), poa.query_batch(queries)
+
+
+def timed_align(gb, qb, flags, queries=True):
+    """-> (seconds, the align log line's (jobs, launches, cells, bytes) or None) of one vc_poa_run_align (global, 5/-4/-8 linear), or
+    with queries=False of the plain vc_poa_run_gaps on the same groups"""
+    import re
+    import tempfile
+    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            status = poa.run_batch_align(gb, qb, p, flags)[1] if queries else poa.run_batch(gb, p)[1]
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read().decode()
+    if int((status != 0).sum()):
+        raise RuntimeError(f"{int((status != 0).sum())} groups not computed")
+    m = re.search(r"vc_large: align jobs=(\d+) launches=(\d+) cells=(\d+) bytes=(\d+)", err)
+    return dt, tuple(map(int, m.groups())) if m else None
+
+
+def main_align(a):
+    """The query stage beside the plain call on the same groups, in one process: its own time is the call minus the plain call;
+    then the consensus-only rate beside the parent commit's library (the shared row body changes how k_lg_fwd is compiled), as
+    --graph --parent-lib does; then one kernel trace for the shares of the query kernels beside k_lg_fwd."""
+    gb, qb = align_batches(a, synth_groups(a))
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_align_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    nq = int(qb.win_seq_off[-1])
+    emit(f"queries against finished POA groups: {a.groups} groups of {a.depth - 1} x {a.len} bp (vc_synth seed 4100; the last member of "
+         f"{a.depth} held out), {nq} queries ({1 + a.queries_per_group} per group: the held-out member and mutated members); 5/-4/-8, "
+         f"global (kNW); one MI355X; synchronous; host clock around one call; one untimed call first, then three of each kind")
+    timed_align(gb, qb, 1)
+    plain = [timed_align(gb, qb, 0, queries=False)[0] for _ in range(3)]
+    emit(f"{'plain (vc_poa_run_gaps)':40s} " + "  ".join(f"{t:.3f}" for t in plain) + " s")
+    base = sorted(plain)[1]
+    for name, flags in (("scores only", 0), ("pairs", 1), ("pairs, both strands", 3)):
+        runs = [timed_align(gb, qb, flags) for _ in range(3)]
+        stage = [max(r[0] - base, 1e-9) for r in runs]
+        jobs, launches, cells, nbytes = runs[0][1]
+        emit(f"{'vc_poa_run_align, ' + name:40s} " + "  ".join(f"{r[0]:.3f}" for r in runs) + " s; the stage (call - median plain call) " +
+             "  ".join(f"{t:.3f}" for t in stage) + f" s = " + "  ".join(f"{cells / t / 1e9:.1f}" for t in stage) +
+             f" GCUPS ({jobs} jobs, {launches} launches, {cells / 1e9:.2f} G cells, {nbytes / 1e6:.1f} MB copied out)")
+    large.release()
+    cmd = [sys.executable, os.path.abspath(__file__), "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth)]
+    # the shared row body is a template over the gap model: every model named by --parent-gaps beside the parent, two alternated
+    # processes each (a warm-up call, then three timed ones)
+    for gaps in (a.parent_gaps.split(",") if a.parent_lib else ()):
+        secs = {"parent": [], "this": []}
+        for which in ("parent", "this", "parent", "this"):
+            p = subprocess.run(cmd + ["--child", "0", "--align", "--gaps", gaps] +
+                               (["--parent-lib", os.path.abspath(a.parent_lib)] if which == "parent" else []),
+                               capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"{which} library: run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1                          # nothing more is started on the device after a failed run
+            t = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            secs[which] += t
+            emit(f"{'consensus only, ' + gaps + ', ' + ('parent commit' if which == 'parent' else 'this library'):40s} " +
+                 "  ".join(f"{a.groups / x:7.1f}" for x in t) + f" groups/s  ({'  '.join(f'{x:.3f}' for x in t)} s; a process of its own)")
+        par, cur = sorted(secs["parent"]), sorted(secs["this"])
+        med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2  # noqa: E731
+        emit(f"consensus only, {gaps} gaps, {a.depth} members: the parent's {par[0]:.3f} .. {par[-1]:.3f} s (median {med(par):.3f}), this "
+             f"library's {cur[0]:.3f} .. {cur[-1]:.3f} s (median {med(cur):.3f}): median against median {(med(cur) / med(par) - 1) * 100:+.2f} %")
+    if not a.no_trace:
+        d = os.path.join(a.trace_dir, "align")
+        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + cmd +
+                           ["--child", "1", "--align", "--queries-per-group", str(a.queries_per_group)], capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return 1
+        ms = kernel_shares(d)
+        tot = sum(ms.values())
+        info = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]
+        emit(f"kernels of one traced call with pairs (a fresh process: 64 groups first, then all), {tot / 1e3:.2f} s: " +
+             ", ".join(f"{k} {v:.1f} ms ({v / tot * 100:.1f} %)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+        fwd, qfwd = sum(v for k, v in ms.items() if k.startswith("k_lg_fwd")), sum(v for k, v in ms.items() if k.startswith("k_lg_qfwd"))
+        if fwd and qfwd:
+            emit(f"cells per forward-kernel second: the build's k_lg_fwd {info['build_cells'] / fwd / 1e6:.1f} G/s, the query stage's k_lg_qfwd "
+                 f"{info['cells'] / qfwd / 1e6:.1f} G/s (both over the traced process: the 64-group call's cells are not in the numerators)")
+    print("wrote", out)
+    return 0
+
+
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    if a.align and a.child == 0:                  # consensus only (vc_poa_run_gaps, global, --gaps), this library's or the parent's
+        batch = synth_groups(a)
+        g, e, q, c = GAPS[a.gaps] or (-8, -8, -8, -8)
+        p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=g, gap_extend=e, gap_open2=q, gap_extend2=c)
+        lib = parent_handle(a.parent_lib) if a.parent_lib else None
+        secs = []
+        for k in range(4):                        # the first call grows the buffer cache
+            t0 = time.perf_counter()
+            status = poa.run_batch(batch, p, lib)[1]
+            secs.append(time.perf_counter() - t0)
+            if int((status != 0).sum()):
+                raise RuntimeError("groups not computed")
+        print(json.dumps(dict(seconds=secs[1:])))
+        return
+    if a.align:
+        gb, qb = align_batches(a, synth_groups(a))
+        small = a.groups if a.groups <= 64 else 64
+        timed_align(gb.slice(0, small), qb.slice(0, small), 1)
+        dt, (jobs, _, cells, _) = timed_align(gb, qb, 1)
+        build_cells = timed(gb, 1, None)[4]                             # the same build once more, for its cells (k_lg_fwd runs twice)
+        print(json.dumps(dict(seconds=dt, jobs=jobs, cells=cells, build_cells=2 * build_cells)))
+        return
     if a.graph:
         batch = synth_groups(a)
         if a.child == 0:                          # consensus only, three calls after a full warm-up (the parent library's run)
@@ -507,13 +648,18 @@ def main():
     ap.add_argument("--msa", action="store_true", help="measure vc_poa_run_msa beside the consensus-only call (profiles/poa_msa_rate.txt)")
     ap.add_argument("--strand", action="store_true", help="measure vc_poa_run_strand beside the plain call (profiles/poa_strand_rate.txt)")
     ap.add_argument("--graph", action="store_true", help="measure vc_poa_run_graph beside the consensus-only call (profiles/poa_graph_rate.txt)")
-    ap.add_argument("--parent-lib", default=None, help="--graph: a libvechat_hip.so of the parent commit, for its consensus-only rate")
+    ap.add_argument("--align", action="store_true", help="measure vc_poa_run_align's query stage beside the plain call (profiles/poa_align_rate.txt)")
+    ap.add_argument("--queries-per-group", type=int, default=32, help="--align: mutated members per group beside the held-out one")
+    ap.add_argument("--parent-gaps", default="linear,affine,convex", help="--align --parent-lib: the gap models compared with the parent's library")
+    ap.add_argument("--parent-lib", default=None, help="--graph / --align: a libvechat_hip.so of the parent commit, for its consensus-only rate")
     ap.add_argument("--check", type=int, default=2, help="--graph: groups whose GFA is compared with the CPU restatement's")
     ap.add_argument("--append", action="store_true", help="--strand: keep what the output file holds and write below it")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
         return child(a)
+    if a.align:
+        return main_align(a)
     if a.graph:
         return main_graph(a)
     if a.strand:

@@ -107,6 +107,20 @@ class VcPoaGraphOut(C.Structure):
     ]
 
 
+VC_POA_ALIGN_PAIRS, VC_POA_ALIGN_STRANDS = 1, 2
+
+
+class VcPoaAlignOut(C.Structure):
+    """vc_poa_align_out: flags in, the rest out and owned by the library until its next vc_poa_* / vc_large_* call"""
+    _fields_ = [
+        ("flags", C.c_uint32), ("n_queries", C.c_uint64),
+        ("status", C.POINTER(C.c_uint8)), ("score", C.POINTER(C.c_int32)), ("score_rev", C.POINTER(C.c_int32)),
+        ("reversed", C.POINTER(C.c_uint8)),
+        ("pair_off", C.POINTER(C.c_uint64)), ("pair_node", C.POINTER(C.c_int32)), ("pair_pos", C.POINTER(C.c_int32)),
+        ("bytes", C.c_uint64),
+    ]
+
+
 class VcStats(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64), ("alignments", C.c_uint64), ("dp_rows", C.c_uint64),
@@ -378,6 +392,11 @@ def load_hip():
         lib.vc_poa_run_graph.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut),
                                          C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut)]
         lib.vc_poa_run_graph.restype = C.c_int
+        # (development: only an A/B variant library named by VECHAT_HIP_LIB may predate this entry point; poa.run_batch_align says so)
+        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_align"):
+            lib.vc_poa_run_align.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaStrandOut),
+                                             C.POINTER(VcPoaGraphOut), C.POINTER(VcBatch), C.POINTER(VcPoaAlignOut)]
+            lib.vc_poa_run_align.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

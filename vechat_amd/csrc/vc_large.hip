@@ -50,6 +50,13 @@
 //               order, <1> the rows ('-' fill, then a scatter over the edge labels), the consensus row and the coverage;
 //   k_lg_graph  vc_poa_run_graph only, one wave per finished group: <0> the counts of the group's graph tables, <1> the tables --
 //               nodes, out-edges as CSR, aligned pairs, a path per sequence, the consensus path (spoa's GFA and dot output).
+//   The query stage, vc_poa_run_align only (spoa's engine->Align(sequence, graph, &score) for sequences that are NOT added), on the
+//   finished groups while their tables are resident; every (group, query) pair is a job (LJob) and independent of the others:
+//   k_lg_rows   one lane per finished group: the graph half of k_lg_prep (graph_rows) once per group, without a next sequence;
+//   k_lg_qfwd   <GM>, a grid of (jobs of the launch, strands), one wave per job and strand: k_lg_fwd's rows (fwd_rows) on the query
+//               batch's bytes or their reverse-complement view (k_lg_views on the query batch);
+//   k_lg_qback  <GM>, one lane per job: k_lg_back's walk (back_walk) into the job's own pair area of rows + length pairs;
+//   k_lg_qpack  one wave per job: the pairs compact behind the host's prefix offsets, nodes and positions apart.
 //
 // Limits, every schedule: a sequence is shorter than 65 535 bases; beyond that only the device memory bounds a window or group,
 // and one whose tables or matrix it cannot hold at all comes back VC_WIN_OVERFLOW.  Where the reference throws (an invalid
@@ -67,8 +74,10 @@
 //                           launch; O launches hold one matrix above the budget), "vc_large: refuse window=W bytes=B budget=B",
 //                           "vc_large: msa launches=K bytes=B" (vc_poa_run_msa with flags: k_lg_msa<1> launches, bytes copied out),
 //                           "vc_large: graph launches=K bytes=B" (vc_poa_run_graph: k_lg_graph<1> launches, bytes copied out),
-//                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes run, their rows x columns
-//                           summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes).
+//                           "vc_large: align jobs=J launches=K cells=C bytes=B" (vc_poa_run_align with queries: the queries of the
+//                           groups that finished, k_lg_qfwd launches, their rows x columns with both strands counted, bytes copied out),
+//                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes of the build, their rows x
+//                           columns summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -161,6 +170,22 @@ struct LArgs {
     const uint64_t* hoff;
     int32_t* H;
     uint8_t* msa_out;
+    // vc_poa_run_align only (nullptr elsewhere): the jobs of the query stage (k_lg_qfwd / k_lg_qback: a.list holds job indices), the
+    // query batch's offsets and bytes, its reverse-complement view (VC_POA_ALIGN_STRANDS), the jobs' pair areas and the packed pairs
+    struct LJob* job;
+    const uint64_t* q_off;
+    const uint8_t *q_bases, *q_rc;
+    int32_t *q_pairs, *q_out;
+};
+
+// One query against the finished graph of its group (vc_poa_run_align): filled by the host but for the results.
+struct LJob {
+    uint32_t win, qs;                                  // the group (index among the windows in flight), the query (sequence of the query batch)
+    uint32_t rows, qlen, status;                       // graph rows, query length; VC_WIN_OK, or VC_WIN_INVALID from the backtrack
+    uint32_t max_i[2], max_j[2];                       // end cell per strand
+    int32_t score[2];                                  // spoa's *score per strand
+    uint32_t rev, npairs;                              // the strand the backtrack walked, its pairs
+    uint64_t area, pair_off;                           // pairs: first of the job's area (rows + qlen of them) in q_pairs, first in q_out
 };
 
 // ------------------------------------------------------------------ graph tables
@@ -617,7 +642,7 @@ __device__ bool prune_and_keep_largest(const LArgs& a, LWin& W) {
 }
 
 // AlignmentEngine::WorstCaseAlignmentScore (alignment_engine.cpp:101-110); e = q = c = g gives the linear engine's
-__device__ int64_t worst_case(int64_t m, int64_t gp, int64_t ge, int64_t gq, int64_t gc, int64_t i, int64_t j) {
+__host__ __device__ inline int64_t worst_case(int64_t m, int64_t gp, int64_t ge, int64_t gq, int64_t gc, int64_t i, int64_t j) {
     auto gap_score = [&](int64_t len) -> int64_t {
         if (len == 0) return 0;
         const int64_t a = gp + (len - 1) * ge, b = gq + (len - 1) * gc;
@@ -663,8 +688,8 @@ __global__ __launch_bounds__(256) void k_lg_views(LArgs a, uint32_t nseq) {
     const uint64_t y = a.seq_off[lo] + (a.seq_off[lo + 1] - 1 - x);
     const uint8_t c = complement(a.bases[x]);
     a.rc_bases[y] = c;
-    a.rv_quals[y] = a.quals[x];
-    a.rt_bases[x] = complement(c);
+    if (a.rv_quals) a.rv_quals[y] = a.quals[x];                            // (a query batch has neither: its bytes are only aligned)
+    if (a.rt_bases) a.rt_bases[x] = complement(c);
 }
 
 __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
@@ -700,6 +725,24 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     W.phase = PH_BUILD; W.j = 1; W.k = 0;
 }
 
+// The graph half of an alignment's preparation, over graph g of W: node -> rank, and per rank the row byte, the sink flag and the
+// predecessor rows (CSR of row indices, in in-edge order).  false: the topological order does not cover the graph.
+__device__ bool graph_rows(LWin& W, const LGraph& g) {
+    const uint32_t N = g.n_nodes;
+    if (g.n_rank != N) return false;                                       // the rows below read rank[0 .. N)
+    for (uint32_t r = 0; r < N; ++r) W.node_rank[g.rank[r]] = r;
+    uint32_t cnt = 0;
+    for (uint32_t r = 0; r < N; ++r) {
+        const uint32_t v = g.rank[r];
+        W.rchar[r] = (uint8_t)W.decoder[g.code[v]];
+        W.sink[r] = g.out_n[v] == 0;
+        W.poff[r] = cnt;
+        for (uint32_t e = g.in_h[v]; e != NONE; e = g.nx_in[e]) W.prank[cnt++] = W.node_rank[g.tail[e]] + 1;
+    }
+    W.poff[N] = cnt;
+    return true;
+}
+
 __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
     const uint32_t w = blockIdx.x * 64 + threadIdx.x;
     if (w >= a.n) return;
@@ -733,18 +776,17 @@ __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
     const uint32_t N = g.n_nodes, len = (uint32_t)(a.seq_off[W.qs + 1] - a.seq_off[W.qs]);
     if (N == 0 || len == 0) return;                                       // an empty alignment
     if (worst_case(W.m, W.g, W.e, W.q, W.c, (int64_t)len + 8, N) < (int64_t)KNEG) { fail_window(W, VC_WIN_INVALID); return; }
-    if (g.n_rank != N) { fail_window(W, VC_WIN_INVALID); return; }      // the rows below read rank[0 .. N)
-    for (uint32_t r = 0; r < N; ++r) W.node_rank[g.rank[r]] = r;
-    uint32_t cnt = 0;
-    for (uint32_t r = 0; r < N; ++r) {
-        const uint32_t v = g.rank[r];
-        W.rchar[r] = (uint8_t)W.decoder[g.code[v]];
-        W.sink[r] = g.out_n[v] == 0;
-        W.poff[r] = cnt;
-        for (uint32_t e = g.in_h[v]; e != NONE; e = g.nx_in[e]) W.prank[cnt++] = W.node_rank[g.tail[e]] + 1;
-    }
-    W.poff[N] = cnt;
+    if (!graph_rows(W, g)) { fail_window(W, VC_WIN_INVALID); return; }
     W.rows = N; W.qlen = len;
+}
+
+// The query stage's rows, once per finished group (vc_poa_run_align): the graph half of k_lg_prep without a next sequence.
+__global__ __launch_bounds__(64) void k_lg_rows(LArgs a) {
+    const uint32_t w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= a.n) return;
+    LWin& W = a.win[w];
+    if (W.phase != PH_DONE || W.grow || W.status != VC_WIN_OK) return;
+    (void)graph_rows(W, W.gr[W.cur]);                                      // (the host has n_rank and n_nodes: it makes no job where they differ)
 }
 
 __device__ __forceinline__ bool better(int32_t s, uint32_t i, uint32_t j, int32_t bs, uint32_t bi, uint32_t bj) {
@@ -786,14 +828,36 @@ __host__ __device__ constexpr uint32_t plane_count(uint32_t gm) { return gm == 0
 struct Mat { uint64_t w; int32_t *H, *F, *E, *O, *Q; };
 
 template <uint32_t GM>
-__device__ __forceinline__ Mat matrix_of(const LArgs& a, uint32_t slot, const LWin& W, uint32_t st) {
+__device__ __forceinline__ Mat matrix_of(const LArgs& a, uint32_t slot, uint32_t rows, uint32_t len, uint32_t st) {
     Mat M{};
-    M.w = (uint64_t)W.qlen + 1;
-    const uint64_t P = ((uint64_t)W.rows + 1) * M.w;
+    M.w = (uint64_t)len + 1;
+    const uint64_t P = ((uint64_t)rows + 1) * M.w;
     M.H = a.H + a.hoff[slot] + st * plane_count(GM) * P;
     if constexpr (GM >= 1) { M.F = M.H + P; M.E = M.F + P; }
     if constexpr (GM == 2) { M.O = M.E + P; M.Q = M.O + P; }
     return M;
+}
+
+// What a forward pass and a backtrack read of their alignment, whoever asks for it -- a step of the build (view_of, from the
+// window) or a query of vc_poa_run_align (query_view, from the job): the size, the engine, the sequence's bytes, the row tables
+// of graph_rows and rank -> node id.
+struct AlnView {
+    uint32_t rows, len, type;                          // graph rows, sequence length, 0 SW / 1 NW / 2 OV
+    int32_t m, x, g, e, q, c;
+    const uint8_t* seq;
+    const uint32_t *poff, *prank;
+    const uint8_t *rchar, *sink;
+    const uint32_t* rank;
+};
+struct EndCell { int32_t s; uint32_t i, j; };
+
+__device__ __forceinline__ AlnView view_of(const LArgs& a, const LWin& W, uint32_t st) {
+    return AlnView{W.rows, W.qlen, W.type, W.m, W.x, W.g, W.e, W.q, W.c, aligned_bases(a, W.qs, st),
+                   W.poff, W.prank, W.rchar, W.sink, W.gr[W.sub ? 1 - W.cur : W.cur].rank};
+}
+__device__ __forceinline__ AlnView query_view(const LArgs& a, const LWin& W, const LJob& J, uint32_t st) {
+    return AlnView{J.rows, J.qlen, a.algorithm, a.match, a.mismatch, a.gap, a.gap_e, a.gap_q, a.gap_c,
+                   (st ? a.q_rc : a.q_bases) + a.q_off[J.qs], W.poff, W.prank, W.rchar, W.sink, W.gr[W.cur].rank};
 }
 
 // g_align's forward pass with linear (GM 0, sisd_alignment_engine.cpp:292-367), affine (GM 1, :462-540) or convex (GM 2,
@@ -811,18 +875,17 @@ __device__ __forceinline__ Mat matrix_of(const LArgs& a, uint32_t slot, const LW
 // versa), so they are scanned a second time over the final H.
 // kOV: column 0 of a graph row is 0 instead of the vertical chain (so the horizontal move starts from 0), and every cell of a
 // sink row is an end-cell candidate, not only the last column.
+// The body is fwd_rows, shared by k_lg_fwd (a step of the build) and k_lg_qfwd (a query against a finished graph): every lane
+// of the wave calls it and every lane gets the end cell back.
 template <uint32_t GM>
-__global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
-    LWin& W = a.win[a.list[blockIdx.x]];
+__device__ __forceinline__ EndCell fwd_rows(const AlnView& W, const Mat& M) {
     const uint32_t lane = threadIdx.x;
-    const uint32_t N = W.rows, len = W.qlen;
-    const uint32_t st = blockIdx.y;                                    // the strand
-    const Mat M = matrix_of<GM>(a, blockIdx.x, W, st);
+    const uint32_t N = W.rows, len = W.len;
     const uint64_t w = M.w;
     int32_t *const H = M.H, *const F = M.F, *const E = M.E, *const O = M.O, *const Q = M.Q;
     const bool sw = W.type == 0, ov = W.type == 2;
     const int32_t m = W.m, x = W.x, gp = W.g, ge = GM == 0 ? gp : W.e, gq = W.q, gc = W.c;
-    const uint8_t* seq = aligned_bases(a, W.qs, st);
+    const uint8_t* seq = W.seq;
     auto vertical = [&](uint64_t c) -> int32_t {                       // F's term from cell c of a predecessor row
         if constexpr (GM == 0) return H[c] + gp;
         else return max(H[c] + gp, F[c] + ge);
@@ -921,7 +984,25 @@ __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
         const uint32_t oi = __shfl_xor(bi, d, 64), oj = __shfl_xor(bj, d, 64);
         if (better(os, oi, oj, bs, bi, bj)) { bs = os; bi = oi; bj = oj; }
     }
-    if (lane == 0) { W.max_i[st] = bi; W.max_j[st] = bj; W.score[st] = bs; }
+    return EndCell{bs, bi, bj};
+}
+
+template <uint32_t GM>
+__global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
+    LWin& W = a.win[a.list[blockIdx.x]];
+    const uint32_t st = blockIdx.y;                                    // the strand
+    const EndCell b = fwd_rows<GM>(view_of(a, W, st), matrix_of<GM>(a, blockIdx.x, W.rows, W.qlen, st));
+    if (threadIdx.x == 0) { W.max_i[st] = b.i; W.max_j[st] = b.j; W.score[st] = b.s; }
+}
+
+// A query of vc_poa_run_align against the finished graph of its group: the same rows on a grid of (jobs of the launch, strands),
+// the bytes from the query batch or its reverse-complement view, the result in the job.
+template <uint32_t GM>
+__global__ __launch_bounds__(64) void k_lg_qfwd(LArgs a) {
+    LJob& J = a.job[a.list[blockIdx.x]];
+    const uint32_t st = blockIdx.y;
+    const EndCell b = fwd_rows<GM>(query_view(a, a.win[J.win], J, st), matrix_of<GM>(a, blockIdx.x, J.rows, J.qlen, st));
+    if (threadIdx.x == 0) { J.max_i[st] = b.i; J.max_j[st] = b.j; J.score[st] = b.s; }
 }
 
 // g_align's backtrack, one lane per alignment, in the reference's order of candidates, literally.
@@ -931,27 +1012,20 @@ __global__ __launch_bounds__(64) void k_lg_fwd(LArgs a) {
 // O + c of a predecessor, an opening when H == H + g / + q); then horizontal (extend_left from E / Q likewise); then the inner
 // loops that emit a whole gap run.  Affine's vertical run stops on F == H + g; convex's tries the extensions over every in-edge
 // first, then the openings (prev_i = 0 when none is found).
+// The body is back_walk, shared by k_lg_back and k_lg_qback: from end cell (i, j), np pairs (node, position) into pairs[0 .. 2 cap)
+// in sequence order.  Returns 0, 1 when the pairs do not fit, 2 where no candidate matches (cannot happen on a DAG).
 template <uint32_t GM>
-__global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
-    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= n) return;
-    LWin& W = a.win[a.list[b]];
-    // the strand: spoa keeps the forward one unless the reverse complement scores higher (main.cpp:297), and walks that matrix
-    const uint32_t st = a.strand && W.score[0] < W.score[1];
-    W.rev = st;
-    const Mat M = matrix_of<GM>(a, b, W, st);
+__device__ __forceinline__ int back_walk(const AlnView& W, const Mat& M, uint32_t i, uint32_t j, int32_t* pairs, uint32_t cap, uint32_t& np) {
     const uint64_t w = M.w;
     const int32_t *const H = M.H, *const F = M.F, *const E = M.E, *const O = M.O, *const Q = M.Q;
-    const LGraph& g = W.gr[W.sub ? 1 - W.cur : W.cur];
-    const uint8_t* seq = aligned_bases(a, W.qs, st);
+    const uint32_t* rank = W.rank;
+    const uint8_t* seq = W.seq;
     const bool sw = W.type == 0, ov = W.type == 2;
     const int32_t gp = W.g, ge = W.e, gq = W.q, gc = W.c;
-    W.npairs = 0;
-    uint32_t i = W.max_i[st], j = W.max_j[st], np = 0;
-    if (i == 0 && j == 0) return;                                          // an empty alignment
+    np = 0;
     auto emit = [&](int32_t node, int32_t pos) -> bool {
-        if (np >= W.PC) { W.grow |= G_PAIRS; return false; }
-        W.pairs[2 * np] = node; W.pairs[2 * np + 1] = pos;
+        if (np >= cap) return false;
+        pairs[2 * np] = node; pairs[2 * np + 1] = pos;
         ++np;
         return true;
     };
@@ -987,14 +1061,14 @@ __global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
             else found = (left = Hij == E[c] + ge) || Hij == H[c] + gp || (left = Hij == Q[c] + gc) || Hij == H[c] + gq;
             if (found) { pi = i; pj = j - 1; }
         }
-        if (!found) { fail_window(W, VC_WIN_INVALID); return; }             // cannot happen on a DAG
-        if (!emit(i == pi ? -1 : (int32_t)g.rank[i - 1], j == pj ? -1 : (int32_t)j - 1)) return;
+        if (!found) return 2;                                              // cannot happen on a DAG
+        if (!emit(i == pi ? -1 : (int32_t)rank[i - 1], j == pj ? -1 : (int32_t)j - 1)) return 1;
         i = pi; j = pj;
         if constexpr (GM != 0) {
             if (left) {
                 for (;;) {
-                    if (j == 0) { fail_window(W, VC_WIN_INVALID); return; } // E[i][0] is kNegativeInfinity: cannot happen
-                    if (!emit(-1, (int32_t)j - 1)) return;
+                    if (j == 0) return 2;                                  // E[i][0] is kNegativeInfinity: cannot happen
+                    if (!emit(-1, (int32_t)j - 1)) return 1;
                     --j;
                     const uint64_t c = (uint64_t)i * w + j;
                     if constexpr (GM == 1) { if (E[c] + ge != E[c + 1]) break; }
@@ -1002,7 +1076,7 @@ __global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
                 }
             } else if (up) {
                 for (;;) {
-                    if (i == 0) { fail_window(W, VC_WIN_INVALID); return; } // F[0][j] is kNegativeInfinity: cannot happen
+                    if (i == 0) return 2;                                  // F[0][j] is kNegativeInfinity: cannot happen
                     const uint64_t c = (uint64_t)i * w + j;
                     const uint32_t qo = W.poff[i - 1], qe = W.poff[i];
                     bool stop;
@@ -1026,7 +1100,7 @@ __global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
                             }
                         }
                     }
-                    if (!emit((int32_t)g.rank[i - 1], -1)) return;
+                    if (!emit((int32_t)rank[i - 1], -1)) return 1;
                     i = prev;
                     if (stop || i == 0) break;
                 }
@@ -1035,11 +1109,58 @@ __global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
     }
     for (uint32_t x = 0; x < np / 2; ++x) {
         const uint32_t y = np - 1 - x;
-        const int32_t t0 = W.pairs[2 * x], t1 = W.pairs[2 * x + 1];
-        W.pairs[2 * x] = W.pairs[2 * y]; W.pairs[2 * x + 1] = W.pairs[2 * y + 1];
-        W.pairs[2 * y] = t0; W.pairs[2 * y + 1] = t1;
+        const int32_t t0 = pairs[2 * x], t1 = pairs[2 * x + 1];
+        pairs[2 * x] = pairs[2 * y]; pairs[2 * x + 1] = pairs[2 * y + 1];
+        pairs[2 * y] = t0; pairs[2 * y + 1] = t1;
     }
+    return 0;
+}
+
+template <uint32_t GM>
+__global__ __launch_bounds__(64) void k_lg_back(LArgs a, uint32_t n) {
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    LWin& W = a.win[a.list[b]];
+    // the strand: spoa keeps the forward one unless the reverse complement scores higher (main.cpp:297), and walks that matrix
+    const uint32_t st = a.strand && W.score[0] < W.score[1];
+    W.rev = st;
+    W.npairs = 0;
+    if (W.max_i[st] == 0 && W.max_j[st] == 0) return;                      // an empty alignment
+    uint32_t np;
+    const int rc = back_walk<GM>(view_of(a, W, st), matrix_of<GM>(a, b, W.rows, W.qlen, st), W.max_i[st], W.max_j[st], W.pairs, W.PC, np);
+    if (rc == 1) { W.grow |= G_PAIRS; return; }
+    if (rc == 2) { fail_window(W, VC_WIN_INVALID); return; }
     W.npairs = np;
+}
+
+// The backtrack of a query, one lane per job of the launch, into the job's own pair area: a step lowers the row, the column or
+// both, so rows + length pairs always fit.  The strand rule is the build's (ties: as given).
+template <uint32_t GM>
+__global__ __launch_bounds__(64) void k_lg_qback(LArgs a, uint32_t n) {
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    LJob& J = a.job[a.list[b]];
+    const uint32_t st = a.q_rc != nullptr && J.score[0] < J.score[1];
+    J.rev = st;
+    J.npairs = 0;
+    if (J.max_i[st] == 0 && J.max_j[st] == 0) return;                      // an empty alignment
+    uint32_t np;
+    const int rc = back_walk<GM>(query_view(a, a.win[J.win], J, st), matrix_of<GM>(a, b, J.rows, J.qlen, st), J.max_i[st], J.max_j[st],
+                                 a.q_pairs + 2 * J.area, J.rows + J.qlen, np);
+    if (rc) { J.status = VC_WIN_INVALID; return; }
+    J.npairs = np;
+}
+
+// The pairs of every job, compact: one wave per job reads its area (node, position interleaved) eight bytes per lane and writes
+// a.q_out[pair_off ..) (nodes) and a.q_out[total + pair_off ..) (positions), consecutive lanes to consecutive words.
+__global__ __launch_bounds__(64) void k_lg_qpack(LArgs a, uint64_t total) {
+    const LJob& J = a.job[blockIdx.x];
+    const int2* src = (const int2*)(a.q_pairs + 2 * J.area);
+    int32_t *node = a.q_out + J.pair_off, *pos = a.q_out + total + J.pair_off;
+    for (uint32_t k = threadIdx.x; k < J.npairs; k += 64) {
+        const int2 p = src[k];
+        node[k] = p.x; pos[k] = p.y;
+    }
 }
 
 __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
@@ -1504,6 +1625,27 @@ struct GraphStore {
     void clear() { *this = GraphStore{}; }
 } g_graph;
 
+// what vc_poa_run_align hands out, with the same lifetime: the arrays of vc_poa_align_out, one entry per query of the batch
+struct AlignStore {
+    std::vector<uint8_t> status, reversed;
+    std::vector<int32_t> score, score_rev, pair_node, pair_pos;
+    std::vector<uint64_t> pair_off;
+    uint64_t bytes = 0;                                // copied out of the device
+    void clear() { *this = AlignStore{}; }
+} g_align;
+
+// The query stage of one vc_poa_run_align call: the query batch, the flags, and what the stages of the host groups leave -- per
+// stage the packed pairs (every node, then every position), per query where its pairs lie -- until assemble puts them in order.
+struct AlignReq {
+    const vc_batch* q = nullptr;
+    uint32_t flags = 0;
+    uint64_t nq = 0, nbytes = 0;                       // sequences and bytes of the query batch
+    std::vector<std::vector<int32_t>> part;
+    std::vector<uint32_t> part_of, count;              // [nq]
+    std::vector<uint64_t> first;                       // [nq]
+    uint64_t jobs = 0, launches = 0, cells = 0;        // VC_LARGE_LOG's "align" line
+};
+
 // a group's block of k_lg_graph<1> on the host, and the counts that lay it out
 struct GraphPart { uint32_t N = 0, E = 0, P = 0, S = 0, T = 0, Cn = 0; std::vector<uint8_t> blk; };
 
@@ -1533,6 +1675,7 @@ struct Run {
     GraphStore* gs = nullptr;                          // vc_poa_run_graph, else nullptr
     std::vector<GraphPart> part;                       // ... per window: its block
     uint32_t graph_launches = 0;
+    AlignReq* al = nullptr;                            // vc_poa_run_align with queries, else nullptr
     bool seqs() const { return msa != nullptr || gs != nullptr; }   // the windows keep sq_begin / sq_member
 };
 
@@ -1580,6 +1723,25 @@ int strand_views(Run& R, DevMem& mem) {
         ok = hipGetLastError() == hipSuccess;
     }
     return ok ? VC_OK : fail(VC_ERR_HIP, "device allocation or launch of the strand views failed");
+}
+
+// vc_poa_run_align: the query batch on the device -- offsets and bytes, and with VC_POA_ALIGN_STRANDS its reverse-complement
+// view (k_lg_views on the query batch's arrays: no quality, no round trip) -- once per call
+int upload_queries(Run& R, DevMem& mem) {
+    AlignReq& A = *R.al;
+    uint64_t* d_off = nullptr;
+    uint8_t *d_b = nullptr, *d_rc = nullptr;
+    const bool strands = (A.flags & VC_POA_ALIGN_STRANDS) != 0;
+    bool ok = mem.alloc(&d_off, A.nq + 1, A.q->seq_off) && mem.alloc(&d_b, A.nbytes, A.q->bases) && (!strands || mem.alloc(&d_rc, A.nbytes));
+    if (ok && strands && A.nbytes) {
+        LArgs v{};
+        v.seq_off = d_off; v.bases = d_b; v.rc_bases = d_rc; v.nbytes = A.nbytes;
+        hipLaunchKernelGGL(k_lg_views, dim3((uint32_t)((A.nbytes + 255) / 256)), dim3(256), 0, 0, v, (uint32_t)A.nq);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (!ok) return fail(VC_ERR_HIP, "device allocation, copy or strand view of the query batch failed");
+    R.a.q_off = d_off; R.a.q_bases = d_b; R.a.q_rc = d_rc;
+    return VC_OK;
 }
 
 // The windows in flight next: as many of the pending ones as the arena budget holds, in order (at least one; a window the device
@@ -1855,6 +2017,117 @@ int collect_graph(Run& R, Group& G) {
     return VC_OK;
 }
 
+template <uint32_t GM>
+void launch_query(const LArgs& f, uint32_t nl, uint32_t ns, bool pairs) {
+    hipLaunchKernelGGL(k_lg_qfwd<GM>, dim3(nl, ns), dim3(64), 0, 0, f);
+    if (pairs) hipLaunchKernelGGL(k_lg_qback<GM>, dim3((nl + 63) / 64), dim3(64), 0, 0, f, nl);
+}
+
+// The query stage of the groups that finished, while their tables are resident (vc_poa_run_align): a job per query, the rows of
+// every finished graph once (k_lg_rows), the jobs' forward passes (and, with VC_POA_ALIGN_PAIRS, backtracks) in launches that fit
+// the matrix budget -- every (group, query) pair is independent, so a launch holds as many as fit --, the job table back in one
+// copy, then the pairs packed behind the host's prefix offsets and out in one copy.
+int collect_align(Run& R, Group& G) {
+    AlignReq& A = *R.al;
+    const LArgs& a = R.a;
+    const vc_batch* q = A.q;
+    const bool pairs = (A.flags & VC_POA_ALIGN_PAIRS) != 0;
+    const uint32_t ns = (A.flags & VC_POA_ALIGN_STRANDS) ? 2 : 1;
+    std::vector<LJob> jobs;
+    std::vector<uint32_t> act, refused;                                    // jobs with a forward pass; jobs whose matrix the device cannot hold
+    uint64_t area = 0;
+    for (uint32_t k = 0; k < G.ids.size(); ++k) {
+        const LWin& W = G.hw[k];
+        const uint32_t w = G.ids[k];
+        if (W.grow || W.status != VC_WIN_OK || R.status[w] != VC_WIN_OK) continue;
+        const LGraph& g = W.gr[W.cur];
+        const uint32_t N = g.n_nodes;
+        for (uint32_t s = q->win_seq_off[w]; s < q->win_seq_off[w + 1]; ++s) {
+            LJob J{};
+            J.win = k; J.qs = s; J.qlen = (uint32_t)(q->seq_off[s + 1] - q->seq_off[s]); J.status = VC_WIN_OK;
+            if (N != 0 && J.qlen != 0) {                                   // else an empty alignment, score 0
+                // the floor of k_lg_prep, and its check of the topological order
+                if (worst_case(a.match, a.gap, a.gap_e, a.gap_q, a.gap_c, (int64_t)J.qlen + 8, N) < (int64_t)KNEG || g.n_rank != N) {
+                    J.status = VC_WIN_INVALID;
+                } else {
+                    J.rows = N; J.area = area;
+                    if (pairs) area += (uint64_t)N + J.qlen;
+                    act.push_back((uint32_t)jobs.size());
+                }
+            }
+            jobs.push_back(J);
+        }
+    }
+    if (jobs.empty()) return VC_OK;
+    A.jobs += jobs.size();
+    uint64_t total = 0;
+    std::vector<int32_t> packed;
+    if (!act.empty()) {
+        DevMem mem;
+        LJob* d_job = nullptr; uint32_t* d_list = nullptr; uint64_t* d_hoff = nullptr; int32_t *d_pairs = nullptr, *d_out = nullptr;
+        if (!mem.alloc(&d_job, jobs.size(), jobs.data()) || !mem.alloc(&d_list, act.size()) || !mem.alloc(&d_hoff, act.size()) ||
+            (pairs && !mem.alloc(&d_pairs, 2 * area)))
+            return fail(VC_ERR_HIP, "device allocation of the query jobs failed");
+        const uint32_t n = (uint32_t)G.ids.size();
+        hipLaunchKernelGGL(k_lg_rows, dim3((n + 63) / 64), dim3(64), 0, 0, a);
+        if (hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "the query stage's row kernel failed");
+        std::vector<uint32_t> list;
+        std::vector<uint64_t> hoff;
+        auto matrix_cells = [&](uint32_t j) { return ((uint64_t)jobs[j].rows + 1) * ((uint64_t)jobs[j].qlen + 1) * R.planes * ns; };
+        for (size_t k0 = 0; k0 < act.size();) {
+            uint64_t cells;
+            k0 = pack_launch(act, k0, R.mat_budget / 4, matrix_cells, list, hoff, cells);
+            int32_t* H = (int32_t*)cached(g_cache.mat, cells * 4);
+            if (!H) {
+                if (list.size() > 1) return fail(VC_ERR_HIP, "device allocation of the query matrices failed");
+                refused.push_back(list[0]);
+                continue;
+            }
+            const uint32_t nl = (uint32_t)list.size();
+            if (hipMemcpy(d_list, list.data(), nl * 4ull, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_hoff, hoff.data(), nl * 8ull, hipMemcpyHostToDevice) != hipSuccess)
+                return fail(VC_ERR_HIP, "copy of a query launch failed");
+            LArgs f = a;
+            f.job = d_job; f.q_pairs = d_pairs; f.list = d_list; f.hoff = d_hoff; f.H = H;
+            if (f.gaps == 0) launch_query<0>(f, nl, ns, pairs);
+            else if (f.gaps == 1) launch_query<1>(f, nl, ns, pairs);
+            else launch_query<2>(f, nl, ns, pairs);
+            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, "a query kernel failed");
+            for (const uint32_t j : list) A.cells += (uint64_t)jobs[j].rows * jobs[j].qlen * ns;
+            A.launches++;
+        }
+        if (hipMemcpy(jobs.data(), d_job, jobs.size() * sizeof(LJob), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(VC_ERR_HIP, "copy of the query jobs failed");
+        g_align.bytes += jobs.size() * sizeof(LJob);
+        for (LJob& J : jobs) { J.pair_off = total; total += J.npairs; }
+        if (total) {
+            packed.resize(2 * total);
+            LArgs f = a;
+            f.job = d_job; f.q_pairs = d_pairs;
+            bool ok = mem.alloc(&d_out, 2 * total) && hipMemcpy(d_job, jobs.data(), jobs.size() * sizeof(LJob), hipMemcpyHostToDevice) == hipSuccess;
+            if (ok) {
+                f.q_out = d_out;
+                hipLaunchKernelGGL(k_lg_qpack, dim3((uint32_t)jobs.size()), dim3(64), 0, 0, f, total);
+                ok = hipGetLastError() == hipSuccess && hipMemcpy(packed.data(), d_out, 8 * total, hipMemcpyDeviceToHost) == hipSuccess;
+            }
+            if (!ok) return fail(VC_ERR_HIP, "the pack kernel of the query stage or its copy failed");
+            g_align.bytes += 8 * total;
+        }
+    }
+    for (const uint32_t j : refused) jobs[j].status = VC_WIN_OVERFLOW;
+    AlignStore& S = g_align;
+    const uint32_t pi = (uint32_t)A.part.size();
+    for (const LJob& J : jobs) {
+        const bool ok = J.status == VC_WIN_OK;
+        S.status[J.qs] = (uint8_t)J.status;
+        S.score[J.qs] = ok ? J.score[0] : 0;
+        if (ns == 2) { S.score_rev[J.qs] = ok ? J.score[1] : 0; S.reversed[J.qs] = ok && J.score[0] < J.score[1]; }
+        A.part_of[J.qs] = pi; A.first[J.qs] = J.pair_off; A.count[J.qs] = ok ? J.npairs : 0;
+    }
+    A.part.push_back(std::move(packed));
+    return VC_OK;
+}
+
 // One group from its tables to its results: a window whose table filled goes back to pending, the others leave their status,
 // consensus and (msa) alignment.  A single window the device has no room for is VC_WIN_OVERFLOW; more than one is an error.
 int run_group(Run& R, Group& G) {
@@ -1878,7 +2151,8 @@ int run_group(Run& R, Group& G) {
             return fail(VC_ERR_HIP, "copy of a consensus failed");
     }
     if (R.msa) if (const int rc = collect_msa(R, G)) return rc;
-    return R.gs ? collect_graph(R, G) : VC_OK;
+    if (R.gs) if (const int rc = collect_graph(R, G)) return rc;
+    return R.al ? collect_align(R, G) : VC_OK;
 }
 
 // vc_poa_run_strand: the choices; zeros for the groups that were not computed
@@ -1948,6 +2222,31 @@ int assemble(Run& R, vc_result* r) {
         }
         if (R.kn.log) std::fprintf(stderr, "vc_large: graph launches=%u bytes=%llu\n", R.graph_launches, (unsigned long long)gs->bytes);
     }
+    if (AlignReq* A = R.al) {                                              // the queries in batch order; a group that was not computed passes its status on
+        AlignStore& S = g_align;
+        const bool pairs = (A->flags & VC_POA_ALIGN_PAIRS) != 0;
+        if (pairs) S.pair_off.assign(A->nq + 1, 0);
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            for (uint32_t s = A->q->win_seq_off[w]; s < A->q->win_seq_off[w + 1]; ++s) {
+                if (R.status[w] != VC_WIN_OK) {
+                    S.status[s] = R.status[w]; S.score[s] = 0; A->count[s] = 0;
+                    if (!S.score_rev.empty()) { S.score_rev[s] = 0; S.reversed[s] = 0; }
+                }
+                if (!pairs) continue;
+                if (A->count[s]) {
+                    const std::vector<int32_t>& part = A->part[A->part_of[s]];
+                    const int32_t* node = part.data() + A->first[s];
+                    const int32_t* pos = node + part.size() / 2;
+                    S.pair_node.insert(S.pair_node.end(), node, node + A->count[s]);
+                    S.pair_pos.insert(S.pair_pos.end(), pos, pos + A->count[s]);
+                }
+                S.pair_off[s + 1] = S.pair_node.size();
+            }
+        }
+        A->part.clear();
+        if (R.kn.log) std::fprintf(stderr, "vc_large: align jobs=%llu launches=%llu cells=%llu bytes=%llu\n", (unsigned long long)A->jobs,
+                                   (unsigned long long)A->launches, (unsigned long long)A->cells, (unsigned long long)S.bytes);
+    }
     if (R.kn.log) std::fprintf(stderr, "vc_large: done alignments=%llu cells=%llu\n", (unsigned long long)R.n_align, (unsigned long long)R.n_cells);
     uint64_t o = 0;
     for (uint32_t w = 0; w < R.nw; ++w) {
@@ -1961,7 +2260,7 @@ int assemble(Run& R, vc_result* r) {
 }
 
 int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<Caps>& caps, bool labels, bool spans, const Knobs& kn, vc_result* r,
-                MsaStore* msa = nullptr, const vc_poa_strand_out* so = nullptr, GraphStore* gs = nullptr) {
+                MsaStore* msa = nullptr, const vc_poa_strand_out* so = nullptr, GraphStore* gs = nullptr, AlignReq* al = nullptr) {
     const uint32_t nw = b->n_windows;
     if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
     if (g_cache.device != device) { release_cache(); g_cache.device = device; }
@@ -1969,6 +2268,13 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     DevMem mem;                                                            // the batch and the strand views: held until the call ends
     if (const int rc = upload_batch(R, mem, spans)) return rc;
     if (so) if (const int rc = strand_views(R, mem)) return rc;
+    if (al && al->nq) {                                                    // (a call without a query is the call without the stage)
+        R.al = al;
+        if (const int rc = upload_queries(R, mem)) return rc;
+        g_align.status.assign(al->nq, VC_WIN_OVERFLOW); g_align.score.assign(al->nq, 0);
+        if (al->flags & VC_POA_ALIGN_STRANDS) { g_align.score_rev.assign(al->nq, 0); g_align.reversed.assign(al->nq, 0); }
+        al->part_of.assign(al->nq, 0); al->count.assign(al->nq, 0); al->first.assign(al->nq, 0);
+    }
 
     // budgets from free device memory (what this library keeps cached counts as free)
     size_t free_b = 0, total_b = 0;
@@ -2000,10 +2306,35 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     return assemble(R, r);
 }
 
+// vc_poa_run_align's own arguments, after the batch and before the device: the output and its flags, the query batch and its
+// count against the groups, the query lengths
+int check_queries(AlignReq& A, const vc_poa_align_out* out, const vc_batch* b) {
+    if (!out) return fail(VC_ERR_ARG, "null align output");
+    if (A.flags & ~(uint32_t)(VC_POA_ALIGN_PAIRS | VC_POA_ALIGN_STRANDS)) return fail(VC_ERR_ARG, "unknown align flag bits");
+    const vc_batch* q = A.q;
+    if (!q) return fail(VC_ERR_ARG, "null query batch");
+    if (q->n_windows != b->n_windows) return fail(VC_ERR_ARG, "the query batch needs one window per group");
+    const uint32_t nw = q->n_windows;
+    if (nw == 0) return VC_OK;
+    if (!q->win_seq_off || !q->seq_off) return fail(VC_ERR_ARG, "null array in the query batch");
+    if (q->win_seq_off[0] != 0) return fail(VC_ERR_ARG, "win_seq_off[0] of the query batch must be 0");
+    for (uint32_t w = 0; w < nw; ++w)
+        if (q->win_seq_off[w + 1] < q->win_seq_off[w]) return fail(VC_ERR_ARG, "win_seq_off of the query batch decreases");
+    const uint32_t nq = q->win_seq_off[nw];
+    if (q->seq_off[0] != 0) return fail(VC_ERR_ARG, "seq_off[0] of the query batch must be 0");
+    for (uint32_t s = 0; s < nq; ++s)
+        if (q->seq_off[s + 1] < q->seq_off[s]) return fail(VC_ERR_ARG, "seq_off of the query batch decreases");
+    if (q->seq_off[nq] && !q->bases) return fail(VC_ERR_ARG, "null bases in the query batch");
+    for (uint32_t s = 0; s < nq; ++s)
+        if (q->seq_off[s + 1] - q->seq_off[s] >= 65535) return fail(VC_ERR_ARG, "query length unsupported (at most 65 534 bases)");
+    A.nq = nq; A.nbytes = q->seq_off[nq];
+    return VC_OK;
+}
+
 // The four vc_poa_* entries after their score checks: the knobs, the batch (still without the device), the device, the run.
 // `a` holds the scores.
 int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, MsaStore* msa, const vc_poa_strand_out* so,
-               GraphStore* gs) {
+               GraphStore* gs, AlignReq* al = nullptr, const vc_poa_align_out* ao = nullptr) {
     Knobs kn;
     if (!read_knobs(kn)) return fail(VC_ERR_ARG, "VC_LARGE_CAPS: expected entries like n:4 (tables n, e, a, l, s, p; shift 0..40)");
     const uint32_t nw = b->n_windows;
@@ -2030,22 +2361,26 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
             caps[w] = initial_caps(b->seq_off[s1] - b->seq_off[s0], mx, s1 - s0, kn);
         }
     }
+    if (al) if (const int rc = check_queries(*al, ao, b)) return rc;
     if (const int rc = check_device(device)) return rc;
     r->cons_off[0] = 0;
     if (nw == 0) return VC_OK;
     a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)algorithm;
-    return run_windows(device, a, b, caps, msa != nullptr || gs != nullptr, false, kn, r, msa, so, gs);
+    return run_windows(device, a, b, caps, msa != nullptr || gs != nullptr, false, kn, r, msa, so, gs, al);
 }
 
 // vc_poa_run_gaps, vc_poa_run_msa (o is required) and vc_poa_run_strand (so is required, o may be NULL); vc_poa_run after its
 // own checks comes in as POA_GAPS; vc_poa_run_graph (go is required, o and so may be NULL: so chooses the strand flow).  The
 // arguments first, without the device, in AlignmentEngine::Create's order (alignment_engine.cpp:39-57; spoa takes the scores as
 // int8_t); then the flags, then the graph output, then the strand output; the batch in run_groups.
-enum PoaCall { POA_GAPS, POA_MSA, POA_STRAND, POA_GRAPH };
+enum PoaCall { POA_GAPS, POA_MSA, POA_STRAND, POA_GRAPH, POA_ALIGN };
 
 int poa_run(PoaCall call, const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* so,
-            vc_poa_graph_out* go = nullptr) {
+            vc_poa_graph_out* go = nullptr, const vc_batch* qb = nullptr, vc_poa_align_out* ao = nullptr) {
     if (go) *go = vc_poa_graph_out{};                                      // a failed call leaves every pointer NULL
+    AlignReq al;
+    if (ao) { al.flags = ao->flags; *ao = vc_poa_align_out{}; ao->flags = al.flags; }
+    al.q = qb;
     if (!p || !b || !r || (call == POA_MSA && !o) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
@@ -2066,13 +2401,27 @@ int poa_run(PoaCall call, const vc_poa_gap_params* p, const vc_batch* b, vc_resu
     a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = q; a.gap_c = c; a.gaps = gaps;
     a.msa = flags;
     a.strand = so ? 1 : 0;
-    a.graph = call == POA_GRAPH ? graph_route() : 0;
+    a.graph = go ? graph_route() : 0;                                      // (vc_poa_run_align may ask for the tables too)
     if (o) { *o = vc_poa_msa_out{}; o->flags = flags; }
-    if (call != POA_GAPS) { g_msa.clear(); g_graph.clear(); }              // what an earlier call handed out ends here
-    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr, so, go ? &g_graph : nullptr);
+    if (call != POA_GAPS) { g_msa.clear(); g_graph.clear(); g_align.clear(); }   // what an earlier call handed out ends here
+    const int rc = run_groups(p->device, p->algorithm, a, b, r, flags ? &g_msa : nullptr, so, go ? &g_graph : nullptr,
+                              call == POA_ALIGN ? &al : nullptr, ao);
     if (rc != VC_OK) {
-        if (call != POA_GAPS) { g_msa.clear(); g_graph.clear(); }
+        if (call != POA_GAPS) { g_msa.clear(); g_graph.clear(); g_align.clear(); }
         return rc;
+    }
+    if (call == POA_ALIGN) {
+        AlignStore& S = g_align;
+        ao->n_queries = al.nq;
+        if (al.nq == 0) {                                                  // no stage ran: the empty tables
+            S.status.clear(); S.score.clear();
+            if (al.flags & VC_POA_ALIGN_PAIRS) S.pair_off.assign(1, 0);
+        }
+        S.status.reserve(1); S.score.reserve(1); S.score_rev.reserve(1); S.reversed.reserve(1); S.pair_node.reserve(1); S.pair_pos.reserve(1);
+        ao->status = S.status.data(); ao->score = S.score.data();
+        if (al.flags & VC_POA_ALIGN_STRANDS) { ao->score_rev = S.score_rev.data(); ao->reversed = S.reversed.data(); }
+        if (al.flags & VC_POA_ALIGN_PAIRS) { ao->pair_off = S.pair_off.data(); ao->pair_node = S.pair_node.data(); ao->pair_pos = S.pair_pos.data(); }
+        ao->bytes = S.bytes;
     }
     if (go) {
         go->n_groups = b->n_windows;
@@ -2107,7 +2456,7 @@ extern "C" {
 
 const char* vc_large_last_error(void) { return g_err.c_str(); }
 
-void vc_large_release(void) { release_cache(); g_msa.clear(); g_graph.clear(); }
+void vc_large_release(void) { release_cache(); g_msa.clear(); g_graph.clear(); g_align.clear(); }
 
 int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
@@ -2170,6 +2519,11 @@ int vc_poa_run_strand(const vc_poa_gap_params* p, const vc_batch* b, vc_result* 
 int vc_poa_run_graph(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s,
                      vc_poa_graph_out* g) {
     return poa_run(POA_GRAPH, p, b, r, o, s, g);
+}
+
+int vc_poa_run_align(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_strand_out* s, vc_poa_graph_out* g,
+                     const vc_batch* q, vc_poa_align_out* a) {
+    return poa_run(POA_ALIGN, p, b, r, nullptr, s, g, q, a);
 }
 
 }  // extern "C"

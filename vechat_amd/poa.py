@@ -5,7 +5,8 @@ semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chos
 (gap_model); no window rules.  No CPU path: without a device the calls raise.
 
     python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [-r 0|1|2]
-                             [--coverage] [--both-strands] [--gfa | --gfa-consensus] [--graphviz FILE] [--device D] FILE [FILE ...]
+                             [--coverage] [--both-strands] [--gfa | --gfa-consensus] [--graphviz FILE]
+                             [--align QUERIES --align-out FILE [--align-both-strands]] [--device D] FILE [FILE ...]
 
 prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`,
 or with -r 1 / -r 2 the multiple sequence alignment of its records as FASTA (`>name` / row, with -r 2 a last row `>Consensus`;
@@ -22,6 +23,9 @@ reverse-complemented, and the better strand is added, ties going forward (spoa's
 poa_consensus_strands(), poa_msa(strand_ambiguous=True)).  It goes with every -r and with --coverage and changes no output
 format: spoa prints nothing about strands there either, and a row shows the bytes that were kept.
 poa_msa() is the same over groups in memory (vc_poa_run_msa).
+--align QUERIES --align-out FILE aligns every record of QUERIES against the finished graph of every input file without adding it
+(spoa's engine->Align(sequence, graph, &score); vc_poa_run_align, poa_align()) and writes FILE (align_tsv); the output on stdout
+is unchanged, and with the consensus or the graph as that output the groups are built once, in the same call.  --align-both-strands tries every query on both strands and reports the better, ties as given.
 The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
 as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
 non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
@@ -375,10 +379,20 @@ def run_batch_graph(batch, params, flags=0, lib=None, strands=False):
     if rc != 0:
         raise PoaError(f"vc_poa_run_graph failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     msas = _msa_results(o, flags, n, cons, off, wso, rev if strands else None)
+    res = _graph_results(g, n, cons, off, msas if flags or strands else None)
+    if strands:
+        return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
+    return res, status[:n]
 
-    def table(ptr, count):
-        """a copy of a whole library-owned table (one view over it, no Python list between)"""
-        return np.ctypeslib.as_array(ptr, shape=(count,)).copy() if count else np.zeros(0, ptr._type_)
+
+def _table(ptr, count):
+    """a copy of a whole library-owned table (one view over it, no Python list between)"""
+    return np.ctypeslib.as_array(ptr, shape=(count,)).copy() if count else np.zeros(0, ptr._type_)
+
+
+def _graph_results(g, n, cons, off, msas=None):
+    """the PoaGraph of every group out of a filled capi.VcPoaGraphOut (msas: the Msa of every group, or None)"""
+    table = _table
     node_off = table(g.node_off, n + 1).astype(np.int64)
     nn = int(node_off[-1])
     out_off = table(g.out_off, nn + n).astype(np.int64)
@@ -405,10 +419,8 @@ def run_batch_graph(batch, params, flags=0, lib=None, strands=False):
                             path_member=path_member[p0:p1].copy(), path_reversed=path_reversed[p0:p1].copy(),
                             path_off=po - po[0], path_node=path_node[int(po[0]):int(po[-1])].copy(),
                             cons_node=cons_node[c0:c1].copy(), consensus=cons[c0:c1].tobytes(),
-                            msa=msas[w] if flags or strands else None))
-    if strands:
-        return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
-    return res, status[:n]
+                            msa=msas[w] if msas is not None else None))
+    return res
 
 
 def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
@@ -424,6 +436,104 @@ def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0
     res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous)[:2]
     bad = _not_computed(status, strict)
     return [None if w in bad else m for w, m in enumerate(res)]
+
+
+class QueryAlignment:
+    """One query's result of poa_align: score and score_rev (spoa's *score as given and reverse-complemented; score_rev is None
+    without both_strands), reversed (True: the reverse complement was kept, and positions count in its bytes), status
+    (capi.VC_WIN_*) and pairs: an (n, 2) int32 array of (node id or -1, position or -1), spoa's Alignment, or None without pairs=."""
+    __slots__ = ("score", "score_rev", "reversed", "status", "pairs")
+
+    def __init__(self, score, score_rev, reversed, status, pairs):
+        self.score, self.score_rev, self.reversed, self.status, self.pairs = score, score_rev, reversed, status, pairs
+
+    def __iter__(self):
+        return iter((self.score, self.score_rev, self.reversed, self.status, self.pairs))
+
+
+def query_batch(queries):
+    """queries (one list of sequences per group) -> capi.Batch of which vc_poa_run_align reads win_seq_off, seq_off and bases"""
+    return group_batch([[_bytes(s, "query") for s in qs] for qs in queries])
+
+
+def run_batch_align(batch, qbatch, params, flags=capi.VC_POA_ALIGN_PAIRS, lib=None, strands=False, graph=False):
+    """vc_poa_run_align (params: capi.VcPoaGapParams; flags: capi.VC_POA_ALIGN_* bits) on a capi.Batch of groups and one of
+    queries, window w of qbatch being the queries of group w -> (consensus bytes per group, status array, per group the list of
+    QueryAlignment, list of PoaGraph or None).  strands=True builds the groups with spoa's -s; graph=True also asks for the
+    graph tables of the same call.  Everything is copied out of the library's buffers before returning.  Raises PoaError on a
+    library error."""
+    lib = lib or capi.load_hip()
+    if not hasattr(lib, "vc_poa_run_align"):
+        raise PoaError("this libvechat_hip.so has no vc_poa_run_align: it was built before the entry point existed; rebuild it")
+    n = batch.n_windows
+    cons, off, status, r, vb = _result_buffers(batch)
+    qv = qbatch.as_struct()
+    qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
+    so = go = None
+    if strands:
+        nseq = max(int(batch.win_seq_off[-1]), 1)
+        rev = np.zeros(nseq, np.uint8)
+        so = C.byref(capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)), None, None))
+    if graph:
+        g = capi.VcPoaGraphOut()
+        go = C.byref(g)
+    a = capi.VcPoaAlignOut(flags=flags)
+    rc = lib.vc_poa_run_align(C.byref(params), C.byref(vb), C.byref(r), so, go, C.byref(qv), C.byref(a))
+    if rc != 0:
+        raise PoaError(f"vc_poa_run_align failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    nq = int(a.n_queries)
+    st, sc = _table(a.status, nq), _table(a.score, nq)
+    both = bool(flags & capi.VC_POA_ALIGN_STRANDS)
+    scr, rv = (_table(a.score_rev, nq), _table(a.reversed, nq)) if both else (None, None)
+    pairs = None
+    if flags & capi.VC_POA_ALIGN_PAIRS:
+        po = _table(a.pair_off, nq + 1).astype(np.int64)
+        pairs = np.stack([_table(a.pair_node, int(po[-1])), _table(a.pair_pos, int(po[-1]))], axis=1) if nq else np.zeros((0, 2), np.int32)
+    wq = [int(x) for x in qbatch.win_seq_off]
+    res = [[QueryAlignment(int(sc[k]), int(scr[k]) if both else None, bool(rv[k]) if both else False, int(st[k]),
+                           pairs[int(po[k]):int(po[k + 1])].copy() if pairs is not None else None) for k in range(wq[w], wq[w + 1])]
+           for w in range(n)]
+    graphs = _graph_results(g, n, cons, off) if graph else None
+    return [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n], res, graphs
+
+
+def poa_align(groups, queries, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+              gap_extend=None, gap_open2=None, gap_extend2=None, pairs=True, both_strands=False, strand_ambiguous=False, graph=False):
+    """Aligns queries against the finished graphs of their groups without adding them (spoa's engine->Align(query, graph,
+    &score); vc_poa_run_align): queries[w] is the list of queries of groups[w] -> per group a list of QueryAlignment; with
+    graph=True -> (that, list of PoaGraph of the same call), whose node ids the pairs refer to.  pairs=False returns the scores
+    only (no backtrack runs).  both_strands aligns every query as given and reverse-complemented and keeps the better, ties as
+    given (VC_POA_ALIGN_STRANDS); strand_ambiguous is the build's -s, as in poa_graph.  Parameters, PoaError and strict as
+    poa_consensus: a group that was not computed raises, or with strict=False its queries carry its status.  ValueError when
+    the number of query lists differs from the number of groups."""
+    if len(queries) != len(groups):
+        raise ValueError(f"{len(queries)} query lists for {len(groups)} groups")
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    flags = (capi.VC_POA_ALIGN_PAIRS if pairs else 0) | (capi.VC_POA_ALIGN_STRANDS if both_strands else 0)
+    _, status, res, graphs = run_batch_align(group_batch(groups), query_batch(queries), p, flags, lib, strands=strand_ambiguous, graph=graph)
+    bad = _not_computed(status, strict)
+    if graph:
+        return res, [None if w in bad else g for w, g in enumerate(graphs)]
+    return res
+
+
+_STATUS_NAME = {capi.VC_WIN_OK: b"OK", capi.VC_WIN_OVERFLOW: b"OVERFLOW", capi.VC_WIN_INVALID: b"INVALID"}
+
+
+def align_tsv(names, files, results):
+    """The text of --align-out: one tab-separated line per (query, group), queries outermost -- query name, group file, status,
+    score (the kept strand's), strand (+ / -), pairs as node:pos,... with * for -1, or * for an empty alignment.
+    results[w][k]: the QueryAlignment of query k against group w."""
+    out = []
+    for k, name in enumerate(names):
+        for w, f in enumerate(files):
+            r = results[w][k]
+            prs = b"*" if r.pairs is None or len(r.pairs) == 0 else \
+                b",".join(b"%s:%s" % (b"*" if v < 0 else b"%d" % v, b"*" if p < 0 else b"%d" % p) for v, p in r.pairs.tolist())
+            out.append(b"%s\t%s\t%s\t%d\t%s\t%s\n" % (_bytes(name, "query name"), _bytes(f, "file name"),
+                                                      _STATUS_NAME.get(r.status, b"%d" % r.status),
+                                                      r.score_rev if r.reversed else r.score, b"-" if r.reversed else b"+", prs))
+    return b"".join(out)
 
 
 def parse_args(argv=None):
@@ -458,6 +568,13 @@ def parse_args(argv=None):
     ap.add_argument("--graphviz", metavar="FILE", default=None,
                     help="also write the graph in Graphviz dot format to FILE (spoa's -d); with several input files FILE is the "
                          "first one's and FILE.2, FILE.3, ... the others'")
+    ap.add_argument("--align", metavar="QUERIES", default=None,
+                    help="also align every record of QUERIES (FASTA / FASTQ) against the graph of every input file, without adding it")
+    ap.add_argument("--align-out", metavar="FILE", default=None,
+                    help="where --align writes: one tab-separated line per (query, group): query name, group file, status, score, "
+                         "strand, pairs (node:pos,... with * for none)")
+    ap.add_argument("--align-both-strands", action="store_true",
+                    help="with --align: align every query as given and reverse-complemented and report the better strand")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="+", metavar="FILE")
     return ap.parse_args(argv)
@@ -473,12 +590,35 @@ def main(argv=None):
     if gfa and (a.r != 0 or a.coverage):
         print("vechat_amd.poa: --gfa / --gfa-consensus do not go with -r 1 / -r 2 / --coverage", file=sys.stderr)
         return 1
+    if (a.align is None) != (a.align_out is None) or (a.align_both_strands and a.align is None):
+        print("vechat_amd.poa: --align QUERIES and --align-out FILE go together (--align-both-strands with them)", file=sys.stderr)
+        return 1
     msa = cons = graphs = None
     try:
         records = [list(seqio.read_sequences(f)) for f in a.files]
         groups = [[(data, qual) for _, data, qual in recs] for recs in records]
         gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
-        if gfa or a.graphviz is not None:
+        if a.align is not None:
+            # every query against every group.  With the consensus or the graph as the output (no alignment rows, no coverage) one
+            # call builds the groups once and gives both; beside -r 1 / -r 2 / --coverage it is a call of its own, since
+            # vc_poa_run_align carries no vc_poa_msa_out
+            qrecs = list(seqio.read_sequences(a.align))
+            one_call = a.r == 0 and not a.coverage
+            p = _gap_params(a.l, a.m, a.n, a.g, a.device, a.gap_extend, a.gap_open2, a.gap_extend2)
+            flags = capi.VC_POA_ALIGN_PAIRS | (capi.VC_POA_ALIGN_STRANDS if a.align_both_strands else 0)
+            c, status, res, gr = run_batch_align(group_batch(groups), query_batch([[data for _, data, _ in qrecs]] * len(groups)), p, flags,
+                                                 strands=a.both_strands, graph=one_call and (gfa or a.graphviz is not None))
+            _not_computed(status, True)
+            with open(a.align_out, "wb") as f:
+                f.write(align_tsv([name for name, _, _ in qrecs], a.files, res))
+            if one_call:
+                cons, graphs = (None if gfa else c), gr
+                for k, g in enumerate(graphs if a.graphviz is not None else ()):
+                    with open(a.graphviz if k == 0 else f"{a.graphviz}.{k + 1}", "wb") as f:
+                        f.write(g.to_dot())
+        if a.align is not None and a.r == 0 and not a.coverage:
+            pass                                                            # (the call above gave the output too)
+        elif gfa or a.graphviz is not None:
             # one call for everything: the graph carries the consensus, and with -r 1 / -r 2 / --coverage the alignment beside it
             flags = 0 if a.r == 0 and not a.coverage else \
                 capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if a.r == 2 else 0) | (capi.VC_POA_COVERAGE if a.coverage else 0)
