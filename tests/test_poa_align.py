@@ -15,13 +15,12 @@ import pytest
 import fixtures
 import poa_align_ref as A
 from poa_strand_ref import reverse_complement
+from poa_common import TYPES, _gp, _workers
 from test_poa import _device_visible, load_fixture, members
-from test_poa_strand import _workers
 from vechat_amd import capi, poa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-TYPES = {"SW": 0, "NW": 1, "OV": 2}
 _FX = {}
 
 
@@ -69,13 +68,6 @@ def test_align_entry_is_declared_exported_and_bound(built):
                                                              C.POINTER(capi.VcBatch), C.POINTER(capi.VcPoaAlignOut)]
     assert (capi.VC_POA_ALIGN_PAIRS, capi.VC_POA_ALIGN_STRANDS) == (1, 2)
     assert C.sizeof(capi.VcPoaGraphOut) == 152 and C.sizeof(capi.VcPoaMsaOut) == 72 and C.sizeof(capi.VcPoaStrandOut) == 24   # unchanged
-
-
-def _gp(**kw):
-    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-6, gap_open2=-10, gap_extend2=-4)
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
 
 
 def _call(lib, params, batch, qbatch, flags=1, out=True, strand="none", graph=False, queries=True, boverride=None, **qoverride):

@@ -16,13 +16,12 @@ import pytest
 
 import poa_align_ref as A
 from poa_strand_ref import reverse_complement
+from poa_common import MODELS, _workers
 from test_poa_align import entries
-from test_poa_strand import _workers
 from vechat_amd import capi, poa
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODELS = {"linear": (5, -4, -8, -8, -8, -8), "affine": (5, -4, -8, -6, -8, -6), "convex": (5, -4, -8, -6, -10, -4)}
 PAIRS, STRANDS = capi.VC_POA_ALIGN_PAIRS, capi.VC_POA_ALIGN_STRANDS
 OK = capi.VC_WIN_OK
 
@@ -239,6 +238,56 @@ def test_schedule_under_the_knobs(built, monkeypatch, capfd):
     assert _flat(grown[2]) == _flat(free[2])
     print(f"[schedule] {nq} queries of {len(groups)} groups: {k0} launch unconstrained, {k1} under a 0.25 MiB matrix budget over several "
           f"host groups ({k2} with both strands, twice the cells), regrown groups' queries counted once; results equal, {time.time() - t0:.1f} s")
+
+
+def test_every_output_stage_through_the_shared_launch_loop(built, monkeypatch, capfd):
+    """The four stages that share the host's launch loop -- the build's alignment steps, the alignment rows, the graph tables and
+    the queries -- in one process, every output asked for: vc_poa_run_graph with rows, coverage and strands, then
+    vc_poa_run_align with pairs, both query strands, the build's strands and the graph.  Once without a knob, once with small
+    tables (every group regrows), an arena of 0.5 MiB (several host groups of several groups each) and a matrix budget of 8 KiB
+    (a group's rows are about 1 KiB, its graph block tens of KiB, a query matrix hundreds: launches of several items, of one
+    item, and of one item above the budget).  Every table, row, score and pair must equal the knob-free call's."""
+    import poa_graph_ref as G
+    rng = random.Random(8450)
+    groups, queries = [], []
+    for w in range(24):
+        truth = bytes(rng.choice(b"ACGT") for _ in range(rng.randrange(30, 151)))
+        g = [(_noisy(rng, truth), None) for _ in range(rng.randrange(2, 7))]
+        if w % 3 == 0:
+            g[-1] = (reverse_complement(g[-1][0]), None)
+        groups.append(g)
+        queries.append([g[0][0], _noisy(rng, truth, 0.15), reverse_complement(_noisy(rng, truth))])
+    groups[7] = []                                                          # an empty group keeps its three queries
+    batch, qbatch = poa.group_batch(groups), poa.query_batch(queries)
+    p = capi.VcPoaGapParams(0, 1, *MODELS["convex"])
+
+    def both():
+        return (poa.run_batch_graph(batch, p, 7, strands=True),
+                poa.run_batch_align(batch, qbatch, p, PAIRS | STRANDS, strands=True, graph=True))
+    t0 = time.time()
+    fg, fa = both()
+    env = {"VC_LARGE_LOG": "1", "VC_LARGE_CAPS": "n:5,e:5,a:7,l:3,s:10,p:6", "VC_LARGE_ARENA_MB": "0.5", "VC_LARGE_MAT_MB": "0.008"}
+    (kg, ka), err = _knobs(monkeypatch, capfd, env, both)
+    launches = {k: [int(x) for x in re.findall(rf"vc_large: {k} (?:jobs=\d+ )?launches=(\d+)", err)] for k in ("msa", "graph", "align")}
+    print(f"[shared loop] launches {launches}, {err.count('vc_large: regrow')} regrow lines, "
+          f"{err.count('vc_large: group windows=')} host groups, {err.count('vc_large: step launches=')} steps of several launches")
+    assert "vc_large: regrow" in err and "vc_large: step launches=" in err
+    assert len(launches["msa"]) == 1 and len(launches["graph"]) == 2 and len(launches["align"]) == 1      # one line per call that has the stage
+    assert all(k >= 2 for ks in launches.values() for k in ks), launches
+    for got, want in ((kg, fg), (ka, fa)):
+        assert got[1].tolist() == want[1].tolist() == [OK] * len(groups)
+    # vc_poa_run_graph: the tables, the rows and the coverage beside them, the strand choices and both strands' scores
+    for w, (x, y) in enumerate(zip(kg[0], fg[0])):
+        assert G.of_poa_graph(x) == G.of_poa_graph(y) and x.consensus == y.consensus, w
+        assert (x.msa.rows, x.msa.members, x.msa.coverage.tolist(), x.msa.reversed.tolist()) == \
+               (y.msa.rows, y.msa.members, y.msa.coverage.tolist(), y.msa.reversed.tolist()), w
+        assert kg[2][w].tolist() == fg[2][w].tolist() and kg[3][w].tolist() == fg[3][w].tolist(), w
+    # vc_poa_run_align: consensus, every query's status, scores, strand and pairs, the graph of the same call
+    assert ka[0] == fa[0] and _flat(ka[2]) == _flat(fa[2]) and len(_flat(fa[2])) == 3 * len(groups)
+    assert [G.of_poa_graph(x) for x in ka[3]] == [G.of_poa_graph(y) for y in fa[3]] == [G.of_poa_graph(y) for y in fg[0]]
+    assert any(r.reversed for qs in fa[2] for r in qs) and any(m.msa.reversed.any() for m in fg[0])
+    print(f"[shared loop] {len(groups)} groups, {3 * len(groups)} queries: tables, rows, coverage, scores and pairs under small tables, arena "
+          f"and matrix budget equal to the knob-free calls, {time.time() - t0:.1f} s")
 
 
 # ------------------------------------------------------------------ 6. statuses

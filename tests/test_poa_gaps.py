@@ -17,12 +17,12 @@ import pytest
 
 import fixtures
 import poa_gaps_ref as R
+from poa_common import TYPES, _gp, _workers
 from test_poa import _device_visible, load_fixture, members
 from vechat_amd import capi, poa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-TYPES = {"SW": 0, "NW": 1, "OV": 2}
 
 
 def load_kats():
@@ -31,10 +31,6 @@ def load_kats():
 
 def load_gaps_fixture():
     return json.load(gzip.open(os.path.join(GOLDEN, "poa_gaps_groups.json.gz"), "rt"))
-
-
-def _workers():
-    return max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
 
 
 def test_gap_entry_is_declared_and_exported(built):
@@ -90,13 +86,6 @@ def _call(lib, params, batch, **override):
     for k, v in override.items():
         setattr(vb, k, v)
     return lib.vc_poa_run_gaps(C.byref(params) if params is not None else None, C.byref(vb), C.byref(r))
-
-
-def _gp(**kw):
-    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-6, gap_open2=-10, gap_extend2=-4)
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
 
 
 def test_gap_argument_errors_come_before_the_device(built):

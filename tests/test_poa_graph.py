@@ -16,13 +16,13 @@ import pytest
 import fixtures
 import poa_graph_ref as G
 import poa_strand_ref as S
+from poa_common import TYPES, _gp, _workers
 from test_poa import _device_visible, load_fixture, members
-from test_poa_strand import _workers, flipped
+from test_poa_strand import flipped
 from vechat_amd import capi, poa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-TYPES = {"SW": 0, "NW": 1, "OV": 2}
 _FX = {}
 
 
@@ -118,13 +118,6 @@ def _call(lib, params, batch, flags=0, out=True, strand="none", graph=True, **ov
     rc = lib.vc_poa_run_graph(C.byref(params) if params is not None else None, C.byref(vb), C.byref(r), C.byref(o) if out else None,
                               C.byref(s) if strand != "none" else None, C.byref(g) if graph else None)
     return rc, g
-
-
-def _gp(**kw):
-    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-6, gap_open2=-10, gap_extend2=-4)
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
 
 
 def test_graph_argument_errors_come_before_the_device(built):

@@ -16,23 +16,18 @@ import pytest
 
 import fixtures
 import poa_graph_ref as G
+from poa_common import MODELS, _kw, _workers
 from test_poa import members
 from test_poa_graph import check_graph, entries, load_graph_fixture, same_text, sample_names
-from test_poa_strand import _workers, flipped
+from test_poa_strand import flipped
 from vechat_amd import capi, poa
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODELS = {"linear": (5, -4, -8, -8, -8, -8), "affine": (5, -4, -8, -6, -8, -6), "convex": (5, -4, -8, -6, -10, -4)}
 
 
 def _graphs(groups, t, scores, flags=0, strands=False):
     return poa.run_batch_graph(poa.group_batch(groups), capi.VcPoaGapParams(0, t, *scores), flags, strands=strands)
-
-
-def _kw(scores):
-    m, n, g, e, q, c = scores
-    return dict(match=m, mismatch=n, gap=g, gap_extend=e, gap_open2=q, gap_extend2=c)
 
 
 # ------------------------------------------------------------------ 1. every fixture entry

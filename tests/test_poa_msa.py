@@ -14,12 +14,12 @@ import pytest
 
 import fixtures
 import poa_msa_ref as M
+from poa_common import TYPES, _gp, _workers
 from test_poa import _device_visible, load_fixture, members
 from vechat_amd import capi, poa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-TYPES = {"SW": 0, "NW": 1, "OV": 2}
 
 
 def load_msa_fixture():
@@ -42,10 +42,6 @@ def entries():
         for t in ("0", "1", "2"):
             out.append((f"{g['name']}/{g['model']}/{t}", groups[g["name"]], int(t), tuple(g["scores"]), g["expected"][t]))
     return out
-
-
-def _workers():
-    return max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
 
 
 # ------------------------------------------------------------------ the boundary
@@ -79,13 +75,6 @@ def _call(lib, params, batch, flags, out=True, **override):
         setattr(vb, k, v)
     o = capi.VcPoaMsaOut(flags=flags)
     return lib.vc_poa_run_msa(C.byref(params) if params is not None else None, C.byref(vb), C.byref(r), C.byref(o) if out else None)
-
-
-def _gp(**kw):
-    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-6, gap_open2=-10, gap_extend2=-4)
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
 
 
 def test_msa_argument_errors_come_before_the_device(built):

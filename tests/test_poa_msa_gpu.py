@@ -17,8 +17,9 @@ import pytest
 
 import fixtures
 import poa_msa_ref as M
+from poa_common import _done, _kw, _workers
 from test_poa import load_fixture, members
-from test_poa_msa import _workers, entries
+from test_poa_msa import entries
 from vechat_amd import capi, large, poa
 
 pytestmark = pytest.mark.gpu
@@ -26,11 +27,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, GOLDEN)
 import make_poa  # noqa: E402
-
-
-def _kw(scores):
-    m, n, g, e, q, c = scores
-    return dict(match=m, mismatch=n, gap=g, gap_extend=e, gap_open2=q, gap_extend2=c)
 
 
 def _same(a, b, label):
@@ -176,10 +172,6 @@ def test_degenerate_groups_beside_valid_ones(built, monkeypatch):
 
 
 # ------------------------------------------------------------------ 5. without flags: vc_poa_run_gaps
-def _done(err):
-    return [l for l in err.splitlines() if l.startswith("vc_large: done")]
-
-
 def test_without_flags_it_is_vc_poa_run_gaps(built, monkeypatch, capfd):
     groups = _fresh(9400, 64)
     batch = poa.group_batch(groups)

@@ -15,12 +15,12 @@ import pytest
 import fixtures
 import poa_msa_ref as M
 import poa_strand_ref as S
+from poa_common import TYPES, _gp, _workers
 from test_poa import _device_visible, load_fixture, members
 from vechat_amd import capi, poa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-TYPES = {"SW": 0, "NW": 1, "OV": 2}
 
 
 def load_strand_fixture():
@@ -55,10 +55,6 @@ def entries():
         for t in ("0", "1", "2"):
             out.append((f"hand/{g['name']}/{t}", members(g), int(t), sc, g["expected"][t]))
     return out
-
-
-def _workers():
-    return max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
 
 
 # ------------------------------------------------------------------ the boundary
@@ -96,13 +92,6 @@ def _call(lib, params, batch, flags, out=True, strand="all", **override):
         s.score, s.score_rev = sc.ctypes.data_as(C.POINTER(C.c_int32)), scr.ctypes.data_as(C.POINTER(C.c_int32))
     return lib.vc_poa_run_strand(C.byref(params) if params is not None else None, C.byref(vb), C.byref(r), C.byref(o) if out else None,
                                  C.byref(s) if strand != "null" else None)
-
-
-def _gp(**kw):
-    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-6, gap_open2=-10, gap_extend2=-4)
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
 
 
 def test_strand_argument_errors_come_before_the_device(built):

@@ -17,8 +17,9 @@ import pytest
 
 import fixtures
 import poa_strand_ref as S
+from poa_common import MODELS, _done, _kw, _workers
 from test_poa import load_fixture, members
-from test_poa_strand import _workers, entries, flipped
+from test_poa_strand import entries, flipped
 from vechat_amd import capi, poa
 
 pytestmark = pytest.mark.gpu
@@ -27,12 +28,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, GOLDEN)
 import make_poa  # noqa: E402
 
-MODELS = {"linear": (5, -4, -8, -8, -8, -8), "affine": (5, -4, -8, -6, -8, -6), "convex": (5, -4, -8, -6, -10, -4)}
-
-
-def _kw(scores):
-    m, n, g, e, q, c = scores
-    return dict(match=m, mismatch=n, gap=g, gap_extend=e, gap_open2=q, gap_extend2=c)
 
 
 def _params(t, scores):
@@ -133,11 +128,6 @@ def test_fresh_groups_against_the_restatement_and_the_plain_path(built, t):
 
 
 # ------------------------------------------------------------------ 3. the host schedule under small budgets
-def _done(err):
-    return [tuple(map(int, re.match(r"vc_large: done alignments=(\d+) cells=(\d+)", l).groups()))
-            for l in err.splitlines() if l.startswith("vc_large: done")]
-
-
 def test_strands_under_small_budgets(built, monkeypatch, capfd):
     fx = load_fixture()
     fixed = [flipped(members(g), range(1, len(g["seqs"]), 2)) for g in fx["groups"]

@@ -139,17 +139,68 @@ def _result_buffers(batch):
     return cons, off, status, r, vb
 
 
-def run_batch(batch, params, lib=None):
-    """vc_poa_run (params: capi.VcPoaParams) or vc_poa_run_gaps (capi.VcPoaGapParams) on a capi.Batch (its seq_begin / seq_end /
-    win_fasta are passed as NULL) -> (consensus bytes per group, status array).  Raises PoaError on a library error."""
+class _Outputs:
+    """what _run copied out of one call; an output that was not asked for is None"""
+    __slots__ = ("cons", "status", "msas", "graphs", "scores", "scores_rev", "queries")
+
+
+def _per_group(x, wso):
+    return [x[wso[w]:wso[w + 1]].copy() for w in range(len(wso) - 1)]
+
+
+def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_scores=True, graph=False, qbatch=None, align_flags=0):
+    """One library call on a capi.Batch (its seq_begin / seq_end / win_fasta are passed as NULL) with the outputs asked for:
+    msa_flags (capi.VC_POA_* bits, None: no vc_poa_msa_out), strands (spoa's -s; strand_scores: with the score arrays), graph,
+    qbatch + align_flags (the queries of vc_poa_run_align).  The entry is the first of vc_poa_run_align (queries), _graph, _strand,
+    _msa that the request needs, else vc_poa_run_gaps (capi.VcPoaGapParams) or vc_poa_run (capi.VcPoaParams).  Everything is
+    copied out of the library's buffers -> _Outputs.  Raises PoaError, naming the entry, on a library error."""
     lib = lib or capi.load_hip()
     n = batch.n_windows
     cons, off, status, r, vb = _result_buffers(batch)
-    name = "vc_poa_run_gaps" if isinstance(params, capi.VcPoaGapParams) else "vc_poa_run"
-    rc = getattr(lib, name)(C.byref(params), C.byref(vb), C.byref(r))
+    wso = [int(x) for x in batch.win_seq_off]
+    o = capi.VcPoaMsaOut(flags=msa_flags) if msa_flags is not None else None
+    g = capi.VcPoaGraphOut() if graph else None
+    rev = sc = scr = so = None
+    if strands:
+        nseq = max(wso[-1], 1)
+        rev = np.zeros(nseq, np.uint8)
+        if strand_scores:
+            sc, scr = np.zeros(nseq, np.int32), np.zeros(nseq, np.int32)
+        so = C.byref(capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         *(x if x is None else x.ctypes.data_as(C.POINTER(C.c_int32)) for x in (sc, scr))))
+    if qbatch is not None:
+        name = "vc_poa_run_align"
+        if not hasattr(lib, name):
+            raise PoaError("this libvechat_hip.so has no vc_poa_run_align: it was built before the entry point existed; rebuild it")
+        qv = qbatch.as_struct()
+        qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
+        a = capi.VcPoaAlignOut(flags=align_flags)
+        args = (so, C.byref(g) if graph else None, C.byref(qv), C.byref(a))
+    elif graph:
+        name, args = "vc_poa_run_graph", (C.byref(o), so, C.byref(g))
+    elif strands:
+        name, args = "vc_poa_run_strand", (C.byref(o), so)
+    elif o is not None:
+        name, args = "vc_poa_run_msa", (C.byref(o),)
+    else:
+        name, args = "vc_poa_run_gaps" if isinstance(params, capi.VcPoaGapParams) else "vc_poa_run", ()
+    rc = getattr(lib, name)(C.byref(params), C.byref(vb), C.byref(r), *args)
     if rc != 0:
         raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
-    return [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n]
+    x = _Outputs()
+    x.cons, x.status = [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n]
+    x.msas = _msa_results(o, msa_flags, n, cons, off, wso, rev) if o is not None else None
+    x.graphs = _graph_results(g, n, cons, off, x.msas if msa_flags or (strands and o is not None) else None) if graph else None
+    x.scores, x.scores_rev = (_per_group(sc, wso), _per_group(scr, wso)) if sc is not None else (None, None)
+    x.queries = _query_results(a, align_flags, [int(k) for k in qbatch.win_seq_off]) if qbatch is not None else None
+    return x
+
+
+def run_batch(batch, params, lib=None):
+    """vc_poa_run (params: capi.VcPoaParams) or vc_poa_run_gaps (capi.VcPoaGapParams) on a capi.Batch (its seq_begin / seq_end /
+    win_fasta are passed as NULL) -> (consensus bytes per group, status array).  Raises PoaError on a library error."""
+    x = _run(batch, params, lib=lib)
+    return x.cons, x.status
 
 
 def _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2):
@@ -225,25 +276,8 @@ def run_batch_msa(batch, params, flags, lib=None, strands=False):
     Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error.
     strands=True: vc_poa_run_strand instead -> (list of Msa with .reversed, status array, forward scores, reverse scores), the
     scores as one int32 array per group."""
-    lib = lib or capi.load_hip()
-    n = batch.n_windows
-    cons, off, status, r, vb = _result_buffers(batch)
-    o = capi.VcPoaMsaOut(flags=flags)
-    wso = [int(x) for x in batch.win_seq_off]
-    if strands:
-        nseq = max(wso[-1], 1)
-        rev, sc, scr = np.zeros(nseq, np.uint8), np.zeros(nseq, np.int32), np.zeros(nseq, np.int32)
-        so = capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)), sc.ctypes.data_as(C.POINTER(C.c_int32)),
-                                 scr.ctypes.data_as(C.POINTER(C.c_int32)))
-        name, rc = "vc_poa_run_strand", lib.vc_poa_run_strand(C.byref(params), C.byref(vb), C.byref(r), C.byref(o), C.byref(so))
-    else:
-        name, rc = "vc_poa_run_msa", lib.vc_poa_run_msa(C.byref(params), C.byref(vb), C.byref(r), C.byref(o))
-    if rc != 0:
-        raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
-    res = _msa_results(o, flags, n, cons, off, wso, rev if strands else None)
-    if strands:
-        return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
-    return res, status[:n]
+    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands)
+    return (x.msas, x.status, x.scores, x.scores_rev) if strands else (x.msas, x.status)
 
 
 def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
@@ -364,25 +398,8 @@ def run_batch_graph(batch, params, flags=0, lib=None, strands=False):
     capi.Batch -> (list of PoaGraph, status array); strands=True builds the groups with spoa's -s and also returns the forward and
     reverse scores per group, as run_batch_msa.  PoaGraph.msa is the group's Msa (its .reversed set with strands).  Everything is
     copied out of the library's buffers before returning.  Raises PoaError on a library error."""
-    lib = lib or capi.load_hip()
-    n = batch.n_windows
-    cons, off, status, r, vb = _result_buffers(batch)
-    o, g = capi.VcPoaMsaOut(flags=flags), capi.VcPoaGraphOut()
-    wso = [int(x) for x in batch.win_seq_off]
-    so = None
-    if strands:
-        nseq = max(wso[-1], 1)
-        rev, sc, scr = np.zeros(nseq, np.uint8), np.zeros(nseq, np.int32), np.zeros(nseq, np.int32)
-        so = C.byref(capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)), sc.ctypes.data_as(C.POINTER(C.c_int32)),
-                                         scr.ctypes.data_as(C.POINTER(C.c_int32))))
-    rc = lib.vc_poa_run_graph(C.byref(params), C.byref(vb), C.byref(r), C.byref(o), so, C.byref(g))
-    if rc != 0:
-        raise PoaError(f"vc_poa_run_graph failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
-    msas = _msa_results(o, flags, n, cons, off, wso, rev if strands else None)
-    res = _graph_results(g, n, cons, off, msas if flags or strands else None)
-    if strands:
-        return res, status[:n], [sc[wso[w]:wso[w + 1]].copy() for w in range(n)], [scr[wso[w]:wso[w + 1]].copy() for w in range(n)]
-    return res, status[:n]
+    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, graph=True)
+    return (x.graphs, x.status, x.scores, x.scores_rev) if strands else (x.graphs, x.status)
 
 
 def _table(ptr, count):
@@ -462,25 +479,12 @@ def run_batch_align(batch, qbatch, params, flags=capi.VC_POA_ALIGN_PAIRS, lib=No
     QueryAlignment, list of PoaGraph or None).  strands=True builds the groups with spoa's -s; graph=True also asks for the
     graph tables of the same call.  Everything is copied out of the library's buffers before returning.  Raises PoaError on a
     library error."""
-    lib = lib or capi.load_hip()
-    if not hasattr(lib, "vc_poa_run_align"):
-        raise PoaError("this libvechat_hip.so has no vc_poa_run_align: it was built before the entry point existed; rebuild it")
-    n = batch.n_windows
-    cons, off, status, r, vb = _result_buffers(batch)
-    qv = qbatch.as_struct()
-    qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
-    so = go = None
-    if strands:
-        nseq = max(int(batch.win_seq_off[-1]), 1)
-        rev = np.zeros(nseq, np.uint8)
-        so = C.byref(capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)), None, None))
-    if graph:
-        g = capi.VcPoaGraphOut()
-        go = C.byref(g)
-    a = capi.VcPoaAlignOut(flags=flags)
-    rc = lib.vc_poa_run_align(C.byref(params), C.byref(vb), C.byref(r), so, go, C.byref(qv), C.byref(a))
-    if rc != 0:
-        raise PoaError(f"vc_poa_run_align failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    x = _run(batch, params, lib=lib, strands=strands, strand_scores=False, graph=graph, qbatch=qbatch, align_flags=flags)
+    return x.cons, x.status, x.queries, x.graphs
+
+
+def _query_results(a, flags, wq):
+    """per group the list of QueryAlignment out of a filled capi.VcPoaAlignOut (wq: the query batch's win_seq_off)"""
     nq = int(a.n_queries)
     st, sc = _table(a.status, nq), _table(a.score, nq)
     both = bool(flags & capi.VC_POA_ALIGN_STRANDS)
@@ -489,12 +493,9 @@ def run_batch_align(batch, qbatch, params, flags=capi.VC_POA_ALIGN_PAIRS, lib=No
     if flags & capi.VC_POA_ALIGN_PAIRS:
         po = _table(a.pair_off, nq + 1).astype(np.int64)
         pairs = np.stack([_table(a.pair_node, int(po[-1])), _table(a.pair_pos, int(po[-1]))], axis=1) if nq else np.zeros((0, 2), np.int32)
-    wq = [int(x) for x in qbatch.win_seq_off]
-    res = [[QueryAlignment(int(sc[k]), int(scr[k]) if both else None, bool(rv[k]) if both else False, int(st[k]),
-                           pairs[int(po[k]):int(po[k + 1])].copy() if pairs is not None else None) for k in range(wq[w], wq[w + 1])]
-           for w in range(n)]
-    graphs = _graph_results(g, n, cons, off) if graph else None
-    return [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n], res, graphs
+    return [[QueryAlignment(int(sc[k]), int(scr[k]) if both else None, bool(rv[k]) if both else False, int(st[k]),
+                            pairs[int(po[k]):int(po[k + 1])].copy() if pairs is not None else None) for k in range(wq[w], wq[w + 1])]
+            for w in range(len(wq) - 1)]
 
 
 def poa_align(groups, queries, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
@@ -593,46 +594,38 @@ def main(argv=None):
     if (a.align is None) != (a.align_out is None) or (a.align_both_strands and a.align is None):
         print("vechat_amd.poa: --align QUERIES and --align-out FILE go together (--align-both-strands with them)", file=sys.stderr)
         return 1
+    # what the command line asks for: the alignment rows or the coverage (a vc_poa_msa_out, which vc_poa_run_align does not carry),
+    # the graph tables, the queries
+    want_msa = a.r != 0 or a.coverage
+    want_graph = gfa or a.graphviz is not None
+    msa_flags = capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if a.r == 2 else 0) | (capi.VC_POA_COVERAGE if a.coverage else 0) if want_msa else 0
     msa = cons = graphs = None
     try:
         records = [list(seqio.read_sequences(f)) for f in a.files]
         groups = [[(data, qual) for _, data, qual in recs] for recs in records]
         gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
+        p = _gap_params(a.l, a.m, a.n, a.g, a.device, **gaps)
         if a.align is not None:
-            # every query against every group.  With the consensus or the graph as the output (no alignment rows, no coverage) one
-            # call builds the groups once and gives both; beside -r 1 / -r 2 / --coverage it is a call of its own, since
-            # vc_poa_run_align carries no vc_poa_msa_out
+            # every query against every group.  Without rows or coverage this one call builds the groups once and gives the
+            # consensus or the graph too; beside them it is a call of its own
             qrecs = list(seqio.read_sequences(a.align))
-            one_call = a.r == 0 and not a.coverage
-            p = _gap_params(a.l, a.m, a.n, a.g, a.device, a.gap_extend, a.gap_open2, a.gap_extend2)
             flags = capi.VC_POA_ALIGN_PAIRS | (capi.VC_POA_ALIGN_STRANDS if a.align_both_strands else 0)
             c, status, res, gr = run_batch_align(group_batch(groups), query_batch([[data for _, data, _ in qrecs]] * len(groups)), p, flags,
-                                                 strands=a.both_strands, graph=one_call and (gfa or a.graphviz is not None))
+                                                 strands=a.both_strands, graph=want_graph and not want_msa)
             _not_computed(status, True)
             with open(a.align_out, "wb") as f:
                 f.write(align_tsv([name for name, _, _ in qrecs], a.files, res))
-            if one_call:
-                cons, graphs = (None if gfa else c), gr
-                for k, g in enumerate(graphs if a.graphviz is not None else ()):
-                    with open(a.graphviz if k == 0 else f"{a.graphviz}.{k + 1}", "wb") as f:
-                        f.write(g.to_dot())
-        if a.align is not None and a.r == 0 and not a.coverage:
-            pass                                                            # (the call above gave the output too)
-        elif gfa or a.graphviz is not None:
+        if a.align is not None and not want_msa:
+            cons, graphs = (None if gfa else c), gr
+        elif want_graph:
             # one call for everything: the graph carries the consensus, and with -r 1 / -r 2 / --coverage the alignment beside it
-            flags = 0 if a.r == 0 and not a.coverage else \
-                capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if a.r == 2 else 0) | (capi.VC_POA_COVERAGE if a.coverage else 0)
-            p = _gap_params(a.l, a.m, a.n, a.g, a.device, a.gap_extend, a.gap_open2, a.gap_extend2)
-            graphs, status = run_batch_graph(group_batch(groups), p, flags, strands=a.both_strands)[:2]
+            graphs, status = run_batch_graph(group_batch(groups), p, msa_flags, strands=a.both_strands)[:2]
             _not_computed(status, True)
-            if flags:
+            if want_msa:
                 msa = [g.msa for g in graphs]
             elif not gfa:
                 cons = [g.consensus for g in graphs]
-            for k, g in enumerate(graphs if a.graphviz is not None else ()):
-                with open(a.graphviz if k == 0 else f"{a.graphviz}.{k + 1}", "wb") as f:
-                    f.write(g.to_dot())
-        elif a.r == 0 and not a.coverage:
+        elif not want_msa:
             if a.both_strands:
                 cons = poa_consensus_strands(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)[0]
             else:
@@ -640,6 +633,9 @@ def main(argv=None):
         else:
             strands = dict(strand_ambiguous=True) if a.both_strands else {}
             msa = poa_msa(groups, a.l, a.m, a.n, a.g, device=a.device, include_consensus=a.r == 2, coverage=a.coverage, **gaps, **strands)
+        for k, g in enumerate(graphs if a.graphviz is not None else ()):
+            with open(a.graphviz if k == 0 else f"{a.graphviz}.{k + 1}", "wb") as f:
+                f.write(g.to_dot())
     except (PoaError, ValueError, OSError) as e:
         print(f"vechat_amd.poa: {e}", file=sys.stderr)
         return 1
