@@ -41,6 +41,11 @@
  * Read on every vc_large_run and vc_poa_run call (vc_large.hip, whose header describes them; tests/test_large_schedule.py):
  *   VC_LARGE_CAPS, VC_LARGE_ARENA_MB, VC_LARGE_MAT_MB, VC_LARGE_LOG (its lines: regrow, group, step, refuse, msa, graph, and for
  *   vc_poa_run_align with queries "vc_large: align jobs=J launches=K cells=C bytes=B"; done), VC_LARGE_GRAPH_WALK
+ * Read on every vc_align call (vc_align.hip, whose header describes them; test knobs of tests/test_align.py):
+ *   VC_ALIGN_BUDGET_MB=x   the chunk budget in MiB instead of half of the free device memory
+ *   VC_ALIGN_MAX_MAT_MB=x  the envelope in MiB instead of a third of the device memory: an overlap whose stored matrix is larger
+ *                          comes back with distance -1 and an empty CIGAR
+ *   VC_ALIGN_LOG           set: one stderr line per chunk, "vc_align: chunk first=K pairs=N mat_dwords=D"
  */
 #ifndef VECHAT_HIP_H_
 #define VECHAT_HIP_H_
@@ -324,7 +329,8 @@ int64_t     vc_io_load(vc_wb* builder, const vc_seqset* targets, const vc_seqset
  * Overlap alignment on the device.  Stands in for the edlib call the reference makes
  * for overlaps without a CIGAR (src/overlap.cpp:205-220): global unit-cost alignment with path, returned
  * as an edlib-standard CIGAR (M / I / D).  The path is optimal; which of several optimal paths is returned
- * is this library's choice (diagonal, then insertion, then deletion, from the end), not edlib's.
+ * is this library's choice (diagonal, then insertion, then deletion, from the end), not edlib's; the rule makes the
+ * path unique, and tests/test_align.py pins it against a CPU DP.
  * q / t hold the pieces to align back to back (the query piece already oriented as it aligns);
  * Any length: scores are kept relative per 2048-column tile.  An overlap whose stored matrix would not fit the
  * device memory is not aligned: its distance comes back as -1 and its CIGAR empty; the others are unaffected.

@@ -4,9 +4,17 @@
 //
 // PARITY UNPINNED, and it cannot be pinned here: edlib 1.2.7 is not vendored (CMake fetches it), and an
 // optimal alignment is not unique -- which of the co-optimal paths comes out depends on edlib's own
-// traceback.  What this file guarantees, and what tests/test_align.py checks against a CPU DP, is that the
-// path is a valid global alignment whose cost equals the unit-cost edit distance.  Ties are broken
-// diagonal first, then insertion (query base only), then deletion (target base only), walking from the end.
+// traceback.  What this file guarantees is that the path is a valid global alignment whose cost equals the
+// unit-cost edit distance, and which one: ties are broken diagonal first, then insertion (query base only),
+// then deletion (target base only), walking from the end.  That rule makes the path unique, and
+// tests/test_align.py pins the path itself: every CIGAR string is compared byte for byte, and every distance,
+// with a CPU DP that keeps the full matrix and applies the same rule (tests/align_ref.py).
+//
+// Test knobs, read with getenv on every vc_align call; unset, each leaves the behaviour as it is:
+//   VC_ALIGN_BUDGET_MB=x    the chunk budget in MiB, instead of half of the free device memory
+//   VC_ALIGN_MAX_MAT_MB=x   the largest stored matrix of one overlap in MiB, instead of a third of the device memory
+//                           (a larger one is outside the envelope: distance -1, empty CIGAR)
+//   VC_ALIGN_LOG            set: one line per chunk on stderr, "vc_align: chunk first=K pairs=N mat_dwords=D"
 //
 // Kernels (gfx950, wave64):
 //   k_aln_fwd    one wave per overlap.  Rows = query bases, columns = target bases in tiles of 2048 (64 lanes x
@@ -22,6 +30,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -242,6 +251,13 @@ uint32_t* mat_buffer(int device, uint64_t dwords) {
     return g_mat.p;
 }
 
+// a knob in MiB as bytes (the header of this file lists them); 0: not set
+uint64_t env_mib(const char* name) {
+    const char* v = getenv(name);
+    const double x = v ? std::atof(v) : 0.0;
+    return x > 0 ? std::max<uint64_t>((uint64_t)(x * 1048576.0), 1) : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -264,14 +280,17 @@ int vc_align(int device, const vc_align_batch* b, char* cigar, uint64_t cigar_ca
     size_t free_b0 = 0, total_b0 = 0;
     (void)hipMemGetInfo(&free_b0, &total_b0);
     // an overlap whose stored matrix alone would not fit the device is reported (distance -1, empty CIGAR)
+    const uint64_t knob_mat = env_mib("VC_ALIGN_MAX_MAT_MB"), knob_budget = env_mib("VC_ALIGN_BUDGET_MB");
+    const bool log = getenv("VC_ALIGN_LOG") != nullptr;
+    const uint64_t max_mat = knob_mat ? knob_mat : total_b0 / 3;
     std::vector<uint8_t> skip(n, 0);
     for (uint32_t k = 0; k < n; ++k) {
         const uint64_t ql = b->q_off[k + 1] - b->q_off[k], tl = b->t_off[k + 1] - b->t_off[k];
-        if (ql >= (1ull << 31) || tl >= (1ull << 31) || ql * ((tl + kTile - 1) / kTile) * kRowDw * 4 > total_b0 / 3) skip[k] = 1;
+        if (ql >= (1ull << 31) || tl >= (1ull << 31) || ql * ((tl + kTile - 1) / kTile) * kRowDw * 4 > max_mat) skip[k] = 1;
     }
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    const uint64_t budget = (uint64_t)((free_b + (g_mat.device == device ? g_mat.dwords * 4 : 0)) * 0.5);
+    const uint64_t budget = knob_budget ? knob_budget : (uint64_t)((free_b + (g_mat.device == device ? g_mat.dwords * 4 : 0)) * 0.5);
     std::vector<void*> fixed;
     uint8_t *d_q = nullptr, *d_t = nullptr;
     uint64_t *d_qo = nullptr, *d_to = nullptr;
@@ -302,6 +321,7 @@ int vc_align(int device, const vc_align_batch* b, char* cigar, uint64_t cigar_ca
             ++k1;
         }
         const uint32_t nj = k1 - k0;
+        if (log) fprintf(stderr, "vc_align: chunk first=%u pairs=%u mat_dwords=%llu\n", k0, nj, (unsigned long long)mat_dw);
         std::vector<void*> tmp;
         AlnArgs a{};
         uint64_t *d_mo = nullptr, *d_bo = nullptr, *d_oo = nullptr;
