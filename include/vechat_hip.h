@@ -576,6 +576,52 @@ typedef struct vc_poa_align_out {
 int         vc_poa_run_align(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_strand_out* s /* may be NULL */,
                              vc_poa_graph_out* g /* may be NULL */, const vc_batch* q, vc_poa_align_out* a);
 
+/* Haplotype-aware correction of every member of a group: VeChat's variation-aware flow (src/window.cpp:176-428 on the vendored
+ * spoa's PruneGraph, LargestSubgraph, AddWeights and GenerateCorrectedSequence, graph.cpp:811-1179) for POA groups, where one
+ * graph serves all its members.  The reference has no group form; the flow is this composition of its public functions:
+ *   1 build     the loop of vc_poa_run_gaps, unchanged; beside it total += the member's length (no quality) or, per base in order,
+ *               1 - 10^((33 - q) / 10) (window.cpp:283,295), in double, in member order;
+ *   2 consensus GenerateConsensus() of the unpruned graph: r holds vc_poa_run_gaps's bytes for the same input;
+ *   3 average   avg = 2.0 * total / L, times 1000 when the first non-empty member has a quality string (window.cpp:301-309); L is
+ *               that member's length.  A group without a non-empty member is VC_WIN_OK with the empty consensus and corrections;
+ *   4 prune     PruneGraph(0, min_confidence, min_support, avg), then LargestSubgraph();
+ *   5 rounds    num_prune - 1 times: every member, in order, is aligned against the pruned graph with the call's own engine
+ *               (algorithm, scores, gap model) and AddWeights adds weight 1 per base, or vc_weight_lut's with a quality
+ *               (window.cpp:351-373; an empty alignment or member adds nothing; an edge it creates is seen by the members after
+ *               it); then PruneGraph and LargestSubgraph again;
+ *   6 correct   every member is aligned against the final graph with a local engine (kSW) of the call's scores and gap model, and
+ *               its correction is GenerateCorrectedSequence(alignment): the decoded base of every pair with a node, in order.
+ *               A member that aligns nowhere, or is empty, has the empty correction; it is not an error.
+ * Unlike the window overload (vc_large_run, mode 0) there is no backbone, no spans or subgraph, no rank sort, no "< 3 sequences"
+ * rule, every round uses the call's engine for every member, and the final engine is local with the call's scores, not 3 / -5 / -4.
+ * The arguments, in this entry's own order: the batch and p as vc_poa_run_gaps, the thresholds (the reference's defaults are
+ * 0.22 / 0.19 / 3), r as vc_poa_run_gaps, and c.  This call takes none of the other outputs: the alignment rows, the graph tables,
+ * the strand flow and the queries stay with their own calls, on the unpruned graph.
+ * c is library-owned as vc_poa_msa_out is: valid until the next vc_poa_* or vc_large_* call or vc_large_release; a failed call
+ * leaves every pointer NULL.  Sequence s of the batch has status[s], score[s] (the local score of step 6; 0 where spoa leaves it
+ * unwritten) and the bytes corr[corr_off[s] .. corr_off[s + 1]).  status: VC_WIN_OK; VC_WIN_INVALID where WorstCaseAlignmentScore
+ * makes spoa throw for that member in step 6; VC_WIN_OVERFLOW for a member whose matrix the device cannot hold; the members of a
+ * group that is not VC_WIN_OK carry the group's status, score 0 and no bytes.
+ * Steps 1-5 run on schedule 2's kernels, one alignment per group and step; step 6 runs all members of all resident groups side by
+ * side (k_lg_rows, k_lg_qfwd, k_lg_qback, k_lg_correct in vc_large.hip).
+ * Checked before the device, in this order: as vc_poa_run_gaps, the batch included (pr and c count among the NULL pointers); then
+ * num_prune == 0 (the reference's num_prune - 1 would wrap); then a min_confidence or min_support that is NaN or negative:
+ * VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these. */
+typedef struct vc_poa_prune_params {
+    double   min_confidence, min_support;
+    uint32_t num_prune;
+} vc_poa_prune_params;
+typedef struct vc_poa_correct_out {
+    uint64_t n_seqs;                /* out: sequences of the batch                                                  */
+    const uint8_t*  status;         /* [n_seqs]                                                                     */
+    const int32_t*  score;          /* [n_seqs] the local score of the final alignment                              */
+    const uint64_t* corr_off;       /* [n_seqs + 1]                                                                 */
+    const uint8_t*  corr;           /* the corrected members, back to back                                          */
+    uint64_t        bytes;          /* copied out of the device for this stage                                      */
+} vc_poa_correct_out;
+int         vc_poa_run_correct(const vc_batch* b, const vc_poa_gap_params* p, const vc_poa_prune_params* pr, vc_result* r,
+                               vc_poa_correct_out* c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -560,8 +560,109 @@ def main_align(a):
     return 0
 
 
+def timed_correct(batch, rounds, correct=True, lib=None):
+    """-> (seconds, (jobs, launches, cells, bytes) of the `correct` line, (alignments, cells) of the `done` line) of one
+    vc_poa_run_correct (global, 5/-4/-8 linear, 0.22 / 0.19 / rounds) on the batch, or with correct=False of the consensus-only
+    vc_poa_run_gaps (lib: another library's handle, see parent_handle)"""
+    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
+    import re
+    import tempfile
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            status = (poa.run_batch_correct(batch, p, capi.VcPoaPruneParams(0.22, 0.19, rounds)) if correct else poa.run_batch(batch, p, lib))[1]
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read().decode()
+    if int((status != 0).sum()):
+        raise RuntimeError(f"{int((status != 0).sum())} groups not computed")
+    m = re.search(r"vc_large: correct jobs=(\d+) launches=(\d+) cells=(\d+) bytes=(\d+)", err)
+    d = re.search(r"vc_large: done alignments=(\d+) cells=(\d+)", err)
+    return dt, tuple(map(int, m.groups())) if m else (0, 0, 0, 0), tuple(map(int, d.groups())) if d else (0, 0)
+
+
+def main_correct(a):
+    """profiles/poa_correct_rate.txt: three plain and three correction calls in one process; with --parent-lib the consensus-only rate
+    of this library beside the parent commit's in alternating processes; one kernel trace of the correction call"""
+    batch = synth_groups(a)
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_correct_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    emit(f"POA groups with haplotype-aware correction: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100, PacBio-like errors, "
+         f"frac_partial=0, FASTQ), {int(batch.seq_off[-1])} bases; 5/-4/-8, global (kNW); 0.22 / 0.19 / {a.prune_rounds} rounds; one MI355X; "
+         f"synchronous; host clock around one call; one untimed call on all groups first, then three calls of each kind in the same process")
+    timed_correct(batch, a.prune_rounds, correct=False)
+    plain = [timed_correct(batch, a.prune_rounds, correct=False) for _ in range(3)]
+    emit(f"{'consensus only (vc_poa_run_gaps)':44s} " + "  ".join(f"{a.groups / r[0]:7.1f}" for r in plain) +
+         f" groups/s  ({'  '.join(f'{r[0]:.2f}' for r in plain)} s; {plain[0][2][0]} forward passes, {plain[0][2][1] / 1e9:.1f} G cells)")
+    runs = [timed_correct(batch, a.prune_rounds) for _ in range(3)]
+    jobs, launches, cells, nbytes = runs[0][1]
+    emit(f"{'correction (vc_poa_run_correct, Python copies incl.)':44s} " + "  ".join(f"{a.groups / r[0]:7.1f}" for r in runs) +
+         f" groups/s  ({'  '.join(f'{r[0]:.2f}' for r in runs)} s; build and rounds {runs[0][2][0]} forward passes, {runs[0][2][1] / 1e9:.1f} G cells; "
+         f"final stage {jobs} jobs in {launches} launches, {cells / 1e9:.1f} G cells, {nbytes / 1e6:.1f} MB copied out of the device)")
+    large.release()
+    if a.parent_lib:
+        # the two libraries alternate, each run a process of its own (a warm-up call, then three timed ones): parent, this, parent, this
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "0", "--correct", "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth)]
+        secs = {"parent": [], "this": []}
+        for which in ("parent", "this", "parent", "this"):
+            p = subprocess.run(cmd + (["--parent-lib", os.path.abspath(a.parent_lib)] if which == "parent" else []),
+                               capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"{which} library: run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1                          # nothing more is started on the device after a failed run
+            t = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            secs[which] += t
+            name = "library of the parent commit" if which == "parent" else "this library"
+            emit(f"{'consensus only, ' + name:44s} " + "  ".join(f"{a.groups / x:7.1f}" for x in t) +
+                 f" groups/s  ({'  '.join(f'{x:.3f}' for x in t)} s; a process of its own)")
+        par, cur = sorted(secs["parent"]), sorted(secs["this"])
+        med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2      # noqa: E731
+        emit(f"consensus-only time over the two alternated processes each: the parent's {par[0]:.3f} .. {par[-1]:.3f} s (median {med(par):.3f}), "
+             f"this library's {cur[0]:.3f} .. {cur[-1]:.3f} s (median {med(cur):.3f}): median against median {(med(cur) / med(par) - 1) * 100:+.2f} %; "
+             f"this library's median lies {'inside (or below)' if med(cur) <= par[-1] else 'ABOVE'} the range of the parent's own runs")
+    if not a.no_trace:
+        d = os.path.join(a.trace_dir, "correct")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+               sys.executable, os.path.abspath(__file__), "--child", "1", "--correct", "--prune-rounds", str(a.prune_rounds), "--groups", str(a.groups),
+               "--len", str(a.len), "--depth", str(a.depth)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"kernel trace: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return 1
+        ms = kernel_shares(d)
+        tot = sum(ms.values())
+        emit(f"kernel times of the correction call, a run of its own under rocprofv3 --kernel-trace --stats (64 groups first, then all): "
+             f"{tot / 1e3:.2f} s: " + ", ".join(f"{k} {v:.1f} ms ({v / tot * 100:.2f} %)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+    print("wrote", out)
+    return 0
+
+
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    if a.correct:
+        batch = synth_groups(a)
+        if a.child == 0:                          # consensus only, three calls after a full warm-up (this library's or the parent's)
+            lib = parent_handle(a.parent_lib) if a.parent_lib else None
+            timed_correct(batch, a.prune_rounds, correct=False, lib=lib)
+            print(json.dumps(dict(seconds=[timed_correct(batch, a.prune_rounds, correct=False, lib=lib)[0] for _ in range(3)])))
+            return
+        timed_correct(batch.slice(0, min(64, batch.n_windows)), a.prune_rounds)
+        dt, stage, done = timed_correct(batch, a.prune_rounds)
+        print(json.dumps(dict(seconds=dt, jobs=stage[0], cells=stage[2], build_cells=done[1])))
+        return
     if a.align and a.child == 0:                  # consensus only (vc_poa_run_gaps, global, --gaps), this library's or the parent's
         batch = synth_groups(a)
         g, e, q, c = GAPS[a.gaps] or (-8, -8, -8, -8)
@@ -649,15 +750,19 @@ def main():
     ap.add_argument("--strand", action="store_true", help="measure vc_poa_run_strand beside the plain call (profiles/poa_strand_rate.txt)")
     ap.add_argument("--graph", action="store_true", help="measure vc_poa_run_graph beside the consensus-only call (profiles/poa_graph_rate.txt)")
     ap.add_argument("--align", action="store_true", help="measure vc_poa_run_align's query stage beside the plain call (profiles/poa_align_rate.txt)")
+    ap.add_argument("--correct", action="store_true", help="measure vc_poa_run_correct beside the consensus-only call (profiles/poa_correct_rate.txt)")
+    ap.add_argument("--prune-rounds", type=int, default=3, help="--correct: num_prune (default 3)")
     ap.add_argument("--queries-per-group", type=int, default=32, help="--align: mutated members per group beside the held-out one")
     ap.add_argument("--parent-gaps", default="linear,affine,convex", help="--align --parent-lib: the gap models compared with the parent's library")
-    ap.add_argument("--parent-lib", default=None, help="--graph / --align: a libvechat_hip.so of the parent commit, for its consensus-only rate")
+    ap.add_argument("--parent-lib", default=None, help="--graph / --align / --correct: a libvechat_hip.so of the parent commit, for its consensus-only rate")
     ap.add_argument("--check", type=int, default=2, help="--graph: groups whose GFA is compared with the CPU restatement's")
     ap.add_argument("--append", action="store_true", help="--strand: keep what the output file holds and write below it")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
         return child(a)
+    if a.correct:
+        return main_correct(a)
     if a.align:
         return main_align(a)
     if a.graph:

@@ -121,6 +121,21 @@ class VcPoaAlignOut(C.Structure):
     ]
 
 
+class VcPoaPruneParams(C.Structure):
+    """vc_poa_prune_params: the thresholds and rounds of vc_poa_run_correct (the reference's defaults: 0.22 / 0.19 / 3)"""
+    _fields_ = [("min_confidence", C.c_double), ("min_support", C.c_double), ("num_prune", C.c_uint32)]
+
+
+class VcPoaCorrectOut(C.Structure):
+    """vc_poa_correct_out: everything out and owned by the library until its next vc_poa_* / vc_large_* call"""
+    _fields_ = [
+        ("n_seqs", C.c_uint64),
+        ("status", C.POINTER(C.c_uint8)), ("score", C.POINTER(C.c_int32)),
+        ("corr_off", C.POINTER(C.c_uint64)), ("corr", C.POINTER(C.c_uint8)),
+        ("bytes", C.c_uint64),
+    ]
+
+
 class VcStats(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64), ("alignments", C.c_uint64), ("dp_rows", C.c_uint64),
@@ -397,6 +412,11 @@ def load_hip():
             lib.vc_poa_run_align.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaStrandOut),
                                              C.POINTER(VcPoaGraphOut), C.POINTER(VcBatch), C.POINTER(VcPoaAlignOut)]
             lib.vc_poa_run_align.restype = C.c_int
+        # (likewise: the parent commit's library, beside which tools/gpu_poa_rate.py --correct measures, has no correction entry)
+        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_correct"):
+            lib.vc_poa_run_correct.argtypes = [C.POINTER(VcBatch), C.POINTER(VcPoaGapParams), C.POINTER(VcPoaPruneParams), C.POINTER(VcResult),
+                                               C.POINTER(VcPoaCorrectOut)]
+            lib.vc_poa_run_correct.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

@@ -58,6 +58,13 @@
 //               batch's bytes or their reverse-complement view (k_lg_views on the query batch);
 //   k_lg_qback  <GM>, one lane per job: k_lg_back's walk (back_walk) into the job's own pair area of rows + length pairs;
 //   k_lg_qpack  one wave per job: the pairs compact behind the host's prefix offsets, nodes and positions apart.
+//   Correction, vc_poa_run_correct only (LArgs::correct): a group goes on after its build and its consensus through the prune
+//   phases of schedule 0 -- prune + largest component, then num_prune - 1 rounds of one alignment per member and step with the
+//   call's engine, add-weights, prune + largest component (k_lg_prep / k_lg_fwd / k_lg_back / k_lg_apply as above) --, and the
+//   finished groups' members are then corrected side by side by the query stage's kernels: a job per member, the "query batch"
+//   being the group batch itself and the type local (k_lg_rows, k_lg_qfwd, k_lg_qback), and
+//   k_lg_correct <0> one wave per job: the pairs with a node, counted; <1> their nodes' bytes, compact behind the host's prefix
+//               offsets (ballot and population count per tile of 64 pairs, a carried total) -- GenerateCorrectedSequence.
 //
 // Limits, every schedule: a sequence is shorter than 65 535 bases; beyond that only the device memory bounds a window or group,
 // and one whose tables or matrix it cannot hold at all comes back VC_WIN_OVERFLOW.  Where the reference throws (an invalid
@@ -77,8 +84,11 @@
 //                           "vc_large: graph launches=K bytes=B" (vc_poa_run_graph: k_lg_graph<1> launches, bytes copied out),
 //                           "vc_large: align jobs=J launches=K cells=C bytes=B" (vc_poa_run_align with queries: the queries of the
 //                           groups that finished, k_lg_qfwd launches, their rows x columns with both strands counted, bytes copied out),
+//                           "vc_large: correct jobs=J launches=K cells=C bytes=B" (vc_poa_run_correct: the members of the groups that
+//                           finished, k_lg_qfwd launches of the final stage, their rows x columns, bytes copied out),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes of the build, their rows x
-//                           columns summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes).
+//                           columns summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes;
+//                           vc_poa_run_correct counts the rounds' passes too, not the final stage's).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -239,7 +249,7 @@ int check_device(int32_t device) {
 
 // What a call wants beside consensus and status, and where each output goes (the caller's out-structs); vc_large_run's is empty.
 struct PoaRequest {
-    enum : uint32_t { MSA = 1, STRAND = 2, GRAPH = 4, ALIGN = 8 };
+    enum : uint32_t { MSA = 1, STRAND = 2, GRAPH = 4, ALIGN = 8, CORRECT = 16 };
     uint32_t required = 0;                             // the outputs the entry cannot do without; 0 leaves what an earlier call handed out alone
     vc_poa_msa_out* msa = nullptr;                     // rows, members and coverage as msa_flags say (0: n_groups only)
     vc_poa_strand_out* strand = nullptr;               // the strand flow, and its choices
@@ -248,6 +258,8 @@ struct PoaRequest {
     vc_poa_align_out* align = nullptr;
     uint32_t msa_flags = 0, route = 0, align_flags = 0;
     uint64_t nq = 0, nbytes = 0;                       // sequences and bytes of the query batch
+    const vc_poa_prune_params* prune = nullptr;        // vc_poa_run_correct: the thresholds and rounds, and the corrected members
+    vc_poa_correct_out* correct = nullptr;
     bool rows() const { return msa_flags != 0; }                           // k_lg_msa runs
     bool keeps_labels() const { return msa_flags != 0 || graph != nullptr; }   // the edges keep sequence labels
     bool keeps_seqs() const { return keeps_labels(); }                     // the windows keep sq_begin / sq_member
@@ -305,6 +317,18 @@ struct Outputs {
             ao->bytes = bytes;
         }
     } align;
+    struct Correct {                                   // vc_poa_correct_out, one entry per sequence of the batch
+        std::vector<uint8_t> status, corr;
+        std::vector<int32_t> score;
+        std::vector<uint64_t> corr_off;
+        uint64_t bytes = 0;                            // copied out of the device
+        void publish(vc_poa_correct_out* co, uint64_t nseq) {
+            if (corr_off.empty()) corr_off.assign(nseq + 1, 0);                 // no run: the empty tables
+            co->n_seqs = nseq;
+            co->status = table(status); co->score = table(score); co->corr_off = corr_off.data(); co->corr = table(corr);
+            co->bytes = bytes;
+        }
+    } correct;
     void clear() { *this = Outputs{}; }
 } g_out;
 
@@ -341,6 +365,11 @@ struct Run {
     std::vector<uint32_t> q_part_of, q_count;          // [nq]
     std::vector<uint64_t> q_first;                     // [nq]
     uint64_t q_jobs = 0, q_launches = 0, q_cells = 0;
+    // the correction stage: per host group the corrected bytes, per sequence of the batch where its own lie; the "correct" line
+    std::vector<std::vector<uint8_t>> c_part;
+    std::vector<uint32_t> c_part_of, c_count;          // [sequences]
+    std::vector<uint64_t> c_first;                     // [sequences]
+    uint64_t c_jobs = 0, c_launches = 0, c_cells = 0;
 };
 
 // the windows in flight together: their ids, their tables in the arena, their LWin here and on the device
@@ -865,6 +894,117 @@ void assemble_align(Run& R) {
                                (unsigned long long)R.q_launches, (unsigned long long)R.q_cells, (unsigned long long)S.bytes);
 }
 
+// The correction stage of the groups that finished, while their tables are resident (vc_poa_run_correct): collect_align's shape
+// with a job per member -- the rows of every final graph once (k_lg_rows), the members' local forward passes and backtracks in
+// launches that fit the matrix budget (a group's members are independent now: nothing is added), the pairs with a node counted
+// (k_lg_correct<0>), the job table back in one copy, the host's prefix offsets, then the bytes compact (k_lg_correct<1>) and out
+// in one copy.
+int collect_correct(Run& R, Group& G) {
+    const vc_batch* b = R.b;
+    Outputs::Correct& S = g_out.correct;
+    LArgs a = R.a;
+    a.algorithm = 0;                                                       // kSW with the call's scores and gap model
+    a.q_off = a.seq_off; a.q_bases = a.bases; a.q_rc = nullptr;            // the "query batch": the group batch's own arrays
+    std::vector<LJob> jobs;
+    std::vector<uint32_t> act, refused;                                    // jobs with a forward pass; jobs whose matrix the device cannot hold
+    uint64_t area = 0;
+    for (const uint32_t k : finished(R, G)) {
+        const LWin& W = G.hw[k];
+        const LGraph& g = W.gr[W.cur];
+        const uint32_t N = g.n_nodes;
+        for (uint32_t s = W.s0; s < W.s0 + W.nseq; ++s) {
+            LJob J{};
+            J.win = k; J.qs = s; J.qlen = (uint32_t)(b->seq_off[s + 1] - b->seq_off[s]); J.status = VC_WIN_OK;
+            if (N != 0 && J.qlen != 0) {                                   // else an empty alignment: the empty correction, score 0
+                if (worst_case(a.match, a.gap, a.gap_e, a.gap_q, a.gap_c, (int64_t)J.qlen + 8, N) < (int64_t)KNEG || g.n_rank != N) {
+                    J.status = VC_WIN_INVALID;
+                } else {
+                    J.rows = N; J.area = area;
+                    area += (uint64_t)N + J.qlen;
+                    act.push_back((uint32_t)jobs.size());
+                }
+            }
+            jobs.push_back(J);
+        }
+    }
+    if (jobs.empty()) return VC_OK;
+    R.c_jobs += jobs.size();
+    uint64_t total = 0;
+    std::vector<uint8_t> bytes;
+    if (!act.empty()) {
+        DevMem mem;
+        LJob* d_job = nullptr; uint32_t* d_list = nullptr; uint64_t* d_hoff = nullptr; int32_t* d_pairs = nullptr; uint8_t* d_out = nullptr;
+        if (!mem.alloc(&d_job, jobs.size(), jobs.data()) || !mem.alloc(&d_list, act.size()) || !mem.alloc(&d_hoff, act.size()) ||
+            !mem.alloc(&d_pairs, 2 * area))
+            return fail(VC_ERR_HIP, "device allocation of the correction jobs failed");
+        a.job = d_job; a.q_pairs = d_pairs;
+        const uint32_t n = (uint32_t)G.ids.size(), nj = (uint32_t)jobs.size();
+        hipLaunchKernelGGL(k_lg_rows, dim3((n + 63) / 64), dim3(64), 0, 0, a);
+        if (hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "the correction stage's row kernel failed");
+        auto matrix_cells = [&](uint32_t j) { return ((uint64_t)jobs[j].rows + 1) * ((uint64_t)jobs[j].qlen + 1) * R.planes; };
+        auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>&, uint64_t, void* H) -> int {
+            const uint32_t nl = (uint32_t)list.size();
+            f.H = (int32_t*)H;
+            if (f.gaps == 0) launch_query<0>(f, nl, 1, true);
+            else if (f.gaps == 1) launch_query<1>(f, nl, 1, true);
+            else launch_query<2>(f, nl, 1, true);
+            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, "a correction kernel failed");
+            for (const uint32_t j : list) R.c_cells += (uint64_t)jobs[j].rows * jobs[j].qlen;
+            return VC_OK;
+        };
+        if (const int rc = launch_loop(a, act, R.mat_budget / 4, 4, d_list, d_hoff,
+                                       {"device allocation of the correction matrices failed", "copy of a correction launch failed"}, R.c_launches,
+                                       matrix_cells, as_packed, [&](uint32_t j) { refused.push_back(j); return VC_OK; }, body))
+            return rc;
+        hipLaunchKernelGGL(k_lg_correct<0>, dim3(nj), dim3(64), 0, 0, a);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(jobs.data(), d_job, jobs.size() * sizeof(LJob), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(VC_ERR_HIP, "the count kernel of the correction stage or the copy of its jobs failed");
+        S.bytes += jobs.size() * sizeof(LJob);
+        for (LJob& J : jobs) { J.pair_off = total; total += J.ncorr; }
+        if (total) {
+            bytes.resize(total);
+            bool ok = mem.alloc(&d_out, total) && hipMemcpy(d_job, jobs.data(), jobs.size() * sizeof(LJob), hipMemcpyHostToDevice) == hipSuccess;
+            if (ok) {
+                a.msa_out = d_out;
+                hipLaunchKernelGGL(k_lg_correct<1>, dim3(nj), dim3(64), 0, 0, a);
+                ok = hipGetLastError() == hipSuccess && hipMemcpy(bytes.data(), d_out, total, hipMemcpyDeviceToHost) == hipSuccess;
+            }
+            if (!ok) return fail(VC_ERR_HIP, "the correction kernel or its copy failed");
+            S.bytes += total;
+        }
+    }
+    for (const uint32_t j : refused) jobs[j].status = VC_WIN_OVERFLOW;
+    const uint32_t pi = (uint32_t)R.c_part.size();
+    for (const LJob& J : jobs) {
+        const bool ok = J.status == VC_WIN_OK;
+        S.status[J.qs] = (uint8_t)J.status;
+        S.score[J.qs] = ok ? J.score[0] : 0;
+        R.c_part_of[J.qs] = pi; R.c_first[J.qs] = J.pair_off; R.c_count[J.qs] = ok ? J.ncorr : 0;
+    }
+    R.c_part.push_back(std::move(bytes));
+    return VC_OK;
+}
+
+// the corrected members in batch order (a group that was not computed passes its status on), and the stage's log line
+void assemble_correct(Run& R) {
+    Outputs::Correct& S = g_out.correct;
+    const vc_batch* b = R.b;
+    S.corr_off.assign(R.nseq_all + 1, 0);
+    for (uint32_t w = 0; w < R.nw; ++w) {
+        for (uint32_t s = b->win_seq_off[w]; s < b->win_seq_off[w + 1]; ++s) {
+            if (R.status[w] != VC_WIN_OK) { S.status[s] = R.status[w]; S.score[s] = 0; R.c_count[s] = 0; }
+            if (R.c_count[s]) {
+                const uint8_t* src = R.c_part[R.c_part_of[s]].data() + R.c_first[s];
+                S.corr.insert(S.corr.end(), src, src + R.c_count[s]);
+            }
+            S.corr_off[s + 1] = S.corr.size();
+        }
+    }
+    R.c_part.clear();
+    if (R.kn.log) std::fprintf(stderr, "vc_large: correct jobs=%llu launches=%llu cells=%llu bytes=%llu\n", (unsigned long long)R.c_jobs,
+                               (unsigned long long)R.c_launches, (unsigned long long)R.c_cells, (unsigned long long)S.bytes);
+}
+
 // One group from its tables to its results: a window whose table filled goes back to pending, the others leave their status,
 // consensus and outputs.  A single window the device has no room for is VC_WIN_OVERFLOW; more than one is an error.
 int run_group(Run& R, Group& G) {
@@ -883,12 +1023,13 @@ int run_group(Run& R, Group& G) {
         const LWin& W = G.hw[k];
         if (W.grow) { regrow(R, w, W); continue; }
         R.status[w] = (uint8_t)W.status;
-        R.out[w].resize(W.cons_n);
-        if (W.cons_n && hipMemcpy(R.out[w].data(), W.cons, W.cons_n, hipMemcpyDeviceToHost) != hipSuccess)
+        R.out[w].resize(R.a.correct && W.status != VC_WIN_OK ? 0 : W.cons_n);          // (a group that failed in a round keeps no consensus)
+        if (!R.out[w].empty() && hipMemcpy(R.out[w].data(), W.cons, W.cons_n, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(VC_ERR_HIP, "copy of a consensus failed");
     }
     if (R.q.rows()) if (const int rc = collect_msa(R, G)) return rc;
     if (R.q.graph) if (const int rc = collect_graph(R, G)) return rc;
+    if (R.q.correct) if (const int rc = collect_correct(R, G)) return rc;
     return R.q.has_queries() ? collect_align(R, G) : VC_OK;
 }
 
@@ -941,6 +1082,11 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
         if (q.query_strands() == 2) { S.score_rev.assign(q.nq, 0); S.reversed.assign(q.nq, 0); }
         R.q_part_of.assign(q.nq, 0); R.q_count.assign(q.nq, 0); R.q_first.assign(q.nq, 0);
     }
+    if (q.correct) {
+        Outputs::Correct& S = g_out.correct;
+        S.status.assign(R.nseq_all, VC_WIN_OVERFLOW); S.score.assign(R.nseq_all, 0);
+        R.c_part_of.assign(R.nseq_all, 0); R.c_count.assign(R.nseq_all, 0); R.c_first.assign(R.nseq_all, 0);
+    }
 
     // budgets from free device memory (what this library keeps cached counts as free)
     size_t free_b = 0, total_b = 0;
@@ -971,6 +1117,7 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     if (q.rows()) assemble_msa(R);
     if (q.graph) assemble_graph(R);
     if (q.has_queries()) assemble_align(R);
+    if (q.correct) assemble_correct(R);
     return assemble(R, r);
 }
 
@@ -1029,10 +1176,17 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
         }
     }
     if (q.required & PoaRequest::ALIGN) if (const int rc = check_queries(q, b)) return rc;
+    a.num_prune = 1;
+    if (q.required & PoaRequest::CORRECT) {
+        // vc_poa_run_correct's own arguments, after the batch and before the device
+        if (q.prune->num_prune == 0) return fail(VC_ERR_ARG, "num_prune must be >= 1 (the reference's num_prune - 1 rounds would wrap)");
+        if (!(q.prune->min_confidence >= 0) || !(q.prune->min_support >= 0)) return fail(VC_ERR_ARG, "min_confidence and min_support must be >= 0 and not NaN");
+        a.correct = 1; a.min_conf = q.prune->min_confidence; a.min_sup = q.prune->min_support; a.num_prune = q.prune->num_prune;
+    }
     if (const int rc = check_device(device)) return rc;
     r->cons_off[0] = 0;
     if (nw == 0) return VC_OK;
-    a.num_prune = 1; a.mode = 2; a.algorithm = (uint32_t)algorithm;
+    a.mode = 2; a.algorithm = (uint32_t)algorithm;
     return run_windows(device, a, b, caps, kn, r, q);
 }
 
@@ -1043,7 +1197,8 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     vc_poa_msa_out* const o = q.msa;
     if (q.graph) *q.graph = vc_poa_graph_out{};                            // a failed call leaves every pointer NULL
     if (q.align) { q.align_flags = q.align->flags; *q.align = vc_poa_align_out{}; q.align->flags = q.align_flags; }
-    if (!p || !b || !r || ((q.required & PoaRequest::MSA) && !o) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+    if (q.correct) *q.correct = vc_poa_correct_out{};
+    if (!p || !b || !r || ((q.required & PoaRequest::MSA) && !o) || ((q.required & PoaRequest::CORRECT) && (!q.prune || !q.correct)) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
     if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
@@ -1069,6 +1224,7 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     if (rc != VC_OK && q.required) g_out.clear();
     if (rc != VC_OK) return rc;
     if (q.required & PoaRequest::ALIGN) g_out.align.publish(q.align, q);
+    if (q.required & PoaRequest::CORRECT) g_out.correct.publish(q.correct, b->n_windows ? b->win_seq_off[b->n_windows] : 0);
     if (q.graph) {
         q.graph->n_groups = b->n_windows;
         if (b->n_windows) g_out.graph.publish(q.graph);
@@ -1152,6 +1308,12 @@ int vc_poa_run_graph(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r
 int vc_poa_run_align(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_strand_out* s, vc_poa_graph_out* g,
                      const vc_batch* q, vc_poa_align_out* a) {
     return poa_run(p, b, r, PoaRequest{PoaRequest::ALIGN, nullptr, s, g, q, a});
+}
+
+int vc_poa_run_correct(const vc_batch* b, const vc_poa_gap_params* p, const vc_poa_prune_params* pr, vc_result* r, vc_poa_correct_out* c) {
+    PoaRequest q{PoaRequest::CORRECT};
+    q.prune = pr; q.correct = c;
+    return poa_run(p, b, r, q);
 }
 
 }  // extern "C"

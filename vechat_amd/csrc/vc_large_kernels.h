@@ -75,6 +75,9 @@ struct LArgs {
     int32_t gap_e, gap_q, gap_c;                       // mode 2: spoa's e, q, c after Create's subtype rule
     uint32_t msa;                                      // mode 2: VC_POA_MSA | VC_POA_MSA_CONSENSUS | VC_POA_COVERAGE, 0 elsewhere
     uint32_t graph;                                    // mode 2, vc_poa_run_graph: 1 paths by scatter and compaction, 2 by the literal walk; 0 elsewhere
+    // mode 2, vc_poa_run_correct: 1 sends a group through the prune phases after its build (min_conf, min_sup, num_prune as in
+    // mode 0; W.L / W.fasta: length of the first non-empty member, 1 where it has no quality); 0 elsewhere
+    uint32_t correct;
     // mode 2, vc_poa_run_strand (strand = 1; nullptr / 0 elsewhere): the strand views of the batch, k_lg_views, laid out as bases /
     // quals are, and the choice per sequence of the batch
     uint32_t strand;
@@ -89,21 +92,25 @@ struct LArgs {
     int32_t* H;
     uint8_t* msa_out;
     // vc_poa_run_align only (nullptr elsewhere): the jobs of the query stage (k_lg_qfwd / k_lg_qback: a.list holds job indices), the
-    // query batch's offsets and bytes, its reverse-complement view (VC_POA_ALIGN_STRANDS), the jobs' pair areas and the packed pairs
+    // query batch's offsets and bytes, its reverse-complement view (VC_POA_ALIGN_STRANDS), the jobs' pair areas and the packed pairs.
+    // vc_poa_run_correct's final stage fills them too: a job per member, q_off / q_bases the group batch's own arrays, algorithm 0,
+    // and k_lg_correct<1> writes the corrected bytes to msa_out
     struct LJob* job;
     const uint64_t* q_off;
     const uint8_t *q_bases, *q_rc;
     int32_t *q_pairs, *q_out;
 };
 
-// One query against the finished graph of its group (vc_poa_run_align): filled by the host but for the results.
+// One query against the finished graph of its group (vc_poa_run_align), or one member against the final pruned graph of its
+// group (vc_poa_run_correct): filled by the host but for the results.
 struct LJob {
     uint32_t win, qs;                                  // the group (index among the windows in flight), the query (sequence of the query batch)
     uint32_t rows, qlen, status;                       // graph rows, query length; VC_WIN_OK, or VC_WIN_INVALID from the backtrack
     uint32_t max_i[2], max_j[2];                       // end cell per strand
     int32_t score[2];                                  // spoa's *score per strand
     uint32_t rev, npairs;                              // the strand the backtrack walked, its pairs
-    uint64_t area, pair_off;                           // pairs: first of the job's area (rows + qlen of them) in q_pairs, first in q_out
+    uint32_t ncorr;                                    // vc_poa_run_correct: the pairs with a node, k_lg_correct<0> (it takes the struct's padding)
+    uint64_t area, pair_off;                           // pairs: first of the job's area (rows + qlen of them) in q_pairs, first in q_out (k_lg_correct<1>: first byte in msa_out)
 };
 
 // ------------------------------------------------------------------ graph tables
@@ -622,6 +629,13 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     W.msa_rows = 0; W.row_size = 0; W.rev = 0; W.gr_cols = 0; W.gr_path = 0;
     if (a.mode == 2) {                                                     // POA group: sequence 0 meets the empty graph in k_lg_prep
         W.phase = PH_BUILD; W.j = 0; W.k = 0;
+        if (a.correct) {                                                   // window_len and if_fasta of window.cpp:301-309: the first non-empty member's
+            W.L = 0; W.fasta = 0;
+            for (uint32_t s = W.s0; s < W.s0 + W.nseq && W.L == 0; ++s) {
+                W.L = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
+                W.fasta = a.has_qual[s] == 0;
+            }
+        }
         if (W.nseq == 0) finish_poa(W);                                    // no sequence: the empty consensus
         return;
     }
@@ -1081,6 +1095,36 @@ __global__ __launch_bounds__(64) void k_lg_qpack(LArgs a, uint64_t total) {
     }
 }
 
+// GenerateCorrectedSequence (graph.cpp:1167-1179) of every member of vc_poa_run_correct, one wave per job: of the job's pairs
+// (k_lg_qback, against the final pruned graph of its group) those with a node are kept, as the decoded byte of the node.
+//   PH 0: J.ncorr, the kept pairs, for the host's prefix offsets.
+//   PH 1: the bytes, compact at a.msa_out + J.pair_off: per tile of 64 pairs a 64-bit ballot of `keep`, the lane's slot from the
+//     population count of the lower lanes plus the total carried over the tiles before.  A store lies below J.ncorr, the job's own
+//     extent, and a node below the graph's count.
+template <uint32_t PH>
+__global__ __launch_bounds__(64) void k_lg_correct(LArgs a) {
+    LJob& J = a.job[blockIdx.x];
+    const uint32_t lane = threadIdx.x, np = J.npairs;
+    if (np == 0) { if (PH == 0 && lane == 0) J.ncorr = 0; return; }        // (no forward pass, an empty alignment or a refused job: no area to read)
+    const int2* src = (const int2*)(a.q_pairs + 2 * J.area);
+    const LWin& W = a.win[J.win];
+    const LGraph& g = W.gr[W.cur];
+    uint8_t* out = a.msa_out + J.pair_off;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < np; base += 64) {
+        const uint32_t k = base + lane;
+        const int32_t node = k < np ? src[k].x : -1;
+        const bool keep = node != -1;
+        const uint64_t b = __ballot(keep);
+        if constexpr (PH == 1) {
+            const uint32_t slot = carry + (uint32_t)__popcll(b & ((1ull << lane) - 1));
+            if (keep && slot < J.ncorr && (uint32_t)node < g.n_nodes) out[slot] = (uint8_t)W.decoder[g.code[node]];
+        }
+        carry += (uint32_t)__popcll(b);
+    }
+    if (PH == 0 && lane == 0) J.ncorr = carry;
+}
+
 __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
     const uint32_t w = blockIdx.x * 64 + threadIdx.x;
     if (w >= a.n) return;
@@ -1095,26 +1139,34 @@ __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
         if (rc == -2) return;
         if (rc) { fail_window(W, VC_WIN_INVALID); return; }
         if (a.strand) { a.s_rev[s] = (uint8_t)W.rev; a.s_score[s] = W.score[0]; a.s_score_rev[s] = W.score[1]; }
-        if (a.mode == 0) {
+        if (a.mode == 0 || a.correct) {
             const uint32_t len = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
             if (!hq) W.total += (double)len;
             else for (uint32_t q = 0; q < len; ++q) W.total += a.lut_d[a.quals[a.seq_off[s] + q]];
         }
         if (++W.j < W.nseq) return;
         if (a.mode == 1) { finish_linear(a, W); return; }
-        if (a.mode == 2) { finish_poa(W); return; }
+        if (a.mode == 2) {
+            finish_poa(W);                                                 // the consensus of the unpruned graph, whatever follows
+            if (!a.correct || W.L == 0) return;                            // (L == 0: no non-empty member, nothing to prune or correct)
+            W.avg = W.fasta ? 2.0 * W.total / W.L : 2.0 * W.total / W.L * 1000;
+            if (!prune_and_keep_largest(a, W)) return;                     // (a table filled: the group runs again)
+            W.j = 0; W.k = 0;
+            if (a.num_prune > 1) W.phase = PH_ROUND;                       // else done: the correction stage reads W.gr[W.cur]
+            return;
+        }
         const uint16_t window_len = (uint16_t)W.L;                         // window.cpp:216
         W.avg = W.fasta ? 2.0 * W.total / window_len : 2.0 * W.total / window_len * 1000;
         if (!prune_and_keep_largest(a, W)) return;
         W.j = 0; W.k = 0;
         W.phase = a.num_prune > 1 ? PH_ROUND : PH_FINAL;
     } else if (W.phase == PH_ROUND) {
-        // the backbone's qualities_[0].first is never nullptr: quality overload (a dummy '!' gives 0)
-        if (!add_weights(a, W, W.gr[W.cur], W.pairs, np, s, W.j == 0 ? true : hq)) return;
+        // the backbone's qualities_[0].first is never nullptr: quality overload (a dummy '!' gives 0); a group has no backbone
+        if (!add_weights(a, W, W.gr[W.cur], W.pairs, np, s, a.mode != 2 && W.j == 0 ? true : hq)) return;
         if (++W.j < W.nseq) return;
         if (!prune_and_keep_largest(a, W)) return;
         W.j = 0;
-        if (++W.k + 1 >= a.num_prune) W.phase = PH_FINAL;
+        if (++W.k + 1 >= a.num_prune) W.phase = a.mode == 2 ? PH_DONE : PH_FINAL;      // a group's members are corrected side by side, k_lg_correct
     } else {                                                               // GenerateCorrectedSequence, graph.cpp:1167-1179
         const LGraph& P = W.gr[W.cur];
         W.cons_n = 0;

@@ -6,7 +6,8 @@ semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chos
 
     python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [-r 0|1|2]
                              [--coverage] [--both-strands] [--gfa | --gfa-consensus] [--graphviz FILE]
-                             [--align QUERIES --align-out FILE [--align-both-strands]] [--device D] FILE [FILE ...]
+                             [--align QUERIES --align-out FILE [--align-both-strands]]
+                             [--correct FILE [--min-confidence D] [--min-support S] [--prune-rounds K]] [--device D] FILE [FILE ...]
 
 prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`,
 or with -r 1 / -r 2 the multiple sequence alignment of its records as FASTA (`>name` / row, with -r 2 a last row `>Consensus`;
@@ -26,6 +27,12 @@ poa_msa() is the same over groups in memory (vc_poa_run_msa).
 --align QUERIES --align-out FILE aligns every record of QUERIES against the finished graph of every input file without adding it
 (spoa's engine->Align(sequence, graph, &score); vc_poa_run_align, poa_align()) and writes FILE (align_tsv); the output on stdout
 is unchanged, and with the consensus or the graph as that output the groups are built once, in the same call.  --align-both-strands tries every query on both strands and reports the better, ties as given.
+--correct FILE writes every record of every input file back with its errors removed and its variants kept: VeChat's
+variation-aware correction on the group's graph (prune by confidence and support, largest component, re-weight and prune again,
+then the record's local alignment against what is left; vc_poa_run_correct, poa_correct()), as FASTA, one record per input
+record under its own name, in input order, a record that aligns nowhere with an empty sequence line.  The output on stdout is
+unchanged.  --min-confidence / --min-support / --prune-rounds default to the reference's 0.22 / 0.19 / 3.  It does not go
+with -r 1 / -r 2, --gfa*, --graphviz, --both-strands or --align: those describe the unpruned graph and stay with their own calls.
 The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
 as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
 non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
@@ -518,6 +525,73 @@ def poa_align(groups, queries, algorithm="global", match=5, mismatch=-4, gap=-8,
     return res
 
 
+class Corrected:
+    """One group's result of poa_correct: consensus (bytes; of the unpruned graph, poa_consensus's), reads (the corrected bytes of
+    every member, in member order; empty where the member aligns nowhere or is empty), scores (numpy int32: the local score of
+    every member against the final graph) and status (numpy uint8, capi.VC_WIN_* per member)."""
+    __slots__ = ("consensus", "reads", "scores", "status")
+
+    def __init__(self, consensus, reads, scores, status):
+        self.consensus, self.reads, self.scores, self.status = consensus, reads, scores, status
+
+    def __iter__(self):
+        return iter((self.consensus, self.reads, self.scores, self.status))
+
+
+def _prune_params(min_confidence, min_support, prune_rounds):
+    """the checks of vc_poa_run_correct, before any batch is made"""
+    if isinstance(prune_rounds, bool) or not isinstance(prune_rounds, (int, np.integer)) or not 1 <= int(prune_rounds) < 2 ** 32:
+        raise ValueError(f"prune_rounds must be an integer >= 1, not {prune_rounds!r}")
+    for name, v in (("min_confidence", min_confidence), ("min_support", min_support)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not float(v) >= 0:
+            raise ValueError(f"{name} must be a number >= 0, not {v!r}")
+    return capi.VcPoaPruneParams(float(min_confidence), float(min_support), int(prune_rounds))
+
+
+def run_batch_correct(batch, params, prune, lib=None):
+    """vc_poa_run_correct (params: capi.VcPoaGapParams; prune: capi.VcPoaPruneParams) on a capi.Batch -> (list of Corrected, status
+    array per group).  Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error."""
+    lib = lib or capi.load_hip()
+    if not hasattr(lib, "vc_poa_run_correct"):
+        raise PoaError("this libvechat_hip.so has no vc_poa_run_correct: it was built before the entry point existed; rebuild it")
+    n = batch.n_windows
+    cons, off, status, r, vb = _result_buffers(batch)
+    co = capi.VcPoaCorrectOut()
+    rc = lib.vc_poa_run_correct(C.byref(vb), C.byref(params), C.byref(prune), C.byref(r), C.byref(co))
+    if rc != 0:
+        raise PoaError(f"vc_poa_run_correct failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    ns = int(co.n_seqs)
+    st, sc, po = _table(co.status, ns), _table(co.score, ns), _table(co.corr_off, ns + 1).astype(np.int64)
+    corr = _table(co.corr, int(po[-1])).tobytes()
+    wso = [int(x) for x in batch.win_seq_off]
+    res = [Corrected(cons[int(off[w]):int(off[w + 1])].tobytes(), [corr[int(po[s]):int(po[s + 1])] for s in range(wso[w], wso[w + 1])],
+                     sc[wso[w]:wso[w + 1]].copy(), st[wso[w]:wso[w + 1]].copy()) for w in range(n)]
+    return res, status[:n]
+
+
+def poa_correct(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+                gap_extend=None, gap_open2=None, gap_extend2=None, min_confidence=0.22, min_support=0.19, prune_rounds=3):
+    """Haplotype-aware correction of every member of every group (vc_poa_run_correct; the flow is in include/vechat_hip.h): the
+    group's graph is built as poa_consensus builds it, pruned by confidence and support down to its largest component,
+    re-weighted by the members and pruned again (prune_rounds - 1 times, with the call's engine), and every member is read off its
+    local alignment against what is left -- its errors removed, its variants kept -> list of Corrected (consensus, reads, scores,
+    status).  The defaults are the reference's.  Parameters, PoaError and strict as poa_consensus: a group that was not computed
+    raises, or with strict=False comes back as None; a member the device could not align carries its own status in
+    Corrected.status and has an empty read.  ValueError for prune_rounds < 1 or a threshold that is negative or NaN."""
+    prune = _prune_params(min_confidence, min_support, prune_rounds)
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    res, status = run_batch_correct(group_batch(groups), p, prune, lib)
+    bad = _not_computed(status, strict)
+    return [None if w in bad else c for w, c in enumerate(res)]
+
+
+def corrected_fasta(records, results):
+    """The text of --correct: records[w] the (name, data, quality) records of group w, results[w] its Corrected -> FASTA, one
+    record per member under its own name, groups in input order; an empty correction has an empty sequence line."""
+    return b"".join(b">%s\n%s\n" % (_bytes(name, "record name"), read)
+                    for recs, c in zip(records, results) for (name, _, _), read in zip(recs, c.reads))
+
+
 _STATUS_NAME = {capi.VC_WIN_OK: b"OK", capi.VC_WIN_OVERFLOW: b"OVERFLOW", capi.VC_WIN_INVALID: b"INVALID"}
 
 
@@ -576,6 +650,12 @@ def parse_args(argv=None):
                          "strand, pairs (node:pos,... with * for none)")
     ap.add_argument("--align-both-strands", action="store_true",
                     help="with --align: align every query as given and reverse-complemented and report the better strand")
+    ap.add_argument("--correct", metavar="FILE", default=None,
+                    help="also write every record, haplotype-aware corrected on its file's graph, to FILE as FASTA (the consensus on "
+                         "stdout is unchanged); not with -r 1 / -r 2, --gfa*, --graphviz, --both-strands or --align")
+    ap.add_argument("--min-confidence", type=float, default=0.22, metavar="D", help="with --correct: minimum confidence of an edge (default 0.22)")
+    ap.add_argument("--min-support", type=float, default=0.19, metavar="S", help="with --correct: minimum support of an edge (default 0.19)")
+    ap.add_argument("--prune-rounds", type=int, default=3, metavar="K", help="with --correct: number of prune rounds, >= 1 (default 3)")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="+", metavar="FILE")
     return ap.parse_args(argv)
@@ -594,6 +674,10 @@ def main(argv=None):
     if (a.align is None) != (a.align_out is None) or (a.align_both_strands and a.align is None):
         print("vechat_amd.poa: --align QUERIES and --align-out FILE go together (--align-both-strands with them)", file=sys.stderr)
         return 1
+    if a.correct is not None and (a.r != 0 or gfa or a.graphviz is not None or a.both_strands or a.align is not None):
+        print("vechat_amd.poa: --correct does not go with -r 1 / -r 2, --gfa / --gfa-consensus, --graphviz, --both-strands or --align "
+              "(they describe the unpruned graph: run them on their own)", file=sys.stderr)
+        return 1
     # what the command line asks for: the alignment rows or the coverage (a vc_poa_msa_out, which vc_poa_run_align does not carry),
     # the graph tables, the queries
     want_msa = a.r != 0 or a.coverage
@@ -605,6 +689,14 @@ def main(argv=None):
         groups = [[(data, qual) for _, data, qual in recs] for recs in records]
         gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
         p = _gap_params(a.l, a.m, a.n, a.g, a.device, **gaps)
+        if a.correct is not None:
+            # one call: the consensus of the unpruned graph (with --coverage a second, plain one below) and every record corrected
+            res, status = run_batch_correct(group_batch(groups), p, _prune_params(a.min_confidence, a.min_support, a.prune_rounds))
+            _not_computed(status, True)
+            with open(a.correct, "wb") as f:
+                f.write(corrected_fasta(records, res))
+            if not want_msa:
+                cons = [c.consensus for c in res]
         if a.align is not None:
             # every query against every group.  Without rows or coverage this one call builds the groups once and gives the
             # consensus or the graph too; beside them it is a call of its own
@@ -617,6 +709,8 @@ def main(argv=None):
                 f.write(align_tsv([name for name, _, _ in qrecs], a.files, res))
         if a.align is not None and not want_msa:
             cons, graphs = (None if gfa else c), gr
+        elif cons is not None:
+            pass
         elif want_graph:
             # one call for everything: the graph carries the consensus, and with -r 1 / -r 2 / --coverage the alignment beside it
             graphs, status = run_batch_graph(group_batch(groups), p, msa_flags, strands=a.both_strands)[:2]
