@@ -622,6 +622,68 @@ typedef struct vc_poa_correct_out {
 int         vc_poa_run_correct(const vc_batch* b, const vc_poa_gap_params* p, const vc_poa_prune_params* pr, vc_result* r,
                                vc_poa_correct_out* c);
 
+/* Groups that go on from a stored graph: spoa's incremental flow -- AddAlignment on a live Graph, and Graph::save / load
+ * (graph.hpp:196-300) -- for POA groups.  A call hands a group's graph out as tables (g and st), and a later call takes them back
+ * (from), adds the new members of b to it and / or aligns queries against it, instead of building the group from nothing.
+ * The state of a group is its vc_poa_graph_out tables plus one more, vc_poa_state_out: every node's full aligned list in list
+ * order.  Everything later steps read follows from them: node ids and bases; each node's out-list (the edge order of out_off),
+ * aligned list (al_off / al_node) and in-list -- a sequence meets a node once, so it creates at most one edge into a head, an
+ * edge's first label is the sequence that created it, and replaying the paths in order rebuilds the in-lists and the labels --;
+ * the edge weights; sequences_ (a path's first node and member); and spoa's coder / decoder, first appearance over the bytes the
+ * paths spell in order.  aligned_a / aligned_b alone do not do: they keep only the larger ids of a node's list, and of a class
+ * c0 < c1 < c2 the list of c2 is [c1, c0] or [c0, c1] depending on which node it was made against (graph.cpp:263-280); that order
+ * drives later topological sorts and with them the rows and tie rules of later alignments.
+ * from == NULL builds every group from nothing, as vc_poa_run_align (q, a given) or vc_poa_run_graph, _strand, _msa, _gaps (the
+ * first that the given outputs need) does, to the launch and the log line when st is NULL too; a state is first obtained that way
+ * with g and st.  Otherwise from->n_groups == b->n_windows and group w starts as graph w of `from` -- which may have no node -- and
+ * window w of b lists its new members, possibly none; they are aligned and added in the order given with this call's engine.
+ * r as vc_poa_run_gaps; a consensus may run through stored nodes, so cons_cap >= the batch's bases plus the stored graphs' nodes
+ * is always enough.
+ * The id rule: node ids are vc_poa_graph_out's, and the stored nodes keep theirs.  The members of b are numbered from
+ * from->n_members[w] in row_member / path_member; earlier members keep their numbers, rows and paths (and path_reversed); the
+ * caller's n_members for the next call is from->n_members[w] plus the members of window w of b, empty ones included.  s has one
+ * entry per sequence of b only.  o, s, g, q and a behave as in vc_poa_run_msa / _strand / _graph / _align; any of o, s, g, st may
+ * be NULL; q and a are both NULL or both given; st requires g.
+ * The contract: for members m0 .. m(n-1) and any k, the tables and state after m0 .. m(k-1), passed back unmodified with
+ * m(k) .. m(n-1) and the same parameters, give the consensus, rows, coverage, graph tables, state, strand choices and query
+ * alignments of one call on m0 .. m(n-1), byte for byte.  The engine may differ between the calls, as in spoa; equality with the
+ * one call is promised for identical parameters only.
+ * vc_poa_run_correct has no `from` form: its average weight needs `total` over every member's bases and qualities
+ * (window.cpp:283-309), and the graph does not hold them.
+ * from is caller-owned and read during the call only: the arrays of a vc_poa_graph_out and a vc_poa_state_out in the same
+ * layout (copy them first: this call's own outputs end the lifetime of the earlier call's).  st is library-owned, lifetime as
+ * vc_poa_graph_out; a failed call leaves every pointer NULL.  g->bytes counts the graph tables alone and st->bytes the state
+ * table, though one copy brings both out.
+ * The checks keep every index on the device in range and every list well formed; they do not prove that the tables are a graph
+ * this library could have written (weights, ranks and list orders are taken as given), and for tables it could not have
+ * written the results are whatever the flow computes from them.
+ * from is untrusted, and everything is checked on the host before the device is touched, in this order: q and a together, st
+ * with g; then as vc_poa_run_align (or the entry the call stands for), the batch and the queries included; then from: the group
+ * count against b; NULL offset tables, n_members or n_nodes; offsets that do not start at 0, decrease, or (path_off) do not
+ * increase -- a path has a node --, node_off against n_nodes, a group of 2^31 nodes, edges, aligned cells or path entries, and
+ * NULL tables where the offsets count an entry; every edge_head, al_node, path_node and rank_to_node below the group's n_nodes;
+ * rank_to_node a permutation in which every edge runs forward; aligned lists without their own node or a node twice, and
+ * symmetric, and never joined by an edge; every consecutive pair of a path an edge of the tail's out-list (the first with that
+ * head), and every edge on some path -- which also refuses a second edge u -> v --; path_member below n_members (and n_members plus the
+ * new members below 2^32 - 1): VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these. */
+typedef struct vc_poa_state_out {          /* library-owned, lifetime as vc_poa_graph_out                                */
+    const uint64_t* al_off;                /* [node_off[n_groups] + n_groups] per group n_nodes + 1 entries, laid out as out_off, into al_node */
+    const uint32_t* al_node;               /* every node's aligned list, in list order                                   */
+    uint64_t        bytes;                 /* copied out of the device for this table                                    */
+} vc_poa_state_out;
+typedef struct vc_poa_graph_in {           /* caller-owned: the arrays of a vc_poa_graph_out and a vc_poa_state_out, same layout */
+    uint32_t n_groups;
+    const uint32_t* n_members;             /* [n_groups] members the group has had so far, empty ones included           */
+    const uint32_t* n_nodes;  const uint64_t* node_off;  const uint8_t* node_base;  const uint32_t* rank_to_node;
+    const uint64_t* out_off;  const uint32_t* edge_head;  const int64_t* edge_weight;
+    const uint64_t* al_off;   const uint32_t* al_node;
+    const uint64_t* path_first; const uint32_t* path_member; const uint8_t* path_reversed;
+    const uint64_t* path_off;   const uint32_t* path_node;
+} vc_poa_graph_in;
+int         vc_poa_run_from(const vc_poa_gap_params* p, const vc_poa_graph_in* from /* NULL: from nothing */, const vc_batch* b,
+                            vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_state_out* st,
+                            const vc_batch* q, vc_poa_align_out* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,18 @@ of each kind after a warm-up in one process: the stage's own time is the call mi
 of the align log line over that time; then the consensus-only rate beside the parent commit's library in alternating processes,
 for every gap model of --parent-gaps (the shared row body, a template over the gap model, changes how k_lg_fwd is compiled); then one rocprofv3 --kernel-trace --stats run of its own for the shares of
 the query kernels and the cells per forward-kernel second of k_lg_qfwd beside k_lg_fwd.
+--resume [--parent-lib LIB]: groups that go on from a stored graph (vc_poa_run_from; profiles/poa_resume_rate.txt), global, 5/-4/-8,
+one process, three calls of each kind after a warm-up, the library call alone on the clock (the stored graphs are packed into a
+vc_poa_graph_in before it, and nothing is copied out of the library's tables inside it):
+  (a) every group built once from all members with its state; then vc_poa_run_from on the stored graphs with no new member and one
+      query per group, beside vc_poa_run_align on the same groups and queries.  Expected: the load plus the query stage, a small
+      fraction of the rebuild, since the --depth dependent steps of the build are skipped; checked as below a quarter of it;
+  (b) the first 3/4 of the members built with their state, then the last quarter added, beside the one-shot build of all, each
+      with the graph tables and the state as outputs.  Expected: about a quarter of the build plus the load; checked as below half
+      of it (the last members meet the largest graphs, so they cost more than the average member);
+  (c) one rocprofv3 --kernel-trace --stats run of its own (build 3/4, add 1/4) for k_lg_load beside k_lg_apply;
+  (d) with --parent-lib the consensus-only rate of this library beside the parent commit's in alternating processes.
+Exits 1 if a stored-graph result differs from the one-shot one or an expectation of (a) or (b) is missed.
 """
 import argparse
 import csv
@@ -650,8 +662,186 @@ def main_correct(a):
     return 0
 
 
+LINEAR_NW = dict(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
+
+
+def resume_call(batch, start=None, qbatch=None, outputs=True, entry="vc_poa_run_from"):
+    """One library call with only the call on the clock -> (seconds, consensus per group, VC_LARGE_LOG lines, pairs digest or None).
+    entry vc_poa_run_from: from = the packed `start` (a list of resumable PoaGraph, or None: from nothing), the graph tables and
+    the state as outputs when `outputs`, the queries of qbatch with their pairs; entry vc_poa_run_align: the same groups and
+    queries through the entry that builds them again."""
+    import ctypes as C
+    import hashlib
+    import tempfile
+    lib = capi.load_hip()
+    p = capi.VcPoaGapParams(**LINEAR_NW)
+    gin, keep = poa._graph_in(start) if start is not None else (None, None)
+    cons, off, status, r, vb = poa._result_buffers(batch, sum(g.n_nodes for g in start) if start is not None else 0)
+    g, st = (capi.VcPoaGraphOut(), capi.VcPoaStateOut()) if outputs else (None, None)
+    qv = al = None
+    if qbatch is not None:
+        qv = qbatch.as_struct()
+        qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
+        al = capi.VcPoaAlignOut(flags=capi.VC_POA_ALIGN_PAIRS)
+    ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            if entry == "vc_poa_run_from":
+                rc = lib.vc_poa_run_from(C.byref(p), ref(gin), C.byref(vb), C.byref(r), None, None, ref(g), ref(st), ref(qv), ref(al))
+            else:
+                rc = lib.vc_poa_run_align(C.byref(p), C.byref(vb), C.byref(r), None, None, ref(qv), ref(al))
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read().decode()
+    del keep
+    if rc != 0 or int((status[:batch.n_windows] != 0).sum()):
+        raise RuntimeError(f"{entry} failed ({rc}): {lib.vc_poa_last_error().decode()}; groups not computed: {int((status != 0).sum())}")
+    digest = None
+    if al is not None:
+        nq = int(al.n_queries)
+        po = poa._table(al.pair_off, nq + 1)
+        h = hashlib.sha256(poa._table(al.score, nq).tobytes() + po.tobytes())
+        h.update(poa._table(al.pair_node, int(po[-1])).tobytes() + poa._table(al.pair_pos, int(po[-1])).tobytes())
+        digest = h.hexdigest()
+    n = batch.n_windows
+    return dt, [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], err, digest
+
+
+def resume_batches(a, batch):
+    """-> (all members per group, the first 3/4, the last 1/4, no member, one query per group: a member with 5 % substitutions)"""
+    import random
+    rng = random.Random(4102)
+    groups, queries = [], []
+    for w in range(batch.n_windows):
+        seqs, quals, _, _ = batch.window(w)
+        groups.append(list(zip(seqs, quals)))
+        s = bytearray(rng.choice(seqs))
+        for _ in range(max(1, len(s) // 20)):
+            s[rng.randrange(len(s))] = rng.choice(b"ACGT")
+        queries.append([bytes(s)])
+    k = a.depth - max(1, a.depth // 4)
+    gb = poa.group_batch
+    return gb(groups), gb([g[:k] for g in groups]), gb([g[k:] for g in groups]), gb([[] for _ in groups]), poa.query_batch(queries), k
+
+
+def stored_graphs(batch):
+    """the groups of the batch built from nothing with their state -> list of resumable PoaGraph"""
+    x = poa._run(batch, capi.VcPoaGapParams(**LINEAR_NW), graph=True, state=True)
+    if int((x.status != 0).sum()):
+        raise RuntimeError("groups not computed")
+    return x.graphs
+
+
+def main_resume(a):
+    """profiles/poa_resume_rate.txt: (a) queries against stored graphs beside vc_poa_run_align, (b) adding a quarter of the members
+    beside the one-shot build, (c) k_lg_load beside k_lg_apply in a traced run of its own, (d) the plain path beside the parent"""
+    import re
+    whole, head, tail, none, qb, k = resume_batches(a, synth_groups(a))
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_resume_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    ok = True
+    fmt = lambda ts: "  ".join(f"{t:.3f}" for t in ts)  # noqa: E731
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    emit(f"POA groups that go on from a stored graph: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100, PacBio-like errors, "
+         f"frac_partial=0, FASTQ); 5/-4/-8, global (kNW); one MI355X; synchronous; host clock around the library call alone (the stored "
+         f"graphs are packed before it, nothing is copied out inside it); one process, one untimed call of each kind first, then three")
+    # (a)
+    graphs = stored_graphs(whole)
+    load = lambda err: (re.search(r"vc_large: load .*", err) or [""])[0]  # noqa: E731
+    emit(f"(a) expectation: a query call on stored graphs costs the load plus the query stage, a small fraction (below a quarter) of the "
+         f"call that builds the groups again, because it skips the {a.depth} dependent steps of the build")
+    resume_call(none, graphs, qb, outputs=False)
+    fr = [resume_call(none, graphs, qb, outputs=False) for _ in range(3)]
+    resume_call(whole, None, qb, outputs=False, entry="vc_poa_run_align")
+    al = [resume_call(whole, None, qb, outputs=False, entry="vc_poa_run_align") for _ in range(3)]
+    same = fr[0][1] == al[0][1] and fr[0][3] == al[0][3]
+    done = re.search(r"vc_large: done .*", fr[0][2])[0]
+    emit(f"    vc_poa_run_from, stored graphs of {a.depth} members, no new member, 1 query per group   {fmt(r[0] for r in fr)} s   [{load(fr[0][2])}; {done}]")
+    emit(f"    vc_poa_run_align, the same groups built again, the same queries                     {fmt(r[0] for r in al)} s")
+    ratio = med([r[0] for r in fr]) / med([r[0] for r in al])
+    met = ratio < 0.25
+    emit(f"    median against median {ratio:.4f} of the rebuild ({1 / ratio:.1f}x): expectation {'met' if met else 'NOT met'}; consensus, scores "
+         f"and pairs of the two {'identical' if same else 'DIFFERENT'}")
+    ok = ok and met and same
+    del graphs
+    # (b)
+    emit(f"(b) expectation: adding the last {a.depth - k} of {a.depth} members to stored graphs costs about {a.depth - k}/{a.depth} of the "
+         f"one-shot build plus the load; checked as below half of it (the last members meet the largest graphs)")
+    graphs = stored_graphs(head)
+    resume_call(tail, graphs)
+    ex = [resume_call(tail, graphs) for _ in range(3)]
+    del graphs
+    resume_call(whole)
+    one = [resume_call(whole) for _ in range(3)]
+    same = ex[0][1] == one[0][1]
+    emit(f"    vc_poa_run_from, stored graphs of {k} members + {a.depth - k} new, graph tables and state out   {fmt(r[0] for r in ex)} s   [{load(ex[0][2])}]")
+    emit(f"    vc_poa_run_from from nothing, {a.depth} members, graph tables and state out                {fmt(r[0] for r in one)} s")
+    ratio = med([r[0] for r in ex]) / med([r[0] for r in one])
+    met = ratio < 0.5
+    emit(f"    median against median {ratio:.4f} of the one-shot build ({(a.depth - k) / a.depth:.4f} would be the members' share): expectation "
+         f"{'met' if met else 'NOT met'}; consensus of the two {'identical' if same else 'DIFFERENT'}")
+    ok = ok and met and same
+    large.release()
+    cmd = [sys.executable, os.path.abspath(__file__), "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth), "--resume"]
+    # (c)
+    if not a.no_trace:
+        d = os.path.join(a.trace_dir, "resume")
+        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + cmd + ["--child", "1"],
+                           capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"(c) rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return 1                              # nothing more is started on the device after a failed run
+        ms = kernel_shares(d)
+        tot = sum(ms.values())
+        ld, ap = sum(v for n, v in ms.items() if n.startswith("k_lg_load")), sum(v for n, v in ms.items() if n.startswith("k_lg_apply"))
+        emit(f"(c) kernels of a traced process of its own (build {k} members with the state, then add {a.depth - k}), {tot / 1e3:.2f} s: k_lg_load "
+             f"{ld:.1f} ms beside k_lg_apply {ap:.1f} ms ({ld / max(ap, 1e-9) * 100:.2f} % of it); all: " +
+             ", ".join(f"{n} {v:.1f} ms" for n, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+    # (d)
+    if a.parent_lib:
+        secs = {"parent": [], "this": []}
+        for which in ("parent", "this", "parent", "this"):
+            p = subprocess.run(cmd + ["--child", "0"] + (["--parent-lib", os.path.abspath(a.parent_lib)] if which == "parent" else []),
+                               capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"(d) {which} library: run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1
+            t = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            secs[which] += t
+            emit(f"(d) {'consensus only, ' + ('parent commit' if which == 'parent' else 'this library'):32s} " +
+                 "  ".join(f"{a.groups / x:7.1f}" for x in t) + f" groups/s  ({fmt(t)} s; a process of its own)")
+        par, cur = sorted(secs["parent"]), sorted(secs["this"])
+        med2 = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2  # noqa: E731
+        emit(f"(d) consensus only over the two alternated processes each: the parent's {par[0]:.3f} .. {par[-1]:.3f} s (median {med2(par):.3f}), "
+             f"this library's {cur[0]:.3f} .. {cur[-1]:.3f} s (median {med2(cur):.3f}): median against median {(med2(cur) / med2(par) - 1) * 100:+.2f} %; "
+             f"the parent's documented spread is 408-417 groups/s, about 2 %")
+    print("wrote", out)
+    return 0 if ok else 1
+
+
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    if a.resume and a.child == 1:                 # the traced run: build 3/4 of the members with the state, then add the rest
+        _, head, tail, _, _, _ = resume_batches(a, synth_groups(a))
+        small = min(64, head.n_windows)
+        resume_call(tail.slice(0, small), stored_graphs(head.slice(0, small)))
+        dt = resume_call(tail, stored_graphs(head))[0]
+        print(json.dumps(dict(seconds=dt)))
+        return
     if a.correct:
         batch = synth_groups(a)
         if a.child == 0:                          # consensus only, three calls after a full warm-up (this library's or the parent's)
@@ -663,7 +853,7 @@ def child(a):
         dt, stage, done = timed_correct(batch, a.prune_rounds)
         print(json.dumps(dict(seconds=dt, jobs=stage[0], cells=stage[2], build_cells=done[1])))
         return
-    if a.align and a.child == 0:                  # consensus only (vc_poa_run_gaps, global, --gaps), this library's or the parent's
+    if (a.align or a.resume) and a.child == 0:    # consensus only (vc_poa_run_gaps, global, --gaps), this library's or the parent's
         batch = synth_groups(a)
         g, e, q, c = GAPS[a.gaps] or (-8, -8, -8, -8)
         p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=g, gap_extend=e, gap_open2=q, gap_extend2=c)
@@ -751,6 +941,7 @@ def main():
     ap.add_argument("--graph", action="store_true", help="measure vc_poa_run_graph beside the consensus-only call (profiles/poa_graph_rate.txt)")
     ap.add_argument("--align", action="store_true", help="measure vc_poa_run_align's query stage beside the plain call (profiles/poa_align_rate.txt)")
     ap.add_argument("--correct", action="store_true", help="measure vc_poa_run_correct beside the consensus-only call (profiles/poa_correct_rate.txt)")
+    ap.add_argument("--resume", action="store_true", help="measure vc_poa_run_from: stored-graph queries, extending, k_lg_load (profiles/poa_resume_rate.txt)")
     ap.add_argument("--prune-rounds", type=int, default=3, help="--correct: num_prune (default 3)")
     ap.add_argument("--queries-per-group", type=int, default=32, help="--align: mutated members per group beside the held-out one")
     ap.add_argument("--parent-gaps", default="linear,affine,convex", help="--align --parent-lib: the gap models compared with the parent's library")
@@ -761,6 +952,8 @@ def main():
     a = ap.parse_args()
     if a.child is not None:
         return child(a)
+    if a.resume:
+        return main_resume(a)
     if a.correct:
         return main_correct(a)
     if a.align:

@@ -121,6 +121,24 @@ class VcPoaAlignOut(C.Structure):
     ]
 
 
+class VcPoaStateOut(C.Structure):
+    """vc_poa_state_out: every node's aligned list, owned by the library as vc_poa_graph_out is"""
+    _fields_ = [("al_off", C.POINTER(C.c_uint64)), ("al_node", C.POINTER(C.c_uint32)), ("bytes", C.c_uint64)]
+
+
+class VcPoaGraphIn(C.Structure):
+    """vc_poa_graph_in: caller-owned arrays of stored graphs, laid out as vc_poa_graph_out and vc_poa_state_out are"""
+    _fields_ = [
+        ("n_groups", C.c_uint32), ("n_members", C.POINTER(C.c_uint32)),
+        ("n_nodes", C.POINTER(C.c_uint32)), ("node_off", C.POINTER(C.c_uint64)), ("node_base", C.POINTER(C.c_uint8)),
+        ("rank_to_node", C.POINTER(C.c_uint32)),
+        ("out_off", C.POINTER(C.c_uint64)), ("edge_head", C.POINTER(C.c_uint32)), ("edge_weight", C.POINTER(C.c_int64)),
+        ("al_off", C.POINTER(C.c_uint64)), ("al_node", C.POINTER(C.c_uint32)),
+        ("path_first", C.POINTER(C.c_uint64)), ("path_member", C.POINTER(C.c_uint32)), ("path_reversed", C.POINTER(C.c_uint8)),
+        ("path_off", C.POINTER(C.c_uint64)), ("path_node", C.POINTER(C.c_uint32)),
+    ]
+
+
 class VcPoaPruneParams(C.Structure):
     """vc_poa_prune_params: the thresholds and rounds of vc_poa_run_correct (the reference's defaults: 0.22 / 0.19 / 3)"""
     _fields_ = [("min_confidence", C.c_double), ("min_support", C.c_double), ("num_prune", C.c_uint32)]
@@ -417,6 +435,12 @@ def load_hip():
             lib.vc_poa_run_correct.argtypes = [C.POINTER(VcBatch), C.POINTER(VcPoaGapParams), C.POINTER(VcPoaPruneParams), C.POINTER(VcResult),
                                                C.POINTER(VcPoaCorrectOut)]
             lib.vc_poa_run_correct.restype = C.c_int
+        # (likewise: the parent commit's library, beside which tools/gpu_poa_rate.py --resume measures, has no such entry)
+        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_from"):
+            lib.vc_poa_run_from.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaGraphIn), C.POINTER(VcBatch), C.POINTER(VcResult),
+                                            C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut),
+                                            C.POINTER(VcPoaStateOut), C.POINTER(VcBatch), C.POINTER(VcPoaAlignOut)]
+            lib.vc_poa_run_from.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

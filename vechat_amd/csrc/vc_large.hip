@@ -51,6 +51,9 @@
 //               order, <1> the rows ('-' fill, then a scatter over the edge labels), the consensus row and the coverage;
 //   k_lg_graph  vc_poa_run_graph only, one wave per finished group: <0> the counts of the group's graph tables, <1> the tables --
 //               nodes, out-edges as CSR, aligned pairs, a path per sequence, the consensus path (spoa's GFA and dot output).
+//   k_lg_load   vc_poa_run_from only, one wave per group behind k_lg_init: the group starts as a stored graph -- nodes, out-lists and
+//               aligned lists from their CSR, in-lists and labels by replaying the paths in order; with a vc_poa_state_out
+//               k_lg_graph<1> also writes every node's aligned list behind the group's block.
 //   The query stage, vc_poa_run_align only (spoa's engine->Align(sequence, graph, &score) for sequences that are NOT added), on the
 //   finished groups while their tables are resident; every (group, query) pair is a job (LJob) and independent of the others:
 //   k_lg_rows   one lane per finished group: the graph half of k_lg_prep (graph_rows) once per group, without a next sequence;
@@ -86,6 +89,10 @@
 //                           groups that finished, k_lg_qfwd launches, their rows x columns with both strands counted, bytes copied out),
 //                           "vc_large: correct jobs=J launches=K cells=C bytes=B" (vc_poa_run_correct: the members of the groups that
 //                           finished, k_lg_qfwd launches of the final stage, their rows x columns, bytes copied out),
+//                           "vc_large: state bytes=B" (vc_poa_run_from with a vc_poa_state_out: the bytes of the state tables, which
+//                           the graph line does not count),
+//                           "vc_large: load groups=G nodes=N edges=E paths=P bytes=B" (vc_poa_run_from with stored graphs: what was
+//                           uploaded, once per call),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes of the build, their rows x
 //                           columns summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes;
 //                           vc_poa_run_correct counts the rounds' passes too, not the final stage's).
@@ -111,7 +118,7 @@ int fail(int rc, const char* m) { g_err = m; return rc; }
 struct Caps { uint64_t NC, EC, AC, LC, SC, PC, nseq; };
 
 // bytes of a window's tables, and (base != nullptr) the pointers into them
-uint64_t layout(LWin* W, uint8_t* base, const Caps& c, bool labels, bool msa) {
+uint64_t layout(LWin* W, uint8_t* base, const Caps& c, bool labels, bool msa, bool stored = false) {
     uint64_t off = 0;
     auto take = [&](auto** p, uint64_t n) {
         using T = std::remove_pointer_t<std::remove_reference_t<decltype(p)>>;
@@ -144,6 +151,7 @@ uint64_t layout(LWin* W, uint8_t* base, const Caps& c, bool labels, bool msa) {
     take(&x->pairs, 2 * c.PC);
     take(&x->cons, c.NC);
     if (msa) { take(&x->sq_begin, c.nseq); take(&x->sq_member, c.nseq); }
+    if (msa && stored) { take(&x->sq_len, c.nseq); take(&x->sq_rev, c.nseq); }         // vc_poa_run_from: the stored paths' lengths and strands
     return (off + 255) & ~255ull;
 }
 
@@ -260,6 +268,8 @@ struct PoaRequest {
     uint64_t nq = 0, nbytes = 0;                       // sequences and bytes of the query batch
     const vc_poa_prune_params* prune = nullptr;        // vc_poa_run_correct: the thresholds and rounds, and the corrected members
     vc_poa_correct_out* correct = nullptr;
+    const vc_poa_graph_in* from = nullptr;             // vc_poa_run_from: the stored graphs the groups start as, and the state table beside the graph's
+    vc_poa_state_out* state = nullptr;
     bool rows() const { return msa_flags != 0; }                           // k_lg_msa runs
     bool keeps_labels() const { return msa_flags != 0 || graph != nullptr; }   // the edges keep sequence labels
     bool keeps_seqs() const { return keeps_labels(); }                     // the windows keep sq_begin / sq_member
@@ -303,6 +313,12 @@ struct Outputs {
             go->bytes = bytes;
         }
     } graph;
+    struct State {                                     // vc_poa_state_out
+        std::vector<uint64_t> al_off;
+        std::vector<uint32_t> al_node;
+        uint64_t bytes = 0;                            // copied out of the device
+        void publish(vc_poa_state_out* st) { st->al_off = al_off.data(); st->al_node = table(al_node); st->bytes = bytes; }
+    } state;
     struct Align {                                     // vc_poa_align_out, one entry per query of the batch
         std::vector<uint8_t> status, reversed;
         std::vector<int32_t> score, score_rev, pair_node, pair_pos;
@@ -333,7 +349,7 @@ struct Outputs {
 } g_out;
 
 // a group's block of k_lg_graph<1> on the host, and the counts that lay it out
-struct GraphPart { uint32_t N = 0, E = 0, P = 0, S = 0, T = 0, Cn = 0; std::vector<uint8_t> blk; };
+struct GraphPart { uint32_t N = 0, E = 0, P = 0, S = 0, T = 0, Cn = 0, A = 0; std::vector<uint8_t> blk; };   // A: cells of the state table behind it
 
 // ------------------------------------------------------------------ the host schedule
 // One call of vc_large_run / vc_poa_run*: the batch on the device (seq_begin / seq_end only with spans), windows in flight in
@@ -360,6 +376,7 @@ struct Run {
     uint64_t msa_launches = 0;
     std::vector<GraphPart> part;                       // graph: per window its block
     uint64_t graph_launches = 0;
+    LLoad load{};                                      // vc_poa_run_from: the stored graphs on the device
     // the query stage: per host group the packed pairs (every node, then every position), per query where its pairs lie; the "align" line
     std::vector<std::vector<int32_t>> q_part;
     std::vector<uint32_t> q_part_of, q_count;          // [nq]
@@ -379,7 +396,8 @@ struct Group {
     uint64_t abytes = 0;
     std::vector<LWin> hw;
     LWin* d_win = nullptr;
-    uint32_t* d_list = nullptr;                        // the windows of one launch (k_lg_fwd / k_lg_back / k_lg_msa<1>) ...
+    uint32_t* d_list = nullptr;                        // the windows of one launch (k_lg_fwd / k_lg_back / k_lg_msa<1>), as indices into d_win;
+                                                       // k_lg_load alone is given the ids of all windows in flight in the BATCH here ...
     uint64_t* d_hoff = nullptr;                        // ... and where their matrices or blocks begin
 };
 
@@ -437,12 +455,46 @@ int upload_queries(Run& R, DevMem& mem) {
     return VC_OK;
 }
 
+// vc_poa_run_from: the stored graphs on the device, once per call -- the arrays as given (check_from has passed them) and the
+// decoder of every group: its bytes in order of first appearance along the paths in order, as add_alignment met them (then any
+// byte of a node that no path visits, which a graph this library wrote does not have) -- and the call's log line
+int upload_stored(Run& R, DevMem& mem) {
+    const vc_poa_graph_in* f = R.q.from;
+    const uint32_t ng = f->n_groups;
+    const uint64_t NN = f->node_off[ng], PP = f->path_first[ng], EE = f->out_off[NN + ng - 1], AA = f->al_off[NN + ng - 1], TT = f->path_off[PP];
+    std::vector<uint8_t> dec(256ull * ng, 0);
+    std::vector<uint32_t> n_codes(ng, 0);
+    for (uint32_t w = 0; w < ng; ++w) {
+        bool seen[256] = {};
+        uint8_t* d = dec.data() + 256ull * w;
+        auto meet = [&](uint8_t c) { if (!seen[c]) { seen[c] = true; d[n_codes[w]++] = c; } };
+        const uint64_t nb = f->node_off[w];
+        for (uint64_t k = f->path_off[f->path_first[w]]; k < f->path_off[f->path_first[w + 1]]; ++k) meet(f->node_base[nb + f->path_node[k]]);
+        for (uint64_t v = 0; v < f->n_nodes[w]; ++v) meet(f->node_base[nb + v]);
+    }
+    LLoad& L = R.load;
+    if (!mem.alloc(&L.n_nodes, ng, f->n_nodes) || !mem.alloc(&L.node_off, ng + 1, f->node_off) || !mem.alloc(&L.node_base, NN, f->node_base) ||
+        !mem.alloc(&L.rank_to_node, NN, f->rank_to_node) || !mem.alloc(&L.out_off, NN + ng, f->out_off) || !mem.alloc(&L.edge_head, EE, f->edge_head) ||
+        !mem.alloc(&L.edge_weight, EE, f->edge_weight) || !mem.alloc(&L.al_off, NN + ng, f->al_off) || !mem.alloc(&L.al_node, AA, f->al_node) ||
+        !mem.alloc(&L.path_first, ng + 1, f->path_first) || !mem.alloc(&L.path_member, PP, f->path_member) ||
+        !mem.alloc(&L.path_reversed, PP, f->path_reversed) || !mem.alloc(&L.path_off, PP + 1, f->path_off) || !mem.alloc(&L.path_node, TT, f->path_node) ||
+        !mem.alloc(&L.dec, dec.size(), dec.data()) || !mem.alloc(&L.n_codes, ng, n_codes.data()))
+        return fail(VC_ERR_HIP, "device allocation or copy of the stored graphs failed");
+    if (R.kn.log) {
+        const uint64_t bytes = 4ull * ng + 8 * (ng + 1) + NN + 4 * NN + 2 * 8 * (NN + ng) + 4 * EE + 8 * EE + 4 * AA + 8 * (ng + 1) + 4 * PP + PP +
+                               8 * (PP + 1) + 4 * TT + dec.size() + 4ull * ng;
+        std::fprintf(stderr, "vc_large: load groups=%u nodes=%llu edges=%llu paths=%llu bytes=%llu\n", ng, (unsigned long long)NN,
+                     (unsigned long long)EE, (unsigned long long)PP, (unsigned long long)bytes);
+    }
+    return VC_OK;
+}
+
 // The windows in flight next: as many of the pending ones as the arena budget holds, in order (at least one; a window the device
 // cannot hold at all is refused).  G.ids is empty when every pending window was refused.
 void next_group(Run& R, Group& G) {
     std::vector<uint32_t> rest;
     for (uint32_t w : R.pending) {
-        const uint64_t need = layout(nullptr, nullptr, R.caps[w], R.labels, R.q.keeps_seqs());
+        const uint64_t need = layout(nullptr, nullptr, R.caps[w], R.labels, R.q.keeps_seqs(), R.q.from != nullptr);
         if (G.ids.empty() && need > R.arena_budget * 2) {                  // the device cannot hold its tables
             R.status[w] = VC_WIN_OVERFLOW;
             if (R.kn.log) std::fprintf(stderr, "vc_large: refuse window=%u bytes=%llu budget=%llu\n", w, (unsigned long long)need, (unsigned long long)R.arena_budget);
@@ -471,7 +523,8 @@ void place_windows(const Run& R, Group& G, uint8_t* arena) {
         const uint32_t w = G.ids[k];
         LWin& W = G.hw[k];
         W = LWin{};
-        layout(&W, arena + G.aoff[k], R.caps[w], R.labels, R.q.keeps_seqs());
+        layout(&W, arena + G.aoff[k], R.caps[w], R.labels, R.q.keeps_seqs(), R.q.from != nullptr);
+        if (const vc_poa_graph_in* f = R.q.from) { W.n_old = (uint32_t)(f->path_first[w + 1] - f->path_first[w]); W.m0 = f->n_members[w]; }
         const Caps& c = R.caps[w];
         W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
         W.L = W.nseq ? (uint32_t)(b->seq_off[W.s0 + 1] - b->seq_off[W.s0]) : 0;     // (POA groups: unused, and may be empty)
@@ -579,6 +632,12 @@ bool lock_step(Run& R, Group& G) {
     const dim3 lanes((n + 63) / 64);
     bool ok = hipMemcpy(G.d_win, G.hw.data(), n * sizeof(LWin), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) { hipLaunchKernelGGL(k_lg_init, lanes, dim3(64), 0, 0, a); ok = hipGetLastError() == hipSuccess; }
+    if (ok && R.q.from) {                                                  // every group starts as its stored graph
+        LArgs f = a;
+        f.list = G.d_list;
+        ok = hipMemcpy(G.d_list, G.ids.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) { hipLaunchKernelGGL(k_lg_load, dim3(n), dim3(64), 0, 0, f, R.load); ok = hipGetLastError() == hipSuccess; }
+    }
     while (ok) {
         hipLaunchKernelGGL(k_lg_prep, lanes, dim3(64), 0, 0, a);
         if (hipMemcpy(G.hw.data(), G.d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) != hipSuccess) return false;
@@ -694,10 +753,13 @@ int collect_graph(Run& R, Group& G) {
         const LWin& W = G.hw[k];
         const LGraph& g = W.gr[W.cur];
         GraphPart p;
-        p.N = g.n_nodes; p.E = g.n_edges; p.P = g.n_al / 2; p.S = g.nseq; p.T = W.gr_path; p.Cn = W.cons_n;
+        p.N = g.n_nodes; p.E = g.n_edges; p.P = g.n_al / 2; p.S = g.nseq; p.T = W.gr_path; p.Cn = W.cons_n; p.A = a.state ? g.n_al : 0;
         return p;
     };
-    auto block_of = [&](uint32_t k) { const GraphPart p = part_of(k); return graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn).bytes; };
+    auto block_of = [&](uint32_t k) {
+        const GraphPart p = part_of(k);
+        return graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn).bytes + (a.state ? state_bytes(p.N, p.A) : 0);
+    };
     auto scratch_of = [&](uint32_t k) { return a.graph == 1 ? graph_scratch_bytes(G.hw[k].gr[G.hw[k].cur].nseq, G.hw[k].gr_cols) : 0; };
     auto need = [&](uint32_t k) { return block_of(k) + scratch_of(k); };
     uint64_t blocks = 0;
@@ -723,7 +785,10 @@ int collect_graph(Run& R, Group& G) {
             p = part_of(list[q]);
             p.blk.assign(host.begin() + hoff[q], host.begin() + (q + 1 < nl ? hoff[q + 1] : blocks));
         }
-        g_out.graph.bytes += blocks;
+        uint64_t st_bytes = 0;                                             // the state tables lie in the same copy: counted apart
+        if (a.state) for (const uint32_t k : list) { const GraphPart p = part_of(k); st_bytes += state_bytes(p.N, p.A); }
+        g_out.graph.bytes += blocks - st_bytes;
+        g_out.state.bytes += st_bytes;
         return VC_OK;
     };
     return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
@@ -739,12 +804,13 @@ void assemble_graph(Run& R) {
         const T* src = (const T*)(p.blk.data() + at);
         dst.insert(dst.end(), src, src + n);
     };
+    Outputs::State& ss = g_out.state;
     gs.node_off.assign(1, 0); gs.aligned_off.assign(1, 0); gs.path_first.assign(1, 0); gs.path_off.assign(1, 0);
     for (uint32_t w = 0; w < R.nw; ++w) {
         if (R.status[w] != VC_WIN_OK) R.part[w] = GraphPart{};
         const GraphPart& p = R.part[w];
         const GraphBlock B = graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn);
-        const uint64_t e0 = gs.edge_head.size(), t0 = gs.path_node.size();
+        const uint64_t e0 = gs.edge_head.size(), t0 = gs.path_node.size(), c0 = ss.al_node.size();
         gs.n_nodes.push_back(p.N);
         if (!p.blk.empty()) {
             put(gs.node_base, p, B.base, p.N); put(gs.node_cons_pos, p, B.cons_pos, p.N); put(gs.rank_to_node, p, B.rank, p.N);
@@ -756,8 +822,14 @@ void assemble_graph(Run& R) {
             for (uint32_t v = 0; v <= p.N; ++v) gs.out_off.push_back(e0 + oo[v]);
             const uint32_t* po = (const uint32_t*)(p.blk.data() + B.p_off);
             for (uint32_t k = 1; k <= p.S; ++k) gs.path_off.push_back(t0 + po[k]);
+            if (R.a.state) {                                               // the state table lies behind the block
+                const uint32_t* ao = (const uint32_t*)(p.blk.data() + B.bytes);
+                for (uint32_t v = 0; v <= p.N; ++v) ss.al_off.push_back(c0 + ao[v]);
+                put(ss.al_node, p, B.bytes + state_list_at(p.N), p.A);
+            }
         } else {
             gs.out_off.push_back(e0);      // a group without a block has no node and no path: its one out_off entry
+            if (R.a.state) ss.al_off.push_back(c0);
         }
         gs.node_off.push_back(gs.node_base.size());
         gs.aligned_off.push_back(gs.aligned_a.size());
@@ -765,6 +837,7 @@ void assemble_graph(Run& R) {
         R.part[w] = GraphPart{};
     }
     if (R.kn.log) std::fprintf(stderr, "vc_large: graph launches=%llu bytes=%llu\n", (unsigned long long)R.graph_launches, (unsigned long long)gs.bytes);
+    if (R.kn.log && R.a.state) std::fprintf(stderr, "vc_large: state bytes=%llu\n", (unsigned long long)ss.bytes);
 }
 
 template <uint32_t GM>
@@ -1075,6 +1148,7 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     DevMem mem;                                                            // the batch and the strand views: held until the call ends
     if (const int rc = upload_batch(R, mem, a.mode != 2)) return rc;
     if (q.strand) if (const int rc = strand_views(R, mem)) return rc;
+    if (q.from) if (const int rc = upload_stored(R, mem)) return rc;
     if (q.has_queries()) {
         if (const int rc = upload_queries(R, mem)) return rc;
         Outputs::Align& S = g_out.align;
@@ -1146,6 +1220,119 @@ int check_queries(PoaRequest& A, const vc_batch* b) {
     return VC_OK;
 }
 
+// The counts of stored graph w of a vc_poa_graph_in that check_from has passed: nodes, edges, aligned-list cells, paths, path entries
+struct StoredCounts { uint64_t N, E, A, S, T; };
+StoredCounts stored_counts(const vc_poa_graph_in* f, uint32_t w) {
+    const uint64_t N = f->n_nodes[w], ob = f->node_off[w] + w, p0 = f->path_first[w], S = f->path_first[w + 1] - p0;
+    return {N, f->out_off[ob + N] - f->out_off[ob], f->al_off[ob + N] - f->al_off[ob], S, f->path_off[p0 + S] - f->path_off[p0]};
+}
+
+// vc_poa_run_from's stored graphs, after the batch and the queries and before the device.  They are untrusted: the kernels index
+// with what they hold, so every rule is checked here, in the order the header states: the arrays and the group count; the
+// offsets; the node ids; the topological order; the aligned lists; the paths; the member numbers.
+int check_from(const vc_poa_graph_in* f, const vc_batch* b) {
+    const uint32_t ng = f->n_groups;
+    if (ng != b->n_windows) return fail(VC_ERR_ARG, "the stored graphs need one graph per group");
+    if (ng == 0) return VC_OK;
+    if (!f->n_members || !f->n_nodes || !f->node_off || !f->out_off || !f->al_off || !f->path_first || !f->path_off)
+        return fail(VC_ERR_ARG, "null array in the stored graphs");
+    // offsets: prefix sums that start at 0 and never decrease; a path has a node; every count of a group stays below 2^31
+    if (f->node_off[0] != 0 || f->path_first[0] != 0 || f->path_off[0] != 0 || f->out_off[0] != 0 || f->al_off[0] != 0)
+        return fail(VC_ERR_ARG, "an offset table of the stored graphs does not start at 0");
+    constexpr uint64_t kMax = 1ull << 31;
+    for (uint32_t w = 0; w < ng; ++w) {
+        if (f->n_nodes[w] >= kMax || f->node_off[w + 1] < f->node_off[w] || f->node_off[w + 1] - f->node_off[w] != f->n_nodes[w])
+            return fail(VC_ERR_ARG, "node_off of the stored graphs is not the prefix sum of n_nodes");
+        if (f->path_first[w + 1] < f->path_first[w] || f->path_first[w + 1] - f->path_first[w] >= kMax)
+            return fail(VC_ERR_ARG, "path_first of the stored graphs decreases");
+    }
+    const uint64_t NN = f->node_off[ng], PP = f->path_first[ng];
+    for (uint64_t k = 1; k < NN + ng; ++k)
+        if (f->out_off[k] < f->out_off[k - 1] || f->al_off[k] < f->al_off[k - 1]) return fail(VC_ERR_ARG, "out_off or al_off of the stored graphs decreases");
+    for (uint64_t k = 0; k < PP; ++k)
+        if (f->path_off[k + 1] <= f->path_off[k]) return fail(VC_ERR_ARG, "path_off of the stored graphs does not increase (a path has at least one node)");
+    const uint64_t EE = f->out_off[NN + ng - 1], AA = f->al_off[NN + ng - 1], TT = f->path_off[PP];
+    for (uint32_t w = 0; w < ng; ++w) {
+        const StoredCounts c = stored_counts(f, w);
+        if (c.E >= kMax || c.A >= kMax || c.T >= kMax) return fail(VC_ERR_ARG, "a stored graph is too large (2^31 edges, aligned cells or path entries)");
+    }
+    if ((NN && (!f->node_base || !f->rank_to_node)) || (EE && (!f->edge_head || !f->edge_weight)) || (AA && !f->al_node) ||
+        (PP && (!f->path_member || !f->path_reversed)) || (TT && !f->path_node))
+        return fail(VC_ERR_ARG, "null array in the stored graphs");
+    // node ids
+    for (uint32_t w = 0; w < ng; ++w) {
+        const uint64_t N = f->n_nodes[w], nb = f->node_off[w], ob = nb + w, p0 = f->path_first[w], p1 = f->path_first[w + 1];
+        for (uint64_t k = f->out_off[ob]; k < f->out_off[ob + N]; ++k) if (f->edge_head[k] >= N) return fail(VC_ERR_ARG, "edge_head of the stored graphs names no node");
+        for (uint64_t k = f->al_off[ob]; k < f->al_off[ob + N]; ++k) if (f->al_node[k] >= N) return fail(VC_ERR_ARG, "al_node of the stored graphs names no node");
+        for (uint64_t k = f->path_off[p0]; k < f->path_off[p1]; ++k) if (f->path_node[k] >= N) return fail(VC_ERR_ARG, "path_node of the stored graphs names no node");
+        for (uint64_t v = 0; v < N; ++v) if (f->rank_to_node[nb + v] >= N) return fail(VC_ERR_ARG, "rank_to_node of the stored graphs names no node");
+    }
+    // the topological order: a permutation in which every edge runs forward
+    std::vector<uint32_t> rank_of;
+    for (uint32_t w = 0; w < ng; ++w) {
+        const uint64_t N = f->n_nodes[w], nb = f->node_off[w], ob = nb + w;
+        rank_of.assign(N, NONE);
+        for (uint64_t r = 0; r < N; ++r) {
+            uint32_t& x = rank_of[f->rank_to_node[nb + r]];
+            if (x != NONE) return fail(VC_ERR_ARG, "rank_to_node of the stored graphs is not a permutation");
+            x = (uint32_t)r;
+        }
+        for (uint64_t v = 0; v < N; ++v)
+            for (uint64_t k = f->out_off[ob + v]; k < f->out_off[ob + v + 1]; ++k)
+                if (rank_of[f->edge_head[k]] <= rank_of[v]) return fail(VC_ERR_ARG, "an edge of the stored graphs runs against rank_to_node");
+    }
+    // aligned lists: not the node itself, no node twice, and symmetric
+    for (uint32_t w = 0; w < ng; ++w) {
+        const uint64_t N = f->n_nodes[w], ob = f->node_off[w] + w;
+        for (uint64_t v = 0; v < N; ++v) {
+            const uint64_t a0 = f->al_off[ob + v], a1 = f->al_off[ob + v + 1];
+            for (uint64_t k = a0; k < a1; ++k) {
+                if (f->al_node[k] == v) return fail(VC_ERR_ARG, "an aligned list of the stored graphs holds its own node");
+                for (uint64_t j = a0; j < k; ++j) if (f->al_node[j] == f->al_node[k]) return fail(VC_ERR_ARG, "an aligned list of the stored graphs holds a node twice");
+            }
+            for (uint64_t k = a0; k < a1; ++k) {
+                const uint32_t u = f->al_node[k];
+                bool back = false;
+                for (uint64_t j = f->al_off[ob + u]; j < f->al_off[ob + u + 1] && !back; ++j) back = f->al_node[j] == v;
+                if (!back) return fail(VC_ERR_ARG, "the aligned lists of the stored graphs are not symmetric");
+            }
+        }
+    }
+    // ... and never joined by an edge (they share a column of the alignment)
+    for (uint32_t w = 0; w < ng; ++w) {
+        const uint64_t N = f->n_nodes[w], ob = f->node_off[w] + w;
+        for (uint64_t v = 0; v < N; ++v)
+            for (uint64_t k = f->out_off[ob + v]; k < f->out_off[ob + v + 1]; ++k)
+                for (uint64_t j = f->al_off[ob + v]; j < f->al_off[ob + v + 1]; ++j)
+                    if (f->al_node[j] == f->edge_head[k]) return fail(VC_ERR_ARG, "aligned nodes of the stored graphs are joined by an edge");
+    }
+    // paths: every consecutive pair is an edge of the tail's out-list (the first with that head, as add_edge finds it), and every
+    // edge lies on a path: an edge no sequence walked would be in no in-list (a second edge u -> v never is walked)
+    std::vector<uint8_t> walked;
+    for (uint32_t w = 0; w < ng; ++w) {
+        const uint64_t N = f->n_nodes[w], ob = f->node_off[w] + w, e0 = f->out_off[ob];
+        walked.assign(f->out_off[ob + N] - e0, 0);
+        for (uint64_t p = f->path_first[w]; p < f->path_first[w + 1]; ++p) {
+            for (uint64_t k = f->path_off[p]; k + 1 < f->path_off[p + 1]; ++k) {
+                const uint32_t u = f->path_node[k], v = f->path_node[k + 1];
+                bool edge = false;
+                for (uint64_t j = f->out_off[ob + u]; j < f->out_off[ob + u + 1] && !edge; ++j)
+                    if ((edge = f->edge_head[j] == v)) walked[j - e0] = 1;
+                if (!edge) return fail(VC_ERR_ARG, "a path of the stored graphs steps along no edge");
+            }
+        }
+        for (const uint8_t x : walked) if (!x) return fail(VC_ERR_ARG, "an edge of the stored graphs lies on no path");
+    }
+    // member numbers; the members to come must still fit 32 bits
+    for (uint32_t w = 0; w < ng; ++w) {
+        for (uint64_t p = f->path_first[w]; p < f->path_first[w + 1]; ++p)
+            if (f->path_member[p] >= f->n_members[w]) return fail(VC_ERR_ARG, "path_member of the stored graphs is not below n_members");
+        if ((uint64_t)f->n_members[w] + (b->win_seq_off[w + 1] - b->win_seq_off[w]) >= VC_POA_ROW_CONSENSUS)
+            return fail(VC_ERR_ARG, "n_members of the stored graphs leaves no room for the new members");
+    }
+    return VC_OK;
+}
+
 // The vc_poa_* entries after their score checks: the knobs, the batch (still without the device), the queries, the device, the
 // run.  `a` holds the scores.
 int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, PoaRequest& q) {
@@ -1176,6 +1363,15 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
         }
     }
     if (q.required & PoaRequest::ALIGN) if (const int rc = check_queries(q, b)) return rc;
+    if (q.from) {
+        if (const int rc = check_from(q.from, b)) return rc;
+        // tables: the stored counts, and beside them the usual allowance for the new members (which alone the knobs shrink)
+        for (uint32_t w = 0; w < nw; ++w) {
+            const StoredCounts c = stored_counts(q.from, w);
+            Caps& k = caps[w];
+            k.NC += c.N; k.EC += c.E; k.AC += c.A; k.LC += c.T; k.SC += c.N + c.E + c.A; k.PC += c.N; k.nseq += c.S;
+        }
+    }
     a.num_prune = 1;
     if (q.required & PoaRequest::CORRECT) {
         // vc_poa_run_correct's own arguments, after the batch and before the device
@@ -1198,6 +1394,7 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     if (q.graph) *q.graph = vc_poa_graph_out{};                            // a failed call leaves every pointer NULL
     if (q.align) { q.align_flags = q.align->flags; *q.align = vc_poa_align_out{}; q.align->flags = q.align_flags; }
     if (q.correct) *q.correct = vc_poa_correct_out{};
+    if (q.state) *q.state = vc_poa_state_out{};
     if (!p || !b || !r || ((q.required & PoaRequest::MSA) && !o) || ((q.required & PoaRequest::CORRECT) && (!q.prune || !q.correct)) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
@@ -1217,7 +1414,7 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     q.route = q.graph ? graph_route() : 0;                                 // (vc_poa_run_align may ask for the tables too)
     LArgs a{};
     a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = g2; a.gap_c = c; a.gaps = gaps;
-    a.msa = q.msa_flags; a.strand = q.strand ? 1 : 0; a.graph = q.route;
+    a.msa = q.msa_flags; a.strand = q.strand ? 1 : 0; a.graph = q.route; a.state = q.state ? 1 : 0;
     if (o) { *o = vc_poa_msa_out{}; o->flags = q.msa_flags; }
     if (q.required) g_out.clear();                                         // what an earlier call handed out ends here
     const int rc = run_groups(p->device, p->algorithm, a, b, r, q);
@@ -1228,6 +1425,7 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     if (q.graph) {
         q.graph->n_groups = b->n_windows;
         if (b->n_windows) g_out.graph.publish(q.graph);
+        if (q.state && b->n_windows) g_out.state.publish(q.state);
     }
     if (o) o->n_groups = b->n_windows;
     if (q.rows() && b->n_windows) g_out.msa.publish(o);
@@ -1308,6 +1506,18 @@ int vc_poa_run_graph(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r
 int vc_poa_run_align(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, vc_poa_strand_out* s, vc_poa_graph_out* g,
                      const vc_batch* q, vc_poa_align_out* a) {
     return poa_run(p, b, r, PoaRequest{PoaRequest::ALIGN, nullptr, s, g, q, a});
+}
+
+int vc_poa_run_from(const vc_poa_gap_params* p, const vc_poa_graph_in* from, const vc_batch* b, vc_result* r, vc_poa_msa_out* o,
+                    vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_state_out* st, const vc_batch* q, vc_poa_align_out* a) {
+    if (st) *st = vc_poa_state_out{};                                      // a failed call leaves every pointer NULL
+    if ((q == nullptr) != (a == nullptr)) return fail(VC_ERR_ARG, "the query batch and the align output go together");
+    if (st && !g) return fail(VC_ERR_ARG, "the state output needs the graph output");
+    // the entry the call would be without `from` and `st`: the first of vc_poa_run_align, _graph, _strand, _msa, _gaps it needs
+    const uint32_t required = q ? PoaRequest::ALIGN : g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0;
+    PoaRequest rq{required, o, s, g, q, a};
+    rq.from = from; rq.state = st;
+    return poa_run(p, b, r, rq);
 }
 
 int vc_poa_run_correct(const vc_batch* b, const vc_poa_gap_params* p, const vc_poa_prune_params* pr, vc_result* r, vc_poa_correct_out* c) {

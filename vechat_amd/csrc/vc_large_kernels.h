@@ -57,6 +57,12 @@ struct LWin {
     uint32_t *sq_begin, *sq_member;                    // [nseq] begin node; index of the group member
     uint32_t msa_rows, row_size;                       // k_lg_msa<0>: rows and columns of the group's alignment
     uint32_t gr_cols, gr_path;                         // k_lg_graph<0>: columns of the alignment, path entries (bases of the added sequences)
+    // vc_poa_run_from only (0 / nullptr otherwise): the group began as a stored graph (k_lg_load).  Its first n_old sequences are
+    // the stored paths -- sq_member holds their member numbers as stored, sq_len / sq_rev their lengths and strand flags --; the
+    // sequences behind them are members of the batch, numbered from m0 in the outputs (seq_member, seq_len, seq_rev below)
+    uint32_t n_old, m0;
+    uint32_t* sq_len;                                  // [nseq]
+    uint8_t* sq_rev;                                   // [nseq]
 };
 
 struct LArgs {
@@ -81,12 +87,15 @@ struct LArgs {
     // mode 2, vc_poa_run_strand (strand = 1; nullptr / 0 elsewhere): the strand views of the batch, k_lg_views, laid out as bases /
     // quals are, and the choice per sequence of the batch
     uint32_t strand;
+    uint32_t state;                                    // mode 2, vc_poa_run_from with a vc_poa_state_out: 1 k_lg_graph writes every node's aligned list behind its block; 0 elsewhere
     uint8_t *rc_bases, *rv_quals, *rt_bases;           // reverse complement, reversed quality, the bytes complemented twice
     uint8_t* s_rev;                                    // [sequences] 1: the reverse complement was kept
     int32_t *s_score, *s_score_rev;                    // [sequences] both strands' scores
     uint64_t nbytes;                                   // k_lg_views: bytes of the batch
-    // k_lg_fwd / k_lg_back: windows of this launch and their matrices (k_lg_msa<1>, k_lg_graph<1>: groups and the byte offsets of
-    // their blocks in msa_out; k_lg_graph<1> has the offsets of the groups' scratch behind them, at hoff[groups + k])
+    // k_lg_fwd / k_lg_back: windows of this launch (indices into win) and their matrices (k_lg_msa<1>, k_lg_graph<1>: groups and the
+    // byte offsets of their blocks in msa_out; k_lg_graph<1> has the offsets of the groups' scratch behind them, at hoff[groups + k]).
+    // k_lg_load is the one other use of list: win is indexed by the block there, and list[block] is the group's index in the BATCH,
+    // which is its index in the stored graphs (LLoad)
     const uint32_t* list;
     const uint64_t* hoff;
     int32_t* H;
@@ -578,6 +587,19 @@ __host__ __device__ inline int64_t worst_case(int64_t m, int64_t gp, int64_t ge,
     return x < y ? x : y;
 }
 
+// Sequence s of a group's sequences_ as the outputs name it: its member number, its length and its strand flag.  A stored path
+// (s < n_old, vc_poa_run_from) carries its own; a member of the batch is numbered from m0 and measured in the batch.
+__device__ __forceinline__ uint32_t seq_member(const LWin& W, uint32_t s) { return s < W.n_old ? W.sq_member[s] : W.m0 + W.sq_member[s]; }
+__device__ __forceinline__ uint32_t seq_len(const LArgs& a, const LWin& W, uint32_t s) {
+    if (s < W.n_old) return W.sq_len[s];
+    const uint32_t q = W.s0 + W.sq_member[s];
+    return (uint32_t)(a.seq_off[q + 1] - a.seq_off[q]);
+}
+__device__ __forceinline__ uint8_t seq_rev(const LArgs& a, const LWin& W, uint32_t s) {
+    if (s < W.n_old) return W.sq_rev[s];
+    return a.strand ? a.s_rev[W.s0 + W.sq_member[s]] : 0;
+}
+
 // ------------------------------------------------------------------ kernels
 // biosoup::Sequence::ReverseAndComplement's byte rule (sequence.hpp:55-77): the complement is chosen on the upper-cased byte and is
 // upper case; S, W, N and every byte without a complement stay as they are, in their own case.
@@ -655,6 +677,116 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
         else for (uint32_t q = 0; q < W.L; ++q) W.total += a.lut_d[a.quals[a.seq_off[W.s0] + q]];
     }
     W.phase = PH_BUILD; W.j = 1; W.k = 0;
+}
+
+// The stored graphs of vc_poa_run_from on the device: the arrays of vc_poa_graph_in (checked by the host, check_from), and per
+// group the decoder the host prepared -- the bytes in order of first appearance along the paths, which is the order in which
+// add_alignment met them --, 256 bytes per group, and their count.
+struct LLoad {
+    const uint32_t* n_nodes;
+    const uint64_t* node_off;
+    const uint8_t* node_base;
+    const uint32_t* rank_to_node;
+    const uint64_t* out_off;
+    const uint32_t* edge_head;
+    const int64_t* edge_weight;
+    const uint64_t* al_off;
+    const uint32_t* al_node;
+    const uint64_t* path_first;
+    const uint32_t* path_member;
+    const uint8_t* path_reversed;
+    const uint64_t* path_off;
+    const uint32_t* path_node;
+    const uint8_t* dec;
+    const uint32_t* n_codes;
+};
+
+// vc_poa_run_from: a group starts as its stored graph.  One wave per group in flight (a.list: its index in the batch), behind
+// k_lg_init, which left the empty graph; the tables of W.gr[0] are filled as add_alignment would have left them, but for the ids
+// of edges and cells, which nothing reads: every stage walks a node's lists in list order.
+//   Nodes, lanes over nodes: the code through the coder, the rank, and the out-list and the aligned list from their CSR -- an
+//     edge's id is its CSR index and its successor in the list the next index, so tail, head, weight and the links follow from
+//     index arithmetic; aligned cells likewise.
+//   Paths, one after the other in sequences_ order; lanes over the consecutive pairs (u, v) of path k.  A lane finds the edge in
+//     u's out-list, appends label k to it (cell: the labels so far + its position in the path) and, where the edge has no label
+//     yet -- this sequence created it --, appends the edge to v's in-list.  A sequence meets a node once, so within one path
+//     every edge and every head is distinct and no two lanes touch the same list; successive paths are ordered by the loop and
+//     its barrier.  So an edge's labels ascend, and a head's in-list holds its in-edges by first label: the order of creation.
+//     Without labels only the in-lists are made (W.prank marks the edges met; graph_rows writes it anew before it is read).
+// The counts are set last; a group without a new member is finished here, on its stored graph.  A table that cannot hold the
+// stored graph sets W.grow like any other.
+__global__ __launch_bounds__(64) void k_lg_load(LArgs a, LLoad f) {
+    const uint32_t lane = threadIdx.x;
+    LWin& W = a.win[blockIdx.x];
+    const uint32_t w = a.list[blockIdx.x];
+    LGraph& g = W.gr[0];
+    const uint64_t nb = f.node_off[w], ob = nb + w, p0 = f.path_first[w];
+    const uint32_t N = f.n_nodes[w], S = (uint32_t)(f.path_first[w + 1] - p0);
+    const uint64_t e0 = f.out_off[ob], c0 = f.al_off[ob], t0 = f.path_off[p0];
+    const uint32_t E = (uint32_t)(f.out_off[ob + N] - e0), A = (uint32_t)(f.al_off[ob + N] - c0), T = (uint32_t)(f.path_off[p0 + S] - t0);
+    const bool labels = g.labels != 0;
+    uint32_t grow = 0;                                                     // (the same in every lane)
+    if (N > W.NC) grow |= G_NODES;
+    if (E > W.EC) grow |= G_EDGES;
+    if (A > W.AC) grow |= G_ALIGNED;
+    if (labels && T - S > W.LC) grow |= G_LABELS;
+    if (grow) { if (lane == 0) W.grow |= grow; return; }
+    const uint32_t nc = f.n_codes[w];
+    for (uint32_t c = lane; c < nc; c += 64) {
+        const uint8_t byte = f.dec[256ull * w + c];
+        W.coder[byte] = (int32_t)c; W.decoder[c] = byte;
+    }
+    __syncthreads();
+    for (uint32_t v = lane; v < N; v += 64) {
+        g.code[v] = (uint8_t)W.coder[f.node_base[nb + v]];
+        g.rank[v] = f.rank_to_node[nb + v];
+        g.in_h[v] = g.in_t[v] = NONE; g.in_n[v] = 0;
+        const uint32_t o0 = (uint32_t)(f.out_off[ob + v] - e0), o1 = (uint32_t)(f.out_off[ob + v + 1] - e0);
+        g.out_h[v] = o1 > o0 ? o0 : NONE; g.out_t[v] = o1 > o0 ? o1 - 1 : NONE; g.out_n[v] = o1 - o0;
+        for (uint32_t e = o0; e < o1; ++e) {
+            g.tail[e] = v; g.head[e] = f.edge_head[e0 + e]; g.weight[e] = f.edge_weight[e0 + e]; g.alive[e] = 1;
+            g.nx_out[e] = e + 1 < o1 ? e + 1 : NONE; g.nx_in[e] = NONE; g.lb_h[e] = g.lb_t[e] = NONE;
+            W.prank[e] = 0;
+        }
+        const uint32_t a0 = (uint32_t)(f.al_off[ob + v] - c0), a1 = (uint32_t)(f.al_off[ob + v + 1] - c0);
+        g.al_h[v] = a1 > a0 ? a0 : NONE; g.al_t[v] = a1 > a0 ? a1 - 1 : NONE; g.al_n[v] = a1 - a0;
+        for (uint32_t c = a0; c < a1; ++c) { g.al_v[c] = f.al_node[c0 + c]; g.al_nx[c] = c + 1 < a1 ? c + 1 : NONE; }
+    }
+    __syncthreads();
+    uint32_t lb = 0;
+    for (uint32_t k = 0; k < S; ++k) {
+        const uint64_t po = f.path_off[p0 + k];
+        const uint32_t len = (uint32_t)(f.path_off[p0 + k + 1] - po);
+        const uint32_t* pn = f.path_node + po;
+        if (lane == 0 && W.sq_begin) {
+            W.sq_begin[k] = pn[0]; W.sq_member[k] = f.path_member[p0 + k];
+            W.sq_len[k] = len; W.sq_rev[k] = f.path_reversed[p0 + k] != 0;
+        }
+        for (uint32_t i = lane; i + 1 < len; i += 64) {
+            const uint32_t u = pn[i], v = pn[i + 1];
+            uint32_t e = g.out_h[u];
+            while (e != NONE && g.head[e] != v) e = g.nx_out[e];
+            if (e == NONE) continue;                                       // (the host has checked that the pair is an edge)
+            if (labels) {
+                const uint32_t c = lb + i;
+                g.lb_v[c] = k; g.lb_nx[c] = NONE;
+                if (g.lb_t[e] == NONE) g.lb_h[e] = c; else g.lb_nx[g.lb_t[e]] = c;
+                g.lb_t[e] = c;
+            }
+            if (W.prank[e] == 0) {
+                W.prank[e] = 1;
+                if (g.in_t[v] == NONE) g.in_h[v] = e; else g.nx_in[g.in_t[v]] = e;
+                g.in_t[v] = e; g.in_n[v]++;
+            }
+        }
+        lb += len - 1;
+        __syncthreads();
+    }
+    if (lane == 0) {
+        g.n_nodes = N; g.n_edges = E; g.n_al = A; g.n_lb = labels ? lb : 0; g.n_rank = N; g.nseq = S;
+        W.num_codes = nc;
+        if (W.nseq == 0) finish_poa(W);                                    // no new member: the consensus of the stored graph
+    }
 }
 
 // The graph half of an alignment's preparation, over graph g of W: node -> rank, and per rank the row byte, the sink flag and the
@@ -1263,7 +1395,7 @@ __global__ __launch_bounds__(64) void k_lg_msa(LArgs a) {
             }
         }
         uint32_t* mem = (uint32_t*)(out + ((total + 15) & ~15ull));
-        for (uint32_t s = lane; s < W.msa_rows; s += 64) mem[s] = s < g.nseq ? W.sq_member[s] : VC_POA_ROW_CONSENSUS;
+        for (uint32_t s = lane; s < W.msa_rows; s += 64) mem[s] = s < g.nseq ? seq_member(W, s) : VC_POA_ROW_CONSENSUS;
         if (a.msa & VC_POA_COVERAGE) {
             uint32_t* cov = mem + ((W.msa_rows + 3) & ~3u);
             for (uint32_t i = lane; i < W.cons_n; i += 64) {
@@ -1300,6 +1432,10 @@ __host__ __device__ inline GraphBlock graph_block(uint64_t N, uint64_t E, uint64
     B.bytes = off;
     return B;
 }
+// The state table of vc_poa_state_out, behind the block when LArgs::state asks for it: N + 1 offsets into A aligned-list cells,
+// then the cells, each part padded to 16 bytes.
+__host__ __device__ inline uint64_t state_list_at(uint64_t N) { return (4 * (N + 1) + 15) & ~15ull; }
+__host__ __device__ inline uint64_t state_bytes(uint64_t N, uint64_t A) { return state_list_at(N) + ((4 * A + 15) & ~15ull); }
 // the (sequence, column) scratch of the path stage beside it
 __host__ __device__ inline uint64_t graph_scratch_bytes(uint64_t S, uint64_t cols) { return (4 * S * cols + 15) & ~15ull; }
 
@@ -1320,7 +1456,8 @@ __host__ __device__ inline uint64_t graph_scratch_bytes(uint64_t S, uint64_t col
 //     the scratch (S x columns of NONE) and every row is compacted with a wave prefix sum behind the sequence's offset (a
 //     prefix sum of the lengths).  a.graph == 2 takes the literal walk instead, a lane per sequence: the dependent chain, kept
 //     to be measured against.  A kept reverse strand's path stays in graph order and is flagged (main.cpp:178-187 reverses it
-//     while printing).
+//     while printing).  With LArgs::state (vc_poa_state_out) every node's whole aligned list follows behind the block, in list
+//     order: offsets from a wave prefix sum of al_n, as out_off is made, then every lane walks its own node's list.
 template <uint32_t PH>
 __global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
     const uint32_t lane = threadIdx.x;
@@ -1330,10 +1467,7 @@ __global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
         const LGraph& g = W.gr[W.cur];
         const uint32_t cols = msa_columns(W, g, lane);
         uint32_t t = 0;
-        for (uint32_t s = lane; s < g.nseq; s += 64) {
-            const uint32_t q = W.s0 + W.sq_member[s];
-            t += (uint32_t)(a.seq_off[q + 1] - a.seq_off[q]);
-        }
+        for (uint32_t s = lane; s < g.nseq; s += 64) t += seq_len(a, W, s);
         for (uint32_t d = 32; d; d >>= 1) t += __shfl_xor(t, d, 64);
         if (lane == 0) { W.gr_cols = cols; W.gr_path = t; }
     } else {
@@ -1350,6 +1484,8 @@ __global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
         uint8_t* rev = out + B.rev;
         uint32_t *p_off = (uint32_t*)(out + B.p_off), *p_node = (uint32_t*)(out + B.p_node), *cons_node = (uint32_t*)(out + B.cons_node);
         uint32_t* scr = (uint32_t*)(a.msa_out + a.hoff[gridDim.x + blockIdx.x]);
+        const uint32_t A = a.state ? g.n_al : 0;                           // the state table behind the block: al_off, al_node
+        uint32_t *st_off = (uint32_t*)(out + B.bytes), *st_node = (uint32_t*)(out + B.bytes + state_list_at(N));
         const uint64_t cells = a.graph == 1 ? (uint64_t)S * cols : 0;
         const uint4 none4 = make_uint4(NONE, NONE, NONE, NONE);
         for (uint64_t k = lane; k < ((uint64_t)N + 3) / 4; k += 64) ((uint4*)cons_pos)[k] = none4;      // -1
@@ -1361,10 +1497,9 @@ __global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
             const uint32_t s = s0 + lane;
             uint32_t len = 0;
             if (s < S) {
-                const uint32_t q = W.s0 + W.sq_member[s];
-                len = (uint32_t)(a.seq_off[q + 1] - a.seq_off[q]);
-                member[s] = W.sq_member[s];
-                rev[s] = a.strand ? a.s_rev[q] : 0;
+                len = seq_len(a, W, s);
+                member[s] = seq_member(W, s);
+                rev[s] = seq_rev(a, W, s);
             }
             const uint32_t x = wave_scan(len, lane);
             if (s < S) p_off[s] = carry + x - len;
@@ -1374,15 +1509,25 @@ __global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
         __syncthreads();
         for (uint32_t i = lane; i < Cn; i += 64) { cons_pos[W.comp[i]] = (int32_t)i; cons_node[i] = W.comp[i]; }
         // out-edges and aligned pairs
-        uint32_t ce = 0, cp = 0;
+        uint32_t ce = 0, cp = 0, ca = 0;
         for (uint32_t v0 = 0; v0 < N; v0 += 64) {
             const uint32_t v = v0 + lane;
-            uint32_t ne = 0, np = 0;
+            uint32_t ne = 0, np = 0, na = 0;
             if (v < N) {
                 ne = g.out_n[v];
                 for (uint32_t q = g.al_h[v]; q != NONE; q = g.al_nx[q]) np += g.al_v[q] > v;
+                na = g.al_n[v];
             }
             const uint32_t xe = wave_scan(ne, lane), xp = wave_scan(np, lane);
+            if (a.state) {                                                 // every node's whole aligned list, in list order
+                const uint32_t xa = wave_scan(na, lane);
+                if (v < N) {
+                    uint32_t k = ca + xa - na;
+                    st_off[v] = k;
+                    for (uint32_t q = g.al_h[v]; q != NONE && k < A; q = g.al_nx[q], ++k) st_node[k] = g.al_v[q];
+                }
+                ca += __shfl(xa, 63, 64);
+            }
             if (v < N) {
                 uint32_t k = ce + xe - ne;
                 out_off[v] = k;
@@ -1394,6 +1539,7 @@ __global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
             ce += __shfl(xe, 63, 64); cp += __shfl(xp, 63, 64);
         }
         if (lane == 0) out_off[N] = ce;
+        if (a.state && lane == 0) st_off[N] = ca;
         // the paths
         if (a.graph == 2) {
             for (uint32_t s = lane; s < S; s += 64) {

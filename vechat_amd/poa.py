@@ -7,7 +7,8 @@ semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chos
     python -m vechat_amd.poa [-m 5] [-n -4] [-g -8] [--gap-extend E] [--gap-open2 Q] [--gap-extend2 C] [-l 0|1|2] [-r 0|1|2]
                              [--coverage] [--both-strands] [--gfa | --gfa-consensus] [--graphviz FILE]
                              [--align QUERIES --align-out FILE [--align-both-strands]]
-                             [--correct FILE [--min-confidence D] [--min-support S] [--prune-rounds K]] [--device D] FILE [FILE ...]
+                             [--correct FILE [--min-confidence D] [--min-support S] [--prune-rounds K]]
+                             [--save-graphs FILE] [--from-graphs FILE] [--device D] FILE [FILE ...]
 
 prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`,
 or with -r 1 / -r 2 the multiple sequence alignment of its records as FASTA (`>name` / row, with -r 2 a last row `>Consensus`;
@@ -33,6 +34,12 @@ then the record's local alignment against what is left; vc_poa_run_correct, poa_
 record under its own name, in input order, a record that aligns nowhere with an empty sequence line.  The output on stdout is
 unchanged.  --min-confidence / --min-support / --prune-rounds default to the reference's 0.22 / 0.19 / 3.  It does not go
 with -r 1 / -r 2, --gfa*, --graphviz, --both-strands or --align: those describe the unpruned graph and stay with their own calls.
+--save-graphs FILE stores the finished graph of every input file, with the state a group goes on from, in one .npz file
+(PoaGraph.save; vc_poa_run_from), and --from-graphs FILE starts from such a file instead of from nothing: input file k then holds
+the records to ADD to stored graph k (poa_extend), and with no input file at all nothing is added and the groups carry the names
+of the files they were stored from.  Both go with the consensus output, --both-strands and --align (which then runs against the
+stored graphs with no build, poa_align(graphs=...)), and with each other; not with -r 1 / -r 2, --coverage, --gfa*, --graphviz or
+--correct, which name records that a stored graph no longer has.
 The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
 as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
 non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
@@ -133,10 +140,11 @@ def group_batch(groups):
                       np.zeros(len(groups), np.uint8))
 
 
-def _result_buffers(batch):
-    """-> (consensus bytes, offsets, status, VcResult over them, the batch as a struct whose seq_begin / seq_end / win_fasta are NULL)"""
+def _result_buffers(batch, stored_nodes=0):
+    """-> (consensus bytes, offsets, status, VcResult over them, the batch as a struct whose seq_begin / seq_end / win_fasta are NULL)
+    stored_nodes: the nodes of the graphs the groups start from (vc_poa_run_from), which the consensus may run through as well"""
     n = batch.n_windows
-    cons = np.zeros(max(int(batch.bases.size), 1), np.uint8)       # a group's consensus is never longer than its sequences
+    cons = np.zeros(max(int(batch.bases.size) + stored_nodes, 1), np.uint8)   # a group's consensus is never longer than its sequences
     off = np.zeros(n + 1, np.uint64)
     status = np.zeros(max(n, 1), np.uint8)
     r = capi.VcResult(off.ctypes.data_as(C.POINTER(C.c_uint64)), cons.ctypes.data_as(C.POINTER(C.c_uint8)), cons.size,
@@ -155,15 +163,45 @@ def _per_group(x, wso):
     return [x[wso[w]:wso[w + 1]].copy() for w in range(len(wso) - 1)]
 
 
-def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_scores=True, graph=False, qbatch=None, align_flags=0):
+def _graph_in(graphs):
+    """stored graphs (PoaGraph made with resumable=True) -> (capi.VcPoaGraphIn, the arrays it points into: keep them alive)"""
+    for g in graphs:
+        if not isinstance(g, PoaGraph) or not g.resumable:
+            raise ValueError("a graph to start from must come from poa_graph(..., resumable=True), poa_extend or PoaGraph.load: "
+                             "without the aligned lists and the member count a group cannot go on (include/vechat_hip.h)")
+    cat = lambda xs, dt: np.ascontiguousarray(np.concatenate([np.zeros(0, dt)] + [np.asarray(x, dt) for x in xs]), dt)
+    offs = lambda xs: np.concatenate([[0], np.cumsum([int(x) for x in xs])]).astype(np.uint64)
+
+    def csr(local, counts):                 # per group nodes + 1 local offsets -> one table, every group rebased behind the one before
+        base = offs(counts)
+        return cat([np.asarray(o, np.uint64) + base[w] for w, o in enumerate(local)], np.uint64)
+
+    keep = dict(
+        n_members=np.array([g.n_members for g in graphs], np.uint32), n_nodes=np.array([g.n_nodes for g in graphs], np.uint32),
+        node_off=offs(g.n_nodes for g in graphs), node_base=cat([g.node_base for g in graphs], np.uint8),
+        rank_to_node=cat([g.rank_to_node for g in graphs], np.uint32),
+        out_off=csr([g.out_off for g in graphs], [g.edge_head.size for g in graphs]),
+        edge_head=cat([g.edge_head for g in graphs], np.uint32), edge_weight=cat([g.edge_weight for g in graphs], np.int64),
+        al_off=csr([g.al_off for g in graphs], [g.al_node.size for g in graphs]), al_node=cat([g.al_node for g in graphs], np.uint32),
+        path_first=offs(g.path_member.size for g in graphs), path_member=cat([g.path_member for g in graphs], np.uint32),
+        path_reversed=cat([g.path_reversed for g in graphs], np.uint8),
+        path_off=offs(n for g in graphs for n in np.diff(g.path_off)), path_node=cat([g.path_node for g in graphs], np.uint32))
+    ct = {np.dtype(np.uint8): C.c_uint8, np.dtype(np.uint32): C.c_uint32, np.dtype(np.uint64): C.c_uint64, np.dtype(np.int64): C.c_int64}
+    return capi.VcPoaGraphIn(len(graphs), **{k: v.ctypes.data_as(C.POINTER(ct[v.dtype])) for k, v in keep.items()}), keep
+
+
+def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_scores=True, graph=False, qbatch=None, align_flags=0,
+         start=None, state=False):
     """One library call on a capi.Batch (its seq_begin / seq_end / win_fasta are passed as NULL) with the outputs asked for:
     msa_flags (capi.VC_POA_* bits, None: no vc_poa_msa_out), strands (spoa's -s; strand_scores: with the score arrays), graph,
     qbatch + align_flags (the queries of vc_poa_run_align).  The entry is the first of vc_poa_run_align (queries), _graph, _strand,
     _msa that the request needs, else vc_poa_run_gaps (capi.VcPoaGapParams) or vc_poa_run (capi.VcPoaParams).  Everything is
-    copied out of the library's buffers -> _Outputs.  Raises PoaError, naming the entry, on a library error."""
+    copied out of the library's buffers -> _Outputs.  Raises PoaError, naming the entry, on a library error.
+    start (a list of resumable PoaGraph, one per group of the batch) and state (with graph: the graphs come back resumable) go
+    through vc_poa_run_from; every other request takes the entry it always took."""
     lib = lib or capi.load_hip()
     n = batch.n_windows
-    cons, off, status, r, vb = _result_buffers(batch)
+    cons, off, status, r, vb = _result_buffers(batch, sum(g.n_nodes for g in start if isinstance(g, PoaGraph)) if start is not None else 0)
     wso = [int(x) for x in batch.win_seq_off]
     o = capi.VcPoaMsaOut(flags=msa_flags) if msa_flags is not None else None
     g = capi.VcPoaGraphOut() if graph else None
@@ -175,13 +213,26 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
             sc, scr = np.zeros(nseq, np.int32), np.zeros(nseq, np.int32)
         so = C.byref(capi.VcPoaStrandOut(rev.ctypes.data_as(C.POINTER(C.c_uint8)),
                                          *(x if x is None else x.ctypes.data_as(C.POINTER(C.c_int32)) for x in (sc, scr))))
+    qv = a = st = keep = None
+    first = ()                                  # what an entry takes between the parameters and the batch
     if qbatch is not None:
-        name = "vc_poa_run_align"
-        if not hasattr(lib, name):
-            raise PoaError("this libvechat_hip.so has no vc_poa_run_align: it was built before the entry point existed; rebuild it")
         qv = qbatch.as_struct()
         qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
         a = capi.VcPoaAlignOut(flags=align_flags)
+    if start is not None or state:
+        name = "vc_poa_run_from"
+        if not hasattr(lib, name):
+            raise PoaError("this libvechat_hip.so has no vc_poa_run_from: it was built before the entry point existed; rebuild it")
+        if start is not None and len(start) != n:
+            raise ValueError(f"{len(start)} graphs to start from for {n} groups")
+        gin, keep = _graph_in(start) if start is not None else (None, None)     # (keep: the arrays gin points into, until the call)
+        st = capi.VcPoaStateOut() if state else None
+        ref = lambda x: None if x is None else C.byref(x)
+        first, args = (ref(gin),), (ref(o), so, ref(g), ref(st), ref(qv), ref(a))
+    elif qbatch is not None:
+        name = "vc_poa_run_align"
+        if not hasattr(lib, name):
+            raise PoaError("this libvechat_hip.so has no vc_poa_run_align: it was built before the entry point existed; rebuild it")
         args = (so, C.byref(g) if graph else None, C.byref(qv), C.byref(a))
     elif graph:
         name, args = "vc_poa_run_graph", (C.byref(o), so, C.byref(g))
@@ -191,13 +242,16 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         name, args = "vc_poa_run_msa", (C.byref(o),)
     else:
         name, args = "vc_poa_run_gaps" if isinstance(params, capi.VcPoaGapParams) else "vc_poa_run", ()
-    rc = getattr(lib, name)(C.byref(params), C.byref(vb), C.byref(r), *args)
+    rc = getattr(lib, name)(C.byref(params), *first, C.byref(vb), C.byref(r), *args)
     if rc != 0:
         raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     x = _Outputs()
     x.cons, x.status = [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n]
     x.msas = _msa_results(o, msa_flags, n, cons, off, wso, rev) if o is not None else None
     x.graphs = _graph_results(g, n, cons, off, x.msas if msa_flags or (strands and o is not None) else None) if graph else None
+    if st is not None:
+        had = [0] * n if start is None else [s.n_members for s in start]
+        _state_results(st, x.graphs, [had[w] + wso[w + 1] - wso[w] for w in range(n)])
     x.scores, x.scores_rev = (_per_group(sc, wso), _per_group(scr, wso)) if sc is not None else (None, None)
     x.queries = _query_results(a, align_flags, [int(k) for k in qbatch.win_seq_off]) if qbatch is not None else None
     return x
@@ -329,14 +383,68 @@ class PoaGraph:
       aligned_a, aligned_b (uint32): pairs of aligned nodes, a < b
       path_member (uint32), path_reversed (bool), path_off (int64, paths + 1), path_node (uint32): one path per member that was
         added -- an empty member has none --, in graph order; a reversed path belongs to a member whose reverse complement was kept
-      cons_node (uint32), consensus (bytes); msa (an Msa, with poa_graph(msa=True), else None)"""
+      cons_node (uint32), consensus (bytes); msa (an Msa, with poa_graph(msa=True), else None)
+    A resumable graph (poa_graph(resumable=True), poa_extend, PoaGraph.load) also carries the state a group goes on from
+    (vc_poa_state_out): al_off (int64, nodes + 1), al_node (uint32) -- node v's whole aligned list, in list order, is
+    al_node[al_off[v] .. al_off[v + 1]); aligned_lists gives them as lists -- and n_members, the members the group has had so
+    far, empty ones included: the next member is numbered n_members."""
     __slots__ = ("node_base", "node_cons_pos", "rank_to_node", "out_off", "edge_head", "edge_weight", "aligned_a", "aligned_b",
-                 "path_member", "path_reversed", "path_off", "path_node", "cons_node", "consensus", "msa")
+                 "path_member", "path_reversed", "path_off", "path_node", "cons_node", "consensus", "msa", "al_off", "al_node", "n_members")
+    _ARRAYS = (("node_base", np.uint8), ("node_cons_pos", np.int32), ("rank_to_node", np.uint32), ("out_off", np.int64),
+               ("edge_head", np.uint32), ("edge_weight", np.int64), ("aligned_a", np.uint32), ("aligned_b", np.uint32),
+               ("path_member", np.uint32), ("path_reversed", np.bool_), ("path_off", np.int64), ("path_node", np.uint32),
+               ("cons_node", np.uint32), ("al_off", np.int64), ("al_node", np.uint32))
 
     def __init__(self, **kw):
-        self.msa = None
+        self.msa = self.al_off = self.al_node = self.n_members = None
         for k, v in kw.items():
             setattr(self, k, v)
+
+    @property
+    def resumable(self):
+        return self.al_off is not None and self.n_members is not None
+
+    @property
+    def aligned_lists(self):
+        """-> per node the list of the nodes aligned to it, in list order (None unless resumable)"""
+        if self.al_off is None:
+            return None
+        ao, an = self.al_off.tolist(), self.al_node.tolist()
+        return [an[ao[v]:ao[v + 1]] for v in range(self.n_nodes)]
+
+    @staticmethod
+    def save(path, graphs, names=None):
+        """Stores a list of resumable graphs as one .npz file at exactly `path`, numpy arrays only: every table of every graph
+        back to back with a table of lengths, the consensus, n_members, and with names= one name (bytes) per graph."""
+        for g in graphs:
+            if not isinstance(g, PoaGraph) or not g.resumable:
+                raise ValueError("only resumable graphs can be stored: poa_graph(..., resumable=True), poa_extend")
+        data = {"n_members": np.array([g.n_members for g in graphs], np.uint32)}
+        for k, dt in PoaGraph._ARRAYS:
+            xs = [np.asarray(getattr(g, k), dt) for g in graphs]
+            data[k] = np.concatenate([np.zeros(0, dt)] + xs)
+            data[k + "_len"] = np.array([x.size for x in xs], np.int64)
+        cons = [bytes(g.consensus) for g in graphs]
+        data["consensus"] = np.frombuffer(b"".join(cons), np.uint8)
+        data["consensus_len"] = np.array([len(c) for c in cons], np.int64)
+        if names is not None:
+            data["names"] = np.array([_bytes(x, "graph name") for x in names], dtype=np.bytes_).reshape(len(graphs))
+        with open(path, "wb") as f:
+            np.savez(f, **data)
+
+    @staticmethod
+    def load(path, names=False):
+        """-> the list of graphs PoaGraph.save stored at `path`; with names=True (that list, their names as bytes or None)"""
+        with np.load(path, allow_pickle=False) as z:
+            data = {k: z[k] for k in z.files}
+        graphs = [PoaGraph(n_members=int(m)) for m in data["n_members"]]
+        for k, dt in PoaGraph._ARRAYS + (("consensus", np.uint8),):
+            at = np.concatenate([[0], np.cumsum(data[k + "_len"])]).astype(np.int64)
+            for w, g in enumerate(graphs):
+                x = data[k][at[w]:at[w + 1]].astype(dt, copy=True)
+                setattr(g, k, x.tobytes() if k == "consensus" else x)
+        stored = [bytes(x) for x in data["names"]] if "names" in data else None
+        return (graphs, stored) if names else graphs
 
     @property
     def n_nodes(self):
@@ -447,19 +555,61 @@ def _graph_results(g, n, cons, off, msas=None):
     return res
 
 
+def _state_results(st, graphs, n_members):
+    """adds the state of a filled capi.VcPoaStateOut to the PoaGraph of every group: al_off, al_node, n_members"""
+    n = len(graphs)
+    nn = sum(g.n_nodes for g in graphs)
+    al_off = _table(st.al_off, nn + n).astype(np.int64) if n else np.zeros(0, np.int64)
+    al_node = _table(st.al_node, int(al_off[-1]) if n else 0)
+    at = 0
+    for w, g in enumerate(graphs):
+        ao = al_off[at:at + g.n_nodes + 1]
+        at += g.n_nodes + 1
+        g.al_off, g.al_node, g.n_members = ao - ao[0], al_node[int(ao[0]):int(ao[-1])].copy(), int(n_members[w])
+
+
 def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-              gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False):
+              gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, resumable=False):
     """The partial order graph of every group (vc_poa_run_graph) -> list of PoaGraph: nodes, weighted edges, aligned nodes, the
     path of every member and the consensus path, as spoa's GFA (-r 3 / -r 4) and dot (-d) output hold them; PoaGraph.to_gfa and
     to_dot give those bytes.  Parameters, PoaError and strict as poa_consensus (a group that was not computed comes back as None
     with strict=False); the gap scores left out are spoa's overload defaults.  strand_ambiguous=True builds the graph with spoa's
     -s (poa_consensus_strands): a member whose reverse complement was kept has a path with reversed=True.  msa=True also asks
-    for the multiple sequence alignment of the same graph in the same call: PoaGraph.msa, as poa_msa() returns it."""
+    for the multiple sequence alignment of the same graph in the same call: PoaGraph.msa, as poa_msa() returns it.
+    resumable=True (vc_poa_run_from) also returns the state a group goes on from -- aligned_lists and n_members --, so that the
+    graphs can be stored (PoaGraph.save), extended (poa_extend) and queried (poa_align(graphs=...)) without building them again."""
     batch = group_batch(groups)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
-    res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous)[:2]
+    if resumable:
+        x = _run(batch, p, lib=lib, msa_flags=capi.VC_POA_MSA if msa else 0, strands=strand_ambiguous, graph=True, state=True)
+        res, status = x.graphs, x.status
+    else:
+        res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous)[:2]
     bad = _not_computed(status, strict)
     return [None if w in bad else m for w, m in enumerate(res)]
+
+
+def poa_extend(graphs, groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+               gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, include_consensus=False,
+               coverage=False):
+    """Adds the members of groups[w] to the stored graph graphs[w] (vc_poa_run_from; spoa's AddAlignment on a live graph) -> (the
+    new graphs, resumable again, the list of consensus bytes); with msa=True or coverage=True -> (graphs, consensus, list of
+    Msa), the alignment of all members so far as poa_msa returns it (include_consensus as there), also at PoaGraph.msa.
+    The new members are numbered from graphs[w].n_members in Msa.members and path_member; with strand_ambiguous=True they are
+    added with spoa's -s and Msa.reversed tells about them alone.  With the parameters of the call that made the graphs, the
+    result is byte for byte the one call on all members.  A graph made without resumable=True raises ValueError; parameters,
+    PoaError and strict as poa_consensus."""
+    if len(graphs) != len(groups):
+        raise ValueError(f"{len(graphs)} graphs for {len(groups)} groups")
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    want_msa = msa or coverage
+    flags = (capi.VC_POA_MSA if msa else 0) | (capi.VC_POA_MSA_CONSENSUS if msa and include_consensus else 0) | (capi.VC_POA_COVERAGE if coverage else 0)
+    x = _run(group_batch(groups), p, lib=lib, msa_flags=flags if want_msa or strand_ambiguous else None, strands=strand_ambiguous,
+             graph=True, start=list(graphs), state=True)
+    bad = _not_computed(x.status, strict)
+    out = [None if w in bad else g for w, g in enumerate(x.graphs)]
+    cons = [None if w in bad else c for w, c in enumerate(x.cons)]
+    return (out, cons, [None if w in bad else m for w, m in enumerate(x.msas)]) if want_msa else (out, cons)
 
 
 class QueryAlignment:
@@ -505,23 +655,40 @@ def _query_results(a, flags, wq):
             for w in range(len(wq) - 1)]
 
 
-def poa_align(groups, queries, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-              gap_extend=None, gap_open2=None, gap_extend2=None, pairs=True, both_strands=False, strand_ambiguous=False, graph=False):
+def poa_align(groups=None, queries=None, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+              gap_extend=None, gap_open2=None, gap_extend2=None, pairs=True, both_strands=False, strand_ambiguous=False, graph=False,
+              graphs=None):
     """Aligns queries against the finished graphs of their groups without adding them (spoa's engine->Align(query, graph,
     &score); vc_poa_run_align): queries[w] is the list of queries of groups[w] -> per group a list of QueryAlignment; with
     graph=True -> (that, list of PoaGraph of the same call), whose node ids the pairs refer to.  pairs=False returns the scores
     only (no backtrack runs).  both_strands aligns every query as given and reverse-complemented and keeps the better, ties as
     given (VC_POA_ALIGN_STRANDS); strand_ambiguous is the build's -s, as in poa_graph.  Parameters, PoaError and strict as
     poa_consensus: a group that was not computed raises, or with strict=False its queries carry its status.  ValueError when
-    the number of query lists differs from the number of groups."""
+    the number of query lists differs from the number of groups.
+    graphs= (resumable PoaGraph, one per query list) aligns against stored graphs with no build in the call (vc_poa_run_from):
+    give either groups or graphs; both together first add groups[w] to graphs[w] and then align, and graph=True then returns the
+    extended graphs, resumable again."""
+    if queries is None:
+        raise ValueError("poa_align needs queries")
+    if groups is None and graphs is None:
+        raise ValueError("poa_align needs groups to build, or graphs to align against (or both, to extend the graphs first)")
+    if groups is None:
+        groups = [[] for _ in graphs]
     if len(queries) != len(groups):
         raise ValueError(f"{len(queries)} query lists for {len(groups)} groups")
+    if graphs is not None and len(graphs) != len(groups):
+        raise ValueError(f"{len(graphs)} graphs for {len(groups)} groups")
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
     flags = (capi.VC_POA_ALIGN_PAIRS if pairs else 0) | (capi.VC_POA_ALIGN_STRANDS if both_strands else 0)
-    _, status, res, graphs = run_batch_align(group_batch(groups), query_batch(queries), p, flags, lib, strands=strand_ambiguous, graph=graph)
+    if graphs is not None:
+        x = _run(group_batch(groups), p, lib=lib, strands=strand_ambiguous, strand_scores=False, graph=graph, qbatch=query_batch(queries),
+                 align_flags=flags, start=list(graphs), state=graph)
+        status, res, out = x.status, x.queries, x.graphs
+    else:
+        _, status, res, out = run_batch_align(group_batch(groups), query_batch(queries), p, flags, lib, strands=strand_ambiguous, graph=graph)
     bad = _not_computed(status, strict)
     if graph:
-        return res, [None if w in bad else g for w, g in enumerate(graphs)]
+        return res, [None if w in bad else g for w, g in enumerate(out)]
     return res
 
 
@@ -656,9 +823,16 @@ def parse_args(argv=None):
     ap.add_argument("--min-confidence", type=float, default=0.22, metavar="D", help="with --correct: minimum confidence of an edge (default 0.22)")
     ap.add_argument("--min-support", type=float, default=0.19, metavar="S", help="with --correct: minimum support of an edge (default 0.19)")
     ap.add_argument("--prune-rounds", type=int, default=3, metavar="K", help="with --correct: number of prune rounds, >= 1 (default 3)")
+    ap.add_argument("--save-graphs", metavar="FILE", default=None,
+                    help="also store the finished graph of every input file in FILE (.npz), to go on from later")
+    ap.add_argument("--from-graphs", metavar="FILE", default=None,
+                    help="start from the graphs stored in FILE: input file k is added to graph k; without input files nothing is added")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
-    ap.add_argument("files", nargs="+", metavar="FILE")
-    return ap.parse_args(argv)
+    ap.add_argument("files", nargs="*", metavar="FILE")
+    a = ap.parse_args(argv)
+    if not a.files and a.from_graphs is None:
+        ap.error("the following arguments are required: FILE")
+    return a
 
 
 def main(argv=None):
@@ -678,6 +852,11 @@ def main(argv=None):
         print("vechat_amd.poa: --correct does not go with -r 1 / -r 2, --gfa / --gfa-consensus, --graphviz, --both-strands or --align "
               "(they describe the unpruned graph: run them on their own)", file=sys.stderr)
         return 1
+    resume = a.save_graphs is not None or a.from_graphs is not None
+    if resume and (a.r != 0 or a.coverage or gfa or a.graphviz is not None or a.correct is not None):
+        print("vechat_amd.poa: --save-graphs / --from-graphs do not go with -r 1 / -r 2, --coverage, --gfa / --gfa-consensus, --graphviz "
+              "or --correct", file=sys.stderr)
+        return 1
     # what the command line asks for: the alignment rows or the coverage (a vc_poa_msa_out, which vc_poa_run_align does not carry),
     # the graph tables, the queries
     want_msa = a.r != 0 or a.coverage
@@ -689,7 +868,28 @@ def main(argv=None):
         groups = [[(data, qual) for _, data, qual in recs] for recs in records]
         gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
         p = _gap_params(a.l, a.m, a.n, a.g, a.device, **gaps)
-        if a.correct is not None:
+        if resume:
+            # one call of vc_poa_run_from: the stored graphs (or none), the records to add (or none), the queries (or none)
+            start, names = PoaGraph.load(a.from_graphs, names=True) if a.from_graphs is not None else (None, None)
+            if start is not None and not a.files:
+                groups, names = [[] for _ in start], names or [b"graph%d" % (k + 1) for k in range(len(start))]
+            else:
+                names = a.files
+            if start is not None and len(start) != len(groups):
+                raise ValueError(f"{a.from_graphs} holds {len(start)} graphs for {len(groups)} input files")
+            qrecs = list(seqio.read_sequences(a.align)) if a.align is not None else None
+            flags = capi.VC_POA_ALIGN_PAIRS | (capi.VC_POA_ALIGN_STRANDS if a.align_both_strands else 0)
+            x = _run(group_batch(groups), p, strands=a.both_strands, strand_scores=False, graph=a.save_graphs is not None,
+                     qbatch=query_batch([[data for _, data, _ in qrecs]] * len(groups)) if qrecs is not None else None,
+                     align_flags=flags, start=start, state=a.save_graphs is not None)
+            _not_computed(x.status, True)
+            if a.save_graphs is not None:
+                PoaGraph.save(a.save_graphs, x.graphs, names)
+            if qrecs is not None:
+                with open(a.align_out, "wb") as f:
+                    f.write(align_tsv([name for name, _, _ in qrecs], names, x.queries))
+            cons = x.cons
+        elif a.correct is not None:
             # one call: the consensus of the unpruned graph (with --coverage a second, plain one below) and every record corrected
             res, status = run_batch_correct(group_batch(groups), p, _prune_params(a.min_confidence, a.min_support, a.prune_rounds))
             _not_computed(status, True)
@@ -697,7 +897,7 @@ def main(argv=None):
                 f.write(corrected_fasta(records, res))
             if not want_msa:
                 cons = [c.consensus for c in res]
-        if a.align is not None:
+        if a.align is not None and not resume:
             # every query against every group.  Without rows or coverage this one call builds the groups once and gives the
             # consensus or the graph too; beside them it is a call of its own
             qrecs = list(seqio.read_sequences(a.align))
@@ -707,7 +907,9 @@ def main(argv=None):
             _not_computed(status, True)
             with open(a.align_out, "wb") as f:
                 f.write(align_tsv([name for name, _, _ in qrecs], a.files, res))
-        if a.align is not None and not want_msa:
+        if resume:
+            pass
+        elif a.align is not None and not want_msa:
             cons, graphs = (None if gfa else c), gr
         elif cons is not None:
             pass
