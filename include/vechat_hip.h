@@ -684,6 +684,43 @@ int         vc_poa_run_from(const vc_poa_gap_params* p, const vc_poa_graph_in* f
                             vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_state_out* st,
                             const vc_batch* q, vc_poa_align_out* a);
 
+/* Span-limited alignment of group members: spoa's Graph::Subgraph / UpdateAlignment (graph.cpp:640-745) for POA groups, as the
+ * reference's Window::generate_consensus uses them (window.cpp:207-213) -- for groups whose members are shorter than their
+ * locus: tiled amplicons, the reads that map to a contig, a long construct sequenced in pieces.  Against the whole graph such a
+ * member costs rows it does not need, a global alignment of it is wrong, a local one loses its ends, and a repeat inside the locus
+ * may attract it to the wrong copy.
+ * p, b, r, o, s and g as vc_poa_run_graph (o, s and g may each be NULL).  spans holds one (begin, end) per sequence of b,
+ * caller-owned and read during the call only.  The flow is spoa's own, per group and in the order given:
+ *   1. sequence 0 is aligned against the (empty) graph and added; its own span entries are ignored;
+ *   2. a later member whose begin == end == VC_POA_SPAN_NONE is aligned against the whole graph, as in every other entry;
+ *   3. any other member is aligned against graph.Subgraph(begin, end, &map) with the call's engine and gap model -- the nodes from
+ *      which `end` can be reached backwards over in-edges and aligned nodes without passing below id `begin` --, the alignment is
+ *      mapped back with UpdateAlignment and added to the full graph with AddAlignment.  What of the member lies before or behind
+ *      what the subgraph aligned becomes new chains, as AddAlignment makes them.
+ * Coordinates: begin and end are inclusive positions on sequence 0 of the group.  A group is built from nothing here, so base k
+ * of sequence 0 is node k (the id rule of vc_poa_run_graph) and the span is a pair of node ids.
+ * The library applies no span rule of its own: racon's "within 1 % of both window ends counts as spanning" (window.cpp:207-208)
+ * is the caller's to apply or not -- it says NONE or gives a span --, and the members stay in the order given, with no rank sort.
+ * With s (spoa's -s) both strands of a member are aligned against the same subgraph and the better one is mapped back and added,
+ * ties going forward; the span is in sequence 0's coordinates whichever strand is kept.
+ * o and g describe the full graph, exactly as in vc_poa_run_msa / vc_poa_run_graph: a subgraph never shows.
+ * An empty member adds nothing, with or without a span.
+ * spans == NULL, or every entry VC_POA_SPAN_NONE, is the entry the same outputs would have selected -- the first of
+ * vc_poa_run_graph (g), _strand (s), _msa (o), _gaps that they need --, byte for byte, launch for launch and log line for log
+ * line: nothing of the spans reaches the device then.
+ * Spans are untrusted: a bad node id on the device would be a fault.  Checked on the host before the device is touched, in this
+ * order: as vc_poa_run_graph (with g == NULL counting as "no graph output", s and o likewise), the batch included; then the span
+ * arrays (NULL beside a sequence); then, member by member in batch order, for every member but the first of its group whose span
+ * is not NONE / NONE: never exactly one of the two entries NONE; begin <= end; end < the length of sequence 0 of its group.  A
+ * violation is VC_ERR_ARG and vc_poa_last_error names the group and the member.  A group whose sequence 0 is empty therefore admits
+ * no span.  VC_ERR_NO_DEVICE only after these.
+ * Out of scope: spans for vc_poa_run_from (in a loaded graph a position on sequence 0 is not a node id without its path), for
+ * vc_poa_run_correct (its rounds rebuild and renumber the graph) and for the queries of vc_poa_run_align. */
+#define VC_POA_SPAN_NONE 0xFFFFFFFFu
+typedef struct vc_poa_span_in { const uint32_t* begin; const uint32_t* end; } vc_poa_span_in;   /* [n_seqs of b], caller-owned */
+int         vc_poa_run_spans(const vc_poa_gap_params* p, const vc_poa_span_in* spans /* NULL: no span */, const vc_batch* b, vc_result* r,
+                             vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g);   /* o, s, g may be NULL, as in vc_poa_run_graph */
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,14 @@ vc_poa_graph_in before it, and nothing is copied out of the library's tables ins
   (c) one rocprofv3 --kernel-trace --stats run of its own (build 3/4, add 1/4) for k_lg_load beside k_lg_apply;
   (d) with --parent-lib the consensus-only rate of this library beside the parent commit's in alternating processes.
 Exits 1 if a stored-graph result differs from the one-shot one or an expectation of (a) or (b) is missed.
+--spans [--groups 512] [--locus 8000] [--len 1000] [--depth 32] [--parent-lib LIB]: span-limited alignment (vc_poa_run_spans;
+profiles/poa_spans_rate.txt).  Every group is one random backbone of --locus bases plus locus / len x depth reads of --len bases
+tiled over it, their true ranges as spans; global, 5/-4/-8, one process, three calls of each kind after a warm-up: the span call
+and the plain call on the same groups, with sub_rows / full_rows of the `spans` log line.  Expected, stated in the file before the
+figures: the forward cells fall by about len / locus, k_lg_apply and the serial subgraph() in k_lg_prep do not, so the time falls
+by less.  With --parent-lib the plain path -- consensus only on the standard 4 096 groups of 32 x 1 kb -- of this library beside
+the parent commit's in alternating processes; then one rocprofv3 --kernel-trace --stats run of its own of the span call for the
+shares of k_lg_prep, k_lg_fwd and k_lg_apply.
 """
 import argparse
 import csv
@@ -662,6 +670,132 @@ def main_correct(a):
     return 0
 
 
+def tiled_groups(a):
+    """--spans: a.groups groups of one random backbone of a.locus bases plus, per tile of a.len bases, a.depth reads of the tile
+    (4 % substitutions, 1 % deletions, 1 % insertions), in tile order, no qualities -> (capi.Batch, (begin, end) span arrays: the
+    reads' true ranges, inclusive; none for the backbone)"""
+    import numpy as np
+    rng = np.random.default_rng(4100)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    groups, begin, end = [], [], []
+    for _ in range(a.groups):
+        backbone = acgt[rng.integers(0, 4, a.locus)]
+        mem = [backbone.tobytes()]
+        begin.append(capi.VC_POA_SPAN_NONE); end.append(capi.VC_POA_SPAN_NONE)
+        for b in range(0, a.locus, a.len):
+            tile = backbone[b:b + a.len]
+            for _ in range(a.depth):
+                x = rng.random(tile.size)
+                s = np.where(x < 0.04, acgt[rng.integers(0, 4, tile.size)], tile)
+                rep = np.where(x > 0.99, 2, np.where(x > 0.98, 0, 1))      # an insertion repeats the base, a deletion drops it
+                mem.append(np.repeat(s, rep).tobytes())
+                begin.append(b); end.append(b + tile.size - 1)
+        groups.append(mem)
+    return poa.group_batch(groups), (np.array(begin, np.uint32), np.array(end, np.uint32))
+
+
+def timed_spans(batch, spans=None):
+    """-> (seconds, (members, sub_rows, full_rows) of the `spans` line or None, (alignments, cells) of the `done` line, consensus) of
+    one vc_poa_run_spans (global, 5/-4/-8 linear) on the batch, or with spans=None of the plain vc_poa_run_gaps on the same groups"""
+    p = capi.VcPoaGapParams(**LINEAR_NW)
+    import re
+    import tempfile
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            cons, status = poa.run_batch(batch, p, spans=spans)
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        err = log.read().decode()
+    if int((status != 0).sum()):
+        raise RuntimeError(f"{int((status != 0).sum())} groups not computed")
+    m = re.search(r"vc_large: spans members=(\d+) sub_rows=(\d+) full_rows=(\d+)", err)
+    d = re.search(r"vc_large: done alignments=(\d+) cells=(\d+)", err)
+    return dt, tuple(map(int, m.groups())) if m else None, tuple(map(int, d.groups())) if d else (0, 0), cons
+
+
+def main_spans(a):
+    """profiles/poa_spans_rate.txt: three plain and three span calls on the tiled groups in one process; with --parent-lib the
+    consensus-only rate of this library beside the parent commit's on the standard groups, in alternating processes; one kernel
+    trace of the span call"""
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_spans_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    batch, spans = tiled_groups(a)
+    reads = a.depth * ((a.locus + a.len - 1) // a.len)
+    emit(f"POA groups with span-limited alignment: {a.groups} groups of one backbone of {a.locus} bp plus {reads} reads of {a.len} bp tiled over it "
+         f"({a.depth} per tile; 4 % substitutions, 1 % deletions, 1 % insertions; no qualities), {int(batch.seq_off[-1])} bases; spans: the reads' "
+         f"true ranges; 5/-4/-8, global (kNW); one MI355X; synchronous; host clock around one call; one untimed call of each kind first, then "
+         f"three calls of each kind in the same process")
+    emit(f"expected before the run: forward cells fall by about len / locus = {a.len / a.locus:.3f}; k_lg_apply and the serial subgraph() in "
+         f"k_lg_prep do not fall, so the call's time falls by less")
+    timed_spans(batch, spans)
+    runs = [timed_spans(batch, spans) for _ in range(3)]
+    m, sub_rows, full_rows = runs[0][1]
+    emit(f"{'spans (vc_poa_run_spans)':44s} " + "  ".join(f"{a.groups / r[0]:7.2f}" for r in runs) +
+         f" groups/s  ({'  '.join(f'{r[0]:.2f}' for r in runs)} s; {runs[0][2][0]} forward passes, {runs[0][2][1] / 1e9:.1f} G cells; "
+         f"spans line: members={m} sub_rows={sub_rows} full_rows={full_rows}, sub_rows / full_rows = {sub_rows / full_rows:.4f})")
+    timed_spans(batch)
+    plain = [timed_spans(batch) for _ in range(3)]
+    emit(f"{'plain, same groups (vc_poa_run_gaps)':44s} " + "  ".join(f"{a.groups / r[0]:7.2f}" for r in plain) +
+         f" groups/s  ({'  '.join(f'{r[0]:.2f}' for r in plain)} s; {plain[0][2][0]} forward passes, {plain[0][2][1] / 1e9:.1f} G cells)")
+    med = lambda v: sorted(v)[len(v) // 2]                                # noqa: E731
+    same = sum(1 for x, y in zip(runs[0][3], plain[0][3]) if x == y)
+    emit(f"span call / plain call: time {med([r[0] for r in runs]) / med([r[0] for r in plain]):.3f} (medians), forward cells "
+         f"{runs[0][2][1] / plain[0][2][1]:.3f}; the two consensus sequences are equal in {same} of {a.groups} groups (they are different "
+         f"alignments: a plain global alignment stretches a tile's read over the whole locus)")
+    large.release()
+    if not a.no_trace:
+        d = os.path.join(a.trace_dir, "spans")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+               sys.executable, os.path.abspath(__file__), "--child", "1", "--spans", "--groups", str(a.groups), "--locus", str(a.locus),
+               "--len", str(a.len), "--depth", str(a.depth)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"kernel trace: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return 1
+        ms = kernel_shares(d)
+        tot = sum(ms.values())
+        emit(f"kernel times of one span call, a run of its own under rocprofv3 --kernel-trace --stats: {tot / 1e3:.2f} s: " +
+             ", ".join(f"{k} {v:.1f} ms ({v / tot * 100:.2f} %)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+    if a.parent_lib:
+        # the plain path on the standard groups; the two libraries alternate, each run a process of its own (a warm-up call, then three
+        # timed ones): parent, this, parent, this
+        std = 4096
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "0", "--graph", "--groups", str(std), "--len", "1000", "--depth", "32"]
+        secs = {"parent": [], "this": []}
+        for which in ("parent", "this", "parent", "this"):
+            p = subprocess.run(cmd + (["--parent-lib", os.path.abspath(a.parent_lib)] if which == "parent" else []),
+                               capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"{which} library: run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1                          # nothing more is started on the device after a failed run
+            t = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            secs[which] += t
+            name = "library of the parent commit" if which == "parent" else "this library"
+            emit(f"{'plain path, ' + name:44s} " + "  ".join(f"{std / x:7.1f}" for x in t) +
+                 f" groups/s  ({'  '.join(f'{x:.3f}' for x in t)} s; consensus only, {std} groups of 32 x 1000 bp, a process of its own)")
+        par, cur = sorted(secs["parent"]), sorted(secs["this"])
+        med2 = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2     # noqa: E731
+        emit(f"plain path over the two alternated processes each: the parent's {std / par[-1]:.1f} .. {std / par[0]:.1f} groups/s, this library's "
+             f"{std / cur[-1]:.1f} .. {std / cur[0]:.1f}; median against median {(med2(cur) / med2(par) - 1) * 100:+.2f} % in time; the parent's "
+             f"documented spread is 408-417 groups/s (profiles/poa_rate.txt)")
+    print("wrote", out)
+    return 0
+
+
 LINEAR_NW = dict(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
 
 
@@ -842,9 +976,14 @@ def child(a):
         dt = resume_call(tail, stored_graphs(head))[0]
         print(json.dumps(dict(seconds=dt)))
         return
+    if a.spans:                                   # the traced run: one span call on the tiled groups
+        batch, spans = tiled_groups(a)
+        dt, line, done, _ = timed_spans(batch, spans)
+        print(json.dumps(dict(seconds=dt, spans=line, cells=done[1])))
+        return
     if a.correct:
         batch = synth_groups(a)
-        if a.child == 0:                          # consensus only, three calls after a full warm-up (this library's or the parent's)
+        if a.child == 0:                         # consensus only, three calls after a full warm-up (this library's or the parent's)
             lib = parent_handle(a.parent_lib) if a.parent_lib else None
             timed_correct(batch, a.prune_rounds, correct=False, lib=lib)
             print(json.dumps(dict(seconds=[timed_correct(batch, a.prune_rounds, correct=False, lib=lib)[0] for _ in range(3)])))
@@ -942,6 +1081,9 @@ def main():
     ap.add_argument("--align", action="store_true", help="measure vc_poa_run_align's query stage beside the plain call (profiles/poa_align_rate.txt)")
     ap.add_argument("--correct", action="store_true", help="measure vc_poa_run_correct beside the consensus-only call (profiles/poa_correct_rate.txt)")
     ap.add_argument("--resume", action="store_true", help="measure vc_poa_run_from: stored-graph queries, extending, k_lg_load (profiles/poa_resume_rate.txt)")
+    ap.add_argument("--spans", action="store_true", help="measure vc_poa_run_spans beside the plain call on tiled groups (profiles/poa_spans_rate.txt; "
+                                                         "--groups defaults to 512 here)")
+    ap.add_argument("--locus", type=int, default=8000, help="--spans: bases of a group's backbone, tiled by reads of --len bases, --depth per tile")
     ap.add_argument("--prune-rounds", type=int, default=3, help="--correct: num_prune (default 3)")
     ap.add_argument("--queries-per-group", type=int, default=32, help="--align: mutated members per group beside the held-out one")
     ap.add_argument("--parent-gaps", default="linear,affine,convex", help="--align --parent-lib: the gap models compared with the parent's library")
@@ -950,8 +1092,12 @@ def main():
     ap.add_argument("--append", action="store_true", help="--strand: keep what the output file holds and write below it")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.spans and "--groups" not in sys.argv:
+        a.groups = 512
     if a.child is not None:
         return child(a)
+    if a.spans:
+        return main_spans(a)
     if a.resume:
         return main_resume(a)
     if a.correct:

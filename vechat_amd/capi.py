@@ -139,6 +139,14 @@ class VcPoaGraphIn(C.Structure):
     ]
 
 
+VC_POA_SPAN_NONE = 0xFFFFFFFF
+
+
+class VcPoaSpanIn(C.Structure):
+    """vc_poa_span_in: caller-owned, one (begin, end) per sequence of the batch; VC_POA_SPAN_NONE in both: the whole graph"""
+    _fields_ = [("begin", C.POINTER(C.c_uint32)), ("end", C.POINTER(C.c_uint32))]
+
+
 class VcPoaPruneParams(C.Structure):
     """vc_poa_prune_params: the thresholds and rounds of vc_poa_run_correct (the reference's defaults: 0.22 / 0.19 / 3)"""
     _fields_ = [("min_confidence", C.c_double), ("min_support", C.c_double), ("num_prune", C.c_uint32)]
@@ -441,6 +449,11 @@ def load_hip():
                                             C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut),
                                             C.POINTER(VcPoaStateOut), C.POINTER(VcBatch), C.POINTER(VcPoaAlignOut)]
             lib.vc_poa_run_from.restype = C.c_int
+        # (likewise: the parent commit's library, beside which tools/gpu_poa_rate.py --spans measures, has no such entry)
+        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_spans"):
+            lib.vc_poa_run_spans.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaSpanIn), C.POINTER(VcBatch), C.POINTER(VcResult),
+                                             C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut)]
+            lib.vc_poa_run_spans.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

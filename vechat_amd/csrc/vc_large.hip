@@ -21,6 +21,14 @@
 //     UpdateAlignment, "< 3 sequences", prune, trim, window type or FASTA-backbone quirk; seq_begin / seq_end / win_fasta are
 //     never uploaded.  An empty sequence adds nothing (graph.cpp:187-190); a group of none, or of empty ones only, has the
 //     empty consensus (graph.cpp:534-537).
+//     vc_poa_run_spans alone brings one window rule back, and only where the caller asks for it member by member: a later
+//     member with a span (inclusive positions on sequence 0, which are node ids in a group built from nothing) is aligned against
+//     Subgraph(begin, end) -- k_lg_prep extracts it into the other graph slot with schedule 0's subgraph(), one lane per group --,
+//     k_lg_fwd / k_lg_back read its rows (view_of), and k_lg_apply maps the pairs back through W.map (UpdateAlignment) before
+//     AddAlignment on the full graph; W.cur never flips.  The library applies no 1 % rule and no rank sort.  The spans travel in
+//     LArgs::seq_begin / seq_end under LArgs::spans; a call without a span uploads none and is the plain call.  Both graph slots,
+//     W.map, W.g2s, W.mark and W.stack have the full capacities in every schedule (layout), so spans change no allocation, and
+//     a table that subgraph() fills (nodes, edges, aligned cells, stack) sets W.grow and the group runs again, as in the build.
 //   kOV (semi-global, sisd_alignment_engine.cpp:227-247, 350-358, 380-382) differs from kNW in three places: column 0 of every
 //   graph row is 0 (row 0 stays j * g); the end cell is the first maximum in (rank, column) order over the cells j >= 1 of the
 //   sink rows; the backtrack stops at i == 0 || j == 0.
@@ -93,6 +101,11 @@
 //                           the graph line does not count),
 //                           "vc_large: load groups=G nodes=N edges=E paths=P bytes=B" (vc_poa_run_from with stored graphs: what was
 //                           uploaded, once per call),
+//                           "vc_large: spans members=M sub_rows=R full_rows=F" (vc_poa_run_spans with at least one span, before the
+//                           "done" line: the members that were aligned against a subgraph, the rows of their forward passes summed,
+//                           and the rows the same passes would have had against the whole graph; the rows count both strands'
+//                           passes; every member counts once: a group that runs again with larger tables starts from zero, and
+//                           a member whose matrix the device refused is not counted),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes of the build, their rows x
 //                           columns summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes;
 //                           vc_poa_run_correct counts the rounds' passes too, not the final stage's).
@@ -270,6 +283,7 @@ struct PoaRequest {
     vc_poa_correct_out* correct = nullptr;
     const vc_poa_graph_in* from = nullptr;             // vc_poa_run_from: the stored graphs the groups start as, and the state table beside the graph's
     vc_poa_state_out* state = nullptr;
+    const vc_poa_span_in* spans = nullptr;             // vc_poa_run_spans with at least one span (check_spans leaves nullptr otherwise)
     bool rows() const { return msa_flags != 0; }                           // k_lg_msa runs
     bool keeps_labels() const { return msa_flags != 0 || graph != nullptr; }   // the edges keep sequence labels
     bool keeps_seqs() const { return keeps_labels(); }                     // the windows keep sq_begin / sq_member
@@ -372,6 +386,10 @@ struct Run {
     std::vector<std::vector<uint8_t>> out;             // per window: the consensus
     std::vector<uint8_t> status;
     uint64_t n_align = 0, n_cells = 0;                 // forward passes run (VC_LARGE_LOG's "done" line)
+    // vc_poa_run_spans (the "spans" line), per group: members aligned to a subgraph, the rows of their forward passes, the whole
+    // graph's rows for the same passes.  A group that runs again starts from zero, so every member counts once
+    struct SpanCount { uint64_t members = 0, rows = 0, full = 0; };
+    std::vector<SpanCount> sp_of;
     std::vector<std::vector<uint32_t>> mem_of, cov_of; // msa: per window the row members and the coverage
     uint64_t msa_launches = 0;
     std::vector<GraphPart> part;                       // graph: per window its block
@@ -649,6 +667,15 @@ bool lock_step(Run& R, Group& G) {
         }
         if (!live) break;
         if (!align_step(R, G, act)) return false;
+        if (a.spans) {
+            // the "spans" line, per group: a member whose forward passes ran on a subgraph (a refused matrix has left rows == 0)
+            for (const uint32_t k : act) {
+                const LWin& W = G.hw[k];
+                if (!W.rows || !W.sub) continue;
+                Run::SpanCount& c = R.sp_of[G.ids[k]];
+                c.members++; c.rows += (uint64_t)W.rows * R.ns; c.full += (uint64_t)W.gr[W.cur].n_nodes * R.ns;
+            }
+        }
         hipLaunchKernelGGL(k_lg_apply, lanes, dim3(64), 0, 0, a);
         ok = hipGetLastError() == hipSuccess;
     }
@@ -661,6 +688,7 @@ bool lock_step(Run& R, Group& G) {
 // a table of window w filled (W.grow): larger tables, and the window runs again unless they outgrow the 32-bit ids
 void regrow(Run& R, uint32_t w, const LWin& W) {
     Caps& c = R.caps[w];
+    if (!R.sp_of.empty()) R.sp_of[w] = Run::SpanCount{};                   // the group runs again: its members are counted then
     if (W.grow & G_NODES) c.NC *= 2;
     if (W.grow & G_EDGES) c.EC *= 2;
     if (W.grow & G_ALIGNED) c.AC *= 2;
@@ -1127,6 +1155,12 @@ int copy_strands(const Run& R) {
 
 // the closing log line, then consensus and status in window order
 int assemble(Run& R, vc_result* r) {
+    if (R.kn.log && R.a.spans) {
+        Run::SpanCount t;
+        for (const Run::SpanCount& c : R.sp_of) { t.members += c.members; t.rows += c.rows; t.full += c.full; }
+        std::fprintf(stderr, "vc_large: spans members=%llu sub_rows=%llu full_rows=%llu\n", (unsigned long long)t.members,
+                     (unsigned long long)t.rows, (unsigned long long)t.full);
+    }
     if (R.kn.log) std::fprintf(stderr, "vc_large: done alignments=%llu cells=%llu\n", (unsigned long long)R.n_align, (unsigned long long)R.n_cells);
     uint64_t o = 0;
     for (uint32_t w = 0; w < R.nw; ++w) {
@@ -1147,6 +1181,13 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     Run R{a, b, caps, kn, q, a.mode == 1 || q.keeps_labels(), nw, b->win_seq_off[nw], b->seq_off[b->win_seq_off[nw]]};
     DevMem mem;                                                            // the batch and the strand views: held until the call ends
     if (const int rc = upload_batch(R, mem, a.mode != 2)) return rc;
+    if (q.spans) {                                                         // vc_poa_run_spans: the spans where the windows' positions go
+        uint32_t *d_sb = nullptr, *d_se = nullptr;
+        if (!mem.alloc(&d_sb, R.nseq_all, q.spans->begin) || !mem.alloc(&d_se, R.nseq_all, q.spans->end))
+            return fail(VC_ERR_HIP, "device allocation or copy of the spans failed");
+        R.a.seq_begin = d_sb; R.a.seq_end = d_se; R.a.spans = 1;
+        R.sp_of.resize(nw);
+    }
     if (q.strand) if (const int rc = strand_views(R, mem)) return rc;
     if (q.from) if (const int rc = upload_stored(R, mem)) return rc;
     if (q.has_queries()) {
@@ -1333,6 +1374,39 @@ int check_from(const vc_poa_graph_in* f, const vc_batch* b) {
     return VC_OK;
 }
 
+// vc_poa_run_spans' spans, after the batch and before the device.  They are untrusted and become node ids on the device, so
+// every rule is checked here, member by member in batch order: both entries NONE or neither; begin <= end; end on sequence 0 of
+// the group (whose base k is node k: the group is built from nothing).  Sequence 0's own entries are not read.  A call in which
+// no member has a span is the call without spans: A.spans is cleared and nothing of them reaches the device.
+int check_spans(PoaRequest& A, const vc_batch* b) {
+    const vc_poa_span_in* sp = A.spans;
+    A.spans = nullptr;
+    const uint32_t nw = b->n_windows;
+    if (!sp || nw == 0 || b->win_seq_off[nw] == 0) return VC_OK;
+    if (!sp->begin || !sp->end) return fail(VC_ERR_ARG, "null span array");
+    bool any = false;
+    char msg[160];
+    for (uint32_t w = 0; w < nw; ++w) {
+        const uint32_t s0 = b->win_seq_off[w], s1 = b->win_seq_off[w + 1];
+        for (uint32_t s = s0 + 1; s < s1; ++s) {
+            const uint32_t sb = sp->begin[s], se = sp->end[s];
+            if (sb == VC_POA_SPAN_NONE && se == VC_POA_SPAN_NONE) continue;
+            const uint64_t L = b->seq_off[s0 + 1] - b->seq_off[s0];
+            const char* what = sb == VC_POA_SPAN_NONE || se == VC_POA_SPAN_NONE ? "has only one of begin and end set to VC_POA_SPAN_NONE"
+                               : sb > se                                       ? "begins behind its end"
+                               : se >= L                                       ? "ends beyond sequence 0 of its group"
+                                                                               : nullptr;
+            if (what) {
+                std::snprintf(msg, sizeof msg, "the span of member %u of group %u %s", s - s0, w, what);
+                return fail(VC_ERR_ARG, msg);
+            }
+            any = true;
+        }
+    }
+    if (any) A.spans = sp;
+    return VC_OK;
+}
+
 // The vc_poa_* entries after their score checks: the knobs, the batch (still without the device), the queries, the device, the
 // run.  `a` holds the scores.
 int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, PoaRequest& q) {
@@ -1372,6 +1446,7 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
             k.NC += c.N; k.EC += c.E; k.AC += c.A; k.LC += c.T; k.SC += c.N + c.E + c.A; k.PC += c.N; k.nseq += c.S;
         }
     }
+    if (const int rc = check_spans(q, b)) return rc;
     a.num_prune = 1;
     if (q.required & PoaRequest::CORRECT) {
         // vc_poa_run_correct's own arguments, after the batch and before the device
@@ -1517,6 +1592,14 @@ int vc_poa_run_from(const vc_poa_gap_params* p, const vc_poa_graph_in* from, con
     const uint32_t required = q ? PoaRequest::ALIGN : g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0;
     PoaRequest rq{required, o, s, g, q, a};
     rq.from = from; rq.state = st;
+    return poa_run(p, b, r, rq);
+}
+
+int vc_poa_run_spans(const vc_poa_gap_params* p, const vc_poa_span_in* spans, const vc_batch* b, vc_result* r, vc_poa_msa_out* o,
+                     vc_poa_strand_out* s, vc_poa_graph_out* g) {
+    // the entry the call would be without `spans`: the first of vc_poa_run_graph, _strand, _msa, _gaps it needs
+    PoaRequest rq{g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0u, o, s, g};
+    rq.spans = spans;
     return poa_run(p, b, r, rq);
 }
 

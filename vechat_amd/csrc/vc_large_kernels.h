@@ -88,6 +88,9 @@ struct LArgs {
     // quals are, and the choice per sequence of the batch
     uint32_t strand;
     uint32_t state;                                    // mode 2, vc_poa_run_from with a vc_poa_state_out: 1 k_lg_graph writes every node's aligned list behind its block; 0 elsewhere
+    // mode 2, vc_poa_run_spans with at least one span (0 elsewhere, and seq_begin / seq_end are nullptr then): seq_begin / seq_end
+    // hold, per sequence of the batch, the inclusive node range on sequence 0 of its group, or NONE / NONE for the whole graph
+    uint32_t spans;
     uint8_t *rc_bases, *rv_quals, *rt_bases;           // reverse complement, reversed quality, the bytes complemented twice
     uint8_t* s_rev;                                    // [sequences] 1: the reverse complement was kept
     int32_t *s_score, *s_score_rev;                    // [sequences] both strands' scores
@@ -818,6 +821,15 @@ __global__ __launch_bounds__(64) void k_lg_prep(LArgs a) {
     if (a.mode == 2) {                                                     // POA group: the next sequence against the whole graph
         W.qs = W.s0 + W.j;
         W.type = a.algorithm; W.m = a.match; W.x = a.mismatch; W.g = a.gap; W.e = a.gap_e; W.q = a.gap_q; W.c = a.gap_c;
+        // vc_poa_run_spans: a later member with a span meets Subgraph(begin, end) of the graph instead (window.cpp:207-213 without
+        // its 1 % rule); an empty one adds nothing either way.  The host has checked the span against sequence 0, whose base k is
+        // node k; a span the graph does not hold is refused here all the same, before any table is indexed with it.
+        if (a.spans && W.j != 0 && a.seq_begin[W.qs] != NONE && a.seq_off[W.qs + 1] != a.seq_off[W.qs]) {
+            const uint32_t sb = a.seq_begin[W.qs], se = a.seq_end[W.qs];
+            if (sb > se || se >= W.gr[W.cur].n_nodes) { fail_window(W, VC_WIN_INVALID); return; }
+            if (!subgraph(W, W.gr[W.cur], W.gr[1 - W.cur], sb, se)) return;
+            gi = 1 - W.cur; W.sub = 1;
+        }
     } else {
         bool nw = true;
         if (W.phase == PH_BUILD) {

@@ -8,7 +8,7 @@ semi-global (kOV) alignment with linear, affine or convex gaps, the subtype chos
                              [--coverage] [--both-strands] [--gfa | --gfa-consensus] [--graphviz FILE]
                              [--align QUERIES --align-out FILE [--align-both-strands]]
                              [--correct FILE [--min-confidence D] [--min-support S] [--prune-rounds K]]
-                             [--save-graphs FILE] [--from-graphs FILE] [--device D] FILE [FILE ...]
+                             [--save-graphs FILE] [--from-graphs FILE] [--spans FILE] [--device D] FILE [FILE ...]
 
 prints, for every FASTA / FASTQ (.gz) file in argument order, the consensus of its records in the record format of spoa's `-r 0`,
 or with -r 1 / -r 2 the multiple sequence alignment of its records as FASTA (`>name` / row, with -r 2 a last row `>Consensus`;
@@ -40,6 +40,11 @@ the records to ADD to stored graph k (poa_extend), and with no input file at all
 of the files they were stored from.  Both go with the consensus output, --both-strands and --align (which then runs against the
 stored graphs with no build, poa_align(graphs=...)), and with each other; not with -r 1 / -r 2, --coverage, --gfa*, --graphviz or
 --correct, which name records that a stored graph no longer has.
+--spans FILE aligns the records it lists against a part of their file's graph only (spoa's Graph::Subgraph / UpdateAlignment;
+vc_poa_run_spans, the spans= keyword of poa_consensus, poa_consensus_strands, poa_msa and poa_graph): tab-separated lines of input
+file name, record name, begin, end -- inclusive positions on the file's first record --, records not listed meeting the whole
+graph; a file or record that does not exist and a record listed twice are errors (parse_spans).  It goes with every -r, --coverage,
+--both-strands, --gfa* and --graphviz; not with --align, --correct, --save-graphs or --from-graphs.
 The files are read with the project's reader (vechat_amd.seqio), which upper-cases the bases and counts an all-'!' quality string
 as none (src/sequence.cpp).  spoa's own command line keeps both verbatim (src/main.cpp:306-310 takes the quality overload for any
 non-empty quality string), so for lower-case / soft-masked input, or FASTQ whose qualities are all '!', the two print different
@@ -140,6 +145,61 @@ def group_batch(groups):
                       np.zeros(len(groups), np.uint8))
 
 
+def racon_spans(backbone_len, positions):
+    """The reference's rule for which layers span their window (window.cpp:207-208): offset = int(0.01 * backbone_len), and a
+    member whose begin < offset and end > backbone_len - offset is aligned against the whole graph.  positions: per member a
+    (begin, end) pair of inclusive positions on sequence 0, or None -> the list for spans=: None for the members that span (and
+    for those given as None), (begin, end) for the others.  The library itself applies no such rule (include/vechat_hip.h)."""
+    offset = int(0.01 * backbone_len)
+    out = []
+    for p in positions:
+        if p is None:
+            out.append(None)
+            continue
+        begin, end = p
+        out.append(None if begin < offset and end > backbone_len - offset else (int(begin), int(end)))
+    return out
+
+
+def span_arrays(groups, spans):
+    """spans (per group None or a list with one entry per member, each None or an inclusive (begin, end) on sequence 0 of the group)
+    -> (begin, end) uint32 arrays with one entry per sequence of group_batch(groups), VC_POA_SPAN_NONE where there is no span; None
+    when no member has a span (the call is then the plain one).  The entry of a group's first member is not read by the library and
+    is stored as none.  ValueError for what vc_poa_run_spans refuses: begin > end, end beyond sequence 0, and malformed entries."""
+    if spans is None:
+        return None
+    if len(spans) != len(groups):
+        raise ValueError(f"{len(spans)} span lists for {len(groups)} groups")
+    begin, end, found = [], [], False
+    for w, (g, sp) in enumerate(zip(groups, spans)):
+        n = len(g)
+        if sp is None:
+            sp = [None] * n
+        if isinstance(sp, (str, bytes)) or len(sp) != n:
+            raise ValueError(f"group {w}: {len(sp)} spans for {n} members (one entry per member, None or (begin, end))")
+        length0 = len(_member(g[0])[0]) if n else 0
+        for k, x in enumerate(sp):
+            if x is None or k == 0:
+                begin.append(capi.VC_POA_SPAN_NONE); end.append(capi.VC_POA_SPAN_NONE)
+                continue
+            if isinstance(x, (str, bytes)) or len(x) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in x):
+                raise ValueError(f"group {w}, member {k}: a span is None or a pair of integers (begin, end), not {x!r}")
+            b, e = int(x[0]), int(x[1])
+            if b < 0 or b > e:
+                raise ValueError(f"group {w}, member {k}: span ({b}, {e}) needs 0 <= begin <= end")
+            if e >= length0:
+                raise ValueError(f"group {w}, member {k}: span ({b}, {e}) ends beyond sequence 0 of its group ({length0} bases)")
+            begin.append(b); end.append(e)
+            found = True
+    return (np.array(begin, np.uint32), np.array(end, np.uint32)) if found else None
+
+
+def _no_spans(spans, what):
+    if spans is not None:
+        raise ValueError(f"{what} takes no spans: positions on sequence 0 are node ids only in a group that one call builds from "
+                         "nothing (include/vechat_hip.h, vc_poa_run_spans)")
+
+
 def _result_buffers(batch, stored_nodes=0):
     """-> (consensus bytes, offsets, status, VcResult over them, the batch as a struct whose seq_begin / seq_end / win_fasta are NULL)
     stored_nodes: the nodes of the graphs the groups start from (vc_poa_run_from), which the consensus may run through as well"""
@@ -191,14 +251,18 @@ def _graph_in(graphs):
 
 
 def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_scores=True, graph=False, qbatch=None, align_flags=0,
-         start=None, state=False):
+         start=None, state=False, spans=None):
     """One library call on a capi.Batch (its seq_begin / seq_end / win_fasta are passed as NULL) with the outputs asked for:
     msa_flags (capi.VC_POA_* bits, None: no vc_poa_msa_out), strands (spoa's -s; strand_scores: with the score arrays), graph,
     qbatch + align_flags (the queries of vc_poa_run_align).  The entry is the first of vc_poa_run_align (queries), _graph, _strand,
     _msa that the request needs, else vc_poa_run_gaps (capi.VcPoaGapParams) or vc_poa_run (capi.VcPoaParams).  Everything is
     copied out of the library's buffers -> _Outputs.  Raises PoaError, naming the entry, on a library error.
     start (a list of resumable PoaGraph, one per group of the batch) and state (with graph: the graphs come back resumable) go
-    through vc_poa_run_from; every other request takes the entry it always took."""
+    through vc_poa_run_from; every other request takes the entry it always took.
+    spans ((begin, end): two uint32 arrays, one entry per sequence of the batch, span_arrays) goes through vc_poa_run_spans with
+    the outputs asked for (params: capi.VcPoaGapParams); not with queries, start or state."""
+    if spans is not None and (qbatch is not None or start is not None or state):
+        raise ValueError("spans do not go with queries or with stored graphs (include/vechat_hip.h: out of scope of vc_poa_run_spans)")
     lib = lib or capi.load_hip()
     n = batch.n_windows
     cons, off, status, r, vb = _result_buffers(batch, sum(g.n_nodes for g in start if isinstance(g, PoaGraph)) if start is not None else 0)
@@ -219,7 +283,16 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         qv = qbatch.as_struct()
         qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
         a = capi.VcPoaAlignOut(flags=align_flags)
-    if start is not None or state:
+    if spans is not None:
+        name = "vc_poa_run_spans"
+        if not hasattr(lib, name):
+            raise PoaError("this libvechat_hip.so has no vc_poa_run_spans: it was built before the entry point existed; rebuild it")
+        sb, se = (np.ascontiguousarray(x, np.uint32) for x in spans)
+        keep = (sb, se)                             # (the arrays the struct points into, until the call)
+        ref = lambda x: None if x is None else C.byref(x)
+        first = (C.byref(capi.VcPoaSpanIn(*(x.ctypes.data_as(C.POINTER(C.c_uint32)) for x in keep))),)
+        args = (ref(o), so, ref(g))
+    elif start is not None or state:
         name = "vc_poa_run_from"
         if not hasattr(lib, name):
             raise PoaError("this libvechat_hip.so has no vc_poa_run_from: it was built before the entry point existed; rebuild it")
@@ -257,10 +330,10 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
     return x
 
 
-def run_batch(batch, params, lib=None):
+def run_batch(batch, params, lib=None, spans=None):
     """vc_poa_run (params: capi.VcPoaParams) or vc_poa_run_gaps (capi.VcPoaGapParams) on a capi.Batch (its seq_begin / seq_end /
     win_fasta are passed as NULL) -> (consensus bytes per group, status array).  Raises PoaError on a library error."""
-    x = _run(batch, params, lib=lib)
+    x = _run(batch, params, lib=lib, spans=spans)
     return x.cons, x.status
 
 
@@ -280,19 +353,23 @@ def _not_computed(status, strict):
 
 
 def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-                  gap_extend=None, gap_open2=None, gap_extend2=None):
+                  gap_extend=None, gap_open2=None, gap_extend2=None, spans=None):
     """Consensus of every group -> list of bytes.  The defaults are spoa's -m / -n / -g.  A group the device could not compute
     (VC_WIN_INVALID: the reference throws on it; VC_WIN_OVERFLOW: too large for the device memory) raises PoaError with the
     indices, or with strict=False comes back as None.
     gap_extend / gap_open2 / gap_extend2 are spoa's e / q / c: all None runs linear gaps through vc_poa_run; otherwise
     vc_poa_run_gaps with spoa's overload defaults (gap_extend = gap, gap_open2 = gap, gap_extend2 = gap_extend), whose subtype
-    follows gap_model()."""
+    follows gap_model().
+    spans (per group None or one entry per member, each None or an inclusive (begin, end) on sequence 0 of its group) aligns the
+    members that have one against spoa's Subgraph(begin, end) only and maps the alignment back before it is added
+    (vc_poa_run_spans; racon_spans applies the reference's 1 % rule to plain positions).  Without any span the call is the plain one."""
     batch = group_batch(groups)
-    if gap_extend is None and gap_open2 is None and gap_extend2 is None:
+    sp = span_arrays(groups, spans)
+    if gap_extend is None and gap_open2 is None and gap_extend2 is None and sp is None:
         p = capi.VcPoaParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap=gap)
     else:
         p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
-    cons, status = run_batch(batch, p, lib)
+    cons, status = run_batch(batch, p, lib, spans=sp)
     bad = _not_computed(status, strict)
     return [None if w in bad else c for w, c in enumerate(cons)]
 
@@ -332,27 +409,28 @@ def _msa_results(o, flags, n, cons, off, wso, rev):
     return res
 
 
-def run_batch_msa(batch, params, flags, lib=None, strands=False):
+def run_batch_msa(batch, params, flags, lib=None, strands=False, spans=None):
     """vc_poa_run_msa (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits) on a capi.Batch -> (list of Msa, status array).
     Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error.
     strands=True: vc_poa_run_strand instead -> (list of Msa with .reversed, status array, forward scores, reverse scores), the
     scores as one int32 array per group."""
-    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands)
+    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, spans=spans)
     return (x.msas, x.status, x.scores, x.scores_rev) if strands else (x.msas, x.status)
 
 
 def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-                          gap_extend=None, gap_open2=None, gap_extend2=None, scores=False):
+                          gap_extend=None, gap_open2=None, gap_extend2=None, scores=False, spans=None):
     """Consensus of every group whose members may come from either strand (spoa's -s, vc_poa_run_strand): every member is
     aligned as given and reverse-complemented and the better strand is added, ties going forward -> (list of consensus bytes,
     list of numpy bool arrays: per group, per member -- empty members included -- True where the reverse complement was kept).
     With scores=True also the forward and the reverse score of every member, two lists of int32 arrays.  The consensus is on the
     strand of the group's first non-empty member.  A kept forward member has been complemented twice: u / U count as T and
     lower-case IUPAC letters as upper case (include/vechat_hip.h).  Parameters, PoaError and strict as poa_consensus; the gap
-    scores left out are spoa's overload defaults."""
+    scores left out are spoa's overload defaults.  spans as in poa_consensus: both strands of a member meet the same subgraph, and
+    the span stays in sequence 0's coordinates whichever strand is kept."""
     batch = group_batch(groups)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
-    res, status, sc, scr = run_batch_msa(batch, p, 0, lib, strands=True)
+    res, status, sc, scr = run_batch_msa(batch, p, 0, lib, strands=True, spans=span_arrays(groups, spans))
     bad = _not_computed(status, strict)
     cons = [None if w in bad else m.consensus for w, m in enumerate(res)]
     rev = [m.reversed for m in res]
@@ -360,17 +438,20 @@ def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=
 
 
 def poa_msa(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-            gap_extend=None, gap_open2=None, gap_extend2=None, include_consensus=False, coverage=False, strand_ambiguous=False):
+            gap_extend=None, gap_open2=None, gap_extend2=None, include_consensus=False, coverage=False, strand_ambiguous=False,
+            spans=None):
     """The multiple sequence alignment of every group (spoa's GenerateMultipleSequenceAlignment(include_consensus)) -> list of
     Msa; with coverage=True also the coverage of every consensus base (GenerateConsensus(&summary, false)).  Parameters,
     PoaError and strict as poa_consensus (a group that was not computed comes back as None with strict=False); the gap scores
     left out are spoa's overload defaults, so the default call runs linear gaps and its consensus is poa_consensus's.
     strand_ambiguous=True is spoa's -s (vc_poa_run_strand, see poa_consensus_strands): Msa.reversed then tells, per group
-    member, whether the reverse complement was kept, and a row shows the kept bytes."""
+    member, whether the reverse complement was kept, and a row shows the kept bytes.  spans as in poa_consensus; the rows describe
+    the full graph."""
     batch = group_batch(groups)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
     flags = capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if include_consensus else 0) | (capi.VC_POA_COVERAGE if coverage else 0)
-    res, status = run_batch_msa(batch, p, flags, lib, strands=True)[:2] if strand_ambiguous else run_batch_msa(batch, p, flags, lib)
+    sp = span_arrays(groups, spans)
+    res, status = run_batch_msa(batch, p, flags, lib, strands=strand_ambiguous, spans=sp)[:2]
     bad = _not_computed(status, strict)
     return [None if w in bad else m for w, m in enumerate(res)]
 
@@ -508,12 +589,12 @@ class PoaGraph:
         return b"".join(out)
 
 
-def run_batch_graph(batch, params, flags=0, lib=None, strands=False):
+def run_batch_graph(batch, params, flags=0, lib=None, strands=False, spans=None):
     """vc_poa_run_graph (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits for the alignment beside it, 0: none) on a
     capi.Batch -> (list of PoaGraph, status array); strands=True builds the groups with spoa's -s and also returns the forward and
     reverse scores per group, as run_batch_msa.  PoaGraph.msa is the group's Msa (its .reversed set with strands).  Everything is
     copied out of the library's buffers before returning.  Raises PoaError on a library error."""
-    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, graph=True)
+    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, graph=True, spans=spans)
     return (x.graphs, x.status, x.scores, x.scores_rev) if strands else (x.graphs, x.status)
 
 
@@ -569,7 +650,7 @@ def _state_results(st, graphs, n_members):
 
 
 def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-              gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, resumable=False):
+              gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, resumable=False, spans=None):
     """The partial order graph of every group (vc_poa_run_graph) -> list of PoaGraph: nodes, weighted edges, aligned nodes, the
     path of every member and the consensus path, as spoa's GFA (-r 3 / -r 4) and dot (-d) output hold them; PoaGraph.to_gfa and
     to_dot give those bytes.  Parameters, PoaError and strict as poa_consensus (a group that was not computed comes back as None
@@ -577,28 +658,33 @@ def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0
     -s (poa_consensus_strands): a member whose reverse complement was kept has a path with reversed=True.  msa=True also asks
     for the multiple sequence alignment of the same graph in the same call: PoaGraph.msa, as poa_msa() returns it.
     resumable=True (vc_poa_run_from) also returns the state a group goes on from -- aligned_lists and n_members --, so that the
-    graphs can be stored (PoaGraph.save), extended (poa_extend) and queried (poa_align(graphs=...)) without building them again."""
+    graphs can be stored (PoaGraph.save), extended (poa_extend) and queried (poa_align(graphs=...)) without building them again.
+    spans as in poa_consensus; the tables describe the full graph.  Not with resumable=True (ValueError)."""
+    if resumable:
+        _no_spans(spans, "poa_graph(resumable=True)")
     batch = group_batch(groups)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    sp = span_arrays(groups, spans)
     if resumable:
         x = _run(batch, p, lib=lib, msa_flags=capi.VC_POA_MSA if msa else 0, strands=strand_ambiguous, graph=True, state=True)
         res, status = x.graphs, x.status
     else:
-        res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous)[:2]
+        res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous, spans=sp)[:2]
     bad = _not_computed(status, strict)
     return [None if w in bad else m for w, m in enumerate(res)]
 
 
 def poa_extend(graphs, groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
                gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, include_consensus=False,
-               coverage=False):
+               coverage=False, spans=None):
     """Adds the members of groups[w] to the stored graph graphs[w] (vc_poa_run_from; spoa's AddAlignment on a live graph) -> (the
     new graphs, resumable again, the list of consensus bytes); with msa=True or coverage=True -> (graphs, consensus, list of
     Msa), the alignment of all members so far as poa_msa returns it (include_consensus as there), also at PoaGraph.msa.
     The new members are numbered from graphs[w].n_members in Msa.members and path_member; with strand_ambiguous=True they are
     added with spoa's -s and Msa.reversed tells about them alone.  With the parameters of the call that made the graphs, the
     result is byte for byte the one call on all members.  A graph made without resumable=True raises ValueError; parameters,
-    PoaError and strict as poa_consensus."""
+    PoaError and strict as poa_consensus.  spans= is refused (ValueError): in a stored graph a position on sequence 0 is no node id."""
+    _no_spans(spans, "poa_extend")
     if len(graphs) != len(groups):
         raise ValueError(f"{len(graphs)} graphs for {len(groups)} groups")
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
@@ -657,7 +743,7 @@ def _query_results(a, flags, wq):
 
 def poa_align(groups=None, queries=None, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
               gap_extend=None, gap_open2=None, gap_extend2=None, pairs=True, both_strands=False, strand_ambiguous=False, graph=False,
-              graphs=None):
+              graphs=None, spans=None):
     """Aligns queries against the finished graphs of their groups without adding them (spoa's engine->Align(query, graph,
     &score); vc_poa_run_align): queries[w] is the list of queries of groups[w] -> per group a list of QueryAlignment; with
     graph=True -> (that, list of PoaGraph of the same call), whose node ids the pairs refer to.  pairs=False returns the scores
@@ -667,7 +753,8 @@ def poa_align(groups=None, queries=None, algorithm="global", match=5, mismatch=-
     the number of query lists differs from the number of groups.
     graphs= (resumable PoaGraph, one per query list) aligns against stored graphs with no build in the call (vc_poa_run_from):
     give either groups or graphs; both together first add groups[w] to graphs[w] and then align, and graph=True then returns the
-    extended graphs, resumable again."""
+    extended graphs, resumable again.  spans= is refused (ValueError): neither the build of this call nor its queries take them."""
+    _no_spans(spans, "poa_align")
     if queries is None:
         raise ValueError("poa_align needs queries")
     if groups is None and graphs is None:
@@ -737,14 +824,16 @@ def run_batch_correct(batch, params, prune, lib=None):
 
 
 def poa_correct(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-                gap_extend=None, gap_open2=None, gap_extend2=None, min_confidence=0.22, min_support=0.19, prune_rounds=3):
+                gap_extend=None, gap_open2=None, gap_extend2=None, min_confidence=0.22, min_support=0.19, prune_rounds=3, spans=None):
     """Haplotype-aware correction of every member of every group (vc_poa_run_correct; the flow is in include/vechat_hip.h): the
     group's graph is built as poa_consensus builds it, pruned by confidence and support down to its largest component,
     re-weighted by the members and pruned again (prune_rounds - 1 times, with the call's engine), and every member is read off its
     local alignment against what is left -- its errors removed, its variants kept -> list of Corrected (consensus, reads, scores,
     status).  The defaults are the reference's.  Parameters, PoaError and strict as poa_consensus: a group that was not computed
     raises, or with strict=False comes back as None; a member the device could not align carries its own status in
-    Corrected.status and has an empty read.  ValueError for prune_rounds < 1 or a threshold that is negative or NaN."""
+    Corrected.status and has an empty read.  ValueError for prune_rounds < 1 or a threshold that is negative or NaN, and for spans=
+    (the rounds rebuild and renumber the graph)."""
+    _no_spans(spans, "poa_correct")
     prune = _prune_params(min_confidence, min_support, prune_rounds)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
     res, status = run_batch_correct(group_batch(groups), p, prune, lib)
@@ -776,6 +865,47 @@ def align_tsv(names, files, results):
                                                       _STATUS_NAME.get(r.status, b"%d" % r.status),
                                                       r.score_rev if r.reversed else r.score, b"-" if r.reversed else b"+", prs))
     return b"".join(out)
+
+
+def parse_spans(text, files, records):
+    """The file of --spans: tab-separated lines `group-file-name, member-name, begin, end` (inclusive positions on the first record
+    of that file; empty lines and lines starting with # are skipped) -> the list for spans=, one list per input file with None
+    for every member that is not listed.  files: the input file names as given on the command line, records[w] the (name, data,
+    quality) records of file w.  ValueError for a malformed line, a file or member that does not exist (or a member name that
+    two records of the file share), and a (file, member) listed twice."""
+    index = {}
+    for w, f in enumerate(files):
+        if _bytes(f, "file name") in index:
+            raise ValueError(f"--spans: the input file {f} is given twice, so its name does not tell the groups apart")
+        index[_bytes(f, "file name")] = w
+    members = []
+    for recs in records:
+        names = {}
+        for k, (name, _, _) in enumerate(recs):
+            names.setdefault(_bytes(name, "record name"), []).append(k)
+        members.append(names)
+    spans = [[None] * len(recs) for recs in records]
+    seen = set()
+    for no, line in enumerate(_bytes(text, "span file").split(b"\n"), 1):
+        line = line.rstrip(b"\r")
+        if not line.strip() or line.startswith(b"#"):
+            continue
+        cols = line.split(b"\t")
+        if len(cols) != 4 or not cols[2].isdigit() or not cols[3].isdigit():
+            raise ValueError(f"--spans line {no}: expected group-file-name, member-name, begin, end separated by tabs")
+        f, name = cols[0], cols[1]
+        if f not in index:
+            raise ValueError(f"--spans line {no}: no input file named {f.decode(errors='replace')}")
+        w = index[f]
+        ks = members[w].get(name, [])
+        if len(ks) != 1:
+            raise ValueError(f"--spans line {no}: {f.decode(errors='replace')} has {'no' if not ks else 'more than one'} record named "
+                             f"{name.decode(errors='replace')}")
+        if (w, ks[0]) in seen:
+            raise ValueError(f"--spans line {no}: {name.decode(errors='replace')} of {f.decode(errors='replace')} is listed twice")
+        seen.add((w, ks[0]))
+        spans[w][ks[0]] = (int(cols[2]), int(cols[3]))
+    return spans
 
 
 def parse_args(argv=None):
@@ -827,6 +957,10 @@ def parse_args(argv=None):
                     help="also store the finished graph of every input file in FILE (.npz), to go on from later")
     ap.add_argument("--from-graphs", metavar="FILE", default=None,
                     help="start from the graphs stored in FILE: input file k is added to graph k; without input files nothing is added")
+    ap.add_argument("--spans", metavar="FILE", default=None,
+                    help="align the listed records against a part of their file's graph only: tab-separated lines of input file name, "
+                         "record name, begin, end (inclusive positions on the file's first record); records not listed meet the whole "
+                         "graph. Not with --align, --correct, --save-graphs or --from-graphs")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="*", metavar="FILE")
     a = ap.parse_args(argv)
@@ -857,6 +991,9 @@ def main(argv=None):
         print("vechat_amd.poa: --save-graphs / --from-graphs do not go with -r 1 / -r 2, --coverage, --gfa / --gfa-consensus, --graphviz "
               "or --correct", file=sys.stderr)
         return 1
+    if a.spans is not None and (resume or a.correct is not None or a.align is not None):
+        print("vechat_amd.poa: --spans does not go with --align, --correct, --save-graphs or --from-graphs", file=sys.stderr)
+        return 1
     # what the command line asks for: the alignment rows or the coverage (a vc_poa_msa_out, which vc_poa_run_align does not carry),
     # the graph tables, the queries
     want_msa = a.r != 0 or a.coverage
@@ -868,6 +1005,11 @@ def main(argv=None):
         groups = [[(data, qual) for _, data, qual in recs] for recs in records]
         gaps = dict(gap_extend=a.gap_extend, gap_open2=a.gap_open2, gap_extend2=a.gap_extend2)
         p = _gap_params(a.l, a.m, a.n, a.g, a.device, **gaps)
+        spans = None
+        if a.spans is not None:
+            with open(a.spans, "rb") as f:
+                spans = parse_spans(f.read(), a.files, records)
+        with_spans = dict(spans=spans) if spans is not None else {}     # (a call without --spans is the call it always was)
         if resume:
             # one call of vc_poa_run_from: the stored graphs (or none), the records to add (or none), the queries (or none)
             start, names = PoaGraph.load(a.from_graphs, names=True) if a.from_graphs is not None else (None, None)
@@ -915,7 +1057,8 @@ def main(argv=None):
             pass
         elif want_graph:
             # one call for everything: the graph carries the consensus, and with -r 1 / -r 2 / --coverage the alignment beside it
-            graphs, status = run_batch_graph(group_batch(groups), p, msa_flags, strands=a.both_strands)[:2]
+            arrays = dict(spans=span_arrays(groups, spans)) if spans is not None else {}
+            graphs, status = run_batch_graph(group_batch(groups), p, msa_flags, strands=a.both_strands, **arrays)[:2]
             _not_computed(status, True)
             if want_msa:
                 msa = [g.msa for g in graphs]
@@ -923,12 +1066,13 @@ def main(argv=None):
                 cons = [g.consensus for g in graphs]
         elif not want_msa:
             if a.both_strands:
-                cons = poa_consensus_strands(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)[0]
+                cons = poa_consensus_strands(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps, **with_spans)[0]
             else:
-                cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps)
+                cons = poa_consensus(groups, a.l, a.m, a.n, a.g, device=a.device, **gaps, **with_spans)
         else:
             strands = dict(strand_ambiguous=True) if a.both_strands else {}
-            msa = poa_msa(groups, a.l, a.m, a.n, a.g, device=a.device, include_consensus=a.r == 2, coverage=a.coverage, **gaps, **strands)
+            msa = poa_msa(groups, a.l, a.m, a.n, a.g, device=a.device, include_consensus=a.r == 2, coverage=a.coverage, **gaps, **strands,
+                          **with_spans)
         for k, g in enumerate(graphs if a.graphviz is not None else ()):
             with open(a.graphviz if k == 0 else f"{a.graphviz}.{k + 1}", "wb") as f:
                 f.write(g.to_dot())
