@@ -721,6 +721,58 @@ typedef struct vc_poa_span_in { const uint32_t* begin; const uint32_t* end; } vc
 int         vc_poa_run_spans(const vc_poa_gap_params* p, const vc_poa_span_in* spans /* NULL: no span */, const vc_batch* b, vc_result* r,
                              vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g);   /* o, s, g may be NULL, as in vc_poa_run_graph */
 
+/* Explicit weights and the per-base profile of the consensus: the two other AddAlignment overloads of spoa::Graph
+ * (graph.hpp:142-170, graph.cpp:132-196) and GenerateConsensus(&summary, true) (graph.cpp:486-529).
+ * p, b, r, o, s and g as vc_poa_run_graph (o, s, g and prof may each be NULL).
+ * Weights.  w holds one mode per sequence of b, caller-owned and read during the call only:
+ *   0  what vc_batch says: the quality overload where the member has a quality (vc_weight_lut), weight 1 for every base otherwise;
+ *   1  seq_weight[s] for every base of the member (the uint32_t weight overload): "this read stands for 37 duplicates";
+ *   2  base_weight[seq_off[s] + i] for base i (the std::vector weights overload).
+ * They are exactly the reference's: the edge between bases i - 1 and i of a member gets weights[i - 1] + weights[i], computed in
+ * uint32_t -- so it wraps modulo 2^32 -- and then added to the edge's int64_t weight (graph.cpp:125, 182-300).  Weight 0 is
+ * legal.  An empty member adds nothing, whatever its mode.  With s (spoa's -s) a kept reverse strand is added with its weight
+ * vector reversed, as its quality string is; a mode-1 member is unaffected.  spoa's "sequence and weights are of unequal size"
+ * cannot be expressed in this layout.  Weights move edge weights, and with them the consensus; they enter no alignment score.
+ * Profile.  prof, library-owned with the lifetime of vc_poa_msa_out, receives for every group the codes of its graph -- the
+ * bytes in order of first appearance, spoa's decoder_ -- and a block of (n_codes + 1) rows of cons_len uint32_t: row k counts,
+ * per consensus position, the members that carry code k in that position's column, the last row those that span it with a
+ * gap (between two of their bases that lie on consensus columns; nothing before a member's first such base or behind its last).
+ * Weights do not enter the counts.  The code rows sum to VC_POA_COVERAGE's figure but for one-base members, which Coverage() misses.  A group that is not
+ * VC_WIN_OK has n_codes = 0 and an empty block; so has a VC_WIN_OK group without a non-empty member.  prof may be asked with or
+ * without weights and with or without o, s and g.  A failed call leaves every pointer NULL.
+ * w == NULL, or every mode 0, together with prof == NULL is the entry the same outputs would have selected -- the first of
+ * vc_poa_run_graph (g), _strand (s), _msa (o), _gaps that they need --, byte for byte, launch for launch and log line for log
+ * line: nothing of the weights reaches the device then.  base_weight is uploaded only when a member has mode 2.
+ * Checked on the host before the device is touched, in this order: as vc_poa_run_graph (with g, s, o == NULL counting as "not
+ * asked"), the batch included; then w->mode NULL (with w given, whatever the batch holds); then a mode above 2 on any member; then
+ * seq_weight NULL beside a mode-1 member; then base_weight NULL beside a mode-2 member -- one kind after the other, and within a
+ * kind the first member in batch order.  A violation is VC_ERR_ARG and vc_poa_last_error names the group and the member.
+ * VC_ERR_NO_DEVICE only after these.
+ * Out of scope: weights or the profile for vc_poa_run_from (stored paths carry no weights and their profile belongs to the call that built them).
+ * Out of scope: weights or the profile for vc_poa_run_align (queries are not added, so they weigh nothing).
+ * Out of scope: weights or the profile for vc_poa_run_correct (its rounds take the quality overload of add-weights only).
+ * Out of scope: weights or the profile for vc_poa_run_spans (one extension per entry; the two do not combine yet). */
+typedef struct vc_poa_weight_in {
+    const uint8_t*  mode;         /* [n_seqs of b]  0: as vc_batch says (quality overload, or 1)
+                                                    1: seq_weight[s] for every base (spoa's uint32_t weight overload)
+                                                    2: base_weight[seq_off[s] + i]  (spoa's vector overload)          */
+    const uint32_t* seq_weight;   /* [n_seqs], read where mode == 1; may be NULL if no member has mode 1                 */
+    const uint32_t* base_weight;  /* at b->seq_off's offsets, read where mode == 2; may be NULL if no member has mode 2  */
+} vc_poa_weight_in;               /* caller-owned, read during the call only */
+
+typedef struct vc_poa_profile_out {   /* library-owned, lifetime as vc_poa_msa_out */
+    uint32_t        n_groups;
+    const uint32_t* n_codes;      /* [n_groups]  the graph's num_codes_                                                  */
+    const uint64_t* code_off;     /* [n_groups + 1] into codes                                                           */
+    const uint8_t*  codes;        /* decoder_[k] for k < n_codes[w]: the byte of row k, in order of first appearance     */
+    const uint64_t* prof_off;     /* [n_groups] offset of the group's block in counts                                    */
+    const uint32_t* counts;       /* block of (n_codes[w] + 1) rows x cons_len[w]; row k at prof_off[w] + k * cons_len;
+                                     the last row counts gaps: summary[code * consensus_.size() + c], graph.cpp:488-517  */
+} vc_poa_profile_out;
+
+int         vc_poa_run_weighted(const vc_poa_gap_params* p, const vc_poa_weight_in* w /* NULL: none */, const vc_batch* b, vc_result* r,
+                                vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_profile_out* prof /* o, s, g, prof may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

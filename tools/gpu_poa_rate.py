@@ -55,6 +55,9 @@ vc_poa_graph_in before it, and nothing is copied out of the library's tables ins
   (c) one rocprofv3 --kernel-trace --stats run of its own (build 3/4, add 1/4) for k_lg_load beside k_lg_apply;
   (d) with --parent-lib the consensus-only rate of this library beside the parent commit's in alternating processes.
 Exits 1 if a stored-graph result differs from the one-shot one or an expectation of (a) or (b) is missed.
+--weights [--parent-lib LIB]: explicit weights and the consensus profile (vc_poa_run_weighted) on the standard groups: the plain path
+beside the parent commit's library in alternating processes, every member weighted per base, the profile call beside the consensus
+and the MSA call with the bytes each copies out, a traced run -> profiles/poa_weights_rate.txt.
 --spans [--groups 512] [--locus 8000] [--len 1000] [--depth 32] [--parent-lib LIB]: span-limited alignment (vc_poa_run_spans;
 profiles/poa_spans_rate.txt).  Every group is one random backbone of --locus bases plus locus / len x depth reads of --len bases
 tiled over it, their true ranges as spans; global, 5/-4/-8, one process, three calls of each kind after a warm-up: the span call
@@ -796,6 +799,101 @@ def main_spans(a):
     return 0
 
 
+def timed_weighted(batch, weights=None, profile=False, msa=False):
+    """-> (seconds, bytes the call copied to the host beside consensus and status, consensus) of one global 5/-4/-8 linear call:
+    vc_poa_run_gaps, or vc_poa_run_weighted with weights (mode, seq_weight, base_weight) and / or the profile, or vc_poa_run_msa"""
+    p = capi.VcPoaGapParams(**LINEAR_NW)
+    t0 = time.perf_counter()
+    x = poa._run(batch, p, msa_flags=capi.VC_POA_MSA if msa else None, weights=weights, profile=profile)
+    dt = time.perf_counter() - t0
+    if int((x.status != 0).sum()):
+        raise RuntimeError(f"{int((x.status != 0).sum())} groups not computed")
+    nbytes = sum(pr.counts.nbytes + len(pr.codes) for pr in x.profiles) if profile else sum(len(r) for m in x.msas for r in m.rows) if msa else 0
+    return dt, nbytes, x.cons
+
+
+def all_mode2(batch, seed=7):
+    """every member of the batch with a weight per base, 0..60 -> the arrays of vc_poa_weight_in"""
+    import numpy as np
+    n, nb = int(batch.win_seq_off[-1]), int(batch.seq_off[-1])
+    return np.full(n, 2, np.uint8), np.zeros(n, np.uint32), np.random.default_rng(seed).integers(0, 61, nb, dtype=np.uint32)
+
+
+def main_weights(a):
+    """profiles/poa_weights_rate.txt: (i) the plain path beside the parent commit's library in alternating processes, (ii) every
+    member weighted per base beside the plain call, (iii) the profile call beside the consensus-only and the MSA call with the
+    bytes each copies out, (iv) the kernel shares of a traced profile call"""
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_weights_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    med = lambda v: sorted(v)[len(v) // 2]                                # noqa: E731
+    emit(f"POA groups with explicit weights and the consensus profile: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100, PacBio-like "
+         f"errors, frac_partial=0, FASTQ); 5/-4/-8, global (kNW); one MI355X; synchronous; host clock around one call")
+    emit("expected before the run: (i) the plain call launches k_lg_apply<false>, whose weight_of is the body it had, so it stays inside the "
+         "parent's own spread; (ii) a per-base weight is one more dependent load per base in k_lg_apply, a lane-serial kernel bound by its "
+         "pointer chases: a few per cent at most; (iii) the profile costs k_lg_msa<0> plus one scatter per group and copies (codes + 1) x 4 "
+         "bytes per consensus base instead of members bytes per column")
+    ok = True
+    if a.parent_lib:
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "0", "--graph", "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth)]
+        secs = {"parent": [], "this": []}
+        for which in ("parent", "this", "parent", "this"):
+            p = subprocess.run(cmd + (["--parent-lib", os.path.abspath(a.parent_lib)] if which == "parent" else []),
+                               capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"{which} library: run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1                          # nothing more is started on the device after a failed run
+            t = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            secs[which] += t
+            name = "library of the parent commit" if which == "parent" else "this library"
+            emit(f"(i) {'plain path, ' + name:42s} " + "  ".join(f"{a.groups / x:7.1f}" for x in t) +
+                 f" groups/s  ({'  '.join(f'{x:.3f}' for x in t)} s; consensus only, a process of its own)")
+        par, cur = sorted(secs["parent"]), sorted(secs["this"])
+        med2 = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2     # noqa: E731
+        slower, spread = med2(cur) - med2(par), par[-1] - par[0]
+        ok = slower <= spread
+        emit(f"(i) medians: parent {med2(par):.3f} s, this {med2(cur):.3f} s, difference {slower:+.3f} s ({slower / med2(par) * 100:+.2f} %); the "
+             f"parent's own runs of this session spread over {spread:.3f} s ({par[0]:.3f} .. {par[-1]:.3f}): "
+             f"{'inside the spread' if ok else 'OUTSIDE the spread'}")
+    batch = synth_groups(a)
+    timed_weighted(batch)
+    plain = [timed_weighted(batch) for _ in range(3)]
+    wts = all_mode2(batch)
+    weighted = [timed_weighted(batch, weights=wts) for _ in range(3)]
+    prof = [timed_weighted(batch, profile=True) for _ in range(3)]
+    msa = [timed_weighted(batch, msa=True) for _ in range(3)]
+    row = lambda name, runs: emit(f"{name:46s} " + "  ".join(f"{a.groups / r[0]:7.1f}" for r in runs) +      # noqa: E731
+                                  f" groups/s  ({'  '.join(f'{r[0]:.3f}' for r in runs)} s; {runs[0][1]} bytes copied out beside the consensus)")
+    row("plain (vc_poa_run_gaps)", plain)
+    row("(ii) every member mode 2 (vc_poa_run_weighted)", weighted)
+    row("(iii) profile only (vc_poa_run_weighted)", prof)
+    row("(iii) alignment rows (vc_poa_run_msa)", msa)
+    m = med([r[0] for r in plain])
+    emit(f"(ii) weighted / plain {med([r[0] for r in weighted]) / m:.3f}; (iii) profile / plain {med([r[0] for r in prof]) / m:.3f}, rows / plain "
+         f"{med([r[0] for r in msa]) / m:.3f} (medians); bytes: profile {prof[0][1]}, rows {msa[0][1]} ({msa[0][1] / max(prof[0][1], 1):.2f}x); the profile "
+         f"call's consensus equals the plain call's in {sum(1 for x, y in zip(prof[0][2], plain[0][2]) if x == y)} of {a.groups} groups")
+    large.release()
+    if not a.no_trace:
+        d = os.path.join(a.trace_dir, "weights")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+               sys.executable, os.path.abspath(__file__), "--child", "1", "--weights", "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"kernel trace: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return 1
+        ms = kernel_shares(d)
+        tot = sum(ms.values())
+        emit(f"(iv) kernel times of one weighted call with the profile, a run of its own under rocprofv3 --kernel-trace --stats: {tot / 1e3:.2f} s: " +
+             ", ".join(f"{k} {v:.1f} ms ({v / tot * 100:.2f} %)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+    print("wrote", out)
+    return 0 if ok else 1
+
+
 LINEAR_NW = dict(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
 
 
@@ -976,6 +1074,11 @@ def child(a):
         dt = resume_call(tail, stored_graphs(head))[0]
         print(json.dumps(dict(seconds=dt)))
         return
+    if a.weights:                                 # the traced run: one call with every member weighted per base and the profile
+        batch = synth_groups(a)
+        dt, nbytes, _ = timed_weighted(batch, weights=all_mode2(batch), profile=True)
+        print(json.dumps(dict(seconds=dt, bytes=nbytes)))
+        return
     if a.spans:                                   # the traced run: one span call on the tiled groups
         batch, spans = tiled_groups(a)
         dt, line, done, _ = timed_spans(batch, spans)
@@ -1083,6 +1186,8 @@ def main():
     ap.add_argument("--resume", action="store_true", help="measure vc_poa_run_from: stored-graph queries, extending, k_lg_load (profiles/poa_resume_rate.txt)")
     ap.add_argument("--spans", action="store_true", help="measure vc_poa_run_spans beside the plain call on tiled groups (profiles/poa_spans_rate.txt; "
                                                          "--groups defaults to 512 here)")
+    ap.add_argument("--weights", action="store_true", help="measure vc_poa_run_weighted: the plain path beside --parent-lib, weights, the profile "
+                                                           "(profiles/poa_weights_rate.txt)")
     ap.add_argument("--locus", type=int, default=8000, help="--spans: bases of a group's backbone, tiled by reads of --len bases, --depth per tile")
     ap.add_argument("--prune-rounds", type=int, default=3, help="--correct: num_prune (default 3)")
     ap.add_argument("--queries-per-group", type=int, default=32, help="--align: mutated members per group beside the held-out one")
@@ -1096,6 +1201,8 @@ def main():
         a.groups = 512
     if a.child is not None:
         return child(a)
+    if a.weights:
+        return main_weights(a)
     if a.spans:
         return main_spans(a)
     if a.resume:

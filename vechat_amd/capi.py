@@ -147,6 +147,17 @@ class VcPoaSpanIn(C.Structure):
     _fields_ = [("begin", C.POINTER(C.c_uint32)), ("end", C.POINTER(C.c_uint32))]
 
 
+class VcPoaWeightIn(C.Structure):
+    """vc_poa_weight_in: caller-owned; mode per sequence of the batch (0 as the batch says, 1 seq_weight, 2 base_weight at seq_off's offsets)"""
+    _fields_ = [("mode", C.POINTER(C.c_uint8)), ("seq_weight", C.POINTER(C.c_uint32)), ("base_weight", C.POINTER(C.c_uint32))]
+
+
+class VcPoaProfileOut(C.Structure):
+    """vc_poa_profile_out: library-owned; per group its codes and a block of (n_codes + 1) rows x consensus length counts, gaps last"""
+    _fields_ = [("n_groups", C.c_uint32), ("n_codes", C.POINTER(C.c_uint32)), ("code_off", C.POINTER(C.c_uint64)),
+                ("codes", C.POINTER(C.c_uint8)), ("prof_off", C.POINTER(C.c_uint64)), ("counts", C.POINTER(C.c_uint32))]
+
+
 class VcPoaPruneParams(C.Structure):
     """vc_poa_prune_params: the thresholds and rounds of vc_poa_run_correct (the reference's defaults: 0.22 / 0.19 / 3)"""
     _fields_ = [("min_confidence", C.c_double), ("min_support", C.c_double), ("num_prune", C.c_uint32)]
@@ -454,6 +465,12 @@ def load_hip():
             lib.vc_poa_run_spans.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaSpanIn), C.POINTER(VcBatch), C.POINTER(VcResult),
                                              C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut)]
             lib.vc_poa_run_spans.restype = C.c_int
+        # (likewise: tools/gpu_poa_rate.py --weights measures beside the parent commit's library)
+        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_weighted"):
+            lib.vc_poa_run_weighted.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaWeightIn), C.POINTER(VcBatch), C.POINTER(VcResult),
+                                                C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut),
+                                                C.POINTER(VcPoaProfileOut)]
+            lib.vc_poa_run_weighted.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

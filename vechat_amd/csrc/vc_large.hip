@@ -57,6 +57,8 @@
 //               walks the winner's matrix only, and k_lg_apply adds the kept view and records the choice (spoa's -s, main.cpp:287-304);
 //   k_lg_msa    vc_poa_run_msa only, one wave per finished group: <0> node -> column by a wave prefix sum over the topological
 //               order, <1> the rows ('-' fill, then a scatter over the edge labels), the consensus row and the coverage;
+//   k_lg_profile vc_poa_run_weighted with a profile only, one wave per finished group behind k_lg_msa<0>: the per-code counts and
+//               the gaps of every consensus position (GenerateConsensus(&summary, true)) by a scatter over the edge labels;
 //   k_lg_graph  vc_poa_run_graph only, one wave per finished group: <0> the counts of the group's graph tables, <1> the tables --
 //               nodes, out-edges as CSR, aligned pairs, a path per sequence, the consensus path (spoa's GFA and dot output).
 //   k_lg_load   vc_poa_run_from only, one wave per group behind k_lg_init: the group starts as a stored graph -- nodes, out-lists and
@@ -106,6 +108,8 @@
 //                           and the rows the same passes would have had against the whole graph; the rows count both strands'
 //                           passes; every member counts once: a group that runs again with larger tables starts from zero, and
 //                           a member whose matrix the device refused is not counted),
+//                           "vc_large: profile launches=K bytes=B" (vc_poa_run_weighted with a profile: k_lg_profile launches, bytes
+//                           copied out),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes of the build, their rows x
 //                           columns summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes;
 //                           vc_poa_run_correct counts the rounds' passes too, not the final stage's).
@@ -284,8 +288,12 @@ struct PoaRequest {
     const vc_poa_graph_in* from = nullptr;             // vc_poa_run_from: the stored graphs the groups start as, and the state table beside the graph's
     vc_poa_state_out* state = nullptr;
     const vc_poa_span_in* spans = nullptr;             // vc_poa_run_spans with at least one span (check_spans leaves nullptr otherwise)
+    const vc_poa_weight_in* weights = nullptr;         // vc_poa_run_weighted with at least one member of mode 1 or 2 (check_weights leaves nullptr otherwise)
+    bool base_weights = false;                         // ... and at least one of mode 2
+    vc_poa_profile_out* profile = nullptr;             // the per-code profile of every consensus
     bool rows() const { return msa_flags != 0; }                           // k_lg_msa runs
-    bool keeps_labels() const { return msa_flags != 0 || graph != nullptr; }   // the edges keep sequence labels
+    bool columns() const { return rows() || profile != nullptr; }          // k_lg_msa<0> runs
+    bool keeps_labels() const { return msa_flags != 0 || graph != nullptr || profile != nullptr; }   // the edges keep sequence labels
     bool keeps_seqs() const { return keeps_labels(); }                     // the windows keep sq_begin / sq_member
     uint32_t strands() const { return strand ? 2 : 1; }                    // forward passes per alignment of the build
     bool has_queries() const { return nq != 0; }                           // the query stage runs (a call without a query is the call without it)
@@ -359,6 +367,16 @@ struct Outputs {
             co->bytes = bytes;
         }
     } correct;
+    struct Profile {                                   // vc_poa_profile_out
+        std::vector<uint32_t> n_codes, counts;
+        std::vector<uint64_t> code_off, prof_off;
+        std::vector<uint8_t> codes;
+        uint64_t bytes = 0;                            // copied out of the device
+        void publish(vc_poa_profile_out* po) {
+            po->n_codes = n_codes.data(); po->code_off = code_off.data(); po->codes = table(codes);
+            po->prof_off = prof_off.data(); po->counts = table(counts);
+        }
+    } profile;
     void clear() { *this = Outputs{}; }
 } g_out;
 
@@ -394,6 +412,9 @@ struct Run {
     uint64_t msa_launches = 0;
     std::vector<GraphPart> part;                       // graph: per window its block
     uint64_t graph_launches = 0;
+    std::vector<std::vector<uint8_t>> prof_of;         // profile: per window its block (counts, then codes), and its code count
+    std::vector<uint32_t> prof_nc;
+    uint64_t profile_launches = 0;
     LLoad load{};                                      // vc_poa_run_from: the stored graphs on the device
     // the query stage: per host group the packed pairs (every node, then every position), per query where its pairs lie; the "align" line
     std::vector<std::vector<int32_t>> q_part;
@@ -676,10 +697,11 @@ bool lock_step(Run& R, Group& G) {
                 c.members++; c.rows += (uint64_t)W.rows * R.ns; c.full += (uint64_t)W.gr[W.cur].n_nodes * R.ns;
             }
         }
-        hipLaunchKernelGGL(k_lg_apply, lanes, dim3(64), 0, 0, a);
+        if (a.wmode) hipLaunchKernelGGL(k_lg_apply<true>, lanes, dim3(64), 0, 0, a);
+        else hipLaunchKernelGGL(k_lg_apply<false>, lanes, dim3(64), 0, 0, a);
         ok = hipGetLastError() == hipSuccess;
     }
-    if (ok && R.q.rows()) hipLaunchKernelGGL(k_lg_msa<0>, dim3(n), dim3(64), 0, 0, a);
+    if (ok && R.q.columns()) hipLaunchKernelGGL(k_lg_msa<0>, dim3(n), dim3(64), 0, 0, a);
     if (ok && R.q.graph) hipLaunchKernelGGL(k_lg_graph<0>, dim3(n), dim3(64), 0, 0, a);
     ok = ok && hipGetLastError() == hipSuccess;
     return ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(G.hw.data(), G.d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) == hipSuccess;
@@ -771,6 +793,66 @@ void assemble_msa(Run& R) {
         }
     }
     if (R.kn.log) std::fprintf(stderr, "vc_large: msa launches=%llu bytes=%llu\n", (unsigned long long)R.msa_launches, (unsigned long long)msa.rows.size());
+}
+
+// The profiles of the groups that finished, as collect_graph: a block (counts, codes) and a scratch per group in the matrix
+// buffer, the blocks in front so that one copy takes them out.  The groups' columns are k_lg_msa<0>'s, of the same lock_step.
+int collect_profile(Run& R, Group& G) {
+    const LArgs& a = R.a;
+    auto block_of = [&](uint32_t k) { return profile_block(G.hw[k].num_codes, G.hw[k].cons_n).bytes; };
+    auto scratch_of = [&](uint32_t k) { return profile_scratch(G.hw[k].gr[G.hw[k].cur].nseq, G.hw[k].gr_cols).bytes; };
+    uint64_t blocks = 0;
+    auto blocks_first = [&](const std::vector<uint32_t>& list, std::vector<uint64_t>& hoff) {      // every block, then every scratch
+        const uint32_t nl = (uint32_t)list.size();
+        blocks = 0;
+        hoff.assign(2 * (size_t)nl, 0);
+        for (uint32_t q = 0; q < nl; ++q) { hoff[q] = blocks; blocks += block_of(list[q]); }
+        uint64_t at = blocks;
+        for (uint32_t q = 0; q < nl; ++q) { hoff[nl + q] = at; at += scratch_of(list[q]); }
+    };
+    std::vector<uint8_t> host;
+    auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t, void* dout) -> int {
+        const uint32_t nl = (uint32_t)list.size();
+        f.msa_out = (uint8_t*)dout;
+        hipLaunchKernelGGL(k_lg_profile, dim3(nl), dim3(64), 0, 0, f);
+        bool ok = hipGetLastError() == hipSuccess;
+        host.resize(blocks);
+        ok = ok && (blocks == 0 || hipMemcpy(host.data(), dout, blocks, hipMemcpyDeviceToHost) == hipSuccess);
+        if (!ok) return fail(VC_ERR_HIP, "the profile kernel or its copy failed");
+        for (uint32_t q = 0; q < nl; ++q) {
+            const uint32_t w = G.ids[list[q]];
+            R.prof_of[w].assign(host.begin() + hoff[q], host.begin() + (q + 1 < nl ? hoff[q + 1] : blocks));
+            R.prof_nc[w] = G.hw[list[q]].num_codes;
+        }
+        g_out.profile.bytes += blocks;
+        return VC_OK;
+    };
+    return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
+                       {"device allocation of the profile blocks failed", "the profile kernel or its copy failed"}, R.profile_launches,
+                       [&](uint32_t k) { return block_of(k) + scratch_of(k); }, blocks_first,
+                       [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
+}
+
+// the tables of vc_poa_profile_out in window order (a group that was not computed has no code and an empty block), and the log line
+void assemble_profile(Run& R) {
+    Outputs::Profile& P = g_out.profile;
+    P.code_off.assign(1, 0);
+    for (uint32_t w = 0; w < R.nw; ++w) {
+        const uint32_t nc = R.status[w] == VC_WIN_OK && !R.prof_of[w].empty() ? R.prof_nc[w] : 0;
+        const uint64_t Cn = R.out[w].size();
+        P.n_codes.push_back(nc);
+        P.prof_off.push_back(P.counts.size());
+        if (nc) {
+            const uint8_t* blk = R.prof_of[w].data();
+            const uint32_t* c = (const uint32_t*)blk;
+            P.counts.insert(P.counts.end(), c, c + (uint64_t)(nc + 1) * Cn);
+            const uint8_t* codes = blk + profile_block(nc, Cn).codes;
+            P.codes.insert(P.codes.end(), codes, codes + nc);
+        }
+        P.code_off.push_back(P.codes.size());
+        R.prof_of[w] = std::vector<uint8_t>{};
+    }
+    if (R.kn.log) std::fprintf(stderr, "vc_large: profile launches=%llu bytes=%llu\n", (unsigned long long)R.profile_launches, (unsigned long long)P.bytes);
 }
 
 // The graphs of the groups that finished, as collect_msa: a block and a scratch per group in the matrix buffer, the blocks in
@@ -1112,7 +1194,7 @@ int run_group(Run& R, Group& G) {
     const uint32_t n = (uint32_t)G.ids.size();
     uint8_t* arena = (uint8_t*)cached(g_cache.arena, G.abytes);
     DevMem mem;
-    if (!arena || !mem.alloc(&G.d_win, n) || !mem.alloc(&G.d_list, n) || !mem.alloc(&G.d_hoff, R.q.graph ? 2 * (size_t)n : n)) {
+    if (!arena || !mem.alloc(&G.d_win, n) || !mem.alloc(&G.d_list, n) || !mem.alloc(&G.d_hoff, R.q.graph || R.q.profile ? 2 * (size_t)n : n)) {
         if (n == 1) { R.status[G.ids[0]] = VC_WIN_OVERFLOW; return VC_OK; }
         return fail(VC_ERR_HIP, "device allocation of the window tables failed");
     }
@@ -1129,6 +1211,7 @@ int run_group(Run& R, Group& G) {
             return fail(VC_ERR_HIP, "copy of a consensus failed");
     }
     if (R.q.rows()) if (const int rc = collect_msa(R, G)) return rc;
+    if (R.q.profile) if (const int rc = collect_profile(R, G)) return rc;
     if (R.q.graph) if (const int rc = collect_graph(R, G)) return rc;
     if (R.q.correct) if (const int rc = collect_correct(R, G)) return rc;
     return R.q.has_queries() ? collect_align(R, G) : VC_OK;
@@ -1188,6 +1271,13 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
         R.a.seq_begin = d_sb; R.a.seq_end = d_se; R.a.spans = 1;
         R.sp_of.resize(nw);
     }
+    if (q.weights) {                                                       // vc_poa_run_weighted with a weighted member: k_lg_apply<true> reads these
+        uint8_t* d_m = nullptr; uint32_t *d_sw = nullptr, *d_bw = nullptr;
+        if (!mem.alloc(&d_m, R.nseq_all, q.weights->mode) || !mem.alloc(&d_sw, R.nseq_all, q.weights->seq_weight) ||
+            (q.base_weights && !mem.alloc(&d_bw, R.nbytes, q.weights->base_weight)))
+            return fail(VC_ERR_HIP, "device allocation or copy of the weights failed");
+        R.a.wmode = d_m; R.a.seq_w = d_sw; R.a.base_w = d_bw;
+    }
     if (q.strand) if (const int rc = strand_views(R, mem)) return rc;
     if (q.from) if (const int rc = upload_stored(R, mem)) return rc;
     if (q.has_queries()) {
@@ -1210,6 +1300,7 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     R.arena_budget = kn.arena ? kn.arena : std::min<uint64_t>(avail / 4, 16ull << 30);
     R.mat_budget = kn.mat ? kn.mat : std::min<uint64_t>(avail / 2, 48ull << 30);
     if (q.graph) R.part.resize(nw);
+    if (q.profile) { R.prof_of.resize(nw); R.prof_nc.assign(nw, 0); }
     R.planes = plane_count(a.gaps);
     R.ns = q.strands();
 
@@ -1230,6 +1321,7 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     }
     if (q.strand) if (const int rc = copy_strands(R)) return rc;
     if (q.rows()) assemble_msa(R);
+    if (q.profile) assemble_profile(R);
     if (q.graph) assemble_graph(R);
     if (q.has_queries()) assemble_align(R);
     if (q.correct) assemble_correct(R);
@@ -1407,6 +1499,36 @@ int check_spans(PoaRequest& A, const vc_batch* b) {
     return VC_OK;
 }
 
+// vc_poa_run_weighted's weights, after the batch and before the device, in the header's order, one kind of violation after the
+// other and each member by member in batch order: the mode array NULL; a mode above 2; seq_weight NULL beside a mode-1 member;
+// base_weight NULL beside a mode-2 member.  A call in which every member has mode 0 is the call without weights: A.weights is
+// cleared and nothing of them reaches the device.
+int check_weights(PoaRequest& A, const vc_batch* b) {
+    const vc_poa_weight_in* wt = A.weights;
+    A.weights = nullptr; A.base_weights = false;
+    if (!wt) return VC_OK;
+    if (!wt->mode) return fail(VC_ERR_ARG, "null weight mode array");
+    const uint32_t nw = b->n_windows;
+    // the first member the rule `bad` names, as the message says it
+    auto first = [&](auto bad, const char* what) -> int {
+        for (uint32_t w = 0; w < nw; ++w)
+            for (uint32_t s0 = b->win_seq_off[w], s = s0; s < b->win_seq_off[w + 1]; ++s)
+                if (bad(wt->mode[s])) {
+                    char msg[160];
+                    std::snprintf(msg, sizeof msg, "the weight mode of member %u of group %u %s", s - s0, w, what);
+                    return fail(VC_ERR_ARG, msg);
+                }
+        return VC_OK;
+    };
+    if (const int rc = first([](uint8_t m) { return m > 2; }, "is not 0, 1 or 2")) return rc;
+    if (!wt->seq_weight) if (const int rc = first([](uint8_t m) { return m == 1; }, "is 1 beside a null seq_weight")) return rc;
+    if (!wt->base_weight) if (const int rc = first([](uint8_t m) { return m == 2; }, "is 2 beside a null base_weight")) return rc;
+    bool any = false;
+    for (uint32_t s = 0, n = nw ? b->win_seq_off[nw] : 0; s < n; ++s) { any |= wt->mode[s] != 0; A.base_weights |= wt->mode[s] == 2; }
+    if (any) A.weights = wt;
+    return VC_OK;
+}
+
 // The vc_poa_* entries after their score checks: the knobs, the batch (still without the device), the queries, the device, the
 // run.  `a` holds the scores.
 int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc_result* r, PoaRequest& q) {
@@ -1447,6 +1569,7 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
         }
     }
     if (const int rc = check_spans(q, b)) return rc;
+    if (const int rc = check_weights(q, b)) return rc;
     a.num_prune = 1;
     if (q.required & PoaRequest::CORRECT) {
         // vc_poa_run_correct's own arguments, after the batch and before the device
@@ -1470,6 +1593,7 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     if (q.align) { q.align_flags = q.align->flags; *q.align = vc_poa_align_out{}; q.align->flags = q.align_flags; }
     if (q.correct) *q.correct = vc_poa_correct_out{};
     if (q.state) *q.state = vc_poa_state_out{};
+    if (q.profile) *q.profile = vc_poa_profile_out{};
     if (!p || !b || !r || ((q.required & PoaRequest::MSA) && !o) || ((q.required & PoaRequest::CORRECT) && (!q.prune || !q.correct)) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
@@ -1490,10 +1614,12 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     LArgs a{};
     a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = g2; a.gap_c = c; a.gaps = gaps;
     a.msa = q.msa_flags; a.strand = q.strand ? 1 : 0; a.graph = q.route; a.state = q.state ? 1 : 0;
+    a.profile = q.profile ? 1 : 0;
     if (o) { *o = vc_poa_msa_out{}; o->flags = q.msa_flags; }
-    if (q.required) g_out.clear();                                         // what an earlier call handed out ends here
+    const bool owns = q.required || q.profile;
+    if (owns) g_out.clear();                                               // what an earlier call handed out ends here
     const int rc = run_groups(p->device, p->algorithm, a, b, r, q);
-    if (rc != VC_OK && q.required) g_out.clear();
+    if (rc != VC_OK && owns) g_out.clear();
     if (rc != VC_OK) return rc;
     if (q.required & PoaRequest::ALIGN) g_out.align.publish(q.align, q);
     if (q.required & PoaRequest::CORRECT) g_out.correct.publish(q.correct, b->n_windows ? b->win_seq_off[b->n_windows] : 0);
@@ -1501,6 +1627,10 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
         q.graph->n_groups = b->n_windows;
         if (b->n_windows) g_out.graph.publish(q.graph);
         if (q.state && b->n_windows) g_out.state.publish(q.state);
+    }
+    if (q.profile) {
+        q.profile->n_groups = b->n_windows;
+        if (b->n_windows) g_out.profile.publish(q.profile);
     }
     if (o) o->n_groups = b->n_windows;
     if (q.rows() && b->n_windows) g_out.msa.publish(o);
@@ -1600,6 +1730,14 @@ int vc_poa_run_spans(const vc_poa_gap_params* p, const vc_poa_span_in* spans, co
     // the entry the call would be without `spans`: the first of vc_poa_run_graph, _strand, _msa, _gaps it needs
     PoaRequest rq{g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0u, o, s, g};
     rq.spans = spans;
+    return poa_run(p, b, r, rq);
+}
+
+int vc_poa_run_weighted(const vc_poa_gap_params* p, const vc_poa_weight_in* w, const vc_batch* b, vc_result* r, vc_poa_msa_out* o,
+                        vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_profile_out* prof) {
+    // the entry the call would be without `w` and `prof`: the first of vc_poa_run_graph, _strand, _msa, _gaps it needs
+    PoaRequest rq{g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0u, o, s, g};
+    rq.weights = w; rq.profile = prof;
     return poa_run(p, b, r, rq);
 }
 

@@ -56,7 +56,7 @@ struct LWin {
     // vc_poa_run_msa only (nullptr otherwise): spoa's sequences_, one entry per sequence that was added (label = index)
     uint32_t *sq_begin, *sq_member;                    // [nseq] begin node; index of the group member
     uint32_t msa_rows, row_size;                       // k_lg_msa<0>: rows and columns of the group's alignment
-    uint32_t gr_cols, gr_path;                         // k_lg_graph<0>: columns of the alignment, path entries (bases of the added sequences)
+    uint32_t gr_cols, gr_path;                         // k_lg_graph<0>: columns of the alignment (k_lg_msa<0> leaves them too for k_lg_profile), path entries (bases of the added sequences)
     // vc_poa_run_from only (0 / nullptr otherwise): the group began as a stored graph (k_lg_load).  Its first n_old sequences are
     // the stored paths -- sq_member holds their member numbers as stored, sq_len / sq_rev their lengths and strand flags --; the
     // sequences behind them are members of the batch, numbered from m0 in the outputs (seq_member, seq_len, seq_rev below)
@@ -91,6 +91,11 @@ struct LArgs {
     // mode 2, vc_poa_run_spans with at least one span (0 elsewhere, and seq_begin / seq_end are nullptr then): seq_begin / seq_end
     // hold, per sequence of the batch, the inclusive node range on sequence 0 of its group, or NONE / NONE for the whole graph
     uint32_t spans;
+    // mode 2, vc_poa_run_weighted with at least one member of mode 1 or 2 (nullptr elsewhere, and k_lg_apply<false> runs): the mode
+    // per sequence of the batch, the per-sequence weights, the per-base weights at seq_off's offsets (nullptr without a mode-2 member)
+    const uint8_t* wmode;
+    const uint32_t *seq_w, *base_w;
+    uint32_t profile;                                  // mode 2, vc_poa_run_weighted with a vc_poa_profile_out: 1 k_lg_msa<0> runs for k_lg_profile; 0 elsewhere
     uint8_t *rc_bases, *rv_quals, *rt_bases;           // reverse complement, reversed quality, the bytes complemented twice
     uint8_t* s_rev;                                    // [sequences] 1: the reverse complement was kept
     int32_t *s_score, *s_score_rev;                    // [sequences] both strands' scores
@@ -190,11 +195,21 @@ __device__ __forceinline__ const uint8_t* kept_bases(const LArgs& a, const LWin&
     return (a.strand ? (W.rev ? a.rc_bases : a.rt_bases) : a.bases) + a.seq_off[s];
 }
 
+// The weight of base i of sequence s as it is added.  WT (k_lg_apply<true>, vc_poa_run_weighted with at least one weighted member)
+// puts the member's mode in front: 1 one weight for every base, 2 a weight per base at seq_off's offsets -- a kept reverse strand
+// reads them back to front, as its quality --, 0 what the batch says.  Without WT the body is what it was before weights existed.
+template <bool WT = false>
 __device__ __forceinline__ uint32_t weight_of(const LArgs& a, const LWin& W, uint32_t s, uint32_t i, bool use_qual) {
+    if constexpr (WT) {
+        const uint32_t m = a.wmode[s];                                     // per lane: k_lg_apply runs one group per lane, so the lanes' modes may differ
+        if (m == 1) return a.seq_w[s];
+        if (m == 2) return a.base_w[a.strand && W.rev ? a.seq_off[s + 1] - 1 - i : a.seq_off[s] + i];
+    }
     return use_qual ? a.lut_w[(a.strand && W.rev ? a.rv_quals : a.quals)[a.seq_off[s] + i]] : 1u;
 }
 
 // g_add_chain: fresh chain for seq[begin, end); *first = first node or NONE
+template <bool WT = false>
 __device__ bool add_chain(const LArgs& a, LWin& W, LGraph& g, uint32_t s, bool uq, uint32_t begin, uint32_t end, uint32_t* first) {
     *first = NONE;
     const uint8_t* seq = kept_bases(a, W, s);
@@ -203,7 +218,7 @@ __device__ bool add_chain(const LArgs& a, LWin& W, LGraph& g, uint32_t s, bool u
         const uint32_t curr = add_node(W, g, (uint32_t)W.coder[seq[i]]);
         if (curr == NONE) return false;
         if (*first == NONE) *first = curr;
-        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, W, s, i - 1, uq) + weight_of(a, W, s, i, uq))) return false;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of<WT>(a, W, s, i - 1, uq) + weight_of<WT>(a, W, s, i, uq))) return false;
         prev = curr;
     }
     return true;
@@ -259,6 +274,7 @@ __device__ bool toposort(LWin& W, LGraph& g) {
 }
 
 // g_add_alignment.  Returns 0, -1 where the reference throws, -2 when a table filled.
+template <bool WT = false>
 __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* A, uint32_t np, uint32_t s, bool uq) {
     const uint32_t len = (uint32_t)(a.seq_off[s + 1] - a.seq_off[s]);
     const uint8_t* seq = kept_bases(a, W, s);
@@ -271,7 +287,7 @@ __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* 
     }
     uint32_t first;
     if (np == 0) {
-        if (!add_chain(a, W, g, s, uq, 0, len, &first)) return -2;
+        if (!add_chain<WT>(a, W, g, s, uq, 0, len, &first)) return -2;
         if (W.sq_begin) { W.sq_begin[g.nseq] = first; W.sq_member[g.nseq] = s - W.s0; }
         g.nseq++;
         return toposort(W, g) ? 0 : -2;
@@ -287,9 +303,9 @@ __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* 
     }
     if (vfront == -1) return -1;
     uint32_t begin, last;
-    if (!add_chain(a, W, g, s, uq, 0, (uint32_t)vfront, &begin)) return -2;
+    if (!add_chain<WT>(a, W, g, s, uq, 0, (uint32_t)vfront, &begin)) return -2;
     uint32_t prev = (begin != NONE) ? g.n_nodes - 1 : NONE;
-    if (!add_chain(a, W, g, s, uq, (uint32_t)vback + 1, len, &last)) return -2;
+    if (!add_chain<WT>(a, W, g, s, uq, (uint32_t)vback + 1, len, &last)) return -2;
     for (uint32_t k = 0; k < np; ++k) {
         const int32_t n = A[2 * k], q = A[2 * k + 1];
         if (q == -1) continue;
@@ -318,10 +334,10 @@ __device__ int add_alignment(const LArgs& a, LWin& W, LGraph& g, const int32_t* 
             }
         }
         if (begin == NONE) begin = curr;
-        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of(a, W, s, q - 1, uq) + weight_of(a, W, s, q, uq))) return -2;
+        if (prev != NONE && !add_edge(W, g, prev, curr, weight_of<WT>(a, W, s, q - 1, uq) + weight_of<WT>(a, W, s, q, uq))) return -2;
         prev = curr;
     }
-    if (last != NONE && !add_edge(W, g, prev, last, weight_of(a, W, s, vback, uq) + weight_of(a, W, s, vback + 1, uq))) return -2;
+    if (last != NONE && !add_edge(W, g, prev, last, weight_of<WT>(a, W, s, vback, uq) + weight_of<WT>(a, W, s, vback + 1, uq))) return -2;
     if (W.sq_begin) { W.sq_begin[g.nseq] = begin; W.sq_member[g.nseq] = s - W.s0; }   // sequences_.emplace_back(begin), graph.cpp:296
     g.nseq++;
     return toposort(W, g) ? 0 : -2;
@@ -649,7 +665,7 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     for (int c = 0; c < 256; ++c) { W.coder[c] = -1; W.decoder[c] = -1; }
     W.num_codes = 0;
     reset_graph(W.gr[0]); reset_graph(W.gr[1]);
-    W.gr[0].labels = a.mode == 1 || a.msa != 0 || a.graph != 0; W.gr[1].labels = 0;
+    W.gr[0].labels = a.mode == 1 || a.msa != 0 || a.graph != 0 || a.profile != 0; W.gr[1].labels = 0;
     W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
     W.msa_rows = 0; W.row_size = 0; W.rev = 0; W.gr_cols = 0; W.gr_path = 0;
     if (a.mode == 2) {                                                     // POA group: sequence 0 meets the empty graph in k_lg_prep
@@ -1269,6 +1285,8 @@ __global__ __launch_bounds__(64) void k_lg_correct(LArgs a) {
     if (PH == 0 && lane == 0) J.ncorr = carry;
 }
 
+// WT: the call has a weighted member (LArgs::wmode is set); the plain instance is the kernel as it was
+template <bool WT>
 __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
     const uint32_t w = blockIdx.x * 64 + threadIdx.x;
     if (w >= a.n) return;
@@ -1279,7 +1297,7 @@ __global__ __launch_bounds__(64) void k_lg_apply(LArgs a) {
     if (W.phase == PH_BUILD) {
         if (W.sub)                                                         // UpdateAlignment, graph.cpp:734-745
             for (uint32_t k = 0; k < np; ++k) if (W.pairs[2 * k] != -1) W.pairs[2 * k] = (int32_t)W.map[W.pairs[2 * k]];
-        const int rc = add_alignment(a, W, W.gr[W.cur], W.pairs, np, s, hq);
+        const int rc = add_alignment<WT>(a, W, W.gr[W.cur], W.pairs, np, s, hq);
         if (rc == -2) return;
         if (rc) { fail_window(W, VC_WIN_INVALID); return; }
         if (a.strand) { a.s_rev[s] = (uint8_t)W.rev; a.s_score[s] = W.score[0]; a.s_score_rev[s] = W.score[1]; }
@@ -1377,9 +1395,10 @@ __global__ __launch_bounds__(64) void k_lg_msa(LArgs a) {
         LWin& W = a.win[blockIdx.x];
         if (W.phase != PH_DONE || W.grow || W.status != VC_WIN_OK) return;
         const LGraph& g = W.gr[W.cur];
-        if (!(a.msa & VC_POA_MSA)) return;
+        if (!(a.msa & VC_POA_MSA) && !a.profile) return;
         const uint32_t cols = msa_columns(W, g, lane);
-        if (lane == 0) { W.row_size = cols; W.msa_rows = g.nseq + ((a.msa & VC_POA_MSA_CONSENSUS) ? 1u : 0u); }
+        if (lane == 0 && (a.msa & VC_POA_MSA)) { W.row_size = cols; W.msa_rows = g.nseq + ((a.msa & VC_POA_MSA_CONSENSUS) ? 1u : 0u); }
+        if (lane == 0 && a.profile) W.gr_cols = cols;                      // (k_lg_graph<0> writes the same number)
     } else {
         LWin& W = a.win[a.list[blockIdx.x]];
         const LGraph& g = W.gr[W.cur];
@@ -1424,6 +1443,90 @@ __global__ __launch_bounds__(64) void k_lg_msa(LArgs a) {
                 cov[i] = cnt;
             }
         }
+    }
+}
+
+// A finished group's block of k_lg_profile: (codes + 1) rows of cons_n uint32 (the last row the gaps), then the group's decoder,
+// a byte per code; beside it the stage's scratch: the consensus position of every column (NONE: none), then first and last hit
+// position per added sequence.  Every part is 16-byte aligned and padded to 16 bytes (the fills store whole uint4).
+struct ProfileBlock { uint64_t codes, bytes; };
+__host__ __device__ inline ProfileBlock profile_block(uint64_t nc, uint64_t Cn) {
+    ProfileBlock B;
+    B.codes = (4 * (nc + 1) * Cn + 15) & ~15ull;
+    B.bytes = B.codes + ((nc + 15) & ~15ull);
+    return B;
+}
+struct ProfileScratch { uint64_t first, last, bytes; };
+__host__ __device__ inline ProfileScratch profile_scratch(uint64_t S, uint64_t cols) {
+    ProfileScratch X;
+    X.first = (4 * cols + 15) & ~15ull;
+    X.last = X.first + ((4 * S + 15) & ~15ull);
+    X.bytes = X.last + ((4 * S + 15) & ~15ull);
+    return X;
+}
+
+// The verbose summary of GenerateConsensus(&summary, true), graph.cpp:486-529, of a finished POA group whose columns k_lg_msa<0>
+// has left in W.map / W.gr_cols: one wave per group of a.list, block at a.msa_out + a.hoff[block], scratch at hoff[groups + block].
+// The reference walks every sequence with Successor(i) and a cursor c into the consensus: a node whose column is the column of
+// consensus position c counts its code there, and the positions strictly between two consecutive hits of one sequence count a
+// gap.  Columns rise strictly along a sequence's path and along the consensus, so a sequence meets a consensus column at most
+// once and its hits come in rising position: the hits are a scatter over the begin nodes and the label cells (the nodes of
+// sequence i are its begin node and the head of every edge with label i, as in k_lg_msa<1>), and the gaps of position j are the
+// sequences with first hit <= j <= last hit less the hits at j.  The first term is a difference array over the gap row -- +1 at a
+// sequence's first hit, -1 behind its last -- and a wave prefix sum in tiles of 64 with a carried total; uint32 wraps as int32 does.
+__global__ __launch_bounds__(64) void k_lg_profile(LArgs a) {
+    const uint32_t lane = threadIdx.x;
+    LWin& W = a.win[a.list[blockIdx.x]];
+    const LGraph& g = W.gr[W.cur];
+    const uint32_t nc = W.num_codes, Cn = W.cons_n, S = g.nseq;
+    const ProfileBlock B = profile_block(nc, Cn);
+    const ProfileScratch X = profile_scratch(S, W.gr_cols);
+    uint8_t* blk = a.msa_out + a.hoff[blockIdx.x];                         // both 16-byte aligned
+    uint8_t* scr = a.msa_out + a.hoff[gridDim.x + blockIdx.x];
+    uint32_t* counts = (uint32_t*)blk;
+    uint32_t *cpos = (uint32_t*)scr, *first = (uint32_t*)(scr + X.first), *last = (uint32_t*)(scr + X.last);
+    uint4 *b4 = (uint4*)blk, *s4 = (uint4*)scr;
+    for (uint64_t k = lane; k < B.bytes / 16; k += 64) b4[k] = make_uint4(0, 0, 0, 0);
+    for (uint64_t k = lane; k < X.last / 16; k += 64) s4[k] = make_uint4(NONE, NONE, NONE, NONE);
+    for (uint64_t k = X.last / 16 + lane; k < X.bytes / 16; k += 64) s4[k] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    for (uint32_t k = lane; k < nc; k += 64) blk[B.codes + k] = (uint8_t)W.decoder[k];
+    for (uint32_t i = lane; i < Cn; i += 64) cpos[W.map[W.comp[i]]] = i;
+    __syncthreads();
+    for (uint32_t s = lane; s < S; s += 64) {
+        const uint32_t v = W.sq_begin[s], p = cpos[W.map[v]];
+        if (p == NONE) continue;
+        atomicAdd(&counts[(uint64_t)g.code[v] * Cn + p], 1u);
+        atomicMin(&first[s], p); atomicMax(&last[s], p);
+    }
+    for (uint32_t e = lane; e < g.n_edges; e += 64) {
+        const uint32_t h = g.head[e], p = cpos[W.map[h]];
+        if (p == NONE) continue;
+        uint32_t* row = counts + (uint64_t)g.code[h] * Cn;
+        for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) {
+            const uint32_t s = g.lb_v[c];
+            atomicAdd(&row[p], 1u);
+            atomicMin(&first[s], p); atomicMax(&last[s], p);
+        }
+    }
+    __syncthreads();
+    uint32_t* gaps = counts + (uint64_t)nc * Cn;
+    for (uint32_t s = lane; s < S; s += 64) {
+        if (first[s] == NONE) continue;                                    // the sequence touches no consensus column
+        atomicAdd(&gaps[first[s]], 1u);
+        if (last[s] + 1 < Cn) atomicAdd(&gaps[last[s] + 1], NONE);         // -1
+    }
+    __syncthreads();
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < Cn; base += 64) {
+        const uint32_t j = base + lane;
+        const uint32_t x = wave_scan(j < Cn ? gaps[j] : 0u, lane);
+        if (j < Cn) {
+            uint32_t hits = 0;
+            for (uint32_t k = 0; k < nc; ++k) hits += counts[(uint64_t)k * Cn + j];
+            gaps[j] = carry + x - hits;
+        }
+        carry += __shfl(x, 63, 64);
     }
 }
 

@@ -200,6 +200,74 @@ def _no_spans(spans, what):
                          "nothing (include/vechat_hip.h, vc_poa_run_spans)")
 
 
+def weight_arrays(groups, weights):
+    """weights (per group None or a list with one entry per member: None -- what the member's quality says, or 1 --, an int in
+    0 .. 2^32 - 1 for every base of the member, or one int per base) -> (mode uint8, seq_weight uint32, base_weight uint32): mode and
+    seq_weight with one entry per sequence of group_batch(groups), base_weight at the batch's base offsets; None when no member has
+    a weight (the call is then the plain one).  ValueError, naming group and member, for anything else, a wrong length (spoa's
+    "sequence and weights are of unequal size") or a value out of uint32."""
+    if weights is None:
+        return None
+    if len(weights) != len(groups):
+        raise ValueError(f"{len(weights)} weight lists for {len(groups)} groups")
+    mode, seq_w, base_w, found = [], [], [], False
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    for w, (g, wt) in enumerate(zip(groups, weights)):
+        n = len(g)
+        if wt is None:
+            wt = [None] * n
+        if isinstance(wt, (str, bytes)) or not hasattr(wt, "__len__") or len(wt) != n:
+            raise ValueError(f"group {w}: weights for {n} members need one entry per member (None, an int or one int per base)")
+        for k, x in enumerate(wt):
+            length = len(_member(g[k])[0])
+            if x is None:
+                mode.append(0); seq_w.append(0); base_w.append(np.zeros(length, np.uint32))
+                continue
+            found = True
+            if is_int(x):
+                if not 0 <= int(x) <= 0xFFFFFFFF:
+                    raise ValueError(f"group {w}, member {k}: weight {int(x)} is not in 0 .. 2^32 - 1")
+                mode.append(1); seq_w.append(int(x)); base_w.append(np.zeros(length, np.uint32))
+                continue
+            if isinstance(x, (str, bytes)) or not hasattr(x, "__len__") or not all(is_int(v) for v in x):
+                raise ValueError(f"group {w}, member {k}: a weight is None, an int or a sequence of ints, not {x!r}")
+            if len(x) != length:
+                raise ValueError(f"group {w}, member {k}: {len(x)} weights for {length} bases (sequence and weights are of unequal size)")
+            if any(not 0 <= int(v) <= 0xFFFFFFFF for v in x):
+                raise ValueError(f"group {w}, member {k}: a per-base weight is not in 0 .. 2^32 - 1")
+            mode.append(2); seq_w.append(0); base_w.append(np.array([int(v) for v in x], np.uint32).reshape(length))
+    if not found:
+        return None
+    return (np.array(mode, np.uint8), np.array(seq_w, np.uint32), np.concatenate([np.zeros(0, np.uint32)] + base_w).astype(np.uint32))
+
+
+def _no_weights(weights, what, profile=False):
+    if weights is not None or profile:
+        raise ValueError(f"{what} takes neither weights nor the profile: they belong to the call that builds a group from nothing "
+                         "(include/vechat_hip.h, vc_poa_run_weighted)")
+
+
+class Profile:
+    """One group's per-base profile of its consensus (spoa's GenerateConsensus(&summary, true)): consensus (bytes), codes (bytes:
+    the group's distinct bytes in order of first appearance), counts (numpy uint32, shape (len(codes) + 1, len(consensus)): row k
+    the members that carry codes[k] in the column of each consensus base, the last row those that span it with a gap) and status."""
+    __slots__ = ("consensus", "codes", "counts", "status")
+
+    def __init__(self, consensus, codes, counts, status):
+        self.consensus, self.codes, self.counts, self.status = consensus, codes, counts, status
+
+
+def _profile_results(po, n, cons, status):
+    res = []
+    for w in range(n):
+        nc, c = int(po.n_codes[w]), cons[w]
+        codes = C.string_at(C.addressof(po.codes.contents) + int(po.code_off[w]), nc) if nc else b""
+        k, at = (nc + 1) * len(c), int(po.prof_off[w])
+        counts = _table(C.cast(C.addressof(po.counts.contents) + 4 * at, C.POINTER(C.c_uint32)), k) if k else np.zeros(0, np.uint32)
+        res.append(Profile(c, codes, counts.reshape(nc + 1, len(c)), int(status[w])))
+    return res
+
+
 def _result_buffers(batch, stored_nodes=0):
     """-> (consensus bytes, offsets, status, VcResult over them, the batch as a struct whose seq_begin / seq_end / win_fasta are NULL)
     stored_nodes: the nodes of the graphs the groups start from (vc_poa_run_from), which the consensus may run through as well"""
@@ -216,7 +284,7 @@ def _result_buffers(batch, stored_nodes=0):
 
 class _Outputs:
     """what _run copied out of one call; an output that was not asked for is None"""
-    __slots__ = ("cons", "status", "msas", "graphs", "scores", "scores_rev", "queries")
+    __slots__ = ("cons", "status", "msas", "graphs", "scores", "scores_rev", "queries", "profiles")
 
 
 def _per_group(x, wso):
@@ -251,7 +319,7 @@ def _graph_in(graphs):
 
 
 def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_scores=True, graph=False, qbatch=None, align_flags=0,
-         start=None, state=False, spans=None):
+         start=None, state=False, spans=None, weights=None, profile=False):
     """One library call on a capi.Batch (its seq_begin / seq_end / win_fasta are passed as NULL) with the outputs asked for:
     msa_flags (capi.VC_POA_* bits, None: no vc_poa_msa_out), strands (spoa's -s; strand_scores: with the score arrays), graph,
     qbatch + align_flags (the queries of vc_poa_run_align).  The entry is the first of vc_poa_run_align (queries), _graph, _strand,
@@ -260,7 +328,13 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
     start (a list of resumable PoaGraph, one per group of the batch) and state (with graph: the graphs come back resumable) go
     through vc_poa_run_from; every other request takes the entry it always took.
     spans ((begin, end): two uint32 arrays, one entry per sequence of the batch, span_arrays) goes through vc_poa_run_spans with
-    the outputs asked for (params: capi.VcPoaGapParams); not with queries, start or state."""
+    the outputs asked for (params: capi.VcPoaGapParams); not with queries, start or state.
+    weights ((mode, seq_weight, base_weight), weight_arrays) and profile (-> _Outputs.profiles, a list of Profile) go through
+    vc_poa_run_weighted with the outputs asked for (params: capi.VcPoaGapParams); not with queries, start, state or spans."""
+    weighted = weights is not None or profile
+    if weighted and (qbatch is not None or start is not None or state or spans is not None):
+        raise ValueError("weights and the profile do not go with queries, stored graphs or spans (include/vechat_hip.h: out of scope "
+                         "of vc_poa_run_weighted)")
     if spans is not None and (qbatch is not None or start is not None or state):
         raise ValueError("spans do not go with queries or with stored graphs (include/vechat_hip.h: out of scope of vc_poa_run_spans)")
     lib = lib or capi.load_hip()
@@ -283,7 +357,22 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         qv = qbatch.as_struct()
         qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
         a = capi.VcPoaAlignOut(flags=align_flags)
-    if spans is not None:
+    prof = None
+    if weighted:
+        name = "vc_poa_run_weighted"
+        if not hasattr(lib, name):
+            raise PoaError("this libvechat_hip.so has no vc_poa_run_weighted: it was built before the entry point existed; rebuild it")
+        ref = lambda x: None if x is None else C.byref(x)
+        win = None
+        if weights is not None:
+            wm, ws, wb = np.ascontiguousarray(weights[0], np.uint8), np.ascontiguousarray(weights[1], np.uint32), np.ascontiguousarray(weights[2], np.uint32)
+            keep = (wm, ws, wb)                         # (the arrays the struct points into, until the call)
+            win = capi.VcPoaWeightIn(wm.ctypes.data_as(C.POINTER(C.c_uint8)), ws.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                     wb.ctypes.data_as(C.POINTER(C.c_uint32)))
+        prof = capi.VcPoaProfileOut() if profile else None
+        first = (ref(win),)
+        args = (ref(o), so, ref(g), ref(prof))
+    elif spans is not None:
         name = "vc_poa_run_spans"
         if not hasattr(lib, name):
             raise PoaError("this libvechat_hip.so has no vc_poa_run_spans: it was built before the entry point existed; rebuild it")
@@ -327,13 +416,14 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         _state_results(st, x.graphs, [had[w] + wso[w + 1] - wso[w] for w in range(n)])
     x.scores, x.scores_rev = (_per_group(sc, wso), _per_group(scr, wso)) if sc is not None else (None, None)
     x.queries = _query_results(a, align_flags, [int(k) for k in qbatch.win_seq_off]) if qbatch is not None else None
+    x.profiles = _profile_results(prof, n, x.cons, status) if prof is not None else None
     return x
 
 
-def run_batch(batch, params, lib=None, spans=None):
+def run_batch(batch, params, lib=None, spans=None, weights=None):
     """vc_poa_run (params: capi.VcPoaParams) or vc_poa_run_gaps (capi.VcPoaGapParams) on a capi.Batch (its seq_begin / seq_end /
     win_fasta are passed as NULL) -> (consensus bytes per group, status array).  Raises PoaError on a library error."""
-    x = _run(batch, params, lib=lib, spans=spans)
+    x = _run(batch, params, lib=lib, spans=spans, weights=weights)
     return x.cons, x.status
 
 
@@ -353,7 +443,7 @@ def _not_computed(status, strict):
 
 
 def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-                  gap_extend=None, gap_open2=None, gap_extend2=None, spans=None):
+                  gap_extend=None, gap_open2=None, gap_extend2=None, spans=None, weights=None):
     """Consensus of every group -> list of bytes.  The defaults are spoa's -m / -n / -g.  A group the device could not compute
     (VC_WIN_INVALID: the reference throws on it; VC_WIN_OVERFLOW: too large for the device memory) raises PoaError with the
     indices, or with strict=False comes back as None.
@@ -362,14 +452,18 @@ def poa_consensus(groups, algorithm="global", match=5, mismatch=-4, gap=-8, devi
     follows gap_model().
     spans (per group None or one entry per member, each None or an inclusive (begin, end) on sequence 0 of its group) aligns the
     members that have one against spoa's Subgraph(begin, end) only and maps the alignment back before it is added
-    (vc_poa_run_spans; racon_spans applies the reference's 1 % rule to plain positions).  Without any span the call is the plain one."""
+    (vc_poa_run_spans; racon_spans applies the reference's 1 % rule to plain positions).  Without any span the call is the plain one.
+    weights (per group None or one entry per member: None, an int -- spoa's AddAlignment(alignment, sequence, weight) --, or one int
+    per base -- its std::vector overload --; weight_arrays) replaces a member's quality weights (vc_poa_run_weighted); not with spans.
+    weights=None, or no member with a weight, is the plain call."""
     batch = group_batch(groups)
     sp = span_arrays(groups, spans)
-    if gap_extend is None and gap_open2 is None and gap_extend2 is None and sp is None:
+    wt = weight_arrays(groups, weights)
+    if gap_extend is None and gap_open2 is None and gap_extend2 is None and sp is None and wt is None:
         p = capi.VcPoaParams(device=device, algorithm=algorithm_code(algorithm), match=match, mismatch=mismatch, gap=gap)
     else:
         p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
-    cons, status = run_batch(batch, p, lib, spans=sp)
+    cons, status = run_batch(batch, p, lib, spans=sp, weights=wt)
     bad = _not_computed(status, strict)
     return [None if w in bad else c for w, c in enumerate(cons)]
 
@@ -378,11 +472,12 @@ class Msa:
     """One group's result of poa_msa: rows (bytes, all of one length; '-' is a gap), members (for every row the index of the group
     member it belongs to -- an empty member has no row --, CONSENSUS_ROW for the consensus row of include_consensus), consensus
     and coverage (numpy uint32 per consensus base, or None)."""
-    __slots__ = ("rows", "members", "consensus", "coverage", "reversed")
+    __slots__ = ("rows", "members", "consensus", "coverage", "reversed", "profile")
 
     def __init__(self, rows, members, consensus, coverage, reversed=None):
         self.rows, self.members, self.consensus, self.coverage = rows, members, consensus, coverage
         self.reversed = reversed                 # poa_msa(strand_ambiguous=True): numpy bool per group member, else None
+        self.profile = None                      # poa_msa(profile=True): the group's Profile, else None
 
     def __iter__(self):
         return iter((self.rows, self.members, self.consensus, self.coverage))
@@ -409,17 +504,19 @@ def _msa_results(o, flags, n, cons, off, wso, rev):
     return res
 
 
-def run_batch_msa(batch, params, flags, lib=None, strands=False, spans=None):
+def run_batch_msa(batch, params, flags, lib=None, strands=False, spans=None, weights=None, profile=False):
     """vc_poa_run_msa (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits) on a capi.Batch -> (list of Msa, status array).
     Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error.
     strands=True: vc_poa_run_strand instead -> (list of Msa with .reversed, status array, forward scores, reverse scores), the
     scores as one int32 array per group."""
-    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, spans=spans)
+    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, spans=spans, weights=weights, profile=profile)
+    for m, pr in zip(x.msas, x.profiles or ()):
+        m.profile = pr
     return (x.msas, x.status, x.scores, x.scores_rev) if strands else (x.msas, x.status)
 
 
 def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-                          gap_extend=None, gap_open2=None, gap_extend2=None, scores=False, spans=None):
+                          gap_extend=None, gap_open2=None, gap_extend2=None, scores=False, spans=None, weights=None):
     """Consensus of every group whose members may come from either strand (spoa's -s, vc_poa_run_strand): every member is
     aligned as given and reverse-complemented and the better strand is added, ties going forward -> (list of consensus bytes,
     list of numpy bool arrays: per group, per member -- empty members included -- True where the reverse complement was kept).
@@ -427,10 +524,11 @@ def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=
     strand of the group's first non-empty member.  A kept forward member has been complemented twice: u / U count as T and
     lower-case IUPAC letters as upper case (include/vechat_hip.h).  Parameters, PoaError and strict as poa_consensus; the gap
     scores left out are spoa's overload defaults.  spans as in poa_consensus: both strands of a member meet the same subgraph, and
-    the span stays in sequence 0's coordinates whichever strand is kept."""
+    the span stays in sequence 0's coordinates whichever strand is kept.  weights as in poa_consensus: a kept reverse strand is added
+    with its per-base weights reversed."""
     batch = group_batch(groups)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
-    res, status, sc, scr = run_batch_msa(batch, p, 0, lib, strands=True, spans=span_arrays(groups, spans))
+    res, status, sc, scr = run_batch_msa(batch, p, 0, lib, strands=True, spans=span_arrays(groups, spans), weights=weight_arrays(groups, weights))
     bad = _not_computed(status, strict)
     cons = [None if w in bad else m.consensus for w, m in enumerate(res)]
     rev = [m.reversed for m in res]
@@ -439,21 +537,48 @@ def poa_consensus_strands(groups, algorithm="global", match=5, mismatch=-4, gap=
 
 def poa_msa(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
             gap_extend=None, gap_open2=None, gap_extend2=None, include_consensus=False, coverage=False, strand_ambiguous=False,
-            spans=None):
+            spans=None, weights=None, profile=False):
     """The multiple sequence alignment of every group (spoa's GenerateMultipleSequenceAlignment(include_consensus)) -> list of
     Msa; with coverage=True also the coverage of every consensus base (GenerateConsensus(&summary, false)).  Parameters,
     PoaError and strict as poa_consensus (a group that was not computed comes back as None with strict=False); the gap scores
     left out are spoa's overload defaults, so the default call runs linear gaps and its consensus is poa_consensus's.
     strand_ambiguous=True is spoa's -s (vc_poa_run_strand, see poa_consensus_strands): Msa.reversed then tells, per group
     member, whether the reverse complement was kept, and a row shows the kept bytes.  spans as in poa_consensus; the rows describe
-    the full graph."""
+    the full graph.  weights as in poa_consensus; profile=True attaches every group's Profile as Msa.profile (see poa_profile)."""
     batch = group_batch(groups)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
     flags = capi.VC_POA_MSA | (capi.VC_POA_MSA_CONSENSUS if include_consensus else 0) | (capi.VC_POA_COVERAGE if coverage else 0)
     sp = span_arrays(groups, spans)
-    res, status = run_batch_msa(batch, p, flags, lib, strands=strand_ambiguous, spans=sp)[:2]
+    res, status = run_batch_msa(batch, p, flags, lib, strands=strand_ambiguous, spans=sp, weights=weight_arrays(groups, weights), profile=profile)[:2]
     bad = _not_computed(status, strict)
     return [None if w in bad else m for w, m in enumerate(res)]
+
+
+def poa_profile(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
+                gap_extend=None, gap_open2=None, gap_extend2=None, weights=None, strand_ambiguous=False):
+    """The per-base profile of every group's consensus (spoa's GenerateConsensus(&summary, true), vc_poa_run_weighted) -> list of
+    Profile: for every consensus base how many members carry each code in its column and how many span it with a gap -- the table
+    a consensus quality, an allele frequency or a het call is derived from --, without the alignment rows.  Weights move the
+    consensus, not the counts.  Parameters, PoaError and strict as poa_consensus (a group that was not computed comes back as None
+    with strict=False); weights as in poa_consensus; strand_ambiguous as in poa_msa."""
+    batch = group_batch(groups)
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    x = _run(batch, p, lib=lib, strands=strand_ambiguous, strand_scores=False, weights=weight_arrays(groups, weights), profile=True)
+    bad = _not_computed(x.status, strict)
+    return [None if w in bad else pr for w, pr in enumerate(x.profiles)]
+
+
+def profile_tsv(names, profiles):
+    """The bytes of --profile: per group a header line `#group, pos, base, one column per code, gaps`, then one tab-separated line per
+    consensus position: group name, position, consensus base, the count of every code in codes order, the gaps."""
+    out = []
+    for name, pr in zip(names, profiles):
+        nm = _bytes(name, "group name")
+        out.append(b"#group\tpos\tbase\t" + b"".join(b"%c\t" % c for c in pr.codes) + b"gaps\n")
+        cols = pr.counts.T.tolist()
+        for j, col in enumerate(cols):
+            out.append(b"%s\t%d\t%c\t%s\n" % (nm, j, pr.consensus[j], b"\t".join(b"%d" % v for v in col)))
+    return b"".join(out)
 
 
 class PoaGraph:
@@ -589,12 +714,12 @@ class PoaGraph:
         return b"".join(out)
 
 
-def run_batch_graph(batch, params, flags=0, lib=None, strands=False, spans=None):
+def run_batch_graph(batch, params, flags=0, lib=None, strands=False, spans=None, weights=None, profile=False):
     """vc_poa_run_graph (params: capi.VcPoaGapParams; flags: capi.VC_POA_* bits for the alignment beside it, 0: none) on a
     capi.Batch -> (list of PoaGraph, status array); strands=True builds the groups with spoa's -s and also returns the forward and
     reverse scores per group, as run_batch_msa.  PoaGraph.msa is the group's Msa (its .reversed set with strands).  Everything is
     copied out of the library's buffers before returning.  Raises PoaError on a library error."""
-    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, graph=True, spans=spans)
+    x = _run(batch, params, lib=lib, msa_flags=flags, strands=strands, graph=True, spans=spans, weights=weights, profile=profile)
     return (x.graphs, x.status, x.scores, x.scores_rev) if strands else (x.graphs, x.status)
 
 
@@ -650,7 +775,8 @@ def _state_results(st, graphs, n_members):
 
 
 def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-              gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, resumable=False, spans=None):
+              gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, resumable=False, spans=None,
+              weights=None):
     """The partial order graph of every group (vc_poa_run_graph) -> list of PoaGraph: nodes, weighted edges, aligned nodes, the
     path of every member and the consensus path, as spoa's GFA (-r 3 / -r 4) and dot (-d) output hold them; PoaGraph.to_gfa and
     to_dot give those bytes.  Parameters, PoaError and strict as poa_consensus (a group that was not computed comes back as None
@@ -659,9 +785,11 @@ def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0
     for the multiple sequence alignment of the same graph in the same call: PoaGraph.msa, as poa_msa() returns it.
     resumable=True (vc_poa_run_from) also returns the state a group goes on from -- aligned_lists and n_members --, so that the
     graphs can be stored (PoaGraph.save), extended (poa_extend) and queried (poa_align(graphs=...)) without building them again.
-    spans as in poa_consensus; the tables describe the full graph.  Not with resumable=True (ValueError)."""
+    spans as in poa_consensus; the tables describe the full graph.  Not with resumable=True (ValueError).
+    weights as in poa_consensus: edge_weight holds the sums.  Not with resumable=True (ValueError)."""
     if resumable:
         _no_spans(spans, "poa_graph(resumable=True)")
+        _no_weights(weights, "poa_graph(resumable=True)")
     batch = group_batch(groups)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
     sp = span_arrays(groups, spans)
@@ -669,14 +797,15 @@ def poa_graph(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0
         x = _run(batch, p, lib=lib, msa_flags=capi.VC_POA_MSA if msa else 0, strands=strand_ambiguous, graph=True, state=True)
         res, status = x.graphs, x.status
     else:
-        res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous, spans=sp)[:2]
+        res, status = run_batch_graph(batch, p, capi.VC_POA_MSA if msa else 0, lib, strands=strand_ambiguous, spans=sp,
+                                      weights=weight_arrays(groups, weights))[:2]
     bad = _not_computed(status, strict)
     return [None if w in bad else m for w, m in enumerate(res)]
 
 
 def poa_extend(graphs, groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
                gap_extend=None, gap_open2=None, gap_extend2=None, strand_ambiguous=False, msa=False, include_consensus=False,
-               coverage=False, spans=None):
+               coverage=False, spans=None, weights=None):
     """Adds the members of groups[w] to the stored graph graphs[w] (vc_poa_run_from; spoa's AddAlignment on a live graph) -> (the
     new graphs, resumable again, the list of consensus bytes); with msa=True or coverage=True -> (graphs, consensus, list of
     Msa), the alignment of all members so far as poa_msa returns it (include_consensus as there), also at PoaGraph.msa.
@@ -685,6 +814,7 @@ def poa_extend(graphs, groups, algorithm="global", match=5, mismatch=-4, gap=-8,
     result is byte for byte the one call on all members.  A graph made without resumable=True raises ValueError; parameters,
     PoaError and strict as poa_consensus.  spans= is refused (ValueError): in a stored graph a position on sequence 0 is no node id."""
     _no_spans(spans, "poa_extend")
+    _no_weights(weights, "poa_extend")
     if len(graphs) != len(groups):
         raise ValueError(f"{len(graphs)} graphs for {len(groups)} groups")
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
@@ -743,7 +873,7 @@ def _query_results(a, flags, wq):
 
 def poa_align(groups=None, queries=None, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
               gap_extend=None, gap_open2=None, gap_extend2=None, pairs=True, both_strands=False, strand_ambiguous=False, graph=False,
-              graphs=None, spans=None):
+              graphs=None, spans=None, weights=None):
     """Aligns queries against the finished graphs of their groups without adding them (spoa's engine->Align(query, graph,
     &score); vc_poa_run_align): queries[w] is the list of queries of groups[w] -> per group a list of QueryAlignment; with
     graph=True -> (that, list of PoaGraph of the same call), whose node ids the pairs refer to.  pairs=False returns the scores
@@ -755,6 +885,7 @@ def poa_align(groups=None, queries=None, algorithm="global", match=5, mismatch=-
     give either groups or graphs; both together first add groups[w] to graphs[w] and then align, and graph=True then returns the
     extended graphs, resumable again.  spans= is refused (ValueError): neither the build of this call nor its queries take them."""
     _no_spans(spans, "poa_align")
+    _no_weights(weights, "poa_align")
     if queries is None:
         raise ValueError("poa_align needs queries")
     if groups is None and graphs is None:
@@ -824,7 +955,8 @@ def run_batch_correct(batch, params, prune, lib=None):
 
 
 def poa_correct(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device=0, strict=True, lib=None, *,
-                gap_extend=None, gap_open2=None, gap_extend2=None, min_confidence=0.22, min_support=0.19, prune_rounds=3, spans=None):
+                gap_extend=None, gap_open2=None, gap_extend2=None, min_confidence=0.22, min_support=0.19, prune_rounds=3, spans=None,
+                weights=None):
     """Haplotype-aware correction of every member of every group (vc_poa_run_correct; the flow is in include/vechat_hip.h): the
     group's graph is built as poa_consensus builds it, pruned by confidence and support down to its largest component,
     re-weighted by the members and pruned again (prune_rounds - 1 times, with the call's engine), and every member is read off its
@@ -834,6 +966,7 @@ def poa_correct(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device
     Corrected.status and has an empty read.  ValueError for prune_rounds < 1 or a threshold that is negative or NaN, and for spans=
     (the rounds rebuild and renumber the graph)."""
     _no_spans(spans, "poa_correct")
+    _no_weights(weights, "poa_correct")
     prune = _prune_params(min_confidence, min_support, prune_rounds)
     p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
     res, status = run_batch_correct(group_batch(groups), p, prune, lib)
@@ -908,6 +1041,51 @@ def parse_spans(text, files, records):
     return spans
 
 
+def parse_weights(text, files, records):
+    """The file of --weights: tab-separated lines `group-file-name, member-name, weight`, weight one integer (for every base of the
+    record) or a comma list with one integer per base (empty lines and lines starting with # are skipped) -> the list for weights=,
+    one list per input file with None for every member that is not listed.  files, records and the ValueErrors as parse_spans; a
+    comma list of the wrong length or a value beyond 2^32 - 1 is a ValueError too."""
+    index = {}
+    for w, f in enumerate(files):
+        if _bytes(f, "file name") in index:
+            raise ValueError(f"--weights: the input file {f} is given twice, so its name does not tell the groups apart")
+        index[_bytes(f, "file name")] = w
+    members = []
+    for recs in records:
+        names = {}
+        for k, (name, _, _) in enumerate(recs):
+            names.setdefault(_bytes(name, "record name"), []).append(k)
+        members.append(names)
+    weights = [[None] * len(recs) for recs in records]
+    seen = set()
+    for no, line in enumerate(_bytes(text, "weight file").split(b"\n"), 1):
+        line = line.rstrip(b"\r")
+        if not line.strip() or line.startswith(b"#"):
+            continue
+        cols = line.split(b"\t")
+        if len(cols) != 3 or not all(v.isdigit() for v in cols[2].split(b",")):
+            raise ValueError(f"--weights line {no}: expected group-file-name, member-name, weight (an integer or a comma list) separated by tabs")
+        f, name = cols[0], cols[1]
+        if f not in index:
+            raise ValueError(f"--weights line {no}: no input file named {f.decode(errors='replace')}")
+        w = index[f]
+        ks = members[w].get(name, [])
+        if len(ks) != 1:
+            raise ValueError(f"--weights line {no}: {f.decode(errors='replace')} has {'no' if not ks else 'more than one'} record named "
+                             f"{name.decode(errors='replace')}")
+        if (w, ks[0]) in seen:
+            raise ValueError(f"--weights line {no}: {name.decode(errors='replace')} of {f.decode(errors='replace')} is listed twice")
+        seen.add((w, ks[0]))
+        vals = [int(v) for v in cols[2].split(b",")]
+        if any(v > 0xFFFFFFFF for v in vals):
+            raise ValueError(f"--weights line {no}: a weight is not in 0 .. 2^32 - 1")
+        if b"," in cols[2] and len(vals) != len(records[w][ks[0]][1]):
+            raise ValueError(f"--weights line {no}: {len(vals)} weights for the {len(records[w][ks[0]][1])} bases of {name.decode(errors='replace')}")
+        weights[w][ks[0]] = vals if b"," in cols[2] else vals[0]
+    return weights
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(
         prog="python -m vechat_amd.poa",
@@ -961,6 +1139,14 @@ def parse_args(argv=None):
                     help="align the listed records against a part of their file's graph only: tab-separated lines of input file name, "
                          "record name, begin, end (inclusive positions on the file's first record); records not listed meet the whole "
                          "graph. Not with --align, --correct, --save-graphs or --from-graphs")
+    ap.add_argument("--weights", metavar="FILE", default=None,
+                    help="weigh the listed records explicitly instead of by their quality: tab-separated lines of input file name, "
+                         "record name, weight -- one integer for every base, or a comma list with one integer per base; records not "
+                         "listed keep their quality weights. Not with --align, --correct, --spans, --save-graphs or --from-graphs")
+    ap.add_argument("--profile", metavar="FILE", default=None,
+                    help="also write the per-base profile of every consensus to FILE: a header line per group naming its codes, then one "
+                         "tab-separated line per consensus position: group, position, base, one count per code, gaps. Not with --align, "
+                         "--correct, --spans, --save-graphs or --from-graphs")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="*", metavar="FILE")
     a = ap.parse_args(argv)
@@ -994,6 +1180,9 @@ def main(argv=None):
     if a.spans is not None and (resume or a.correct is not None or a.align is not None):
         print("vechat_amd.poa: --spans does not go with --align, --correct, --save-graphs or --from-graphs", file=sys.stderr)
         return 1
+    if (a.weights is not None or a.profile is not None) and (resume or a.correct is not None or a.align is not None or a.spans is not None):
+        print("vechat_amd.poa: --weights / --profile do not go with --align, --correct, --spans, --save-graphs or --from-graphs", file=sys.stderr)
+        return 1
     # what the command line asks for: the alignment rows or the coverage (a vc_poa_msa_out, which vc_poa_run_align does not carry),
     # the graph tables, the queries
     want_msa = a.r != 0 or a.coverage
@@ -1010,6 +1199,25 @@ def main(argv=None):
             with open(a.spans, "rb") as f:
                 spans = parse_spans(f.read(), a.files, records)
         with_spans = dict(spans=spans) if spans is not None else {}     # (a call without --spans is the call it always was)
+        weights = None
+        if a.weights is not None:
+            with open(a.weights, "rb") as f:
+                weights = parse_weights(f.read(), a.files, records)
+        if weights is not None or a.profile is not None:
+            # one call of vc_poa_run_weighted for everything the command line asks for, and the profile beside it
+            wt = weight_arrays(groups, weights)
+            x = _run(group_batch(groups), p, msa_flags=msa_flags if want_msa or want_graph or a.both_strands else None, strands=a.both_strands,
+                     strand_scores=False, graph=want_graph, weights=wt, profile=a.profile is not None)
+            _not_computed(x.status, True)
+            if a.profile is not None:
+                with open(a.profile, "wb") as f:
+                    f.write(profile_tsv(a.files, x.profiles))
+            if want_graph:
+                graphs = x.graphs
+            if want_msa:
+                msa = x.msas
+            elif not gfa:
+                cons = x.cons
         if resume:
             # one call of vc_poa_run_from: the stored graphs (or none), the records to add (or none), the queries (or none)
             start, names = PoaGraph.load(a.from_graphs, names=True) if a.from_graphs is not None else (None, None)
@@ -1049,7 +1257,7 @@ def main(argv=None):
             _not_computed(status, True)
             with open(a.align_out, "wb") as f:
                 f.write(align_tsv([name for name, _, _ in qrecs], a.files, res))
-        if resume:
+        if resume or weights is not None or a.profile is not None:
             pass
         elif a.align is not None and not want_msa:
             cons, graphs = (None if gfa else c), gr
