@@ -54,6 +54,7 @@ __device__ __forceinline__ uint32_t pku_max_bcast_hi(uint32_t a, uint32_t b) {
 // Does a global alignment of 64 * cpl columns against nrows rows stay inside unsigned 16 bits in the doubly tilted form, with byte-packed
 // rows?  (0 <= T'' <= max(m, 0) * columns + (rows + columns) * (-g); the diagonal term score - 2g must not be negative, or a cell could
 // dip below 0 on the way to its maximum.)
+// (restated in tests/fwd_cases.py, whose case table holds this predicate's edge cases: change the two together)
 __host__ __device__ inline bool vc_dt_ok(long long m, long long n, long long g, long long nrows, long long cpl) {
     if (g >= 0 || n - 2 * g < 0 || m - 2 * g < 0) return false;
     const long long cols = 64 * cpl + 1, mm = m > 0 ? m : 0;

@@ -66,6 +66,7 @@ __device__ __forceinline__ uint32_t vc_weight(const VcBatchDev& b, uint64_t off,
 }
 
 // columns-per-lane class of a sequence: the smallest instantiated k_fwd width that holds it
+// (restated in tests/fwd_cases.py, whose case table holds this predicate's edge cases: change the two together)
 __host__ __device__ inline uint32_t vc_cpl_for(uint32_t len) {
     const uint32_t opts[11] = {4, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64};
     for (int i = 0; i < 11; ++i) if (64 * opts[i] >= len) return opts[i];
@@ -79,6 +80,7 @@ __host__ __device__ inline uint32_t vc_cpl_for(uint32_t len) {
 // for a global alignment (column 0 is H[i][0] >= g * i, the virtual row is 0), T >= 0 for a local one -- and rises by at most
 // m - g per column.  1 024 of headroom below, as before.  (Round 4: 3 kb reads against a 7 000-row graph fit; they used to go
 // to the int32 kernel on H's account.)
+// (restated in tests/fwd_cases.py, whose case table holds this predicate's edge cases: change the two together)
 __host__ __device__ inline bool vc_int16_ok(long long m, long long n, long long g, long long nrows, long long cpl, bool nw) {
     if (g >= 0 || (!nw && n >= 0)) return false;
     long long dec = -g;
@@ -1324,6 +1326,7 @@ __device__ __forceinline__ unsigned long long* vc_stat_slot(unsigned long long* 
 #define VC_STAT_WORDS (8 * VC_STAT_SLOTS + 2 * VC_STAT_SLOTS)
 __device__ __forceinline__ unsigned long long* vc_clk_slot(unsigned long long* stat) { return stat + 8 * VC_STAT_SLOTS + (blockIdx.x % VC_STAT_SLOTS) * 2; }
 
+// (restated in tests/fwd_cases.py, whose case table holds this predicate's edge cases: change the two together)
 __host__ __device__ inline bool vc_row_packed(int m, int n, int g, int cpl) {
     return g < 0 && (cpl - 1) * ((m > n ? m : n) - 2 * g) <= 255;
 }
