@@ -317,6 +317,29 @@ def test_a_group_that_is_not_computed_and_a_group_without_queries(built, monkeyp
           f"without them, {time.time() - t0:.1f} s")
 
 
+def test_a_call_whose_jobs_are_all_empty_allocates_nothing(built, monkeypatch, capfd):
+    """Every job of the call is an empty alignment -- an empty query, or any query against the graph of an empty group -- so the job
+    stage lists its jobs and stops before its device allocation: the log line counts the jobs and no launch, cell or byte.  Every
+    query is VC_WIN_OK with the restatement's result (score 0, no pair), with one strand and with both."""
+    groups, _ = _fresh(8550, 3)
+    groups.append([])
+    queries = [[b"", b""], [b""], [b"", b"", b""], [b"ACGTACGT", b""]]
+    scores = MODELS["affine"]
+    env = {"VC_LARGE_LOG": "1", "VC_LARGE_MAT_MB": "0.01", "VC_LARGE_ARENA_MB": "0.5"}
+    t0 = time.time()
+    built_ = [A.build(g, 1, *scores) for g in groups]
+    for flags, strands in ((PAIRS, False), (PAIRS | STRANDS, True)):
+        got, err = _knobs(monkeypatch, capfd, env, lambda: _align(groups, queries, 1, scores, flags))
+        assert _log(err) == (sum(len(qs) for qs in queries), 0, 0, 0) and sum(len(qs) for qs in queries) == 8, err
+        assert got[1].tolist() == [OK] * 4 and got[0][3] == b"" and all(got[0][:3])
+        for (eng, gr), qs, res in zip(built_, queries, got[2]):
+            assert len(res) == len(qs)
+            for s, r in zip(qs, res):
+                assert r.status == OK and A.of_query_alignment(r) == A.align_one(eng, gr, s, strands), (flags, s)
+    print(f"[empty jobs] 8 queries, every one an empty alignment: 8 jobs, no launch, no cell, no byte copied; equal to the restatement, "
+          f"{time.time() - t0:.1f} s")
+
+
 # ------------------------------------------------------------------ 7. calls without queries
 def test_calls_without_queries_are_unchanged(built, monkeypatch, capfd):
     groups, queries = _fresh(8600, 24)

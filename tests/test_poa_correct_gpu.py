@@ -284,6 +284,23 @@ def test_a_group_that_is_not_computed_beside_valid_ones(built, monkeypatch, capf
     print(f"[statuses] a refused group's members carry its status; the rest equal to the call without it, {time.time() - t0:.1f} s")
 
 
+def test_a_call_whose_jobs_are_all_empty_allocates_nothing(built, monkeypatch, capfd):
+    """Every member of the call is empty, so every final graph has no node and every job is an empty alignment: the job stage lists
+    its jobs and stops before its device allocation -- the log line counts the jobs and no launch, cell or byte.  (A correction job
+    is empty only where the member or the graph is, so the members here cannot have bases.)  Every member is VC_WIN_OK with the
+    restatement's result: the empty correction, score 0."""
+    groups = [[(b"", None)] * 4, [(b"", None)] * 6, [], [(b"", None)] * 5]
+    env = {"VC_LARGE_LOG": "1", "VC_LARGE_MAT_MB": "0.01", "VC_LARGE_ARENA_MB": "0.5"}
+    t0 = time.time()
+    for model in MODELS:
+        got, err = _knobs(monkeypatch, capfd, env, lambda: _correct(groups, 1, MODELS[model]))
+        assert _log(err) == (15, 0, 0, 0), err
+        assert got[1].tolist() == [OK] * 4
+        _same(got[0], _refs(groups, 1, MODELS[model]), ("empty", model))
+    print(f"[empty jobs] 15 empty members of 4 groups, three gap models: 15 jobs, no launch, no cell, no byte copied; equal to the "
+          f"restatement, {time.time() - t0:.1f} s")
+
+
 # ------------------------------------------------------------------ 7. calls without correction
 def test_calls_without_correction_are_unchanged(built, monkeypatch, capfd):
     groups = _fresh(9700, 24, hi=150, kmax=8)

@@ -79,6 +79,15 @@
 //   k_lg_correct <0> one wave per job: the pairs with a node, counted; <1> their nodes' bytes, compact behind the host's prefix
 //               offsets (ballot and population count per tile of 64 pairs, a carried total) -- GenerateCorrectedSequence.
 //
+// Host schedule (Run, run_windows, run_group, lock_step): the windows or groups of a call run in host groups that fit the arena
+// budget, one alignment of each per lock-step step, the forward passes in launches that fit the matrix budget (launch_loop).  What
+// a vc_poa_* call hands out beside consensus and status comes from output stages (Stage): msa, profile, graph with the state
+// table, correct and align.  A stage owns its tables and its per-call state and has four steps -- size, collect from a host group
+// that finished while its tables are resident, assemble in window order with its log line, publish into the caller's out-struct --
+// and the schedule walks the stages a call asks for without naming them.  Align and correct are one job stage (JobStage) with
+// two kinds; graph and profile share their launch layout, every block in front of every scratch, and the copy that takes the
+// blocks out.
+//
 // Limits, every schedule: a sequence is shorter than 65 535 bases; beyond that only the device memory bounds a window or group,
 // and one whose tables or matrix it cannot hold at all comes back VC_WIN_OVERFLOW.  Where the reference throws (an invalid
 // alignment, the score floor of WorstCaseAlignmentScore) that window or group is VC_WIN_INVALID and the rest are computed.
@@ -293,8 +302,8 @@ struct PoaRequest {
     vc_poa_profile_out* profile = nullptr;             // the per-code profile of every consensus
     bool rows() const { return msa_flags != 0; }                           // k_lg_msa runs
     bool columns() const { return rows() || profile != nullptr; }          // k_lg_msa<0> runs
-    bool keeps_labels() const { return msa_flags != 0 || graph != nullptr || profile != nullptr; }   // the edges keep sequence labels
-    bool keeps_seqs() const { return keeps_labels(); }                     // the windows keep sq_begin / sq_member
+    // the edges keep sequence labels, and the windows sq_begin / sq_member beside them
+    bool keeps_labels() const { return msa_flags != 0 || graph != nullptr || profile != nullptr; }
     uint32_t strands() const { return strand ? 2 : 1; }                    // forward passes per alignment of the build
     bool has_queries() const { return nq != 0; }                           // the query stage runs (a call without a query is the call without it)
     bool query_pairs() const { return (align_flags & VC_POA_ALIGN_PAIRS) != 0; }
@@ -304,90 +313,12 @@ struct PoaRequest {
 // an empty table is still a pointer
 template <class T> T* table(std::vector<T>& v) { v.reserve(1); return v.data(); }
 
-// What the vc_poa_* entries hand out: owned here, valid until the next call that has an output of its own or vc_large_release.
-struct Outputs {
-    struct Msa {                                       // vc_poa_msa_out
-        std::vector<uint32_t> n_rows, row_size, row_member, coverage;
-        std::vector<uint64_t> row_off, member_off;
-        std::vector<uint8_t> rows;
-        void publish(vc_poa_msa_out* o) {
-            o->n_rows = n_rows.data(); o->row_size = row_size.data(); o->row_off = row_off.data();
-            o->member_off = member_off.data(); o->row_member = row_member.data();
-            o->rows = rows.data(); o->rows_bytes = rows.size();
-            if (o->flags & VC_POA_COVERAGE) o->coverage = coverage.data();
-        }
-    } msa;
-    struct Graph {                                     // vc_poa_graph_out
-        std::vector<uint32_t> n_nodes, rank_to_node, edge_head, aligned_a, aligned_b, path_member, path_node, cons_node;
-        std::vector<uint64_t> node_off, out_off, aligned_off, path_first, path_off;
-        std::vector<uint8_t> node_base, path_reversed;
-        std::vector<int32_t> node_cons_pos;
-        std::vector<int64_t> edge_weight;
-        uint64_t bytes = 0;                            // copied out of the device
-        void publish(vc_poa_graph_out* go) {
-            go->n_nodes = table(n_nodes); go->node_off = node_off.data(); go->node_base = table(node_base);
-            go->node_cons_pos = table(node_cons_pos); go->rank_to_node = table(rank_to_node);
-            go->out_off = out_off.data(); go->edge_head = table(edge_head); go->edge_weight = table(edge_weight);
-            go->aligned_off = aligned_off.data(); go->aligned_a = table(aligned_a); go->aligned_b = table(aligned_b);
-            go->path_first = path_first.data(); go->path_member = table(path_member); go->path_reversed = table(path_reversed);
-            go->path_off = path_off.data(); go->path_node = table(path_node);
-            go->cons_node = table(cons_node);
-            go->bytes = bytes;
-        }
-    } graph;
-    struct State {                                     // vc_poa_state_out
-        std::vector<uint64_t> al_off;
-        std::vector<uint32_t> al_node;
-        uint64_t bytes = 0;                            // copied out of the device
-        void publish(vc_poa_state_out* st) { st->al_off = al_off.data(); st->al_node = table(al_node); st->bytes = bytes; }
-    } state;
-    struct Align {                                     // vc_poa_align_out, one entry per query of the batch
-        std::vector<uint8_t> status, reversed;
-        std::vector<int32_t> score, score_rev, pair_node, pair_pos;
-        std::vector<uint64_t> pair_off;
-        uint64_t bytes = 0;                            // copied out of the device
-        void publish(vc_poa_align_out* ao, const PoaRequest& q) {
-            ao->n_queries = q.nq;
-            if (!q.has_queries() && q.query_pairs()) pair_off.assign(1, 0);     // no stage ran: the empty tables
-            ao->status = table(status); ao->score = table(score);
-            if (q.query_strands() == 2) { ao->score_rev = table(score_rev); ao->reversed = table(reversed); }
-            if (q.query_pairs()) { ao->pair_off = pair_off.data(); ao->pair_node = table(pair_node); ao->pair_pos = table(pair_pos); }
-            ao->bytes = bytes;
-        }
-    } align;
-    struct Correct {                                   // vc_poa_correct_out, one entry per sequence of the batch
-        std::vector<uint8_t> status, corr;
-        std::vector<int32_t> score;
-        std::vector<uint64_t> corr_off;
-        uint64_t bytes = 0;                            // copied out of the device
-        void publish(vc_poa_correct_out* co, uint64_t nseq) {
-            if (corr_off.empty()) corr_off.assign(nseq + 1, 0);                 // no run: the empty tables
-            co->n_seqs = nseq;
-            co->status = table(status); co->score = table(score); co->corr_off = corr_off.data(); co->corr = table(corr);
-            co->bytes = bytes;
-        }
-    } correct;
-    struct Profile {                                   // vc_poa_profile_out
-        std::vector<uint32_t> n_codes, counts;
-        std::vector<uint64_t> code_off, prof_off;
-        std::vector<uint8_t> codes;
-        uint64_t bytes = 0;                            // copied out of the device
-        void publish(vc_poa_profile_out* po) {
-            po->n_codes = n_codes.data(); po->code_off = code_off.data(); po->codes = table(codes);
-            po->prof_off = prof_off.data(); po->counts = table(counts);
-        }
-    } profile;
-    void clear() { *this = Outputs{}; }
-} g_out;
-
-// a group's block of k_lg_graph<1> on the host, and the counts that lay it out
-struct GraphPart { uint32_t N = 0, E = 0, P = 0, S = 0, T = 0, Cn = 0, A = 0; std::vector<uint8_t> blk; };   // A: cells of the state table behind it
-
 // ------------------------------------------------------------------ the host schedule
 // One call of vc_large_run / vc_poa_run*: the batch on the device (seq_begin / seq_end only with spans), windows in flight in
 // groups that fit the arena budget, one alignment of each per lock-step step with the forward passes in launches that fit the
 // matrix budget, and a window whose table filled run again with larger tables.  `a` holds the scores and the schedule, `q` what
-// the call wants beside the consensus; every output stage keeps what it gathers per window here until its assemble_* orders it.
+// the call wants beside the consensus, `stages` the output stages that deliver it (below; they keep their own state).
+struct Stage;
 struct Run {
     LArgs a;
     const vc_batch* b;
@@ -408,24 +339,8 @@ struct Run {
     // graph's rows for the same passes.  A group that runs again starts from zero, so every member counts once
     struct SpanCount { uint64_t members = 0, rows = 0, full = 0; };
     std::vector<SpanCount> sp_of;
-    std::vector<std::vector<uint32_t>> mem_of, cov_of; // msa: per window the row members and the coverage
-    uint64_t msa_launches = 0;
-    std::vector<GraphPart> part;                       // graph: per window its block
-    uint64_t graph_launches = 0;
-    std::vector<std::vector<uint8_t>> prof_of;         // profile: per window its block (counts, then codes), and its code count
-    std::vector<uint32_t> prof_nc;
-    uint64_t profile_launches = 0;
     LLoad load{};                                      // vc_poa_run_from: the stored graphs on the device
-    // the query stage: per host group the packed pairs (every node, then every position), per query where its pairs lie; the "align" line
-    std::vector<std::vector<int32_t>> q_part;
-    std::vector<uint32_t> q_part_of, q_count;          // [nq]
-    std::vector<uint64_t> q_first;                     // [nq]
-    uint64_t q_jobs = 0, q_launches = 0, q_cells = 0;
-    // the correction stage: per host group the corrected bytes, per sequence of the batch where its own lie; the "correct" line
-    std::vector<std::vector<uint8_t>> c_part;
-    std::vector<uint32_t> c_part_of, c_count;          // [sequences]
-    std::vector<uint64_t> c_first;                     // [sequences]
-    uint64_t c_jobs = 0, c_launches = 0, c_cells = 0;
+    std::vector<Stage*> stages;                        // the output stages of this call, in their order (Outputs::active)
 };
 
 // the windows in flight together: their ids, their tables in the arena, their LWin here and on the device
@@ -533,7 +448,7 @@ int upload_stored(Run& R, DevMem& mem) {
 void next_group(Run& R, Group& G) {
     std::vector<uint32_t> rest;
     for (uint32_t w : R.pending) {
-        const uint64_t need = layout(nullptr, nullptr, R.caps[w], R.labels, R.q.keeps_seqs(), R.q.from != nullptr);
+        const uint64_t need = layout(nullptr, nullptr, R.caps[w], R.labels, R.q.keeps_labels(), R.q.from != nullptr);
         if (G.ids.empty() && need > R.arena_budget * 2) {                  // the device cannot hold its tables
             R.status[w] = VC_WIN_OVERFLOW;
             if (R.kn.log) std::fprintf(stderr, "vc_large: refuse window=%u bytes=%llu budget=%llu\n", w, (unsigned long long)need, (unsigned long long)R.arena_budget);
@@ -562,7 +477,7 @@ void place_windows(const Run& R, Group& G, uint8_t* arena) {
         const uint32_t w = G.ids[k];
         LWin& W = G.hw[k];
         W = LWin{};
-        layout(&W, arena + G.aoff[k], R.caps[w], R.labels, R.q.keeps_seqs(), R.q.from != nullptr);
+        layout(&W, arena + G.aoff[k], R.caps[w], R.labels, R.q.keeps_labels(), R.q.from != nullptr);
         if (const vc_poa_graph_in* f = R.q.from) { W.n_old = (uint32_t)(f->path_first[w + 1] - f->path_first[w]); W.m0 = f->n_members[w]; }
         const Caps& c = R.caps[w];
         W.s0 = b->win_seq_off[w]; W.nseq = b->win_seq_off[w + 1] - W.s0;
@@ -629,6 +544,14 @@ std::vector<uint32_t> finished(const Run& R, const Group& G) {
     return fin;
 }
 
+// launch(gm) with the gap model LArgs::gaps as a constant: the <GM> of k_lg_fwd / k_lg_back and of the query stage's kernels
+template <class Launch>
+void with_gap_model(uint32_t gaps, Launch launch) {
+    if (gaps == 0) launch(std::integral_constant<uint32_t, 0>{});
+    else if (gaps == 1) launch(std::integral_constant<uint32_t, 1>{});
+    else launch(std::integral_constant<uint32_t, 2>{});
+}
+
 template <uint32_t GM>
 void launch_align(const LArgs& f, uint32_t nl, uint32_t ns) {
     hipLaunchKernelGGL(k_lg_fwd<GM>, dim3(nl, ns), dim3(64), 0, 0, f);
@@ -649,9 +572,7 @@ bool align_step(Run& R, Group& G, const std::vector<uint32_t>& act) {
     auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>&, uint64_t cells, void* H) -> int {
         const uint32_t nl = (uint32_t)list.size();
         f.H = (int32_t*)H;
-        if (f.gaps == 0) launch_align<0>(f, nl, R.ns);
-        else if (f.gaps == 1) launch_align<1>(f, nl, R.ns);
-        else launch_align<2>(f, nl, R.ns);
+        with_gap_model(f.gaps, [&](auto gm) { launch_align<decltype(gm)::value>(f, nl, R.ns); });
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, failed);
         for (const uint32_t k : list) R.n_cells += (uint64_t)G.hw[k].rows * G.hw[k].qlen * R.ns;
         R.n_align += (uint64_t)nl * R.ns;
@@ -731,6 +652,22 @@ void regrow(Run& R, uint32_t w, const LWin& W) {
         R.pending.push_back(w);
 }
 
+// ------------------------------------------------------------------ the output stages
+// What a vc_poa_* call hands out beside consensus and status, one stage per output: msa, profile, graph (with the state table),
+// correct and align.  A stage owns the tables it hands out and what it keeps per window during a call, and has four steps:
+// size() for the call; collect() from the groups of a Group that finished, while their tables are resident; assemble() in window
+// order, with the stage's log line; publish() into the caller's out-struct, where the call has one.  The stages live in g_out
+// (below), so their tables stay valid until the next call that has an output of its own, or vc_large_release.
+struct Stage {
+    virtual ~Stage() = default;
+    virtual void size(const Run& R) = 0;
+    virtual int collect(Run& R, Group& G) = 0;
+    virtual void assemble(const Run& R) = 0;
+    virtual void publish(const PoaRequest& q, const vc_batch* b) = 0;
+};
+
+int refuse_group(Run& R, uint32_t w) { R.status[w] = VC_WIN_OVERFLOW; R.out[w].clear(); return VC_OK; }   // a stage has no room for the one group w
+
 // A finished group's block of k_lg_msa<1>: msa_rows x row_size bytes, then (16-byte aligned) the row members at mem_at, then
 // (16-byte aligned, VC_POA_COVERAGE) the coverage at cov_at.
 struct MsaBlock { uint64_t mem_at, cov_at, bytes; };
@@ -742,213 +679,277 @@ MsaBlock msa_block(const LWin& W, uint32_t flags) {
     return B;
 }
 
-int refuse_group(Run& R, uint32_t w) { R.status[w] = VC_WIN_OVERFLOW; R.out[w].clear(); return VC_OK; }   // a stage has no room for the one group w
+// The alignments and the coverage (vc_poa_msa_out): blocks laid out in the matrix buffer (free after the last step), in launches
+// that fit the matrix budget, each copied out at once, straight into `rows`.
+struct MsaStage : Stage {
+    std::vector<uint32_t> n_rows, row_size, row_member, coverage;
+    std::vector<uint64_t> row_off, member_off;
+    std::vector<uint8_t> rows;
+    std::vector<std::vector<uint32_t>> mem_of, cov_of; // until assemble(), per window: the row members and the coverage
+    uint64_t launches = 0;
 
-// The alignments and coverage of the groups that finished, while their tables are resident: blocks laid out in the matrix buffer
-// (free after the last step), in launches that fit the matrix budget, each copied out at once.
-int collect_msa(Run& R, Group& G) {
-    const LArgs& a = R.a;
-    Outputs::Msa& msa = g_out.msa;
-    auto block_bytes = [&](uint32_t k) { return msa_block(G.hw[k], a.msa).bytes; };
-    auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t bytes, void* dout) -> int {
-        const uint32_t nl = (uint32_t)list.size();
-        const uint64_t at = msa.rows.size();
-        f.msa_out = (uint8_t*)dout;
-        hipLaunchKernelGGL(k_lg_msa<1>, dim3(nl), dim3(64), 0, 0, f);
-        bool ok = hipGetLastError() == hipSuccess;
-        msa.rows.resize(at + bytes);
-        ok = ok && hipMemcpy(msa.rows.data() + at, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-        if (!ok) return fail(VC_ERR_HIP, "the alignment-row kernel or its copy failed");
-        for (uint32_t q = 0; q < nl; ++q) {
-            const LWin& W = G.hw[list[q]];
-            const uint32_t w = G.ids[list[q]];
-            const MsaBlock B = msa_block(W, a.msa);
-            const uint8_t* blk = msa.rows.data() + at + hoff[q];
-            msa.n_rows[w] = W.msa_rows; msa.row_size[w] = W.row_size; msa.row_off[w] = at + hoff[q];
-            R.mem_of[w].resize(W.msa_rows);
-            if (W.msa_rows) std::memcpy(R.mem_of[w].data(), blk + B.mem_at, 4ull * W.msa_rows);
-            if (a.msa & VC_POA_COVERAGE) {
-                R.cov_of[w].resize(W.cons_n);
-                if (W.cons_n) std::memcpy(R.cov_of[w].data(), blk + B.cov_at, 4ull * W.cons_n);
+    void size(const Run& R) override {
+        mem_of.resize(R.nw); cov_of.resize(R.nw);
+        n_rows.assign(R.nw, 0); row_size.assign(R.nw, 0); row_off.assign(R.nw, 0); member_off.assign(R.nw + 1, 0);
+    }
+    int collect(Run& R, Group& G) override {
+        const LArgs& a = R.a;
+        auto block_bytes = [&](uint32_t k) { return msa_block(G.hw[k], a.msa).bytes; };
+        auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t bytes, void* dout) -> int {
+            const uint32_t nl = (uint32_t)list.size();
+            const uint64_t at = rows.size();
+            f.msa_out = (uint8_t*)dout;
+            hipLaunchKernelGGL(k_lg_msa<1>, dim3(nl), dim3(64), 0, 0, f);
+            bool ok = hipGetLastError() == hipSuccess;
+            rows.resize(at + bytes);
+            ok = ok && hipMemcpy(rows.data() + at, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+            if (!ok) return fail(VC_ERR_HIP, "the alignment-row kernel or its copy failed");
+            for (uint32_t q = 0; q < nl; ++q) {
+                const LWin& W = G.hw[list[q]];
+                const uint32_t w = G.ids[list[q]];
+                const MsaBlock B = msa_block(W, a.msa);
+                const uint8_t* blk = rows.data() + at + hoff[q];
+                n_rows[w] = W.msa_rows; row_size[w] = W.row_size; row_off[w] = at + hoff[q];
+                mem_of[w].resize(W.msa_rows);
+                if (W.msa_rows) std::memcpy(mem_of[w].data(), blk + B.mem_at, 4ull * W.msa_rows);
+                if (a.msa & VC_POA_COVERAGE) {
+                    cov_of[w].resize(W.cons_n);
+                    if (W.cons_n) std::memcpy(cov_of[w].data(), blk + B.cov_at, 4ull * W.cons_n);
+                }
+            }
+            return VC_OK;
+        };
+        return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
+                           {"device allocation of the alignment rows failed", "the alignment-row kernel or its copy failed"}, launches,
+                           block_bytes, as_packed, [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
+    }
+    // the per-row and per-base tables in window order
+    void assemble(const Run& R) override {
+        member_off[0] = 0;
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            if (R.status[w] != VC_WIN_OK) { n_rows[w] = 0; row_size[w] = 0; mem_of[w].clear(); cov_of[w].clear(); }
+            row_member.insert(row_member.end(), mem_of[w].begin(), mem_of[w].end());
+            member_off[w + 1] = row_member.size();
+            if (R.a.msa & VC_POA_COVERAGE) {
+                cov_of[w].resize(R.out[w].size());
+                coverage.insert(coverage.end(), cov_of[w].begin(), cov_of[w].end());
             }
         }
-        return VC_OK;
-    };
-    return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
-                       {"device allocation of the alignment rows failed", "the alignment-row kernel or its copy failed"}, R.msa_launches,
-                       block_bytes, as_packed, [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
-}
-
-// the per-row and per-base tables in window order, and the stage's log line
-void assemble_msa(Run& R) {
-    Outputs::Msa& msa = g_out.msa;
-    msa.member_off[0] = 0;
-    for (uint32_t w = 0; w < R.nw; ++w) {
-        if (R.status[w] != VC_WIN_OK) { msa.n_rows[w] = 0; msa.row_size[w] = 0; R.mem_of[w].clear(); R.cov_of[w].clear(); }
-        msa.row_member.insert(msa.row_member.end(), R.mem_of[w].begin(), R.mem_of[w].end());
-        msa.member_off[w + 1] = msa.row_member.size();
-        if (R.a.msa & VC_POA_COVERAGE) {
-            R.cov_of[w].resize(R.out[w].size());
-            msa.coverage.insert(msa.coverage.end(), R.cov_of[w].begin(), R.cov_of[w].end());
-        }
+        if (R.kn.log) std::fprintf(stderr, "vc_large: msa launches=%llu bytes=%llu\n", (unsigned long long)launches, (unsigned long long)rows.size());
     }
-    if (R.kn.log) std::fprintf(stderr, "vc_large: msa launches=%llu bytes=%llu\n", (unsigned long long)R.msa_launches, (unsigned long long)msa.rows.size());
-}
-
-// The profiles of the groups that finished, as collect_graph: a block (counts, codes) and a scratch per group in the matrix
-// buffer, the blocks in front so that one copy takes them out.  The groups' columns are k_lg_msa<0>'s, of the same lock_step.
-int collect_profile(Run& R, Group& G) {
-    const LArgs& a = R.a;
-    auto block_of = [&](uint32_t k) { return profile_block(G.hw[k].num_codes, G.hw[k].cons_n).bytes; };
-    auto scratch_of = [&](uint32_t k) { return profile_scratch(G.hw[k].gr[G.hw[k].cur].nseq, G.hw[k].gr_cols).bytes; };
-    uint64_t blocks = 0;
-    auto blocks_first = [&](const std::vector<uint32_t>& list, std::vector<uint64_t>& hoff) {      // every block, then every scratch
-        const uint32_t nl = (uint32_t)list.size();
-        blocks = 0;
-        hoff.assign(2 * (size_t)nl, 0);
-        for (uint32_t q = 0; q < nl; ++q) { hoff[q] = blocks; blocks += block_of(list[q]); }
-        uint64_t at = blocks;
-        for (uint32_t q = 0; q < nl; ++q) { hoff[nl + q] = at; at += scratch_of(list[q]); }
-    };
-    std::vector<uint8_t> host;
-    auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t, void* dout) -> int {
-        const uint32_t nl = (uint32_t)list.size();
-        f.msa_out = (uint8_t*)dout;
-        hipLaunchKernelGGL(k_lg_profile, dim3(nl), dim3(64), 0, 0, f);
-        bool ok = hipGetLastError() == hipSuccess;
-        host.resize(blocks);
-        ok = ok && (blocks == 0 || hipMemcpy(host.data(), dout, blocks, hipMemcpyDeviceToHost) == hipSuccess);
-        if (!ok) return fail(VC_ERR_HIP, "the profile kernel or its copy failed");
-        for (uint32_t q = 0; q < nl; ++q) {
-            const uint32_t w = G.ids[list[q]];
-            R.prof_of[w].assign(host.begin() + hoff[q], host.begin() + (q + 1 < nl ? hoff[q + 1] : blocks));
-            R.prof_nc[w] = G.hw[list[q]].num_codes;
-        }
-        g_out.profile.bytes += blocks;
-        return VC_OK;
-    };
-    return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
-                       {"device allocation of the profile blocks failed", "the profile kernel or its copy failed"}, R.profile_launches,
-                       [&](uint32_t k) { return block_of(k) + scratch_of(k); }, blocks_first,
-                       [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
-}
-
-// the tables of vc_poa_profile_out in window order (a group that was not computed has no code and an empty block), and the log line
-void assemble_profile(Run& R) {
-    Outputs::Profile& P = g_out.profile;
-    P.code_off.assign(1, 0);
-    for (uint32_t w = 0; w < R.nw; ++w) {
-        const uint32_t nc = R.status[w] == VC_WIN_OK && !R.prof_of[w].empty() ? R.prof_nc[w] : 0;
-        const uint64_t Cn = R.out[w].size();
-        P.n_codes.push_back(nc);
-        P.prof_off.push_back(P.counts.size());
-        if (nc) {
-            const uint8_t* blk = R.prof_of[w].data();
-            const uint32_t* c = (const uint32_t*)blk;
-            P.counts.insert(P.counts.end(), c, c + (uint64_t)(nc + 1) * Cn);
-            const uint8_t* codes = blk + profile_block(nc, Cn).codes;
-            P.codes.insert(P.codes.end(), codes, codes + nc);
-        }
-        P.code_off.push_back(P.codes.size());
-        R.prof_of[w] = std::vector<uint8_t>{};
+    void publish(const PoaRequest& q, const vc_batch* b) override {
+        vc_poa_msa_out* o = q.msa;
+        if (!o) return;
+        o->n_groups = b->n_windows;
+        if (!q.rows() || !b->n_windows) return;                            // without flags: n_groups only
+        o->n_rows = n_rows.data(); o->row_size = row_size.data(); o->row_off = row_off.data();
+        o->member_off = member_off.data(); o->row_member = row_member.data();
+        o->rows = rows.data(); o->rows_bytes = rows.size();
+        if (o->flags & VC_POA_COVERAGE) o->coverage = coverage.data();
     }
-    if (R.kn.log) std::fprintf(stderr, "vc_large: profile launches=%llu bytes=%llu\n", (unsigned long long)R.profile_launches, (unsigned long long)P.bytes);
-}
+};
 
-// The graphs of the groups that finished, as collect_msa: a block and a scratch per group in the matrix buffer, the blocks in
-// front so that one copy takes them out and leaves the scratch behind.
-int collect_graph(Run& R, Group& G) {
-    const LArgs& a = R.a;
-    auto part_of = [&](uint32_t k) {
-        const LWin& W = G.hw[k];
-        const LGraph& g = W.gr[W.cur];
-        GraphPart p;
-        p.N = g.n_nodes; p.E = g.n_edges; p.P = g.n_al / 2; p.S = g.nseq; p.T = W.gr_path; p.Cn = W.cons_n; p.A = a.state ? g.n_al : 0;
-        return p;
-    };
-    auto block_of = [&](uint32_t k) {
-        const GraphPart p = part_of(k);
-        return graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn).bytes + (a.state ? state_bytes(p.N, p.A) : 0);
-    };
-    auto scratch_of = [&](uint32_t k) { return a.graph == 1 ? graph_scratch_bytes(G.hw[k].gr[G.hw[k].cur].nseq, G.hw[k].gr_cols) : 0; };
-    auto need = [&](uint32_t k) { return block_of(k) + scratch_of(k); };
+// The launch layout of the stages that copy a block per group out and leave a scratch per group behind (graph, profile): every
+// block, then every scratch -- hoff[q] and hoff[groups + q] for group list[q] -- so that one copy takes the blocks out.  Returns
+// the blocks' bytes.
+template <class Block, class Scratch>
+uint64_t blocks_first(const std::vector<uint32_t>& list, std::vector<uint64_t>& hoff, Block block_of, Scratch scratch_of) {
+    const uint32_t nl = (uint32_t)list.size();
     uint64_t blocks = 0;
-    auto blocks_first = [&](const std::vector<uint32_t>& list, std::vector<uint64_t>& hoff) {      // every block, then every scratch
-        const uint32_t nl = (uint32_t)list.size();
-        blocks = 0;
-        hoff.assign(2 * (size_t)nl, 0);
-        for (uint32_t q = 0; q < nl; ++q) { hoff[q] = blocks; blocks += block_of(list[q]); }
-        uint64_t at = blocks;
-        for (uint32_t q = 0; q < nl; ++q) { hoff[nl + q] = at; at += scratch_of(list[q]); }
-    };
-    std::vector<uint8_t> host;
-    auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t, void* dout) -> int {
-        const uint32_t nl = (uint32_t)list.size();
-        f.msa_out = (uint8_t*)dout;
-        hipLaunchKernelGGL(k_lg_graph<1>, dim3(nl), dim3(64), 0, 0, f);
-        bool ok = hipGetLastError() == hipSuccess;
-        host.resize(blocks);
-        ok = ok && hipMemcpy(host.data(), dout, blocks, hipMemcpyDeviceToHost) == hipSuccess;
-        if (!ok) return fail(VC_ERR_HIP, "the graph kernel or its copy failed");
-        for (uint32_t q = 0; q < nl; ++q) {
-            GraphPart& p = R.part[G.ids[list[q]]];
-            p = part_of(list[q]);
-            p.blk.assign(host.begin() + hoff[q], host.begin() + (q + 1 < nl ? hoff[q + 1] : blocks));
-        }
-        uint64_t st_bytes = 0;                                             // the state tables lie in the same copy: counted apart
-        if (a.state) for (const uint32_t k : list) { const GraphPart p = part_of(k); st_bytes += state_bytes(p.N, p.A); }
-        g_out.graph.bytes += blocks - st_bytes;
-        g_out.state.bytes += st_bytes;
-        return VC_OK;
-    };
-    return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
-                       {"device allocation of the graph tables failed", "the graph kernel or its copy failed"}, R.graph_launches,
-                       need, blocks_first, [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
+    hoff.assign(2 * (size_t)nl, 0);
+    for (uint32_t q = 0; q < nl; ++q) { hoff[q] = blocks; blocks += block_of(list[q]); }
+    uint64_t at = blocks;
+    for (uint32_t q = 0; q < nl; ++q) { hoff[nl + q] = at; at += scratch_of(list[q]); }
+    return blocks;
 }
 
-// the tables of vc_poa_graph_out in window order, every offset rebased from its block to the batch, and the stage's log line
-void assemble_graph(Run& R) {
-    Outputs::Graph& gs = g_out.graph;
-    auto put = [](auto& dst, const GraphPart& p, uint64_t at, uint64_t n) {
-        using T = typename std::remove_reference_t<decltype(dst)>::value_type;
-        const T* src = (const T*)(p.blk.data() + at);
-        dst.insert(dst.end(), src, src + n);
-    };
-    Outputs::State& ss = g_out.state;
-    gs.node_off.assign(1, 0); gs.aligned_off.assign(1, 0); gs.path_first.assign(1, 0); gs.path_off.assign(1, 0);
-    for (uint32_t w = 0; w < R.nw; ++w) {
-        if (R.status[w] != VC_WIN_OK) R.part[w] = GraphPart{};
-        const GraphPart& p = R.part[w];
-        const GraphBlock B = graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn);
-        const uint64_t e0 = gs.edge_head.size(), t0 = gs.path_node.size(), c0 = ss.al_node.size();
-        gs.n_nodes.push_back(p.N);
-        if (!p.blk.empty()) {
-            put(gs.node_base, p, B.base, p.N); put(gs.node_cons_pos, p, B.cons_pos, p.N); put(gs.rank_to_node, p, B.rank, p.N);
-            put(gs.edge_head, p, B.head, p.E); put(gs.edge_weight, p, B.weight, p.E);
-            put(gs.aligned_a, p, B.al_a, p.P); put(gs.aligned_b, p, B.al_b, p.P);
-            put(gs.path_member, p, B.member, p.S); put(gs.path_reversed, p, B.rev, p.S); put(gs.path_node, p, B.p_node, p.T);
-            put(gs.cons_node, p, B.cons_node, p.Cn);
-            const uint32_t* oo = (const uint32_t*)(p.blk.data() + B.out_off);
-            for (uint32_t v = 0; v <= p.N; ++v) gs.out_off.push_back(e0 + oo[v]);
-            const uint32_t* po = (const uint32_t*)(p.blk.data() + B.p_off);
-            for (uint32_t k = 1; k <= p.S; ++k) gs.path_off.push_back(t0 + po[k]);
-            if (R.a.state) {                                               // the state table lies behind the block
-                const uint32_t* ao = (const uint32_t*)(p.blk.data() + B.bytes);
-                for (uint32_t v = 0; v <= p.N; ++v) ss.al_off.push_back(c0 + ao[v]);
-                put(ss.al_node, p, B.bytes + state_list_at(p.N), p.A);
+// ... and that copy: the blocks in front of dout into `host`, then block q into the bytes that part_of(q) names
+template <class Part>
+bool blocks_out(const void* dout, uint64_t blocks, const std::vector<uint64_t>& hoff, uint32_t nl, std::vector<uint8_t>& host, Part part_of) {
+    host.resize(blocks);
+    if (blocks && hipMemcpy(host.data(), dout, blocks, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (uint32_t q = 0; q < nl; ++q) part_of(q).assign(host.begin() + hoff[q], host.begin() + (q + 1 < nl ? hoff[q + 1] : blocks));
+    return true;
+}
+
+// The per-code profile of every consensus (vc_poa_profile_out): a block (counts, then codes) and a scratch per group in the matrix
+// buffer.  The groups' columns are k_lg_msa<0>'s, of the same lock_step.
+struct ProfileStage : Stage {
+    std::vector<uint32_t> n_codes, counts;
+    std::vector<uint64_t> code_off, prof_off;
+    std::vector<uint8_t> codes;
+    uint64_t bytes = 0;                                // copied out of the device
+    std::vector<std::vector<uint8_t>> blk;             // until assemble(), per window: its block and its code count
+    std::vector<uint32_t> nc_of;
+    uint64_t launches = 0;
+
+    void size(const Run& R) override { blk.resize(R.nw); nc_of.assign(R.nw, 0); }
+    int collect(Run& R, Group& G) override {
+        auto block_of = [&](uint32_t k) { return profile_block(G.hw[k].num_codes, G.hw[k].cons_n).bytes; };
+        auto scratch_of = [&](uint32_t k) { return profile_scratch(G.hw[k].gr[G.hw[k].cur].nseq, G.hw[k].gr_cols).bytes; };
+        uint64_t blocks = 0;
+        std::vector<uint8_t> host;
+        auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t, void* dout) -> int {
+            const uint32_t nl = (uint32_t)list.size();
+            f.msa_out = (uint8_t*)dout;
+            hipLaunchKernelGGL(k_lg_profile, dim3(nl), dim3(64), 0, 0, f);
+            auto part_of = [&](uint32_t q) -> std::vector<uint8_t>& {
+                const uint32_t w = G.ids[list[q]];
+                nc_of[w] = G.hw[list[q]].num_codes;
+                return blk[w];
+            };
+            if (hipGetLastError() != hipSuccess || !blocks_out(dout, blocks, hoff, nl, host, part_of))
+                return fail(VC_ERR_HIP, "the profile kernel or its copy failed");
+            bytes += blocks;
+            return VC_OK;
+        };
+        return launch_loop(R.a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
+                           {"device allocation of the profile blocks failed", "the profile kernel or its copy failed"}, launches,
+                           [&](uint32_t k) { return block_of(k) + scratch_of(k); },
+                           [&](const std::vector<uint32_t>& list, std::vector<uint64_t>& hoff) { blocks = blocks_first(list, hoff, block_of, scratch_of); },
+                           [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
+    }
+    // the tables in window order (a group that was not computed has no code and an empty block)
+    void assemble(const Run& R) override {
+        code_off.assign(1, 0);
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            const uint32_t nc = R.status[w] == VC_WIN_OK && !blk[w].empty() ? nc_of[w] : 0;
+            const uint64_t Cn = R.out[w].size();
+            n_codes.push_back(nc);
+            prof_off.push_back(counts.size());
+            if (nc) {
+                const uint32_t* c = (const uint32_t*)blk[w].data();
+                counts.insert(counts.end(), c, c + (uint64_t)(nc + 1) * Cn);
+                const uint8_t* cd = blk[w].data() + profile_block(nc, Cn).codes;
+                codes.insert(codes.end(), cd, cd + nc);
             }
-        } else {
-            gs.out_off.push_back(e0);      // a group without a block has no node and no path: its one out_off entry
-            if (R.a.state) ss.al_off.push_back(c0);
+            code_off.push_back(codes.size());
+            blk[w] = std::vector<uint8_t>{};
         }
-        gs.node_off.push_back(gs.node_base.size());
-        gs.aligned_off.push_back(gs.aligned_a.size());
-        gs.path_first.push_back(gs.path_member.size());
-        R.part[w] = GraphPart{};
+        if (R.kn.log) std::fprintf(stderr, "vc_large: profile launches=%llu bytes=%llu\n", (unsigned long long)launches, (unsigned long long)bytes);
     }
-    if (R.kn.log) std::fprintf(stderr, "vc_large: graph launches=%llu bytes=%llu\n", (unsigned long long)R.graph_launches, (unsigned long long)gs.bytes);
-    if (R.kn.log && R.a.state) std::fprintf(stderr, "vc_large: state bytes=%llu\n", (unsigned long long)ss.bytes);
-}
+    void publish(const PoaRequest& q, const vc_batch* b) override {
+        vc_poa_profile_out* po = q.profile;
+        if (!po) return;
+        po->n_groups = b->n_windows;
+        if (!b->n_windows) return;
+        po->n_codes = n_codes.data(); po->code_off = code_off.data(); po->codes = table(codes);
+        po->prof_off = prof_off.data(); po->counts = table(counts);
+    }
+};
+
+// The graph tables (vc_poa_graph_out) and, with a vc_poa_state_out, the state table beside them: a block and a scratch per group
+// in the matrix buffer; k_lg_graph<1> writes a group's state table behind its block, so the same copy takes it out.
+struct GraphStage : Stage {
+    std::vector<uint32_t> n_nodes, rank_to_node, edge_head, aligned_a, aligned_b, path_member, path_node, cons_node;
+    std::vector<uint64_t> node_off, out_off, aligned_off, path_first, path_off;
+    std::vector<uint8_t> node_base, path_reversed;
+    std::vector<int32_t> node_cons_pos;
+    std::vector<int64_t> edge_weight;
+    uint64_t bytes = 0;                                // copied out of the device
+    std::vector<uint64_t> al_off;                      // vc_poa_state_out
+    std::vector<uint32_t> al_node;
+    uint64_t state_copied = 0;                         // its bytes, which `bytes` does not count
+    // until assemble(), per window: its block of k_lg_graph<1> and the counts that lay it out (A: cells of the state table behind it)
+    struct Part { uint32_t N = 0, E = 0, P = 0, S = 0, T = 0, Cn = 0, A = 0; std::vector<uint8_t> blk; };
+    std::vector<Part> part;
+    uint64_t launches = 0;
+
+    void size(const Run& R) override { part.resize(R.nw); }
+    int collect(Run& R, Group& G) override {
+        const LArgs& a = R.a;
+        auto counts_of = [&](uint32_t k) {
+            const LWin& W = G.hw[k];
+            const LGraph& g = W.gr[W.cur];
+            Part p;
+            p.N = g.n_nodes; p.E = g.n_edges; p.P = g.n_al / 2; p.S = g.nseq; p.T = W.gr_path; p.Cn = W.cons_n; p.A = a.state ? g.n_al : 0;
+            return p;
+        };
+        auto state_of = [&](uint32_t k) { const Part p = counts_of(k); return a.state ? state_bytes(p.N, p.A) : 0; };
+        auto block_of = [&](uint32_t k) { const Part p = counts_of(k); return graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn).bytes + state_of(k); };
+        auto scratch_of = [&](uint32_t k) { return a.graph == 1 ? graph_scratch_bytes(G.hw[k].gr[G.hw[k].cur].nseq, G.hw[k].gr_cols) : 0; };
+        uint64_t blocks = 0;
+        std::vector<uint8_t> host;
+        auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t, void* dout) -> int {
+            const uint32_t nl = (uint32_t)list.size();
+            f.msa_out = (uint8_t*)dout;
+            hipLaunchKernelGGL(k_lg_graph<1>, dim3(nl), dim3(64), 0, 0, f);
+            auto part_of = [&](uint32_t q) -> std::vector<uint8_t>& {
+                Part& p = part[G.ids[list[q]]];
+                p = counts_of(list[q]);
+                return p.blk;
+            };
+            if (hipGetLastError() != hipSuccess || !blocks_out(dout, blocks, hoff, nl, host, part_of))
+                return fail(VC_ERR_HIP, "the graph kernel or its copy failed");
+            uint64_t st = 0;                                               // the state tables lie in the same copy: counted apart
+            for (const uint32_t k : list) st += state_of(k);
+            bytes += blocks - st;
+            state_copied += st;
+            return VC_OK;
+        };
+        return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
+                           {"device allocation of the graph tables failed", "the graph kernel or its copy failed"}, launches,
+                           [&](uint32_t k) { return block_of(k) + scratch_of(k); },
+                           [&](const std::vector<uint32_t>& list, std::vector<uint64_t>& hoff) { blocks = blocks_first(list, hoff, block_of, scratch_of); },
+                           [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
+    }
+    // the tables in window order, every offset rebased from its block to the batch
+    void assemble(const Run& R) override {
+        auto put = [](auto& dst, const Part& p, uint64_t at, uint64_t n) {
+            using T = typename std::remove_reference_t<decltype(dst)>::value_type;
+            const T* src = (const T*)(p.blk.data() + at);
+            dst.insert(dst.end(), src, src + n);
+        };
+        node_off.assign(1, 0); aligned_off.assign(1, 0); path_first.assign(1, 0); path_off.assign(1, 0);
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            if (R.status[w] != VC_WIN_OK) part[w] = Part{};
+            const Part& p = part[w];
+            const GraphBlock B = graph_block(p.N, p.E, p.P, p.S, p.T, p.Cn);
+            const uint64_t e0 = edge_head.size(), t0 = path_node.size(), c0 = al_node.size();
+            n_nodes.push_back(p.N);
+            if (!p.blk.empty()) {
+                put(node_base, p, B.base, p.N); put(node_cons_pos, p, B.cons_pos, p.N); put(rank_to_node, p, B.rank, p.N);
+                put(edge_head, p, B.head, p.E); put(edge_weight, p, B.weight, p.E);
+                put(aligned_a, p, B.al_a, p.P); put(aligned_b, p, B.al_b, p.P);
+                put(path_member, p, B.member, p.S); put(path_reversed, p, B.rev, p.S); put(path_node, p, B.p_node, p.T);
+                put(cons_node, p, B.cons_node, p.Cn);
+                const uint32_t* oo = (const uint32_t*)(p.blk.data() + B.out_off);
+                for (uint32_t v = 0; v <= p.N; ++v) out_off.push_back(e0 + oo[v]);
+                const uint32_t* po = (const uint32_t*)(p.blk.data() + B.p_off);
+                for (uint32_t k = 1; k <= p.S; ++k) path_off.push_back(t0 + po[k]);
+                if (R.a.state) {                                           // the state table lies behind the block
+                    const uint32_t* ao = (const uint32_t*)(p.blk.data() + B.bytes);
+                    for (uint32_t v = 0; v <= p.N; ++v) al_off.push_back(c0 + ao[v]);
+                    put(al_node, p, B.bytes + state_list_at(p.N), p.A);
+                }
+            } else {
+                out_off.push_back(e0);         // a group without a block has no node and no path: its one out_off entry
+                if (R.a.state) al_off.push_back(c0);
+            }
+            node_off.push_back(node_base.size());
+            aligned_off.push_back(aligned_a.size());
+            path_first.push_back(path_member.size());
+            part[w] = Part{};
+        }
+        if (R.kn.log) std::fprintf(stderr, "vc_large: graph launches=%llu bytes=%llu\n", (unsigned long long)launches, (unsigned long long)bytes);
+        if (R.kn.log && R.a.state) std::fprintf(stderr, "vc_large: state bytes=%llu\n", (unsigned long long)state_copied);
+    }
+    void publish(const PoaRequest& q, const vc_batch* b) override {
+        vc_poa_graph_out* go = q.graph;
+        if (!go) return;
+        go->n_groups = b->n_windows;
+        if (!b->n_windows) return;
+        go->n_nodes = table(n_nodes); go->node_off = node_off.data(); go->node_base = table(node_base);
+        go->node_cons_pos = table(node_cons_pos); go->rank_to_node = table(rank_to_node);
+        go->out_off = out_off.data(); go->edge_head = table(edge_head); go->edge_weight = table(edge_weight);
+        go->aligned_off = aligned_off.data(); go->aligned_a = table(aligned_a); go->aligned_b = table(aligned_b);
+        go->path_first = path_first.data(); go->path_member = table(path_member); go->path_reversed = table(path_reversed);
+        go->path_off = path_off.data(); go->path_node = table(path_node);
+        go->cons_node = table(cons_node);
+        go->bytes = bytes;
+        if (vc_poa_state_out* st = q.state) { st->al_off = al_off.data(); st->al_node = table(al_node); st->bytes = state_copied; }
+    }
+};
 
 template <uint32_t GM>
 void launch_query(const LArgs& f, uint32_t nl, uint32_t ns, bool pairs) {
@@ -956,237 +957,239 @@ void launch_query(const LArgs& f, uint32_t nl, uint32_t ns, bool pairs) {
     if (pairs) hipLaunchKernelGGL(k_lg_qback<GM>, dim3((nl + 63) / 64), dim3(64), 0, 0, f, nl);
 }
 
-// The query stage of the groups that finished, while their tables are resident (vc_poa_run_align): a job per query, the rows of
-// every finished graph once (k_lg_rows), the jobs' forward passes (and, with VC_POA_ALIGN_PAIRS, backtracks) in launches that fit
-// the matrix budget -- every (group, query) pair is independent, so a launch holds as many as fit --, the job table back in one
-// copy, then the pairs packed behind the host's prefix offsets and out in one copy.
-int collect_align(Run& R, Group& G) {
-    const LArgs& a = R.a;
-    const vc_batch* q = R.q.queries;
-    const bool pairs = R.q.query_pairs();
-    const uint32_t ns = R.q.query_strands();
-    Outputs::Align& S = g_out.align;
-    std::vector<LJob> jobs;
-    std::vector<uint32_t> act, refused;                                    // jobs with a forward pass; jobs whose matrix the device cannot hold
-    uint64_t area = 0;
-    for (const uint32_t k : finished(R, G)) {
-        const LWin& W = G.hw[k];
-        const uint32_t w = G.ids[k];
-        const LGraph& g = W.gr[W.cur];
-        const uint32_t N = g.n_nodes;
-        for (uint32_t s = q->win_seq_off[w]; s < q->win_seq_off[w + 1]; ++s) {
-            LJob J{};
-            J.win = k; J.qs = s; J.qlen = (uint32_t)(q->seq_off[s + 1] - q->seq_off[s]); J.status = VC_WIN_OK;
-            if (N != 0 && J.qlen != 0) {                                   // else an empty alignment, score 0
-                // the floor of k_lg_prep, and its check of the topological order
-                if (worst_case(a.match, a.gap, a.gap_e, a.gap_q, a.gap_c, (int64_t)J.qlen + 8, N) < (int64_t)KNEG || g.n_rank != N) {
-                    J.status = VC_WIN_INVALID;
-                } else {
-                    J.rows = N; J.area = area;
-                    if (pairs) area += (uint64_t)N + J.qlen;
-                    act.push_back((uint32_t)jobs.size());
+// The job stage behind align and correct: sequences aligned against the finished graph of their group, while its tables are
+// resident, and not added to it -- the group's queries (align) or its own members (correct).  Every (group, sequence) pair is a
+// job (LJob), independent of the others, so a launch holds as many as fit the matrix budget.  What a job hands back beside status
+// and scores is NP planes of T: the node and the position of every pair (align), the corrected bytes (correct).
+template <class T, uint32_t NP>
+struct JobStage : Stage {
+    // one entry per sequence of the source batch (score_rev and reversed: with both strands only); off: where its entries of every plane begin
+    std::vector<uint8_t> status, reversed;
+    std::vector<int32_t> score, score_rev;
+    std::vector<uint64_t> off;
+    std::vector<T> plane[NP];
+    uint64_t bytes = 0;                                // copied out of the device
+    // until assemble(): per collect() the packed planes one behind the other, per sequence which of them and where in a plane
+    std::vector<std::vector<T>> part;
+    std::vector<uint32_t> part_of, count;
+    std::vector<uint64_t> first;
+    uint64_t n_jobs = 0, launches = 0, n_cells = 0;    // the log line's counts
+
+    // What the two stages differ in.  The messages: allocation, k_lg_rows, a launch's kernels, launch_loop's two, the count kernel
+    // or the copy of the job table, the pack kernel or its copy; then the log line.
+    struct Kind {
+        LArgs a;                                       // the call's, with the source batch as the query batch
+        const vc_batch* src;                           // the jobs of group w: the sequences of src's window w
+        uint32_t ns;                                   // strands per job
+        bool pairs;                                    // the backtrack runs, and the planes are filled
+        uint32_t LJob::*n;                             // a job's entries per plane ...
+        void (*count)(const LArgs& a, uint32_t nj);    // ... and the kernel that counts them before the job table comes back (nullptr: none)
+        void (*pack)(LArgs a, T* d_out, uint32_t nj, uint64_t total);      // the kernel that packs every job's entries behind its pair_off
+        const char *no_jobs, *no_rows, *no_kernel;
+        StageErrors launch;
+        const char *no_count, *no_pack, *log;
+    };
+    virtual Kind kind(const Run& R) const = 0;
+
+    void size(const Run& R) override {
+        const Kind K = kind(R);
+        const uint64_t n = K.src->win_seq_off[R.nw];
+        status.assign(n, VC_WIN_OVERFLOW); score.assign(n, 0);
+        if (K.ns == 2) { score_rev.assign(n, 0); reversed.assign(n, 0); }
+        part_of.assign(n, 0); count.assign(n, 0); first.assign(n, 0);
+    }
+    // The rows of every finished graph once (k_lg_rows), the jobs' forward passes (and, with pairs, backtracks) in launches that fit
+    // the matrix budget, the entries counted, the job table back in one copy, then the entries packed behind the host's prefix
+    // offsets and out in one copy.  A job without a forward pass (an empty sequence or graph, the floor of k_lg_prep) never
+    // reaches the device; one whose matrix the device cannot hold is VC_WIN_OVERFLOW, and the others run.
+    int collect(Run& R, Group& G) override {
+        const Kind K = kind(R);
+        LArgs a = K.a;
+        std::vector<LJob> jobs;
+        std::vector<uint32_t> act, refused;                                // jobs with a forward pass; jobs whose matrix the device cannot hold
+        uint64_t area = 0;
+        for (const uint32_t k : finished(R, G)) {
+            const LWin& W = G.hw[k];
+            const uint32_t w = G.ids[k];
+            const LGraph& g = W.gr[W.cur];
+            const uint32_t N = g.n_nodes;
+            for (uint32_t s = K.src->win_seq_off[w]; s < K.src->win_seq_off[w + 1]; ++s) {
+                LJob J{};
+                J.win = k; J.qs = s; J.qlen = (uint32_t)(K.src->seq_off[s + 1] - K.src->seq_off[s]); J.status = VC_WIN_OK;
+                if (N != 0 && J.qlen != 0) {                               // else an empty alignment, score 0
+                    // the floor of k_lg_prep, and its check of the topological order
+                    if (worst_case(a.match, a.gap, a.gap_e, a.gap_q, a.gap_c, (int64_t)J.qlen + 8, N) < (int64_t)KNEG || g.n_rank != N) {
+                        J.status = VC_WIN_INVALID;
+                    } else {
+                        J.rows = N; J.area = area;
+                        if (K.pairs) area += (uint64_t)N + J.qlen;
+                        act.push_back((uint32_t)jobs.size());
+                    }
                 }
+                jobs.push_back(J);
             }
-            jobs.push_back(J);
         }
-    }
-    if (jobs.empty()) return VC_OK;
-    R.q_jobs += jobs.size();
-    uint64_t total = 0;
-    std::vector<int32_t> packed;
-    if (!act.empty()) {
-        DevMem mem;
-        LJob* d_job = nullptr; uint32_t* d_list = nullptr; uint64_t* d_hoff = nullptr; int32_t *d_pairs = nullptr, *d_out = nullptr;
-        if (!mem.alloc(&d_job, jobs.size(), jobs.data()) || !mem.alloc(&d_list, act.size()) || !mem.alloc(&d_hoff, act.size()) ||
-            (pairs && !mem.alloc(&d_pairs, 2 * area)))
-            return fail(VC_ERR_HIP, "device allocation of the query jobs failed");
-        const uint32_t n = (uint32_t)G.ids.size();
-        hipLaunchKernelGGL(k_lg_rows, dim3((n + 63) / 64), dim3(64), 0, 0, a);
-        if (hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "the query stage's row kernel failed");
-        auto matrix_cells = [&](uint32_t j) { return ((uint64_t)jobs[j].rows + 1) * ((uint64_t)jobs[j].qlen + 1) * R.planes * ns; };
-        auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>&, uint64_t, void* H) -> int {
-            const uint32_t nl = (uint32_t)list.size();
-            f.job = d_job; f.q_pairs = d_pairs; f.H = (int32_t*)H;
-            if (f.gaps == 0) launch_query<0>(f, nl, ns, pairs);
-            else if (f.gaps == 1) launch_query<1>(f, nl, ns, pairs);
-            else launch_query<2>(f, nl, ns, pairs);
-            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, "a query kernel failed");
-            for (const uint32_t j : list) R.q_cells += (uint64_t)jobs[j].rows * jobs[j].qlen * ns;
-            return VC_OK;
-        };
-        if (const int rc = launch_loop(a, act, R.mat_budget / 4, 4, d_list, d_hoff,
-                                       {"device allocation of the query matrices failed", "copy of a query launch failed"}, R.q_launches,
-                                       matrix_cells, as_packed, [&](uint32_t j) { refused.push_back(j); return VC_OK; }, body))
-            return rc;
-        if (hipMemcpy(jobs.data(), d_job, jobs.size() * sizeof(LJob), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(VC_ERR_HIP, "copy of the query jobs failed");
-        S.bytes += jobs.size() * sizeof(LJob);
-        for (LJob& J : jobs) { J.pair_off = total; total += J.npairs; }
-        if (total) {
-            packed.resize(2 * total);
-            LArgs f = a;
-            f.job = d_job; f.q_pairs = d_pairs;
-            bool ok = mem.alloc(&d_out, 2 * total) && hipMemcpy(d_job, jobs.data(), jobs.size() * sizeof(LJob), hipMemcpyHostToDevice) == hipSuccess;
-            if (ok) {
-                f.q_out = d_out;
-                hipLaunchKernelGGL(k_lg_qpack, dim3((uint32_t)jobs.size()), dim3(64), 0, 0, f, total);
-                ok = hipGetLastError() == hipSuccess && hipMemcpy(packed.data(), d_out, 8 * total, hipMemcpyDeviceToHost) == hipSuccess;
+        if (jobs.empty()) return VC_OK;
+        n_jobs += jobs.size();
+        std::vector<T> packed;
+        if (!act.empty()) {
+            DevMem mem;
+            LJob* d_job = nullptr; uint32_t* d_list = nullptr; uint64_t* d_hoff = nullptr; int32_t* d_pairs = nullptr; T* d_out = nullptr;
+            if (!mem.alloc(&d_job, jobs.size(), jobs.data()) || !mem.alloc(&d_list, act.size()) || !mem.alloc(&d_hoff, act.size()) ||
+                (K.pairs && !mem.alloc(&d_pairs, 2 * area)))
+                return fail(VC_ERR_HIP, K.no_jobs);
+            a.job = d_job; a.q_pairs = d_pairs;
+            const uint32_t n = (uint32_t)G.ids.size(), nj = (uint32_t)jobs.size();
+            hipLaunchKernelGGL(k_lg_rows, dim3((n + 63) / 64), dim3(64), 0, 0, a);
+            if (hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, K.no_rows);
+            auto matrix_cells = [&](uint32_t j) { return ((uint64_t)jobs[j].rows + 1) * ((uint64_t)jobs[j].qlen + 1) * R.planes * K.ns; };
+            auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>&, uint64_t, void* H) -> int {
+                const uint32_t nl = (uint32_t)list.size();
+                f.H = (int32_t*)H;
+                with_gap_model(f.gaps, [&](auto gm) { launch_query<decltype(gm)::value>(f, nl, K.ns, K.pairs); });
+                if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, K.no_kernel);
+                for (const uint32_t j : list) n_cells += (uint64_t)jobs[j].rows * jobs[j].qlen * K.ns;
+                return VC_OK;
+            };
+            if (const int rc = launch_loop(a, act, R.mat_budget / 4, 4, d_list, d_hoff, K.launch, launches, matrix_cells, as_packed,
+                                           [&](uint32_t j) { refused.push_back(j); return VC_OK; }, body))
+                return rc;
+            if (K.count) {
+                K.count(a, nj);
+                if (hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, K.no_count);
             }
-            if (!ok) return fail(VC_ERR_HIP, "the pack kernel of the query stage or its copy failed");
-            S.bytes += 8 * total;
-        }
-    }
-    for (const uint32_t j : refused) jobs[j].status = VC_WIN_OVERFLOW;
-    const uint32_t pi = (uint32_t)R.q_part.size();
-    for (const LJob& J : jobs) {
-        const bool ok = J.status == VC_WIN_OK;
-        S.status[J.qs] = (uint8_t)J.status;
-        S.score[J.qs] = ok ? J.score[0] : 0;
-        if (ns == 2) { S.score_rev[J.qs] = ok ? J.score[1] : 0; S.reversed[J.qs] = ok && J.score[0] < J.score[1]; }
-        R.q_part_of[J.qs] = pi; R.q_first[J.qs] = J.pair_off; R.q_count[J.qs] = ok ? J.npairs : 0;
-    }
-    R.q_part.push_back(std::move(packed));
-    return VC_OK;
-}
-
-// the queries in batch order (a group that was not computed passes its status on), and the stage's log line
-void assemble_align(Run& R) {
-    Outputs::Align& S = g_out.align;
-    const vc_batch* q = R.q.queries;
-    const bool pairs = R.q.query_pairs();
-    if (pairs) S.pair_off.assign(R.q.nq + 1, 0);
-    for (uint32_t w = 0; w < R.nw; ++w) {
-        for (uint32_t s = q->win_seq_off[w]; s < q->win_seq_off[w + 1]; ++s) {
-            if (R.status[w] != VC_WIN_OK) {
-                S.status[s] = R.status[w]; S.score[s] = 0; R.q_count[s] = 0;
-                if (!S.score_rev.empty()) { S.score_rev[s] = 0; S.reversed[s] = 0; }
-            }
-            if (!pairs) continue;
-            if (R.q_count[s]) {
-                const std::vector<int32_t>& part = R.q_part[R.q_part_of[s]];
-                const int32_t* node = part.data() + R.q_first[s];
-                const int32_t* pos = node + part.size() / 2;
-                S.pair_node.insert(S.pair_node.end(), node, node + R.q_count[s]);
-                S.pair_pos.insert(S.pair_pos.end(), pos, pos + R.q_count[s]);
-            }
-            S.pair_off[s + 1] = S.pair_node.size();
-        }
-    }
-    R.q_part.clear();
-    if (R.kn.log) std::fprintf(stderr, "vc_large: align jobs=%llu launches=%llu cells=%llu bytes=%llu\n", (unsigned long long)R.q_jobs,
-                               (unsigned long long)R.q_launches, (unsigned long long)R.q_cells, (unsigned long long)S.bytes);
-}
-
-// The correction stage of the groups that finished, while their tables are resident (vc_poa_run_correct): collect_align's shape
-// with a job per member -- the rows of every final graph once (k_lg_rows), the members' local forward passes and backtracks in
-// launches that fit the matrix budget (a group's members are independent now: nothing is added), the pairs with a node counted
-// (k_lg_correct<0>), the job table back in one copy, the host's prefix offsets, then the bytes compact (k_lg_correct<1>) and out
-// in one copy.
-int collect_correct(Run& R, Group& G) {
-    const vc_batch* b = R.b;
-    Outputs::Correct& S = g_out.correct;
-    LArgs a = R.a;
-    a.algorithm = 0;                                                       // kSW with the call's scores and gap model
-    a.q_off = a.seq_off; a.q_bases = a.bases; a.q_rc = nullptr;            // the "query batch": the group batch's own arrays
-    std::vector<LJob> jobs;
-    std::vector<uint32_t> act, refused;                                    // jobs with a forward pass; jobs whose matrix the device cannot hold
-    uint64_t area = 0;
-    for (const uint32_t k : finished(R, G)) {
-        const LWin& W = G.hw[k];
-        const LGraph& g = W.gr[W.cur];
-        const uint32_t N = g.n_nodes;
-        for (uint32_t s = W.s0; s < W.s0 + W.nseq; ++s) {
-            LJob J{};
-            J.win = k; J.qs = s; J.qlen = (uint32_t)(b->seq_off[s + 1] - b->seq_off[s]); J.status = VC_WIN_OK;
-            if (N != 0 && J.qlen != 0) {                                   // else an empty alignment: the empty correction, score 0
-                if (worst_case(a.match, a.gap, a.gap_e, a.gap_q, a.gap_c, (int64_t)J.qlen + 8, N) < (int64_t)KNEG || g.n_rank != N) {
-                    J.status = VC_WIN_INVALID;
-                } else {
-                    J.rows = N; J.area = area;
-                    area += (uint64_t)N + J.qlen;
-                    act.push_back((uint32_t)jobs.size());
+            if (hipMemcpy(jobs.data(), d_job, jobs.size() * sizeof(LJob), hipMemcpyDeviceToHost) != hipSuccess) return fail(VC_ERR_HIP, K.no_count);
+            bytes += jobs.size() * sizeof(LJob);
+            uint64_t total = 0;
+            for (LJob& J : jobs) { J.pair_off = total; total += J.*K.n; }
+            if (total) {
+                packed.resize(NP * total);
+                bool ok = mem.alloc(&d_out, NP * total) && hipMemcpy(d_job, jobs.data(), jobs.size() * sizeof(LJob), hipMemcpyHostToDevice) == hipSuccess;
+                if (ok) {
+                    K.pack(a, d_out, nj, total);
+                    ok = hipGetLastError() == hipSuccess && hipMemcpy(packed.data(), d_out, NP * total * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
                 }
+                if (!ok) return fail(VC_ERR_HIP, K.no_pack);
+                bytes += NP * total * sizeof(T);
             }
-            jobs.push_back(J);
         }
+        for (const uint32_t j : refused) jobs[j].status = VC_WIN_OVERFLOW;
+        const uint32_t pi = (uint32_t)part.size();
+        for (const LJob& J : jobs) {
+            const bool ok = J.status == VC_WIN_OK;
+            status[J.qs] = (uint8_t)J.status;
+            score[J.qs] = ok ? J.score[0] : 0;
+            if (K.ns == 2) { score_rev[J.qs] = ok ? J.score[1] : 0; reversed[J.qs] = ok && J.score[0] < J.score[1]; }
+            part_of[J.qs] = pi; first[J.qs] = J.pair_off; count[J.qs] = ok ? J.*K.n : 0;
+        }
+        part.push_back(std::move(packed));
+        return VC_OK;
     }
-    if (jobs.empty()) return VC_OK;
-    R.c_jobs += jobs.size();
-    uint64_t total = 0;
-    std::vector<uint8_t> bytes;
-    if (!act.empty()) {
-        DevMem mem;
-        LJob* d_job = nullptr; uint32_t* d_list = nullptr; uint64_t* d_hoff = nullptr; int32_t* d_pairs = nullptr; uint8_t* d_out = nullptr;
-        if (!mem.alloc(&d_job, jobs.size(), jobs.data()) || !mem.alloc(&d_list, act.size()) || !mem.alloc(&d_hoff, act.size()) ||
-            !mem.alloc(&d_pairs, 2 * area))
-            return fail(VC_ERR_HIP, "device allocation of the correction jobs failed");
-        a.job = d_job; a.q_pairs = d_pairs;
-        const uint32_t n = (uint32_t)G.ids.size(), nj = (uint32_t)jobs.size();
-        hipLaunchKernelGGL(k_lg_rows, dim3((n + 63) / 64), dim3(64), 0, 0, a);
-        if (hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "the correction stage's row kernel failed");
-        auto matrix_cells = [&](uint32_t j) { return ((uint64_t)jobs[j].rows + 1) * ((uint64_t)jobs[j].qlen + 1) * R.planes; };
-        auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>&, uint64_t, void* H) -> int {
-            const uint32_t nl = (uint32_t)list.size();
-            f.H = (int32_t*)H;
-            if (f.gaps == 0) launch_query<0>(f, nl, 1, true);
-            else if (f.gaps == 1) launch_query<1>(f, nl, 1, true);
-            else launch_query<2>(f, nl, 1, true);
-            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, "a correction kernel failed");
-            for (const uint32_t j : list) R.c_cells += (uint64_t)jobs[j].rows * jobs[j].qlen;
-            return VC_OK;
-        };
-        if (const int rc = launch_loop(a, act, R.mat_budget / 4, 4, d_list, d_hoff,
-                                       {"device allocation of the correction matrices failed", "copy of a correction launch failed"}, R.c_launches,
-                                       matrix_cells, as_packed, [&](uint32_t j) { refused.push_back(j); return VC_OK; }, body))
-            return rc;
-        hipLaunchKernelGGL(k_lg_correct<0>, dim3(nj), dim3(64), 0, 0, a);
-        if (hipGetLastError() != hipSuccess || hipMemcpy(jobs.data(), d_job, jobs.size() * sizeof(LJob), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(VC_ERR_HIP, "the count kernel of the correction stage or the copy of its jobs failed");
-        S.bytes += jobs.size() * sizeof(LJob);
-        for (LJob& J : jobs) { J.pair_off = total; total += J.ncorr; }
-        if (total) {
-            bytes.resize(total);
-            bool ok = mem.alloc(&d_out, total) && hipMemcpy(d_job, jobs.data(), jobs.size() * sizeof(LJob), hipMemcpyHostToDevice) == hipSuccess;
-            if (ok) {
-                a.msa_out = d_out;
-                hipLaunchKernelGGL(k_lg_correct<1>, dim3(nj), dim3(64), 0, 0, a);
-                ok = hipGetLastError() == hipSuccess && hipMemcpy(bytes.data(), d_out, total, hipMemcpyDeviceToHost) == hipSuccess;
+    // the sequences in batch order (a group that was not computed passes its status on)
+    void assemble(const Run& R) override {
+        const Kind K = kind(R);
+        if (K.pairs) off.assign(K.src->win_seq_off[R.nw] + 1, 0);
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            for (uint32_t s = K.src->win_seq_off[w]; s < K.src->win_seq_off[w + 1]; ++s) {
+                if (R.status[w] != VC_WIN_OK) {
+                    status[s] = R.status[w]; score[s] = 0; count[s] = 0;
+                    if (!score_rev.empty()) { score_rev[s] = 0; reversed[s] = 0; }
+                }
+                if (!K.pairs) continue;
+                if (count[s]) {
+                    const std::vector<T>& p = part[part_of[s]];
+                    for (uint32_t x = 0; x < NP; ++x) {
+                        const T* src = p.data() + x * (p.size() / NP) + first[s];
+                        plane[x].insert(plane[x].end(), src, src + count[s]);
+                    }
+                }
+                off[s + 1] = plane[0].size();
             }
-            if (!ok) return fail(VC_ERR_HIP, "the correction kernel or its copy failed");
-            S.bytes += total;
         }
+        part.clear();
+        if (R.kn.log) std::fprintf(stderr, K.log, (unsigned long long)n_jobs, (unsigned long long)launches, (unsigned long long)n_cells, (unsigned long long)bytes);
     }
-    for (const uint32_t j : refused) jobs[j].status = VC_WIN_OVERFLOW;
-    const uint32_t pi = (uint32_t)R.c_part.size();
-    for (const LJob& J : jobs) {
-        const bool ok = J.status == VC_WIN_OK;
-        S.status[J.qs] = (uint8_t)J.status;
-        S.score[J.qs] = ok ? J.score[0] : 0;
-        R.c_part_of[J.qs] = pi; R.c_first[J.qs] = J.pair_off; R.c_count[J.qs] = ok ? J.ncorr : 0;
-    }
-    R.c_part.push_back(std::move(bytes));
-    return VC_OK;
-}
+};
 
-// the corrected members in batch order (a group that was not computed passes its status on), and the stage's log line
-void assemble_correct(Run& R) {
-    Outputs::Correct& S = g_out.correct;
-    const vc_batch* b = R.b;
-    S.corr_off.assign(R.nseq_all + 1, 0);
-    for (uint32_t w = 0; w < R.nw; ++w) {
-        for (uint32_t s = b->win_seq_off[w]; s < b->win_seq_off[w + 1]; ++s) {
-            if (R.status[w] != VC_WIN_OK) { S.status[s] = R.status[w]; S.score[s] = 0; R.c_count[s] = 0; }
-            if (R.c_count[s]) {
-                const uint8_t* src = R.c_part[R.c_part_of[s]].data() + R.c_first[s];
-                S.corr.insert(S.corr.end(), src, src + R.c_count[s]);
-            }
-            S.corr_off[s + 1] = S.corr.size();
-        }
+// vc_poa_run_align (spoa's engine->Align(sequence, graph, &score) for sequences that are NOT added): a job per query of the
+// group, the call's engine and the align flags' strands and pairs; the planes are pair_node and pair_pos (k_lg_qpack).
+struct AlignStage : JobStage<int32_t, 2> {
+    Kind kind(const Run& R) const override {
+        return {R.a, R.q.queries, R.q.query_strands(), R.q.query_pairs(), &LJob::npairs, nullptr,
+                [](LArgs a, int32_t* d_out, uint32_t nj, uint64_t total) {
+                    a.q_out = d_out;
+                    hipLaunchKernelGGL(k_lg_qpack, dim3(nj), dim3(64), 0, 0, a, total);
+                },
+                "device allocation of the query jobs failed", "the query stage's row kernel failed", "a query kernel failed",
+                {"device allocation of the query matrices failed", "copy of a query launch failed"},
+                "copy of the query jobs failed", "the pack kernel of the query stage or its copy failed",
+                "vc_large: align jobs=%llu launches=%llu cells=%llu bytes=%llu\n"};
     }
-    R.c_part.clear();
-    if (R.kn.log) std::fprintf(stderr, "vc_large: correct jobs=%llu launches=%llu cells=%llu bytes=%llu\n", (unsigned long long)R.c_jobs,
-                               (unsigned long long)R.c_launches, (unsigned long long)R.c_cells, (unsigned long long)S.bytes);
-}
+    void publish(const PoaRequest& q, const vc_batch*) override {
+        vc_poa_align_out* ao = q.align;
+        if (!ao) return;
+        ao->n_queries = q.nq;
+        if (!q.has_queries() && q.query_pairs()) off.assign(1, 0);         // no stage ran: the empty tables
+        ao->status = table(status); ao->score = table(score);
+        if (q.query_strands() == 2) { ao->score_rev = table(score_rev); ao->reversed = table(reversed); }
+        if (q.query_pairs()) { ao->pair_off = off.data(); ao->pair_node = table(plane[0]); ao->pair_pos = table(plane[1]); }
+        ao->bytes = bytes;
+    }
+};
+
+// vc_poa_run_correct (GenerateCorrectedSequence of a final local alignment): a job per member of the group, so the "query batch"
+// is the group batch itself; kSW with the call's scores and gap model, one strand, always pairs; the pairs with a node are
+// counted (k_lg_correct<0>) and the one plane is their nodes' bytes (k_lg_correct<1>, which writes to msa_out).
+struct CorrectStage : JobStage<uint8_t, 1> {
+    Kind kind(const Run& R) const override {
+        LArgs a = R.a;
+        a.algorithm = 0;
+        a.q_off = a.seq_off; a.q_bases = a.bases; a.q_rc = nullptr;
+        return {a, R.b, 1, true, &LJob::ncorr,
+                [](const LArgs& a, uint32_t nj) { hipLaunchKernelGGL(k_lg_correct<0>, dim3(nj), dim3(64), 0, 0, a); },
+                [](LArgs a, uint8_t* d_out, uint32_t nj, uint64_t) {
+                    a.msa_out = d_out;
+                    hipLaunchKernelGGL(k_lg_correct<1>, dim3(nj), dim3(64), 0, 0, a);
+                },
+                "device allocation of the correction jobs failed", "the correction stage's row kernel failed", "a correction kernel failed",
+                {"device allocation of the correction matrices failed", "copy of a correction launch failed"},
+                "the count kernel of the correction stage or the copy of its jobs failed", "the correction kernel or its copy failed",
+                "vc_large: correct jobs=%llu launches=%llu cells=%llu bytes=%llu\n"};
+    }
+    void publish(const PoaRequest& q, const vc_batch* b) override {
+        vc_poa_correct_out* co = q.correct;
+        if (!co) return;
+        const uint64_t nseq = b->n_windows ? b->win_seq_off[b->n_windows] : 0;
+        if (off.empty()) off.assign(nseq + 1, 0);                          // no run: the empty tables
+        co->n_seqs = nseq;
+        co->status = table(status); co->score = table(score); co->corr_off = off.data(); co->corr = table(plane[0]);
+        co->bytes = bytes;
+    }
+};
+
+// The stages of the process, and with them what the vc_poa_* entries hand out: valid until the next call that has an output of
+// its own (poa_run clears them then, and when such a call fails) or vc_large_release.
+struct Outputs {
+    MsaStage msa;
+    ProfileStage profile;
+    GraphStage graph;
+    CorrectStage correct;
+    AlignStage align;
+    // The stages that run in a call, in the order run_group collects and run_windows assembles them.  Correct stands before
+    // align as run_group always had them, align before correct in run_windows: one order serves both, because the two never
+    // occur in one call (only vc_poa_run_correct asks for correction, and it takes no query batch).
+    std::vector<Stage*> active(const PoaRequest& q) {
+        std::vector<Stage*> s;
+        if (q.rows()) s.push_back(&msa);
+        if (q.profile) s.push_back(&profile);
+        if (q.graph) s.push_back(&graph);
+        if (q.correct) s.push_back(&correct);
+        if (q.has_queries()) s.push_back(&align);
+        return s;
+    }
+    std::vector<Stage*> all() { return {&msa, &profile, &graph, &correct, &align}; }
+    void clear() { *this = Outputs{}; }
+} g_out;
 
 // One group from its tables to its results: a window whose table filled goes back to pending, the others leave their status,
 // consensus and outputs.  A single window the device has no room for is VC_WIN_OVERFLOW; more than one is an error.
@@ -1210,11 +1213,8 @@ int run_group(Run& R, Group& G) {
         if (!R.out[w].empty() && hipMemcpy(R.out[w].data(), W.cons, W.cons_n, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(VC_ERR_HIP, "copy of a consensus failed");
     }
-    if (R.q.rows()) if (const int rc = collect_msa(R, G)) return rc;
-    if (R.q.profile) if (const int rc = collect_profile(R, G)) return rc;
-    if (R.q.graph) if (const int rc = collect_graph(R, G)) return rc;
-    if (R.q.correct) if (const int rc = collect_correct(R, G)) return rc;
-    return R.q.has_queries() ? collect_align(R, G) : VC_OK;
+    for (Stage* s : R.stages) if (const int rc = s->collect(R, G)) return rc;
+    return VC_OK;
 }
 
 // vc_poa_run_strand: the choices; zeros for the groups that were not computed
@@ -1280,18 +1280,7 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     }
     if (q.strand) if (const int rc = strand_views(R, mem)) return rc;
     if (q.from) if (const int rc = upload_stored(R, mem)) return rc;
-    if (q.has_queries()) {
-        if (const int rc = upload_queries(R, mem)) return rc;
-        Outputs::Align& S = g_out.align;
-        S.status.assign(q.nq, VC_WIN_OVERFLOW); S.score.assign(q.nq, 0);
-        if (q.query_strands() == 2) { S.score_rev.assign(q.nq, 0); S.reversed.assign(q.nq, 0); }
-        R.q_part_of.assign(q.nq, 0); R.q_count.assign(q.nq, 0); R.q_first.assign(q.nq, 0);
-    }
-    if (q.correct) {
-        Outputs::Correct& S = g_out.correct;
-        S.status.assign(R.nseq_all, VC_WIN_OVERFLOW); S.score.assign(R.nseq_all, 0);
-        R.c_part_of.assign(R.nseq_all, 0); R.c_count.assign(R.nseq_all, 0); R.c_first.assign(R.nseq_all, 0);
-    }
+    if (q.has_queries()) if (const int rc = upload_queries(R, mem)) return rc;
 
     // budgets from free device memory (what this library keeps cached counts as free)
     size_t free_b = 0, total_b = 0;
@@ -1299,18 +1288,13 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     const uint64_t avail = free_b + g_cache.arena.bytes + g_cache.mat.bytes;
     R.arena_budget = kn.arena ? kn.arena : std::min<uint64_t>(avail / 4, 16ull << 30);
     R.mat_budget = kn.mat ? kn.mat : std::min<uint64_t>(avail / 2, 48ull << 30);
-    if (q.graph) R.part.resize(nw);
-    if (q.profile) { R.prof_of.resize(nw); R.prof_nc.assign(nw, 0); }
     R.planes = plane_count(a.gaps);
     R.ns = q.strands();
 
     R.out.resize(nw);
     R.status.assign(nw, VC_WIN_OVERFLOW);
-    if (q.rows()) {
-        Outputs::Msa& msa = g_out.msa;
-        R.mem_of.resize(nw); R.cov_of.resize(nw);
-        msa.n_rows.assign(nw, 0); msa.row_size.assign(nw, 0); msa.row_off.assign(nw, 0); msa.member_off.assign(nw + 1, 0);
-    }
+    R.stages = g_out.active(q);
+    for (Stage* s : R.stages) s->size(R);
     R.pending.resize(nw);
     for (uint32_t w = 0; w < nw; ++w) R.pending[w] = w;
     while (!R.pending.empty()) {
@@ -1320,11 +1304,7 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
         if (const int rc = run_group(R, G)) return rc;
     }
     if (q.strand) if (const int rc = copy_strands(R)) return rc;
-    if (q.rows()) assemble_msa(R);
-    if (q.profile) assemble_profile(R);
-    if (q.graph) assemble_graph(R);
-    if (q.has_queries()) assemble_align(R);
-    if (q.correct) assemble_correct(R);
+    for (Stage* s : R.stages) s->assemble(R);
     return assemble(R, r);
 }
 
@@ -1621,20 +1601,14 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     const int rc = run_groups(p->device, p->algorithm, a, b, r, q);
     if (rc != VC_OK && owns) g_out.clear();
     if (rc != VC_OK) return rc;
-    if (q.required & PoaRequest::ALIGN) g_out.align.publish(q.align, q);
-    if (q.required & PoaRequest::CORRECT) g_out.correct.publish(q.correct, b->n_windows ? b->win_seq_off[b->n_windows] : 0);
-    if (q.graph) {
-        q.graph->n_groups = b->n_windows;
-        if (b->n_windows) g_out.graph.publish(q.graph);
-        if (q.state && b->n_windows) g_out.state.publish(q.state);
-    }
-    if (q.profile) {
-        q.profile->n_groups = b->n_windows;
-        if (b->n_windows) g_out.profile.publish(q.profile);
-    }
-    if (o) o->n_groups = b->n_windows;
-    if (q.rows() && b->n_windows) g_out.msa.publish(o);
+    for (Stage* s : g_out.all()) s->publish(q, b);                         // every stage whose out-struct the call has, run or not
     return VC_OK;
+}
+
+// PoaRequest::required of the entries that add an input to another entry's call (vc_poa_run_from, _spans, _weighted): the entry
+// the call would be without it -- the first of vc_poa_run_align, _graph, _strand, _msa, _gaps that it needs
+uint32_t base_entry(const vc_batch* queries, const vc_poa_graph_out* g, const vc_poa_strand_out* s, const vc_poa_msa_out* o) {
+    return queries ? PoaRequest::ALIGN : g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0u;
 }
 
 }  // namespace
@@ -1718,25 +1692,21 @@ int vc_poa_run_from(const vc_poa_gap_params* p, const vc_poa_graph_in* from, con
     if (st) *st = vc_poa_state_out{};                                      // a failed call leaves every pointer NULL
     if ((q == nullptr) != (a == nullptr)) return fail(VC_ERR_ARG, "the query batch and the align output go together");
     if (st && !g) return fail(VC_ERR_ARG, "the state output needs the graph output");
-    // the entry the call would be without `from` and `st`: the first of vc_poa_run_align, _graph, _strand, _msa, _gaps it needs
-    const uint32_t required = q ? PoaRequest::ALIGN : g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0;
-    PoaRequest rq{required, o, s, g, q, a};
+    PoaRequest rq{base_entry(q, g, s, o), o, s, g, q, a};
     rq.from = from; rq.state = st;
     return poa_run(p, b, r, rq);
 }
 
 int vc_poa_run_spans(const vc_poa_gap_params* p, const vc_poa_span_in* spans, const vc_batch* b, vc_result* r, vc_poa_msa_out* o,
                      vc_poa_strand_out* s, vc_poa_graph_out* g) {
-    // the entry the call would be without `spans`: the first of vc_poa_run_graph, _strand, _msa, _gaps it needs
-    PoaRequest rq{g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0u, o, s, g};
+    PoaRequest rq{base_entry(nullptr, g, s, o), o, s, g};
     rq.spans = spans;
     return poa_run(p, b, r, rq);
 }
 
 int vc_poa_run_weighted(const vc_poa_gap_params* p, const vc_poa_weight_in* w, const vc_batch* b, vc_result* r, vc_poa_msa_out* o,
                         vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_profile_out* prof) {
-    // the entry the call would be without `w` and `prof`: the first of vc_poa_run_graph, _strand, _msa, _gaps it needs
-    PoaRequest rq{g ? PoaRequest::GRAPH : s ? PoaRequest::STRAND : o ? PoaRequest::MSA : 0u, o, s, g};
+    PoaRequest rq{base_entry(nullptr, g, s, o), o, s, g};
     rq.weights = w; rq.profile = prof;
     return poa_run(p, b, r, rq);
 }
