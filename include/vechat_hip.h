@@ -40,7 +40,7 @@
  *   VC_HOSTBUF=0|1|2       host buffers: malloc / mmap + huge pages (default) / mmap; read once per process (tools/gpu_files_host.sh)
  * Read on every vc_large_run and vc_poa_run call (vc_large.hip, whose header describes them; tests/test_large_schedule.py):
  *   VC_LARGE_CAPS, VC_LARGE_ARENA_MB, VC_LARGE_MAT_MB, VC_LARGE_LOG (its lines: regrow, group, step, refuse, msa, graph, and for
- *   vc_poa_run_align with queries "vc_large: align jobs=J launches=K cells=C bytes=B"; done), VC_LARGE_GRAPH_WALK
+ *   vc_poa_run_align with queries "vc_large: align jobs=J launches=K cells=C bytes=B", for vc_poa_run_assign "vc_large: assign ..."; done), VC_LARGE_GRAPH_WALK
  * Read on every vc_align call (vc_align.hip, whose header describes them; test knobs of tests/test_align.py):
  *   VC_ALIGN_BUDGET_MB=x   the chunk budget in MiB instead of half of the free device memory
  *   VC_ALIGN_MAX_MAT_MB=x  the envelope in MiB instead of a third of the device memory: an overlap whose stored matrix is larger
@@ -683,6 +683,55 @@ typedef struct vc_poa_graph_in {           /* caller-owned: the arrays of a vc_p
 int         vc_poa_run_from(const vc_poa_gap_params* p, const vc_poa_graph_in* from /* NULL: from nothing */, const vc_batch* b,
                             vc_result* r, vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_state_out* st,
                             const vc_batch* q, vc_poa_align_out* a);
+
+/* Queries assigned to groups: `engine->Align(sequence, graph, &score)` for every query against EVERY group, and per query the
+ * best and the second group by score -- the family a read belongs to, and how far ahead of the runner-up it is.  With
+ * vc_poa_run_align a caller has to copy every query into every group and reduce on the host, and every copy stores a full
+ * matrix that nothing reads; here a pair costs a ring of the graph's live rows and the reduction runs on the device.
+ * The groups are built as vc_poa_run_from builds them with the same p, from and b (from == NULL: from nothing, as
+ * vc_poa_run_gaps), and r comes back as that call returns it.  Every sequence of q is a query against every group: of q only
+ * the sequence count (win_seq_off[n_windows]; 0 when n_windows is 0), seq_off and bases are read, and its window boundaries
+ * mean nothing.  a->flags selects:
+ *     VC_POA_ASSIGN_STRANDS  every query as given and reverse-complemented, the rule of VC_POA_ALIGN_STRANDS (main.cpp:287-304:
+ *                            score >= score_rev keeps the query as given), and the kept strand's score is the pair's score
+ *     VC_POA_ASSIGN_SCORES   also the dense table: one score and one status per (query, group), query-major
+ * The score, the strand choice and the status of pair (k, w) are exactly what vc_poa_run_align without VC_POA_ALIGN_PAIRS
+ * reports for query k placed in group w: the empty query and the local alignment without a positive cell score 0; where
+ * WorstCaseAlignmentScore makes spoa throw the pair is VC_WIN_INVALID; a pair whose rows the device cannot hold is
+ * VC_WIN_OVERFLOW; the pairs of a group that is not VC_WIN_OK carry its status and score 0.
+ * A pair is ranked when its group is VC_WIN_OK and has at least one node and the pair itself is VC_WIN_OK.  (A group with an
+ * empty graph scores 0 for everything and would win every global assignment: it is scored, never ranked.)  best is the
+ * highest ranked score, ties to the lower group index; second is the best over the other groups by the same rule.  status[k]
+ * is VC_WIN_OVERFLOW if any pair of k overflowed, else VC_WIN_INVALID if any was invalid, else VC_WIN_OK; the ranked pairs are
+ * reported either way.
+ * The stage runs per batch of resident groups after their build (k_lg_rows, k_lg_slots, k_lg_sfwd, k_lg_assign in
+ * vc_large.hip): row r of a graph is read by its successors only, so a forward pass that needs no backtrack keeps a row only
+ * until the last of them is complete -- n_slots rows, the width of the graph's bubbles, instead of all of them -- and computes
+ * the same cells with the same recurrence.
+ * Lifetime and failure as vc_poa_align_out: the library owns every array of a until the next vc_poa_* or vc_large_* call or
+ * vc_large_release, and a failed call leaves every pointer NULL.  A call with no query or no group runs no stage and returns
+ * the arrays empty or filled with the "none" values below.
+ * Checked before the device, in this order: q and a (both required); then as vc_poa_run_from with q and a given -- the batch,
+ * the query batch's arrays and lengths, from --; then flag bits other than the two above: VC_ERR_ARG.  VC_ERR_NO_DEVICE only
+ * after these. */
+#define VC_POA_ASSIGN_STRANDS 1u
+#define VC_POA_ASSIGN_SCORES  2u
+typedef struct vc_poa_assign_out {
+    uint32_t flags;                 /* in: VC_POA_ASSIGN_* bits                                                     */
+    uint64_t n_queries;             /* out: sequences of the query batch                                            */
+    uint32_t n_groups;              /* out: groups of the batch                                                     */
+    const uint8_t*  status;         /* [n_queries]                                                                  */
+    const int32_t*  best_group;     /* [n_queries] -1 where no pair was ranked                                      */
+    const int32_t*  best_score;     /* [n_queries] 0 where no pair was ranked                                       */
+    const int32_t*  second_group;   /* [n_queries] the best over the other groups, same rule, -1 where none         */
+    const int32_t*  second_score;   /* [n_queries] 0 where none                                                     */
+    const uint8_t*  reversed;       /* [n_queries] the strand kept against best_group, NULL without VC_POA_ASSIGN_STRANDS */
+    const int32_t*  scores;         /* [n_queries * n_groups] query-major, NULL without VC_POA_ASSIGN_SCORES        */
+    const uint8_t*  pair_status;    /* [n_queries * n_groups], NULL without VC_POA_ASSIGN_SCORES                    */
+    uint64_t        bytes;          /* copied out of the device for this stage                                      */
+} vc_poa_assign_out;
+int         vc_poa_run_assign(const vc_poa_gap_params* p, const vc_poa_graph_in* from /* may be NULL */, const vc_batch* b,
+                              vc_result* r, const vc_batch* q, vc_poa_assign_out* a);
 
 /* Span-limited alignment of group members: spoa's Graph::Subgraph / UpdateAlignment (graph.cpp:640-745) for POA groups, as the
  * reference's Window::generate_consensus uses them (window.cpp:207-213) -- for groups whose members are shorter than their

@@ -66,6 +66,14 @@ figures: the forward cells fall by about len / locus, k_lg_apply and the serial 
 by less.  With --parent-lib the plain path -- consensus only on the standard 4 096 groups of 32 x 1 kb -- of this library beside
 the parent commit's in alternating processes; then one rocprofv3 --kernel-trace --stats run of its own of the span call for the
 shares of k_lg_prep, k_lg_fwd and k_lg_apply.
+--assign [--groups 256] [--queries 1024] [--len 1000] [--depth 32]: queries assigned to groups (vc_poa_run_assign;
+profiles/poa_assign_rate.txt).  The queries are mutated members of the groups in turn; global, 5/-4/-8, one strand.  The assign
+call with the dense table beside the existing route to the same scores -- vc_poa_run_align without pairs on the queries repeated
+per group -- in one process on the same pairs, one untimed call of each, then two of each alternating: pairs/s and GCUPS of the
+stage (call minus the build alone), forward launches, ring_cells / full_cells of the `assign` log line, sampled scores compared;
+then one rocprofv3 --kernel-trace --stats run of its own with one call of each route on a quarter of the pairs for the shares of
+k_lg_sfwd, k_lg_qfwd, k_lg_slots and k_lg_assign.  The expectation is stated in the file before the figures.  Exits 1 if the
+assign call is slower than the existing route beyond that route's own spread between its two runs.
 """
 import argparse
 import csv
@@ -1065,8 +1073,134 @@ def main_resume(a):
     return 0 if ok else 1
 
 
+def assign_inputs(a):
+    """the groups, and --queries queries: members of the groups in turn, mutated (4 % substitutions, 1 % deletions, 1 % insertions)"""
+    import random
+    batch = synth_groups(a)
+    rng = random.Random(4200)
+    wso, so = batch.win_seq_off, batch.seq_off
+    queries = []
+    for k in range(a.queries):
+        w = k % batch.n_windows
+        s = int(wso[w]) + rng.randrange(int(wso[w + 1]) - int(wso[w]))
+        out = bytearray()
+        for ch in batch.bases[int(so[s]):int(so[s + 1])].tobytes():
+            x = rng.random()
+            if x < 0.01:
+                continue
+            out.append(rng.choice(b"ACGT") if x < 0.05 else ch)
+            if x > 0.99:
+                out.append(rng.choice(b"ACGT"))
+        queries.append(bytes(out))
+    return batch, queries
+
+
+def _logged(f):
+    """f() with VC_LARGE_LOG=1 -> (seconds, f's result, the library's stderr lines)"""
+    import tempfile
+    with tempfile.TemporaryFile() as log:
+        saved = os.dup(2)
+        os.dup2(log.fileno(), 2)
+        os.environ["VC_LARGE_LOG"] = "1"
+        try:
+            t0 = time.perf_counter()
+            res = f()
+            dt = time.perf_counter() - t0
+        finally:
+            del os.environ["VC_LARGE_LOG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        return dt, res, log.read().decode()
+
+
+def _kv(err, what):
+    line = [l for l in err.splitlines() if l.startswith("vc_large: " + what)][-1]
+    return {k: int(v) for k, v in (t.split("=") for t in line.split()[2:])}
+
+
+def assign_routes(a, batch, queries):
+    """-> (plain(), assign(), align()): the build alone, the assign call, and the existing route to the same table --
+    vc_poa_run_align without pairs on the queries repeated per group -- each -> (seconds, result, log)"""
+    p = capi.VcPoaGapParams(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
+    qb = poa.query_batch([queries])
+    rep = poa.query_batch([queries] * batch.n_windows)
+    return (lambda: _logged(lambda: poa.run_batch(batch, p)),
+            lambda: _logged(lambda: poa.run_batch_assign(batch, qb, p, capi.VC_POA_ASSIGN_SCORES)),
+            lambda: _logged(lambda: poa.run_batch_align(batch, rep, p, 0)))
+
+
+def main_assign(a):
+    """profiles/poa_assign_rate.txt: the assign call beside the existing route to the same scores, both in one process on the same
+    pairs; one kernel trace of a quarter of the pairs through both"""
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_assign_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    batch, queries = assign_inputs(a)
+    pairs = a.groups * a.queries
+    emit(f"Queries assigned to POA groups: {a.groups} groups of {a.depth} x {a.len} bp (vc_synth seed 4100), {a.queries} queries (mutated members, "
+         f"about {a.len} bp), {pairs} pairs; 5/-4/-8, global (kNW), one strand; one MI355X; synchronous; host clock around one call, the "
+         f"build included; both routes in one process, one untimed call of each first, then alternating")
+    emit("expected before the run: the cells computed are equal; the int32 cells stored fall by about rows / n_slots (ring_cells / full_cells "
+         "below); the launches fall to a handful; so the assign call should be faster than vc_poa_run_align without pairs on the queries "
+         "repeated per group")
+    plain, assign, align = assign_routes(a, batch, queries)
+    plain(); assign(); align()
+    tp = [plain()[0] for _ in range(2)]
+    runs_s, runs_q = [], []
+    for _ in range(2):
+        runs_s.append(assign())
+        runs_q.append(align())
+    ks, kq = _kv(runs_s[0][2], "assign"), _kv(runs_q[0][2], "align")
+    table = runs_s[0][1][3]
+    old = runs_q[0][1][2]
+    same = all(int(table[k, w]) == old[w][k].score for w in range(a.groups) for k in range(0, a.queries, max(1, a.queries // 64)))
+    build = min(tp)
+    cells = kq["cells"]
+    for name, runs, launches in (("assign (vc_poa_run_assign, scores table)", runs_s, ks["launches"]), ("existing route (vc_poa_run_align, no pairs)", runs_q, kq["launches"])):
+        t = [r[0] for r in runs]
+        emit(f"{name:46s} " + "  ".join(f"{x:7.3f}" for x in t) + " s per call; stage = call - build: " +
+             "  ".join(f"{pairs / max(x - build, 1e-9):9.0f}" for x in t) + " pairs/s, " +
+             "  ".join(f"{cells / max(x - build, 1e-9) / 1e9:6.2f}" for x in t) + f" GCUPS; {launches} forward launches")
+    emit(f"build alone (vc_poa_run_gaps): {'  '.join(f'{x:.3f}' for x in tp)} s; forward cells of the pairs (rows x columns): {cells / 1e9:.2f} G")
+    emit(f"assign line: slots_max={ks['slots_max']} ring_cells={ks['ring_cells']} full_cells={ks['full_cells']}, ring_cells / full_cells = "
+         f"{ks['ring_cells'] / max(ks['full_cells'], 1):.5f}; sampled scores equal between the routes: {same}")
+    ts, tq = sorted(r[0] for r in runs_s), sorted(r[0] for r in runs_q)
+    spread = tq[-1] - tq[0]
+    ok = same and (ts[0] + ts[-1]) / 2 <= (tq[0] + tq[-1]) / 2 + spread
+    emit(f"bar: the assign call's mean {(ts[0] + ts[-1]) / 2:.3f} s against the existing route's {(tq[0] + tq[-1]) / 2:.3f} s + its spread between "
+         f"two runs {spread:.3f} s: {'met' if ok else 'MISSED'} (call time ratio {(ts[0] + ts[-1]) / (tq[0] + tq[-1]):.3f})")
+    large.release()
+    if ok and not a.no_trace:
+        d = os.path.join(a.trace_dir, "assign")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+               sys.executable, os.path.abspath(__file__), "--child", "1", "--assign", "--groups", str(max(a.groups // 2, 1)),
+               "--queries", str(max(a.queries // 2, 1)), "--len", str(a.len), "--depth", str(a.depth)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"kernel trace: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return 1
+        ms = kernel_shares(d)
+        tot = sum(ms.values())
+        emit(f"kernel times of one assign call and one call of the existing route on a quarter of the pairs, a run of its own under rocprofv3 "
+             f"--kernel-trace --stats: {tot / 1e3:.2f} s: " +
+             ", ".join(f"{k} {v:.1f} ms ({v / tot * 100:.2f} %)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+    print("wrote", out)
+    return 0 if ok else 1
+
+
 def child(a):
     """one algorithm's call, for the kernel trace: warm-up and timed call as above, JSON on stdout"""
+    if a.assign:                                  # the traced run: one assign call and one call of the existing route
+        batch, queries = assign_inputs(a)
+        _, assign, align = assign_routes(a, batch, queries)
+        print(json.dumps(dict(assign=assign()[0], align=align()[0])))
+        return
     if a.resume and a.child == 1:                 # the traced run: build 3/4 of the members with the state, then add the rest
         _, head, tail, _, _, _ = resume_batches(a, synth_groups(a))
         small = min(64, head.n_windows)
@@ -1188,6 +1322,9 @@ def main():
                                                          "--groups defaults to 512 here)")
     ap.add_argument("--weights", action="store_true", help="measure vc_poa_run_weighted: the plain path beside --parent-lib, weights, the profile "
                                                            "(profiles/poa_weights_rate.txt)")
+    ap.add_argument("--assign", action="store_true", help="measure vc_poa_run_assign beside vc_poa_run_align without pairs on the queries repeated "
+                                                          "per group (profiles/poa_assign_rate.txt; --groups defaults to 256)")
+    ap.add_argument("--queries", type=int, default=1024, help="--assign: queries of the call")
     ap.add_argument("--locus", type=int, default=8000, help="--spans: bases of a group's backbone, tiled by reads of --len bases, --depth per tile")
     ap.add_argument("--prune-rounds", type=int, default=3, help="--correct: num_prune (default 3)")
     ap.add_argument("--queries-per-group", type=int, default=32, help="--align: mutated members per group beside the held-out one")
@@ -1199,8 +1336,12 @@ def main():
     a = ap.parse_args()
     if a.spans and "--groups" not in sys.argv:
         a.groups = 512
+    if a.assign and "--groups" not in sys.argv:
+        a.groups = 256
     if a.child is not None:
         return child(a)
+    if a.assign:
+        return main_assign(a)
     if a.weights:
         return main_weights(a)
     if a.spans:

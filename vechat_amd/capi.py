@@ -121,6 +121,22 @@ class VcPoaAlignOut(C.Structure):
     ]
 
 
+VC_POA_ASSIGN_STRANDS, VC_POA_ASSIGN_SCORES = 1, 2
+
+
+class VcPoaAssignOut(C.Structure):
+    """vc_poa_assign_out: flags in, the rest out and owned by the library until its next vc_poa_* / vc_large_* call"""
+    _fields_ = [
+        ("flags", C.c_uint32), ("n_queries", C.c_uint64), ("n_groups", C.c_uint32),
+        ("status", C.POINTER(C.c_uint8)),
+        ("best_group", C.POINTER(C.c_int32)), ("best_score", C.POINTER(C.c_int32)),
+        ("second_group", C.POINTER(C.c_int32)), ("second_score", C.POINTER(C.c_int32)),
+        ("reversed", C.POINTER(C.c_uint8)),
+        ("scores", C.POINTER(C.c_int32)), ("pair_status", C.POINTER(C.c_uint8)),
+        ("bytes", C.c_uint64),
+    ]
+
+
 class VcPoaStateOut(C.Structure):
     """vc_poa_state_out: every node's aligned list, owned by the library as vc_poa_graph_out is"""
     _fields_ = [("al_off", C.POINTER(C.c_uint64)), ("al_node", C.POINTER(C.c_uint32)), ("bytes", C.c_uint64)]
@@ -460,6 +476,11 @@ def load_hip():
                                             C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut),
                                             C.POINTER(VcPoaStateOut), C.POINTER(VcBatch), C.POINTER(VcPoaAlignOut)]
             lib.vc_poa_run_from.restype = C.c_int
+        # (likewise: tools/gpu_poa_rate.py --assign may be pointed at the parent commit's library for its own route)
+        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_assign"):
+            lib.vc_poa_run_assign.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaGraphIn), C.POINTER(VcBatch), C.POINTER(VcResult),
+                                              C.POINTER(VcBatch), C.POINTER(VcPoaAssignOut)]
+            lib.vc_poa_run_assign.restype = C.c_int
         # (likewise: the parent commit's library, beside which tools/gpu_poa_rate.py --spans measures, has no such entry)
         if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_spans"):
             lib.vc_poa_run_spans.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaSpanIn), C.POINTER(VcBatch), C.POINTER(VcResult),

@@ -71,6 +71,13 @@
 //               batch's bytes or their reverse-complement view (k_lg_views on the query batch);
 //   k_lg_qback  <GM>, one lane per job: k_lg_back's walk (back_walk) into the job's own pair area of rows + length pairs;
 //   k_lg_qpack  one wave per job: the pairs compact behind the host's prefix offsets, nodes and positions apart.
+//   Assignment, vc_poa_run_assign only: every query of the call against every finished group, scores only, so no matrix is kept:
+//   k_lg_slots  one lane per finished group behind k_lg_rows: the last reader of every row and, by a lowest-free-slot walk over
+//               the ranks, the row's slot in a ring of n_slots rows (a row is kept only while a successor still reads it);
+//   k_lg_sfwd   <GM>, a grid of (pairs of the launch, strands): fwd_rows with the row base taken from the slot, on a scratch of
+//               n_slots x (len + 1) cells per plane; it leaves the score in the job;
+//   k_lg_assign one lane per query: the scores of the chunk's pairs folded into the running best and second group (and, with
+//               VC_POA_ASSIGN_SCORES, written into the dense table).
 //   Correction, vc_poa_run_correct only (LArgs::correct): a group goes on after its build and its consensus through the prune
 //   phases of schedule 0 -- prune + largest component, then num_prune - 1 rounds of one alignment per member and step with the
 //   call's engine, add-weights, prune + largest component (k_lg_prep / k_lg_fwd / k_lg_back / k_lg_apply as above) --, and the
@@ -108,6 +115,11 @@
 //                           groups that finished, k_lg_qfwd launches, their rows x columns with both strands counted, bytes copied out),
 //                           "vc_large: correct jobs=J launches=K cells=C bytes=B" (vc_poa_run_correct: the members of the groups that
 //                           finished, k_lg_qfwd launches of the final stage, their rows x columns, bytes copied out),
+//                           "vc_large: assign groups=G queries=Q pairs=P launches=L slots_max=S ring_cells=C full_cells=F"
+//                           (vc_poa_run_assign with queries: the groups and queries of the call, the pairs of the groups that
+//                           finished, k_lg_sfwd launches, the largest n_slots of a group with a node, the int32 cells the launches
+//                           stored -- slots x columns, every plane and strand -- and the cells k_lg_qfwd would have stored for the
+//                           same pairs),
 //                           "vc_large: state bytes=B" (vc_poa_run_from with a vc_poa_state_out: the bytes of the state tables, which
 //                           the graph line does not count),
 //                           "vc_large: load groups=G nodes=N edges=E paths=P bytes=B" (vc_poa_run_from with stored graphs: what was
@@ -128,6 +140,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -283,7 +296,7 @@ int check_device(int32_t device) {
 
 // What a call wants beside consensus and status, and where each output goes (the caller's out-structs); vc_large_run's is empty.
 struct PoaRequest {
-    enum : uint32_t { MSA = 1, STRAND = 2, GRAPH = 4, ALIGN = 8, CORRECT = 16 };
+    enum : uint32_t { MSA = 1, STRAND = 2, GRAPH = 4, ALIGN = 8, CORRECT = 16, ASSIGN = 32 };
     uint32_t required = 0;                             // the outputs the entry cannot do without; 0 leaves what an earlier call handed out alone
     vc_poa_msa_out* msa = nullptr;                     // rows, members and coverage as msa_flags say (0: n_groups only)
     vc_poa_strand_out* strand = nullptr;               // the strand flow, and its choices
@@ -300,6 +313,8 @@ struct PoaRequest {
     const vc_poa_weight_in* weights = nullptr;         // vc_poa_run_weighted with at least one member of mode 1 or 2 (check_weights leaves nullptr otherwise)
     bool base_weights = false;                         // ... and at least one of mode 2
     vc_poa_profile_out* profile = nullptr;             // the per-code profile of every consensus
+    vc_poa_assign_out* assign = nullptr;               // vc_poa_run_assign: `queries` are the queries of every group, and their best groups go here
+    uint32_t assign_flags = 0;
     bool rows() const { return msa_flags != 0; }                           // k_lg_msa runs
     bool columns() const { return rows() || profile != nullptr; }          // k_lg_msa<0> runs
     // the edges keep sequence labels, and the windows sq_begin / sq_member beside them
@@ -307,7 +322,8 @@ struct PoaRequest {
     uint32_t strands() const { return strand ? 2 : 1; }                    // forward passes per alignment of the build
     bool has_queries() const { return nq != 0; }                           // the query stage runs (a call without a query is the call without it)
     bool query_pairs() const { return (align_flags & VC_POA_ALIGN_PAIRS) != 0; }
-    uint32_t query_strands() const { return (align_flags & VC_POA_ALIGN_STRANDS) ? 2 : 1; }
+    uint32_t query_strands() const { return (align_flags & VC_POA_ALIGN_STRANDS) || (assign_flags & VC_POA_ASSIGN_STRANDS) ? 2 : 1; }
+    bool assign_scores() const { return (assign_flags & VC_POA_ASSIGN_SCORES) != 0; }
 };
 
 // an empty table is still a pointer
@@ -390,8 +406,8 @@ int strand_views(Run& R, DevMem& mem) {
     return ok ? VC_OK : fail(VC_ERR_HIP, "device allocation or launch of the strand views failed");
 }
 
-// vc_poa_run_align: the query batch on the device -- offsets and bytes, and with VC_POA_ALIGN_STRANDS its reverse-complement
-// view (k_lg_views on the query batch's arrays: no quality, no round trip) -- once per call
+// vc_poa_run_align, vc_poa_run_assign: the query batch on the device -- offsets and bytes, and with VC_POA_ALIGN_STRANDS /
+// VC_POA_ASSIGN_STRANDS its reverse-complement view (k_lg_views on the query batch's arrays: no quality, no round trip) -- once per call
 int upload_queries(Run& R, DevMem& mem) {
     const PoaRequest& A = R.q;
     uint64_t* d_off = nullptr;
@@ -1167,6 +1183,172 @@ struct CorrectStage : JobStage<uint8_t, 1> {
     }
 };
 
+// vc_poa_run_assign: every query of the call against every group, for the best and the second group of each query.  No matrix is
+// kept -- a score needs a row only while a successor still reads it --, so a pair costs its group's ring, n_slots x (len + 1)
+// cells per plane and strand (k_lg_slots, k_lg_sfwd), and the pairs of a batch of resident groups fill few launches.  The pairs
+// are numbered query-major over the batch's finished groups and go through a job table of at most kChunk entries at a time:
+// built on the host, uploaded, run in launches that fit the matrix budget, folded on the device (k_lg_assign) and never copied
+// back.  What comes back is per query, once per call, and with VC_POA_ASSIGN_SCORES the dense table.
+struct AssignStage : Stage {
+    static constexpr uint64_t kChunk = 1ull << 16;     // pairs per job table
+    std::vector<uint8_t> status, reversed, pair_status;
+    std::vector<int32_t> best_g, best_s, sec_g, sec_s, scores;
+    uint64_t bytes = 0;                                // copied out of the device
+    // until assemble(): the running results on the device, and the job table with its launch lists
+    struct Dev {
+        DevMem mem;
+        LAssign s{};
+        LJob* job = nullptr; uint32_t* list = nullptr; uint64_t* hoff = nullptr;
+    };
+    std::shared_ptr<Dev> dev;
+    uint64_t nq = 0, n_pairs = 0, launches = 0, ring_cells = 0, full_cells = 0;
+    uint32_t ng = 0, slots_max = 0;
+
+    void size(const Run& R) override { nq = R.q.nq; ng = R.nw; }
+    int make_device(const Run& R) {
+        static const char* const msg = "device allocation of the assignment tables failed";
+        dev = std::make_shared<Dev>();
+        Dev& D = *dev;
+        LAssign& s = D.s;
+        const uint64_t cells = R.q.assign_scores() ? nq * ng : 0;
+        if (!D.mem.alloc(&s.best_g, nq) || !D.mem.alloc(&s.best_s, nq) || !D.mem.alloc(&s.sec_g, nq) || !D.mem.alloc(&s.sec_s, nq) ||
+            !D.mem.alloc(&s.rev, nq) || !D.mem.alloc(&s.flag, nq) || (cells && (!D.mem.alloc(&s.scores, cells) || !D.mem.alloc(&s.pair_status, cells))) ||
+            !D.mem.alloc(&D.job, kChunk) || !D.mem.alloc(&D.list, kChunk) || !D.mem.alloc(&D.hoff, kChunk))
+            return fail(VC_ERR_HIP, msg);
+        bool ok = hipMemset(s.best_g, 0xFF, nq * 4) == hipSuccess && hipMemset(s.sec_g, 0xFF, nq * 4) == hipSuccess &&
+                  hipMemset(s.best_s, 0, nq * 4) == hipSuccess && hipMemset(s.sec_s, 0, nq * 4) == hipSuccess &&
+                  hipMemset(s.rev, 0, nq) == hipSuccess && hipMemset(s.flag, 0, nq) == hipSuccess;
+        if (cells) ok = ok && hipMemset(s.scores, 0, cells * 4) == hipSuccess && hipMemset(s.pair_status, 0, cells) == hipSuccess;
+        s.ng = ng; s.strands = R.q.query_strands();
+        return ok ? VC_OK : fail(VC_ERR_HIP, msg);
+    }
+    int collect(Run& R, Group& G) override {
+        static const char* const failed = "an assignment kernel failed";
+        const std::vector<uint32_t> fin = finished(R, G);
+        if (fin.empty()) return VC_OK;
+        if (!dev) if (const int rc = make_device(R)) return rc;
+        Dev& D = *dev;
+        LArgs a = R.a;
+        const uint32_t n = (uint32_t)G.ids.size(), ns = R.q.query_strands();
+        // the rows and the slots of every finished graph, once; n_slots back with the windows
+        uint32_t* d_gid = nullptr;
+        DevMem mem;
+        if (!mem.alloc(&d_gid, n, G.ids.data())) return fail(VC_ERR_HIP, "device allocation of the assignment tables failed");
+        hipLaunchKernelGGL(k_lg_rows, dim3((n + 63) / 64), dim3(64), 0, 0, a);
+        hipLaunchKernelGGL(k_lg_slots, dim3((n + 63) / 64), dim3(64), 0, 0, a);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(G.hw.data(), G.d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(VC_ERR_HIP, "the assignment stage's row or slot kernel failed");
+        for (const uint32_t k : fin) if (G.hw[k].gr[G.hw[k].cur].n_nodes) slots_max = std::max(slots_max, G.hw[k].n_slots);
+        a.job = D.job;
+        LAssign s = D.s;
+        s.gid = d_gid; s.nfin = (uint32_t)fin.size();
+        const uint64_t T = nq * fin.size();
+        std::vector<LJob> jobs;
+        std::vector<uint32_t> act;
+        const vc_batch* qb = R.q.queries;
+        for (uint64_t t0 = 0; t0 < T; t0 += kChunk) {
+            const uint64_t t1 = std::min(T, t0 + kChunk);
+            jobs.assign(t1 - t0, LJob{});
+            act.clear();
+            for (uint64_t t = t0; t < t1; ++t) {
+                LJob& J = jobs[t - t0];
+                const uint32_t k = fin[t % fin.size()];
+                const LGraph& g = G.hw[k].gr[G.hw[k].cur];
+                const uint32_t N = g.n_nodes;
+                J.win = k; J.qs = (uint32_t)(t / fin.size()); J.qlen = (uint32_t)(qb->seq_off[J.qs + 1] - qb->seq_off[J.qs]); J.status = VC_WIN_OK;
+                if (N == 0 || J.qlen == 0) continue;                       // an empty alignment, score 0
+                // the floor of k_lg_prep, and its check of the topological order (JobStage::collect)
+                if (worst_case(a.match, a.gap, a.gap_e, a.gap_q, a.gap_c, (int64_t)J.qlen + 8, N) < (int64_t)KNEG || g.n_rank != N || G.hw[k].n_slots == 0) {
+                    J.status = VC_WIN_INVALID;
+                    continue;
+                }
+                J.rows = N;
+                act.push_back((uint32_t)(t - t0));
+            }
+            if (hipMemcpy(D.job, jobs.data(), jobs.size() * sizeof(LJob), hipMemcpyHostToDevice) != hipSuccess)
+                return fail(VC_ERR_HIP, "copy of the assignment jobs failed");
+            auto columns = [&](uint32_t j) { return ((uint64_t)jobs[j].qlen + 1) * R.planes * ns; };
+            auto ring = [&](uint32_t j) { return (uint64_t)G.hw[jobs[j].win].n_slots * columns(j); };
+            auto refuse = [&](uint32_t j) -> int {                         // the device has no room for this one ring
+                jobs[j].status = VC_WIN_OVERFLOW;
+                return hipMemcpy(D.job + j, &jobs[j], sizeof(LJob), hipMemcpyHostToDevice) == hipSuccess ? VC_OK : fail(VC_ERR_HIP, failed);
+            };
+            auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>&, uint64_t cells, void* H) -> int {
+                f.H = (int32_t*)H;
+                with_gap_model(f.gaps, [&](auto gm) { hipLaunchKernelGGL(k_lg_sfwd<decltype(gm)::value>, dim3((uint32_t)list.size(), ns), dim3(64), 0, 0, f); });
+                if (hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, failed);
+                ring_cells += cells;
+                for (const uint32_t j : list) full_cells += ((uint64_t)jobs[j].rows + 1) * columns(j);
+                return VC_OK;
+            };
+            if (const int rc = launch_loop(a, act, R.mat_budget / 4, 4, D.list, D.hoff,
+                                           {"device allocation of the assignment rings failed", "copy of an assignment launch failed"}, launches,
+                                           ring, as_packed, refuse, body))
+                return rc;
+            s.t0 = t0; s.t1 = t1;
+            const uint64_t lanes = (t1 - 1) / fin.size() - t0 / fin.size() + 1;
+            hipLaunchKernelGGL(k_lg_assign, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, 0, a, s);
+            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, failed);
+            n_pairs += t1 - t0;
+        }
+        return VC_OK;
+    }
+    // the per-query results back, once; the groups that were not computed pass their status on to their pairs
+    void assemble(const Run& R) override {
+        const bool dense = R.q.assign_scores();
+        status.assign(nq, VC_WIN_OK); reversed.assign(nq, 0);
+        best_g.assign(nq, -1); sec_g.assign(nq, -1); best_s.assign(nq, 0); sec_s.assign(nq, 0);
+        if (dense) { scores.assign(nq * ng, 0); pair_status.assign(nq * ng, VC_WIN_OK); }
+        std::vector<uint8_t> flag(nq, 0);
+        if (dev) {
+            const LAssign& s = dev->s;
+            bool ok = hipMemcpy(best_g.data(), s.best_g, nq * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                      hipMemcpy(best_s.data(), s.best_s, nq * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                      hipMemcpy(sec_g.data(), s.sec_g, nq * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                      hipMemcpy(sec_s.data(), s.sec_s, nq * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                      hipMemcpy(reversed.data(), s.rev, nq, hipMemcpyDeviceToHost) == hipSuccess &&
+                      hipMemcpy(flag.data(), s.flag, nq, hipMemcpyDeviceToHost) == hipSuccess;
+            bytes += 18 * nq;
+            if (dense && nq * ng) {
+                ok = ok && hipMemcpy(scores.data(), s.scores, nq * ng * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                     hipMemcpy(pair_status.data(), s.pair_status, nq * ng, hipMemcpyDeviceToHost) == hipSuccess;
+                bytes += 5 * nq * ng;
+            }
+            copy_failed = !ok;
+            dev.reset();
+        }
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            if (R.status[w] == VC_WIN_OK) continue;
+            for (uint64_t k = 0; k < nq; ++k) {
+                flag[k] |= R.status[w] == VC_WIN_OVERFLOW ? 1 : 2;
+                if (dense) { scores[k * ng + w] = 0; pair_status[k * ng + w] = R.status[w]; }
+            }
+        }
+        for (uint64_t k = 0; k < nq; ++k) status[k] = (flag[k] & 1) ? VC_WIN_OVERFLOW : (flag[k] & 2) ? VC_WIN_INVALID : VC_WIN_OK;
+        if (R.kn.log)
+            std::fprintf(stderr, "vc_large: assign groups=%u queries=%llu pairs=%llu launches=%llu slots_max=%u ring_cells=%llu full_cells=%llu\n", ng,
+                         (unsigned long long)nq, (unsigned long long)n_pairs, (unsigned long long)launches, slots_max,
+                         (unsigned long long)ring_cells, (unsigned long long)full_cells);
+    }
+    bool copy_failed = false;                          // assemble() cannot fail: poa_run asks afterwards
+    void publish(const PoaRequest& q, const vc_batch* b) override {
+        vc_poa_assign_out* o = q.assign;
+        if (!o) return;
+        const uint64_t cells = q.nq * b->n_windows;
+        if (best_g.size() != q.nq) {                                       // no stage ran (no query, or no group): the "none" values
+            status.assign(q.nq, VC_WIN_OK); reversed.assign(q.nq, 0);
+            best_g.assign(q.nq, -1); sec_g.assign(q.nq, -1); best_s.assign(q.nq, 0); sec_s.assign(q.nq, 0);
+        }
+        if (q.assign_scores() && scores.size() != cells) { scores.assign(cells, 0); pair_status.assign(cells, VC_WIN_OK); }
+        o->n_queries = q.nq; o->n_groups = b->n_windows;
+        o->status = table(status);
+        o->best_group = table(best_g); o->best_score = table(best_s); o->second_group = table(sec_g); o->second_score = table(sec_s);
+        if (q.query_strands() == 2) o->reversed = table(reversed);
+        if (q.assign_scores()) { o->scores = table(scores); o->pair_status = table(pair_status); }
+        o->bytes = bytes;
+    }
+};
+
 // The stages of the process, and with them what the vc_poa_* entries hand out: valid until the next call that has an output of
 // its own (poa_run clears them then, and when such a call fails) or vc_large_release.
 struct Outputs {
@@ -1175,6 +1357,7 @@ struct Outputs {
     GraphStage graph;
     CorrectStage correct;
     AlignStage align;
+    AssignStage assign;
     // The stages that run in a call, in the order run_group collects and run_windows assembles them.  Correct stands before
     // align as run_group always had them, align before correct in run_windows: one order serves both, because the two never
     // occur in one call (only vc_poa_run_correct asks for correction, and it takes no query batch).
@@ -1184,10 +1367,11 @@ struct Outputs {
         if (q.profile) s.push_back(&profile);
         if (q.graph) s.push_back(&graph);
         if (q.correct) s.push_back(&correct);
-        if (q.has_queries()) s.push_back(&align);
+        if (q.has_queries() && q.align) s.push_back(&align);
+        if (q.has_queries() && q.assign) s.push_back(&assign);
         return s;
     }
-    std::vector<Stage*> all() { return {&msa, &profile, &graph, &correct, &align}; }
+    std::vector<Stage*> all() { return {&msa, &profile, &graph, &correct, &align, &assign}; }
     void clear() { *this = Outputs{}; }
 } g_out;
 
@@ -1305,17 +1489,19 @@ int run_windows(int32_t device, const LArgs& a, const vc_batch* b, std::vector<C
     }
     if (q.strand) if (const int rc = copy_strands(R)) return rc;
     for (Stage* s : R.stages) s->assemble(R);
+    if (g_out.assign.copy_failed) return fail(VC_ERR_HIP, "copy of the assignment results failed");
     return assemble(R, r);
 }
 
 // vc_poa_run_align's own arguments, after the batch and before the device: the output and its flags, the query batch and its
-// count against the groups, the query lengths
+// count against the groups, the query lengths.  vc_poa_run_assign shares the query batch's checks: its windows mean nothing
+// (their last offset is the sequence count), its output was checked at the entry and its flags come after `from`.
 int check_queries(PoaRequest& A, const vc_batch* b) {
-    if (!A.align) return fail(VC_ERR_ARG, "null align output");
+    if (!A.assign && !A.align) return fail(VC_ERR_ARG, "null align output");
     if (A.align_flags & ~(uint32_t)(VC_POA_ALIGN_PAIRS | VC_POA_ALIGN_STRANDS)) return fail(VC_ERR_ARG, "unknown align flag bits");
     const vc_batch* q = A.queries;
     if (!q) return fail(VC_ERR_ARG, "null query batch");
-    if (q->n_windows != b->n_windows) return fail(VC_ERR_ARG, "the query batch needs one window per group");
+    if (!A.assign && q->n_windows != b->n_windows) return fail(VC_ERR_ARG, "the query batch needs one window per group");
     const uint32_t nw = q->n_windows;
     if (nw == 0) return VC_OK;
     if (!q->win_seq_off || !q->seq_off) return fail(VC_ERR_ARG, "null array in the query batch");
@@ -1538,7 +1724,7 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
             caps[w] = initial_caps(b->seq_off[s1] - b->seq_off[s0], mx, s1 - s0, kn);
         }
     }
-    if (q.required & PoaRequest::ALIGN) if (const int rc = check_queries(q, b)) return rc;
+    if (q.required & (PoaRequest::ALIGN | PoaRequest::ASSIGN)) if (const int rc = check_queries(q, b)) return rc;
     if (q.from) {
         if (const int rc = check_from(q.from, b)) return rc;
         // tables: the stored counts, and beside them the usual allowance for the new members (which alone the knobs shrink)
@@ -1548,6 +1734,7 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
             k.NC += c.N; k.EC += c.E; k.AC += c.A; k.LC += c.T; k.SC += c.N + c.E + c.A; k.PC += c.N; k.nseq += c.S;
         }
     }
+    if (q.assign_flags & ~(uint32_t)(VC_POA_ASSIGN_STRANDS | VC_POA_ASSIGN_SCORES)) return fail(VC_ERR_ARG, "unknown assign flag bits");
     if (const int rc = check_spans(q, b)) return rc;
     if (const int rc = check_weights(q, b)) return rc;
     a.num_prune = 1;
@@ -1574,6 +1761,7 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     if (q.correct) *q.correct = vc_poa_correct_out{};
     if (q.state) *q.state = vc_poa_state_out{};
     if (q.profile) *q.profile = vc_poa_profile_out{};
+    if (q.assign) { q.assign_flags = q.assign->flags; *q.assign = vc_poa_assign_out{}; q.assign->flags = q.assign_flags; }
     if (!p || !b || !r || ((q.required & PoaRequest::MSA) && !o) || ((q.required & PoaRequest::CORRECT) && (!q.prune || !q.correct)) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
@@ -1694,6 +1882,15 @@ int vc_poa_run_from(const vc_poa_gap_params* p, const vc_poa_graph_in* from, con
     if (st && !g) return fail(VC_ERR_ARG, "the state output needs the graph output");
     PoaRequest rq{base_entry(q, g, s, o), o, s, g, q, a};
     rq.from = from; rq.state = st;
+    return poa_run(p, b, r, rq);
+}
+
+int vc_poa_run_assign(const vc_poa_gap_params* p, const vc_poa_graph_in* from, const vc_batch* b, vc_result* r, const vc_batch* q,
+                      vc_poa_assign_out* a) {
+    if (a) { const uint32_t flags = a->flags; *a = vc_poa_assign_out{}; a->flags = flags; }   // a failed call leaves every pointer NULL
+    if (!q || !a) return fail(VC_ERR_ARG, "the query batch and the assign output are both required");
+    PoaRequest rq{PoaRequest::ASSIGN};
+    rq.queries = q; rq.assign = a; rq.from = from;
     return poa_run(p, b, r, rq);
 }
 

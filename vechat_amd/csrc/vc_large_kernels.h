@@ -63,6 +63,9 @@ struct LWin {
     uint32_t n_old, m0;
     uint32_t* sq_len;                                  // [nseq]
     uint8_t* sq_rev;                                   // [nseq]
+    // vc_poa_run_assign only: k_lg_slots's count of row slots of the finished graph, row 0's included; the slot of rank r is
+    // map[r] (map, g2s and fr_v are free once a group has finished: k_lg_slots keeps slot, last reader and free heap in them)
+    uint32_t n_slots;
 };
 
 struct LArgs {
@@ -940,6 +943,7 @@ struct AlnView {
     const uint32_t *poff, *prank;
     const uint8_t *rchar, *sink;
     const uint32_t* rank;
+    const uint32_t* slot;                              // fwd_rows<GM, true> only: rank -> row slot of the ring (k_lg_slots)
 };
 struct EndCell { int32_t s; uint32_t i, j; };
 
@@ -969,7 +973,11 @@ __device__ __forceinline__ AlnView query_view(const LArgs& a, const LWin& W, con
 // sink row is an end-cell candidate, not only the last column.
 // The body is fwd_rows, shared by k_lg_fwd (a step of the build) and k_lg_qfwd (a query against a finished graph): every lane
 // of the wave calls it and every lane gets the end cell back.
-template <uint32_t GM>
+// SLOTS (k_lg_sfwd, vc_poa_run_assign) is the one switch: row i lives at slot W.slot[i - 1] of a ring instead of at i (row 0 at
+// slot 0 either way), so the planes hold n_slots rows and only the score of the end cell means anything afterwards.  A row
+// shares its slot with no row it reads and with no row a later row still reads (k_lg_slots), so the cells computed, the order of
+// the maxima and the barrier per row are the same.
+template <uint32_t GM, bool SLOTS = false>
 __device__ __forceinline__ EndCell fwd_rows(const AlnView& W, const Mat& M) {
     const uint32_t lane = threadIdx.x;
     const uint32_t N = W.rows, len = W.len;
@@ -978,6 +986,10 @@ __device__ __forceinline__ EndCell fwd_rows(const AlnView& W, const Mat& M) {
     const bool sw = W.type == 0, ov = W.type == 2;
     const int32_t m = W.m, x = W.x, gp = W.g, ge = GM == 0 ? gp : W.e, gq = W.q, gc = W.c;
     const uint8_t* seq = W.seq;
+    auto row_at = [&](uint64_t i) -> uint64_t {                        // where row i begins in a plane
+        if constexpr (SLOTS) return (i ? (uint64_t)W.slot[i - 1] : 0) * w;
+        else return i * w;
+    };
     auto vertical = [&](uint64_t c) -> int32_t {                       // F's term from cell c of a predecessor row
         if constexpr (GM == 0) return H[c] + gp;
         else return max(H[c] + gp, F[c] + ge);
@@ -998,15 +1010,15 @@ __device__ __forceinline__ EndCell fwd_rows(const AlnView& W, const Mat& M) {
     int32_t bs = sw ? 0 : KNEG;
     uint32_t bi = 0, bj = 0;
     for (uint32_t r = 0; r < N; ++r) {
-        const uint64_t i = (uint64_t)r + 1, ro = i * w;
+        const uint64_t i = (uint64_t)r + 1, ro = row_at(i);
         const uint32_t po = W.poff[r], pe = W.poff[r + 1];
         const uint8_t ch = W.rchar[r];
         const bool sink = W.sink[r] != 0;
         const int32_t* F0 = GM == 0 ? H : F;                           // column 0's vertical chain
         int32_t f0 = pe == po ? gp - ge : KNEG, o0 = pe == po ? gq - gc : KNEG;
         for (uint32_t k = po; k < pe; ++k) {
-            f0 = max(f0, F0[(uint64_t)W.prank[k] * w]);
-            if constexpr (GM == 2) o0 = max(o0, O[(uint64_t)W.prank[k] * w]);
+            f0 = max(f0, F0[row_at(W.prank[k])]);
+            if constexpr (GM == 2) o0 = max(o0, O[row_at(W.prank[k])]);
         }
         f0 += ge; o0 += gc;
         const int32_t h0 = (sw || ov) ? 0 : (GM == 2 ? max(o0, f0) : f0);
@@ -1028,11 +1040,11 @@ __device__ __forceinline__ EndCell fwd_rows(const AlnView& W, const Mat& M) {
                 xv[q] = KNEG;
                 if (j > len) continue;
                 const int32_t s = seq[j - 1] == ch ? m : x;
-                uint64_t p = pe == po ? 0 : (uint64_t)W.prank[po] * w;
+                uint64_t p = pe == po ? 0 : row_at(W.prank[po]);
                 int32_t d = H[p + j - 1] + s, f = vertical(p + j), o = KNEG;
                 if constexpr (GM == 2) o = max(H[p + j] + gq, O[p + j] + gc);
                 for (uint32_t k = po + 1; k < pe; ++k) {
-                    p = (uint64_t)W.prank[k] * w;
+                    p = row_at(W.prank[k]);
                     d = max(d, H[p + j - 1] + s);
                     f = max(f, vertical(p + j));
                     if constexpr (GM == 2) o = max(o, max(H[p + j] + gq, O[p + j] + gc));
@@ -1095,6 +1107,110 @@ __global__ __launch_bounds__(64) void k_lg_qfwd(LArgs a) {
     const uint32_t st = blockIdx.y;
     const EndCell b = fwd_rows<GM>(query_view(a, a.win[J.win], J, st), matrix_of<GM>(a, blockIdx.x, J.rows, J.qlen, st));
     if (threadIdx.x == 0) { J.max_i[st] = b.i; J.max_j[st] = b.j; J.score[st] = b.s; }
+}
+
+// ------------------------------------------------------------------ vc_poa_run_assign: every query against every group, scores only
+// The slots of a finished graph's rows, one lane per group behind k_lg_rows.  Row i (rank i - 1) is read by its successors only,
+// so it is dead once the last of them is complete: last[r] is the highest row that reads row r + 1 (the row itself where nobody
+// does), found from poff / prank in one pass because the ranks ascend.  Then the rows upward with a free list: a row takes the
+// LOWEST free slot (a binary min-heap; a fresh slot when none is free), and only when it is complete do the rows it read last --
+// and the row itself, when nobody reads it -- give their slots back.  So a row shares a slot neither with a row it reads nor with
+// one that a later row still reads.  Row 0, which every source reads, keeps slot 0 for good.  Deterministic: the same rule in
+// Python (tests/poa_assign_ref.py) gives the same slots.
+__global__ __launch_bounds__(64) void k_lg_slots(LArgs a) {
+    const uint32_t w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= a.n) return;
+    LWin& W = a.win[w];
+    W.n_slots = 0;
+    if (W.phase != PH_DONE || W.grow || W.status != VC_WIN_OK) return;
+    const uint32_t N = W.gr[W.cur].n_nodes;
+    if (W.gr[W.cur].n_rank != N) return;                                   // (the host makes no job for such a graph)
+    uint32_t *const slot = W.map, *const last = W.g2s, *const heap = W.fr_v;
+    for (uint32_t r = 0; r < N; ++r) last[r] = r + 1;
+    for (uint32_t r = 0; r < N; ++r)
+        for (uint32_t k = W.poff[r]; k < W.poff[r + 1]; ++k) if (W.prank[k]) last[W.prank[k] - 1] = r + 1;
+    uint32_t nh = 0, ns = 1;
+    auto give = [&](uint32_t s) {
+        uint32_t c = nh++;
+        for (; c && heap[(c - 1) / 2] > s; c = (c - 1) / 2) heap[c] = heap[(c - 1) / 2];
+        heap[c] = s;
+    };
+    auto take = [&]() -> uint32_t {
+        if (!nh) return ns++;
+        const uint32_t s = heap[0], x = heap[--nh];
+        uint32_t c = 0;
+        for (;;) {
+            uint32_t k = 2 * c + 1;
+            if (k >= nh) break;
+            if (k + 1 < nh && heap[k + 1] < heap[k]) ++k;
+            if (heap[k] >= x) break;
+            heap[c] = heap[k]; c = k;
+        }
+        if (nh) heap[c] = x;
+        return s;
+    };
+    for (uint32_t r = 0; r < N; ++r) {
+        const uint32_t s = take();
+        slot[r] = s;
+        for (uint32_t k = W.poff[r]; k < W.poff[r + 1]; ++k) {
+            const uint32_t p = W.prank[k];
+            if (p && last[p - 1] == r + 1) { give(slot[p - 1]); last[p - 1] = NONE; }   // (NONE: an edge listed twice gives once)
+        }
+        if (last[r] == r + 1) give(s);
+    }
+    W.n_slots = ns;
+}
+
+// One (query, group) pair of vc_poa_run_assign: fwd_rows on the ring of the group's slots, n_slots x (len + 1) cells per plane
+// in place of (rows + 1) x (len + 1), on a grid of (pairs of the launch, strands).  It leaves the score in the job, nothing else.
+template <uint32_t GM>
+__global__ __launch_bounds__(64) void k_lg_sfwd(LArgs a) {
+    LJob& J = a.job[a.list[blockIdx.x]];
+    const uint32_t st = blockIdx.y;
+    const LWin& W = a.win[J.win];
+    AlnView V = query_view(a, W, J, st);
+    V.slot = W.map;
+    const EndCell b = fwd_rows<GM, true>(V, matrix_of<GM>(a, blockIdx.x, W.n_slots - 1, J.qlen, st));
+    if (threadIdx.x == 0) J.score[st] = b.s;
+}
+
+// What k_lg_assign folds into, per query of the call (device arrays that live as long as the call), and the chunk of pairs at
+// hand: the pairs of a batch of resident groups are numbered query-major over its `nfin` finished groups, pair t being query
+// t / nfin against the (t % nfin)-th of them, and a.job holds the pairs t0 .. t1 - 1.
+struct LAssign {
+    const uint32_t* gid;                               // [windows in flight] the group's index in the call
+    uint64_t t0, t1;
+    uint32_t nfin, ng, strands;
+    int32_t *best_g, *best_s, *sec_g, *sec_s;          // [queries]
+    uint8_t *rev, *flag;                               // [queries] the strand kept against best_g; 1: a pair overflowed, 2: a pair was invalid
+    int32_t* scores;                                   // [queries x ng], nullptr without VC_POA_ASSIGN_SCORES
+    uint8_t* pair_status;
+};
+
+// One lane per query with a pair in the chunk: its pairs, which lie side by side in group order, folded into the running best
+// and second.  A pair is ranked when it is VC_WIN_OK and its group has a node; it replaces on a greater score, or on an equal
+// one from a lower group, so neither the chunks nor the order in which groups became resident show in the result.  No atomics:
+// a query has one lane per launch, and the launches of a call follow one another.
+__global__ __launch_bounds__(64) void k_lg_assign(LArgs a, LAssign s) {
+    const uint64_t k = s.t0 / s.nfin + (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    if (k > (s.t1 - 1) / s.nfin) return;
+    const uint64_t lo = max(s.t0, k * s.nfin), hi = min(s.t1, (k + 1) * s.nfin);
+    int32_t bg = s.best_g[k], bs = s.best_s[k], cg = s.sec_g[k], cs = s.sec_s[k];
+    uint8_t brev = s.rev[k], fl = s.flag[k];
+    for (uint64_t t = lo; t < hi; ++t) {
+        const LJob& J = a.job[t - s.t0];
+        const LWin& W = a.win[J.win];
+        const int32_t g = (int32_t)s.gid[J.win];
+        const bool ok = J.status == VC_WIN_OK, rv = ok && s.strands == 2 && J.score[0] < J.score[1];
+        const int32_t sc = ok ? J.score[rv ? 1 : 0] : 0;
+        if (J.status == VC_WIN_OVERFLOW) fl |= 1;
+        else if (!ok) fl |= 2;
+        if (s.scores) { s.scores[k * s.ng + g] = sc; s.pair_status[k * s.ng + g] = (uint8_t)J.status; }
+        if (!ok || W.gr[W.cur].n_nodes == 0) continue;
+        if (bg < 0 || sc > bs || (sc == bs && g < bg)) { cg = bg; cs = bs; bg = g; bs = sc; brev = rv; }
+        else if (cg < 0 || sc > cs || (sc == cs && g < cg)) { cg = g; cs = sc; }
+    }
+    s.best_g[k] = bg; s.best_s[k] = bs; s.sec_g[k] = cg; s.sec_s[k] = cs; s.rev[k] = brev; s.flag[k] = fl;
 }
 
 // g_align's backtrack, one lane per alignment, in the reference's order of candidates, literally.

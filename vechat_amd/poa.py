@@ -910,6 +910,83 @@ def poa_align(groups=None, queries=None, algorithm="global", match=5, mismatch=-
     return res
 
 
+class Assignment:
+    """One query's result of poa_assign: best_group and second_group (indices into the groups, -1 where no pair was ranked),
+    their scores (0 where none), reversed (True: the reverse complement scored higher against best_group; always False without
+    both_strands) and status (capi.VC_WIN_*: OVERFLOW if any pair of the query overflowed, else INVALID if any was invalid)."""
+    __slots__ = ("best_group", "best_score", "second_group", "second_score", "reversed", "status")
+
+    def __init__(self, best_group, best_score, second_group, second_score, reversed, status):
+        self.best_group, self.best_score, self.second_group, self.second_score = best_group, best_score, second_group, second_score
+        self.reversed, self.status = reversed, status
+
+    def __iter__(self):
+        return iter((self.best_group, self.best_score, self.second_group, self.second_score, self.reversed, self.status))
+
+    def __repr__(self):
+        return "Assignment(best_group=%d, best_score=%d, second_group=%d, second_score=%d, reversed=%r, status=%d)" % tuple(self)
+
+
+def run_batch_assign(batch, qbatch, params, flags=0, lib=None, start=None):
+    """vc_poa_run_assign (params: capi.VcPoaGapParams; flags: capi.VC_POA_ASSIGN_* bits) on a capi.Batch of groups and one of
+    queries, every sequence of qbatch being a query against every group; start: resumable PoaGraph, one per group, or None ->
+    (consensus bytes per group, status array of the groups, list of Assignment, the (queries, groups) int32 score table or None,
+    the uint8 pair status table or None).  Everything is copied out of the library's buffers.  Raises PoaError on a library error."""
+    lib = lib or capi.load_hip()
+    if not hasattr(lib, "vc_poa_run_assign"):
+        raise PoaError("this libvechat_hip.so has no vc_poa_run_assign: it was built before the entry point existed; rebuild it")
+    n = batch.n_windows
+    if start is not None and len(start) != n:
+        raise ValueError(f"{len(start)} graphs to start from for {n} groups")
+    cons, off, status, r, vb = _result_buffers(batch, sum(g.n_nodes for g in start if isinstance(g, PoaGraph)) if start is not None else 0)
+    gin, keep = _graph_in(start) if start is not None else (None, None)     # (keep: the arrays gin points into, until the call)
+    qv = qbatch.as_struct()
+    qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
+    a = capi.VcPoaAssignOut(flags=flags)
+    rc = lib.vc_poa_run_assign(C.byref(params), None if gin is None else C.byref(gin), C.byref(vb), C.byref(r), C.byref(qv), C.byref(a))
+    del keep
+    if rc != 0:
+        raise PoaError(f"vc_poa_run_assign failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    nq, ng = int(a.n_queries), int(a.n_groups)
+    st, bg, bs = _table(a.status, nq), _table(a.best_group, nq), _table(a.best_score, nq)
+    sg, ss = _table(a.second_group, nq), _table(a.second_score, nq)
+    rv = _table(a.reversed, nq) if flags & capi.VC_POA_ASSIGN_STRANDS else np.zeros(nq, np.uint8)
+    res = [Assignment(int(bg[k]), int(bs[k]), int(sg[k]), int(ss[k]), bool(rv[k]), int(st[k])) for k in range(nq)]
+    table = pst = None
+    if flags & capi.VC_POA_ASSIGN_SCORES:
+        table, pst = _table(a.scores, nq * ng).reshape(nq, ng), _table(a.pair_status, nq * ng).reshape(nq, ng)
+    return [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)], status[:n], res, table, pst
+
+
+def poa_assign(groups=None, queries=None, *, graphs=None, both_strands=False, scores=False, algorithm="global", match=5, mismatch=-4,
+               gap=-8, device=0, strict=True, lib=None, gap_extend=None, gap_open2=None, gap_extend2=None, spans=None, weights=None):
+    """Scores every query against EVERY group without adding it (spoa's engine->Align(query, graph, &score); vc_poa_run_assign)
+    and assigns it: queries is one flat list of sequences -> one Assignment per query, the best and the second group by score
+    (ties to the lower index; a group with an empty graph is scored but never ranked).  With scores=True -> (that, the
+    (queries, groups) int32 numpy array of every pair's score, the kept strand's with both_strands).  both_strands scores every
+    query as given and reverse-complemented and keeps the better, ties as given.  Only scores are computed -- no alignment is
+    kept -- so a pair stores the graph's live rows alone; follow up with poa_align on the winners for the pairs.
+    graphs= (resumable PoaGraph) scores against stored graphs; with groups too, groups[w] is first added to graphs[w].
+    Parameters, PoaError and strict as poa_consensus: a group that was not computed raises, or with strict=False its pairs carry
+    its status.  spans= and weights= are refused (ValueError), as by poa_align."""
+    _no_spans(spans, "poa_assign")
+    _no_weights(weights, "poa_assign")
+    if queries is None:
+        raise ValueError("poa_assign needs queries")
+    if groups is None and graphs is None:
+        raise ValueError("poa_assign needs groups to build, or graphs to score against (or both, to extend the graphs first)")
+    if groups is None:
+        groups = [[] for _ in graphs]
+    if graphs is not None and len(graphs) != len(groups):
+        raise ValueError(f"{len(graphs)} graphs for {len(groups)} groups")
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    flags = (capi.VC_POA_ASSIGN_STRANDS if both_strands else 0) | (capi.VC_POA_ASSIGN_SCORES if scores else 0)
+    _, status, res, table, _ = run_batch_assign(group_batch(groups), query_batch([list(queries)]), p, flags, lib,
+                                                start=list(graphs) if graphs is not None else None)
+    _not_computed(status, strict)
+    return (res, table) if scores else res
+
+
 class Corrected:
     """One group's result of poa_correct: consensus (bytes; of the unpruned graph, poa_consensus's), reads (the corrected bytes of
     every member, in member order; empty where the member aligns nowhere or is empty), scores (numpy int32: the local score of
@@ -998,6 +1075,23 @@ def align_tsv(names, files, results):
                                                       _STATUS_NAME.get(r.status, b"%d" % r.status),
                                                       r.score_rev if r.reversed else r.score, b"-" if r.reversed else b"+", prs))
     return b"".join(out)
+
+
+def assign_tsv(names, files, results):
+    """The text of --assign-out, beside align_tsv: one tab-separated line per query -- query name, the best group's file, its
+    score, the second group's file, its score, strand (+ / -, against the best group), status; * and 0 where no group was ranked.
+    results[k]: the Assignment of query k."""
+    f = [_bytes(x, "file name") for x in files]
+    return b"".join(b"%s\t%s\t%d\t%s\t%d\t%s\t%s\n" % (_bytes(name, "query name"), f[r.best_group] if r.best_group >= 0 else b"*", r.best_score,
+                                                      f[r.second_group] if r.second_group >= 0 else b"*", r.second_score,
+                                                      b"-" if r.reversed else b"+", _STATUS_NAME.get(r.status, b"%d" % r.status))
+                    for name, r in zip(names, results))
+
+
+def assign_scores_tsv(names, files, table):
+    """The text of --assign-scores: a header line `query` and the group files, then per query its name and its score against every group"""
+    head = b"query" + b"".join(b"\t" + _bytes(x, "file name") for x in files) + b"\n"
+    return head + b"".join(_bytes(name, "query name") + b"".join(b"\t%d" % v for v in row) + b"\n" for name, row in zip(names, table.tolist()))
 
 
 def parse_spans(text, files, records):
@@ -1125,6 +1219,16 @@ def parse_args(argv=None):
                          "strand, pairs (node:pos,... with * for none)")
     ap.add_argument("--align-both-strands", action="store_true",
                     help="with --align: align every query as given and reverse-complemented and report the better strand")
+    ap.add_argument("--assign", metavar="QUERIES", default=None,
+                    help="also score every record of QUERIES (FASTA / FASTQ) against the graph of every input file, without adding it, "
+                         "and report the best and the second file per record (scores only: far cheaper than --align)")
+    ap.add_argument("--assign-out", metavar="FILE", default=None,
+                    help="where --assign writes: one tab-separated line per query: query name, best group's file, score, second "
+                         "group's file, second score, strand, status")
+    ap.add_argument("--assign-both-strands", action="store_true",
+                    help="with --assign: score every query as given and reverse-complemented and keep the better strand")
+    ap.add_argument("--assign-scores", metavar="FILE", default=None,
+                    help="with --assign: also write the score of every (query, file) pair to FILE, one tab-separated line per query")
     ap.add_argument("--correct", metavar="FILE", default=None,
                     help="also write every record, haplotype-aware corrected on its file's graph, to FILE as FASTA (the consensus on "
                          "stdout is unchanged); not with -r 1 / -r 2, --gfa*, --graphviz, --both-strands or --align")
@@ -1167,6 +1271,13 @@ def main(argv=None):
         return 1
     if (a.align is None) != (a.align_out is None) or (a.align_both_strands and a.align is None):
         print("vechat_amd.poa: --align QUERIES and --align-out FILE go together (--align-both-strands with them)", file=sys.stderr)
+        return 1
+    if (a.assign is None) != (a.assign_out is None) or ((a.assign_both_strands or a.assign_scores is not None) and a.assign is None):
+        print("vechat_amd.poa: --assign QUERIES and --assign-out FILE go together (--assign-both-strands and --assign-scores with them)",
+              file=sys.stderr)
+        return 1
+    if a.assign is not None and (a.correct is not None or a.spans is not None or a.weights is not None or a.profile is not None):
+        print("vechat_amd.poa: --assign does not go with --correct, --spans, --weights or --profile", file=sys.stderr)
         return 1
     if a.correct is not None and (a.r != 0 or gfa or a.graphviz is not None or a.both_strands or a.align is not None):
         print("vechat_amd.poa: --correct does not go with -r 1 / -r 2, --gfa / --gfa-consensus, --graphviz, --both-strands or --align "
@@ -1218,6 +1329,7 @@ def main(argv=None):
                 msa = x.msas
             elif not gfa:
                 cons = x.cons
+        start, names = None, a.files
         if resume:
             # one call of vc_poa_run_from: the stored graphs (or none), the records to add (or none), the queries (or none)
             start, names = PoaGraph.load(a.from_graphs, names=True) if a.from_graphs is not None else (None, None)
@@ -1281,6 +1393,18 @@ def main(argv=None):
             strands = dict(strand_ambiguous=True) if a.both_strands else {}
             msa = poa_msa(groups, a.l, a.m, a.n, a.g, device=a.device, include_consensus=a.r == 2, coverage=a.coverage, **gaps, **strands,
                           **with_spans)
+        if a.assign is not None:
+            # a call of its own: every query against every group (the stored graphs with the input files added, with --from-graphs)
+            qrecs = list(seqio.read_sequences(a.assign))
+            flags = capi.VC_POA_ASSIGN_STRANDS if a.assign_both_strands else 0
+            flags |= capi.VC_POA_ASSIGN_SCORES if a.assign_scores is not None else 0
+            _, status, res, table, _ = run_batch_assign(group_batch(groups), query_batch([[data for _, data, _ in qrecs]]), p, flags, start=start)
+            _not_computed(status, True)
+            with open(a.assign_out, "wb") as f:
+                f.write(assign_tsv([name for name, _, _ in qrecs], names, res))
+            if a.assign_scores is not None:
+                with open(a.assign_scores, "wb") as f:
+                    f.write(assign_scores_tsv([name for name, _, _ in qrecs], names, table))
         for k, g in enumerate(graphs if a.graphviz is not None else ()):
             with open(a.graphviz if k == 0 else f"{a.graphviz}.{k + 1}", "wb") as f:
                 f.write(g.to_dot())
