@@ -822,6 +822,136 @@ typedef struct vc_poa_profile_out {   /* library-owned, lifetime as vc_poa_msa_o
 int         vc_poa_run_weighted(const vc_poa_gap_params* p, const vc_poa_weight_in* w /* NULL: none */, const vc_batch* b, vc_result* r,
                                 vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_profile_out* prof /* o, s, g, prof may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------
+ * All-vs-all read overlaps on the device (vechat_amd/csrc/vc_overlap.hip): the first step of both rounds, which the reference's
+ * wrapper leaves to an external command (scripts/vechat:36-49).
+ *
+ * THIS IS THE LIBRARY'S OWN RULE.  It is written in the spirit of
+ *     minimap2 -x ava-ont | awk '$11>=500' | fpa drop --same-name --internalmatch
+ * (minimizer sketch, seeds by shared minimizer, colinear chaining, PAF records, internal matches dropped) and it is NOT a
+ * byte-for-byte restatement of either tool: their heuristics (secondary chains, z-drop, homopolymer compression, occurrence
+ * thresholds as fractions) are left out.  Everything below is integer arithmetic and every tie is decided, so the records are a
+ * function of the input alone; tests/overlap_ref.py restates the rule on the CPU and the device is pinned to it array for array.
+ *
+ * Input: two sequence sets, targets and queries, each as offsets plus bases (any byte; only ACGTacgt make k-mers).  With same_set
+ * the queries ARE the targets: `queries` is not read (it may be NULL), one table is sketched, and pair (i, i) is never produced --
+ * pair (i, j) and pair (j, i) both are, as `--dual=yes` gives them.
+ *
+ * Sketch.  Bases are coded A 0, C 1, G 2, T 3 (either case).  The k-mer whose LAST base is position p exists when the k bases
+ * p - k + 1 .. p are all ACGTacgt.  fw is its 2k-bit value, first base highest; rv is the value of its reverse complement.
+ * fw == rv: the k-mer is skipped -- it holds its place in a window and can never be the minimum.  Otherwise strand = (rv < fw)
+ * and hash = mix(min(fw, rv)), Wang's invertible mix on 2k bits, with mask = 2^(2k) - 1:
+ *     x = (~x + (x << 21)) & mask;   x ^= x >> 24;   x = (x + (x << 3) + (x << 8)) & mask;   x ^= x >> 14;
+ *     x = (x + (x << 2) + (x << 4)) & mask;   x ^= x >> 28;   x = (x + (x << 31)) & mask;
+ * A window is w consecutive positions whose k-mers all exist (so no window contains or crosses a byte outside ACGTacgt, and a
+ * stretch with fewer than w k-mers has none: a sequence shorter than k + w - 1 has no minimizer).  Position p is a minimizer
+ * when its k-mer is not skipped and it is the leftmost minimum hash, over the k-mers not skipped, of at least one window.
+ * vc_overlap_sketch returns the table (hash, seq, pos = p, strand) sorted by (seq, pos).  No homopolymer compression.
+ *
+ * Seeds.  The entries of both tables (of the one table with same_set) are sorted by hash.  A hash with more than max_occ
+ * entries, counted over targets and queries together (over the one table with same_set), is dropped.  For every other hash,
+ * every (target entry, query entry) gives an anchor -- with same_set: every ordered pair of entries of different sequences.
+ * rel_strand = target strand ^ query strand.  The anchor's key is (t_id, q_id, rel_strand) and its positions are (t_pos, q_pos),
+ * t_pos = the target entry's pos, q_pos = the query entry's pos for rel_strand 0 and q_len - pos + k - 2 for rel_strand 1: the
+ * last base of the same k-mer on the reverse-complemented query.
+ * The anchors of a call may not fit the device: the target range is cut into pieces of consecutive targets whose anchors fit
+ * the budget (half of the free device memory; at least one target per piece) and run piece by piece.  Keys never span pieces,
+ * so the records do not depend on the cut.
+ *
+ * Chain.  One problem per key.  Its anchors are sorted by (t_pos, q_pos) and numbered 0 .. n - 1.  With dt = t_pos(i) - t_pos(j),
+ * dq = q_pos(i) - q_pos(j), d = |dt - dq|, anchor j is an admissible predecessor of i when i - lookback <= j < i,
+ * 0 < dt <= max_gap, 0 < dq <= max_gap and d <= bandwidth; then
+ *     gain(j, i) = min(dt, dq, k)        cost(j, i) = d == 0 ? 0 : (d * k) / 100 + ilog2(d) / 2        (integer divisions)
+ *     v(i) = max over admissible j of f(j) + gain - cost, ties to the largest j
+ *     f(i) = v(i), pred(i) = that j   when v(i) > k;        f(i) = k, pred(i) = none   otherwise.
+ * The chain of the key ends at the anchor of maximum f, ties to the smallest i, and follows pred back.  score = that f,
+ * n_anchors = its length; it is kept when score >= min_chain_score and n_anchors >= min_anchors.  One chain per key.
+ *
+ * Record.  With first / last the chain's first and last anchor: t_begin = t_pos(first) - k + 1, t_end = t_pos(last) + 1, and the
+ * same on the query in its orientation, qb and qe; q_begin = qb, q_end = qe for strand 0 and q_begin = q_len - qe,
+ * q_end = q_len - qb for strand 1 (PAF's forward coordinates).  block = max(q_end - q_begin, t_end - t_begin);
+ * matches = k + the sum of gain along the chain.  A record with block < min_overlap is dropped.  With drop_internal, with
+ * left = min(qb, t_begin) and right = min(q_len - qe, t_len - t_end) -- the shorter unanchored end on each side in the query's
+ * orientation.  A chain ends at its outermost shared minimizer, not where the alignment ends: shared minimizers fall along an
+ * overlap like a Poisson process of mean spacing block / n_anchors, so the alignment reaches a further spacing beyond the chain on
+ * average and more than three spacings with probability e^-3 = 5 %.  Each end is therefore granted
+ *     slack = (3 * block) / n_anchors                                                       (integer division)
+ * and the overhangs and the aligned part are  l = max(left - slack, 0),  r = max(right - slack, 0),
+ * aligned = block + (left - l) + (right - r).  A record is an internal match and dropped when
+ *     l > 1000   or   r > 1000   or   5 * aligned < 4 * (aligned + l + r).
+ * (At 6 % errors per read the slack is some 70 bases; at 10 % some 250, where the test on the bare chain ends took 134 of 214
+ * chained true overlaps of 1.5 kb reads for internal matches.)
+ * Containments are kept.  A record that passes this test is a dovetail or a containment up to its overhangs, and a chain ends
+ * where the last shared minimizer happens to lie -- at 6 % errors per read often hundreds of bases short of the read end.  So,
+ * with drop_internal only, the ends are then moved out along the chain's end diagonals to the nearer read end: qb and t_begin
+ * decrease by left, qe and t_end increase by right (before the query is mapped to forward coordinates), and block is taken
+ * again from the new ends; matches stays the chain's.  Without drop_internal the ends are the chain's.
+ * The records are ordered by (q_id, t_id, strand), whatever the launch shape and the budget.
+ *
+ * Envelope: at most VC_OVL_MAX_SEQS sequences per set, each at most VC_OVL_MAX_LEN bases; max_occ <= VC_OVL_MAX_OCC; max_gap and
+ * bandwidth <= VC_OVL_MAX_GAP; fewer than 2^31 minimizers per call and fewer than 2^31 anchors per target (VC_ERR_HIP with a
+ * text, found on the device).
+ * Checked on the host before the device is touched, in this order: p, targets, queries (without same_set), out NULL, or a set
+ * without offsets; offsets that do not start at 0 or decrease, or bases missing beside a non-empty set; k outside 4..28; w outside
+ * 1..64; lookback other than 64; a zero or negative max_occ, max_gap, bandwidth, min_chain_score, min_anchors or min_overlap, or
+ * drop_internal / same_set other than 0 / 1; a limit, a sequence count or a length beyond the envelope: VC_ERR_ARG.
+ * VC_ERR_NO_DEVICE only after these.  vc_overlap_sketch checks its own arguments in the same order.
+ * Lifetime: the library owns every array of vc_overlap_out and vc_overlap_sketch_out -- one set each per process, not
+ * thread-safe.  They stay valid until the next call of the same entry or vc_overlap_release; a failed call leaves every
+ * pointer NULL.  vc_overlap_last_error has the text of the last failure.
+ * Test knobs, read on every vc_overlap call: VC_OVL_BUDGET_MB=x (the budget of one piece in MiB, fractions allowed) and
+ * VC_OVL_LOG (one stderr line per piece, "vc_overlap: piece first=T targets=N anchors=A keys=K records=R").
+ * ------------------------------------------------------------------------------------------------ */
+#define VC_OVL_MAX_SEQS 0x7FFFFFFFull
+#define VC_OVL_MAX_LEN  0x40000000ull
+#define VC_OVL_MAX_OCC  65536
+#define VC_OVL_MAX_GAP  16777216
+typedef struct vc_overlap_seqs {
+    uint64_t        n;               /* sequences                          */
+    const uint64_t* off;             /* [n + 1] into bases, off[0] == 0    */
+    const uint8_t*  bases;
+} vc_overlap_seqs;
+typedef struct vc_overlap_params {   /* vc_overlap_default_params fills in the defaults named here                    */
+    int32_t device;                  /* 0                                                                            */
+    int32_t k;                       /* 15   (4..28)                                                                 */
+    int32_t w;                       /* 5    (1..64)                                                                 */
+    int32_t max_occ;                 /* 100                                                                          */
+    int32_t max_gap;                 /* 5000                                                                         */
+    int32_t bandwidth;               /* 500                                                                          */
+    int32_t lookback;                /* 64: the only value accepted                                                  */
+    int32_t min_chain_score;         /* 40                                                                           */
+    int32_t min_anchors;             /* 3                                                                            */
+    int32_t min_overlap;             /* 500                                                                          */
+    int32_t drop_internal;           /* 1                                                                            */
+    int32_t same_set;                /* 0; 1: the queries are the targets, pair (i, i) is never produced             */
+} vc_overlap_params;
+typedef struct vc_overlap_out {      /* library-owned; [n] each, ordered by (q_id, t_id, strand)                      */
+    uint64_t        n;
+    const uint32_t* q_id;
+    const uint32_t* t_id;
+    const uint8_t*  strand;          /* 1: the query is reverse-complemented                                         */
+    const uint32_t* q_begin; const uint32_t* q_end;      /* forward coordinates, end exclusive                       */
+    const uint32_t* t_begin; const uint32_t* t_end;
+    const uint32_t* n_anchors;
+    const int32_t*  score;
+    const uint32_t* matches;         /* PAF column 10                                                                */
+    const uint32_t* block;           /* PAF column 11                                                                */
+    uint64_t n_minimizers, n_anchors_total, n_keys_total;     /* what the call went through                          */
+} vc_overlap_out;
+typedef struct vc_overlap_sketch_out {   /* library-owned; [n] each, sorted by (seq, pos)                             */
+    uint64_t        n;
+    const uint64_t* hash;
+    const uint32_t* seq;
+    const uint32_t* pos;             /* of the k-mer's last base                                                     */
+    const uint8_t*  strand;          /* 1: the reverse complement is the smaller value                               */
+} vc_overlap_sketch_out;
+void        vc_overlap_default_params(vc_overlap_params* p);
+int         vc_overlap(const vc_overlap_params* p, const vc_overlap_seqs* targets, const vc_overlap_seqs* queries /* not read with same_set */,
+                       vc_overlap_out* out);
+int         vc_overlap_sketch(int32_t device, int32_t k, int32_t w, const vc_overlap_seqs* s, vc_overlap_sketch_out* o);
+const char* vc_overlap_last_error(void);
+void        vc_overlap_release(void);
+
 #ifdef __cplusplus
 }
 #endif

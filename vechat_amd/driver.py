@@ -10,9 +10,11 @@ corrected FASTA of round i is the input of round i+1 (reads.corrected.tmp<i>.fa)
 the temporaries are removed (scripts/vechat:371-397).
 
 The external tools are commands, not libraries, exactly as in the reference (minimap2 | awk | fpa, yacrd): this module
-only builds their command lines.  They are pluggable templates so that another overlapper -- or the stub of
-tests/test_driver.py -- can stand in:
-  --overlapper-r1 / --overlapper-r2   fields {platform} {targets} {reads} {threads} {out} {min_ovlplen} {min_identity}
+only builds their command lines.  `--overlapper device` replaces the minimap2 pipeline of both rounds by this package's own
+overlapper on the GPU (`python -m vechat_amd.overlap`, a child process like the others), so a FASTQ nobody has overlapped
+goes to corrected reads without minimap2 or fpa installed.  The commands are pluggable templates so that another overlapper
+-- or the stub of tests/test_driver.py -- can stand in:
+  --overlapper-r1 / --overlapper-r2   fields {platform} {targets} {reads} {threads} {out} {min_ovlplen} {min_identity} {python}
   --polisher                          the command that replaces build/bin/vechat_racon; default: this package's
                                       `python -m vechat_amd.polish` (one process per GPU under torch.distributed.run when --gpus > 1)
 Nothing here computes on the CPU what the reference computes in vechat_racon; without a GPU the polisher command fails.
@@ -33,6 +35,13 @@ OVERLAPPER_R1_BASE = ("minimap2 -cx ava-{platform} --dual=yes {targets} {reads} 
                       "awk '$11>=500 && $10/$11>={min_identity}'|cut -f 1-12|fpa drop --same-name --internalmatch  - >{out}")
 OVERLAPPER_R2 = ("minimap2 -cx ava-{platform} --dual=yes {targets} {reads} -t {threads} 2>/dev/null|"
                  "awk '$11>={min_ovlplen} && $10/$11>={min_identity}'|cut -f 1-12|fpa drop --same-name --internalmatch  - >{out}")
+# --overlapper device: this package's own overlapper (vechat_amd.overlap over vc_overlap), a fresh child process per call; the
+# same three cases.  --min-identity makes it align every record on the device, so columns 10 and 11 are exact where a filter reads them
+OVERLAPPER_DEVICE_R1 = "{python} -m vechat_amd.overlap -x ava-{platform} --threads {threads} {targets} {reads} >{out}"
+OVERLAPPER_DEVICE_R1_BASE = ("{python} -m vechat_amd.overlap -x ava-{platform} --min-identity {min_identity} --threads {threads} "
+                             "{targets} {reads} >{out}")
+OVERLAPPER_DEVICE_R2 = ("{python} -m vechat_amd.overlap -x ava-{platform} --min-overlap {min_ovlplen} --min-identity {min_identity} "
+                        "--threads {threads} {targets} {reads} >{out}")
 
 
 def fq_or_fa(path):
@@ -147,12 +156,14 @@ def run_error_correction(a, sequences, chunk_targets, corrected_file, iteration,
     linear = a.linear or iteration == 2                      # the second iteration computes the consensus (scripts/vechat:26-27)
     overlap = os.path.join(workdir, "overlap.paf")
     fields = dict(platform=a.platform, targets=shlex.quote(chunk_targets), reads=shlex.quote(sequences), threads=a.threads,
-                  out=shlex.quote(overlap))
+                  out=shlex.quote(overlap), python=shlex.quote(sys.executable))
+    device = getattr(a, "overlapper", "minimap2") == "device"
     if iteration == 1:
-        tmpl = a.overlapper_r1 or (OVERLAPPER_R1_BASE if a.base else OVERLAPPER_R1)
+        tmpl = a.overlapper_r1 or ((OVERLAPPER_DEVICE_R1_BASE if a.base else OVERLAPPER_DEVICE_R1) if device else
+                                   (OVERLAPPER_R1_BASE if a.base else OVERLAPPER_R1))
         cmd = tmpl.format(min_identity=a.min_identity, min_ovlplen=500, **fields)
     else:
-        tmpl = a.overlapper_r2 or OVERLAPPER_R2
+        tmpl = a.overlapper_r2 or (OVERLAPPER_DEVICE_R2 if device else OVERLAPPER_R2)
         cmd = tmpl.format(min_identity=a.min_identity_cns, min_ovlplen=a.min_ovlplen_cns, **fields)
     _sh(cmd, workdir)
     sub_reads = extract_sub_sequences(sequences, overlap, chunk_targets, workdir) if a.split else sequences
@@ -243,6 +254,8 @@ def main(argv=None):
     ap.add_argument("--gpus", default=1, type=int, help="GPUs of this node for the polisher (one process per GPU)")
     ap.add_argument("--master-port", default=29561, type=int)
     ap.add_argument("--workdir", default=".", help="where the round files live (the reference uses the current directory)")
+    ap.add_argument("--overlapper", default="minimap2", choices=("minimap2", "device"), help="minimap2: the reference's minimap2|awk|fpa "
+                    "pipelines; device: this package's overlapper on the GPU (python -m vechat_amd.overlap), no external tool needed")
     ap.add_argument("--overlapper-r1", default=None, help="command template replacing the minimap2|awk|fpa pipeline of round 1")
     ap.add_argument("--overlapper-r2", default=None, help="... of round 2")
     ap.add_argument("--polisher", default=None, help="command replacing `python -m vechat_amd.polish`")
