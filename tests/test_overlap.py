@@ -5,10 +5,13 @@ import ctypes as C
 import functools
 import io
 import os
+import re
+import tempfile
 
 import numpy as np
 import pytest
 
+import align_ref
 import overlap_cases as OC
 import overlap_ref as R
 from test_driver import simulate
@@ -47,11 +50,7 @@ def test_restated_overlaps_on_the_case_table(name):
     c = OC.OVERLAP_CASES[name]
     r = R.overlaps(c["targets"], c["queries"], **c["params"])
     got = rows(r)
-    assert got == sorted(got, key=lambda x: x[:3])
-    qs = c["targets"] if c["queries"] is None else c["queries"]
-    for q, t, st, qb, qe, tb, te, n, score, matches, block in got:
-        assert 0 <= qb < qe <= len(qs[q]) and 0 <= tb < te <= len(c["targets"][t]) and block == max(qe - qb, te - tb) and matches <= block
-        assert c["queries"] is not None or q != t
+    record_invariants(got, c["targets"], c["queries"])
     if c["expect"] is not None:
         assert got == c["expect"]
 
@@ -71,9 +70,9 @@ def test_restated_records_of_whole_reads():
 
 # --------------------------------------------------------------------------------------------------------- recall
 @functools.lru_cache(maxsize=None)
-def simulated(err, seed=11):
-    """60 reads of 3 kb from a 20 kb genome (two haplotypes), both strands: (sequences, (start, end, strand) per read, records)"""
-    import tempfile
+def simulated(err, seed=11, **params):
+    """60 reads of 3 kb from a 20 kb genome (two haplotypes), both strands: (sequences, (start, end, strand) per read, records of
+    the restatement under `params`)"""
     with tempfile.TemporaryDirectory() as d:
         recs, _ = simulate(os.path.join(d, "sim.fq"), n_reads=60, genome_len=20000, read_len=3000, err=err, seed=seed)
     info = []
@@ -81,11 +80,11 @@ def simulated(err, seed=11):
         a = n.split("_")
         info.append((int(a[1]), int(a[2]), a[3]))
     seqs = tuple(s for _, s in recs)
-    return seqs, tuple(info), R.overlaps(list(seqs))
+    return seqs, tuple(info), R.overlaps(list(seqs), **params)
 
 
-def recall(err, min_len):
-    seqs, info, ov = simulated(err)
+def recall(err, min_len, **params):
+    seqs, info, ov = simulated(err, **params)
     got = {(int(r["q_id"]), int(r["t_id"])): r for r in ov}
     true = found = 0
     worst = 0
@@ -121,6 +120,189 @@ def test_recall_on_simulated_reads():
     assert found == true
     assert worst <= 100
     assert false == 0
+
+
+def test_recall_on_simulated_reads_ava_pb():
+    """The same four assertions at the product's default preset (ava-pb: k 19, w 5), on reads with 1 % errors: every true overlap of
+    >= 2000 bp with the right strand and its ends within 100 bp of the interpolated truth, no false pair."""
+    found, true, false, worst = recall(0.01, 2000, k=19, w=5)
+    print(f"1 % errors, k 19 w 5, >= 2000 bp: found {found} of {true}, false pairs {false}, worst end {worst:.1f} bp, "
+          f"{len(simulated(0.01, k=19, w=5)[2])} records")
+    assert true > 300
+    assert found == true
+    assert worst <= 100
+    assert false == 0
+
+
+# ------------------------------------------------------------------------------- what the device tests are held to
+# Shared with tests/test_overlap_gpu.py: each restatement is computed once a process.  The conditions that keep a device test from
+# passing on an empty or one-sided answer are checked here, on the restatement, with no device.
+CLASSES = ((4, 1), (4, 5), (16, 5), (17, 5), (19, 5), (19, 1), (28, 5), (28, 64), (15, 64))
+
+
+@functools.lru_cache(maxsize=None)
+def sixteen_reads():
+    """16 reads of 1.2 kb with 2 % errors from a 4 kb genome, both strands"""
+    with tempfile.TemporaryDirectory() as d:
+        recs, _ = simulate(os.path.join(d, "sim.fq"), n_reads=16, genome_len=4000, read_len=1200, err=0.02, seed=5)
+    return tuple(s for _, s in recs)
+
+
+@functools.lru_cache(maxsize=None)
+def restated_class(k, w):
+    """the 16 reads against themselves at (k, w), min_overlap 300: (minimizer table, records, seeds by key)"""
+    seqs = list(sixteen_reads())
+    return R.sketch(seqs, k, w), R.overlaps(seqs, None, k=k, w=w, min_overlap=300), R.seeds(seqs, seqs, k, w, R.DEFAULTS["max_occ"], 1)
+
+
+def class_preconditions(k, w):
+    tab, recs, keys = restated_class(k, w)
+    assert len(tab) and set(int(s) for s in recs["strand"]) == {0, 1}
+    if k >= 17:
+        assert int(tab["hash"].max()) >= 1 << 32
+    if (k, w) == (4, 1):
+        assert len(keys) >= 400 and len(recs) >= 1
+    else:
+        assert len(recs) >= 50
+    return tab, recs, keys
+
+
+@pytest.mark.parametrize("k,w", CLASSES)
+def test_every_k_and_w_class_has_something_to_compare(k, w):
+    tab, recs, keys = class_preconditions(k, w)
+    print(f"k {k} w {w}: {len(tab)} minimizers, {len(recs)} records, {sum(len(a) for a in keys.values())} anchors in {len(keys)} keys")
+
+
+@functools.lru_cache(maxsize=None)
+def restated_repeats(max_occ):
+    reads = OC.repeat_reads()
+    return R.overlaps(reads, None, min_overlap=300, max_occ=max_occ), R.seeds(reads, reads, R.DEFAULTS["k"], R.DEFAULTS["w"], max_occ, 1)
+
+
+def repeat_preconditions():
+    (full, keys), (capped, _) = restated_repeats(R.DEFAULTS["max_occ"]), restated_repeats(20)
+    assert max(len(a) for a in keys.values()) >= 1000
+    assert len(full) and len(capped) and rows(full) != rows(capped)
+
+
+def test_repeat_reads_fill_keys_and_max_occ_decides():
+    repeat_preconditions()
+    full, keys = restated_repeats(R.DEFAULTS["max_occ"])
+    print(f"repeat reads: largest key {max(len(a) for a in keys.values())} anchors, {len(full)} records, {len(restated_repeats(20)[0])} with max_occ 20")
+
+
+def _restate_config(c):
+    P = dict(R.DEFAULTS, **c["params"])
+    same = c["queries"] is None
+    keys = R.seeds(c["targets"], c["targets"] if same else c["queries"], P["k"], P["w"], P["max_occ"], 1 if same else 0)
+    tabs = [R.sketch(s, P["k"], P["w"]) for s in ((c["targets"],) if same else (c["targets"], c["queries"]))]
+    return R.overlaps(c["targets"], c["queries"], **c["params"]), sum(len(a) for a in keys.values()), len(keys), tabs
+
+
+@functools.lru_cache(maxsize=None)
+def restated_sweep():
+    """per configuration of overlap_cases.sweep(): (records, anchors, keys, [minimizer table of each set]); about a second in all"""
+    return tuple(_restate_config(c) for c in OC.sweep())
+
+
+def record_invariants(got, targets, queries):
+    assert got == sorted(got, key=lambda x: x[:3])
+    qs = targets if queries is None else queries
+    for q, t, st, qb, qe, tb, te, n, score, matches, block in got:
+        assert 0 <= qb < qe <= len(qs[q]) and 0 <= tb < te <= len(targets[t]) and block == max(qe - qb, te - tb) and matches <= block
+        assert queries is not None or q != t
+
+
+def test_sweep_configurations_give_records():
+    """the 24 configurations of the seeded sweep: what they draw, the invariants of every record, and enough records that the device
+    test compares something -- at least 16 configurations with a record and 200 records together"""
+    cs, res = OC.sweep(), restated_sweep()
+    assert len(cs) == len(res) == 24
+    for c, (recs, _, _, _) in zip(cs, res):
+        record_invariants(rows(recs), c["targets"], c["queries"])
+        reads = c["targets"] + (c["queries"] or [])
+        assert b"" in reads and any(0 < len(r) < c["params"]["k"] for r in reads) and all(len(r) <= 901 for r in reads)
+    assert {c["budget_mb"] for c in cs} == {None, 0.01} and {c["queries"] is None for c in cs} == {False, True}
+    assert any(r != r.upper() for c in cs for r in c["targets"]) and any(set(r) - set(b"ACGTacgt") for c in cs for r in c["targets"])
+    counts = [len(recs) for recs, _, _, _ in res]
+    print("records per configuration:", counts)
+    assert sum(1 for n in counts if n) >= 16 and sum(counts) >= 200
+    assert any(int(r["strand"]) for recs, _, _, _ in res for r in recs)
+
+
+def test_twin_kmers_differ_above_bit_31_only():
+    """what the case hashes_equal_in_their_low_32_bits stands on, checked with the restatement's own hash: two different 19-mers a pair,
+    hashes equal below bit 32 and different above, and one minimizer entry for each k-mer of the four reads"""
+    for (a, b, ha, hb), bit in zip(OC._tw, (32, 37)):
+        assert a != b and len(a) == len(b) == 19
+        got = [R.kmers(s, 19)[18] for s in (a, b)]
+        assert [g[0] for g in got] == [ha, hb] and ha ^ hb == 1 << bit and ha & 0xFFFFFFFF == hb & 0xFFFFFFFF
+        assert R.mix(OC.unmix(ha, 19), 19) == ha
+    c = OC.OVERLAP_CASES["hashes_equal_in_their_low_32_bits"]
+    assert [len(R.sketch([s], 19, 1)) for s in c["targets"] + c["queries"]] == [2, 2, 2, 2]
+    keys = R.seeds(c["targets"], c["queries"], 19, 1, 100, 0)
+    assert {k: len(a) for k, a in keys.items()} == {(0, 0, 0): 1, (1, 1, 0): 1}
+
+
+def test_both_strands_of_one_pair():
+    """target X + Y against query X + rc(Y): one pair, two keys, a record on each strand"""
+    c = OC.OVERLAP_CASES["both_strands_of_one_pair"]
+    got = rows(R.overlaps(c["targets"], c["queries"], **c["params"]))
+    assert [x[:3] for x in got] == [(0, 0, 0), (0, 0, 1)]
+
+
+# ---- the command line: two files, ava-pb
+CLI_SEED = 7          # 11 and 12 PAF lines on both strands, 4 records dropped for their names
+CLI_ARGS = (("-x", "ava-pb", "--min-overlap", "400", "--min-identity", "0.9", "targets.fa", "reads.fa"),
+            ("-x", "ava-pb", "--min-overlap", "400", "targets.fa", "targets.fa"))
+_COMP = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+@functools.lru_cache(maxsize=None)
+def command_line_files(seed=None):
+    """((name, sequence) of targets.fa, of reads.fa): six reads; reads 2..5 again under their own names and read 1 under a new one"""
+    with tempfile.TemporaryDirectory() as d:
+        recs, _ = simulate(os.path.join(d, "sim.fa"), n_reads=6, genome_len=1500, read_len=800, err=0.02, seed=CLI_SEED if seed is None else seed, fastq=False)
+    return tuple(recs), tuple(recs[2:6]) + (("elsewhere", recs[1][1]),)
+
+
+@functools.lru_cache(maxsize=None)
+def command_line_expected(seed=None):
+    """The PAF text of the two commands of CLI_ARGS, from the restatement and the aligner's CPU DP alone, and the number of records
+    dropped for their names.  Nothing here calls into vechat_amd.overlap."""
+    targets, reads = command_line_files(seed)
+    texts, dropped = [], 0
+    for queries, identity in ((reads, 0.9), (None, None)):
+        qs = targets if queries is None else queries
+        recs = rows(R.overlaps([s for _, s in targets], None if queries is None else [s for _, s in queries], k=19, w=5, min_overlap=400))
+        kept = [r for r in recs if qs[r[0]][0] != targets[r[1]][0]]
+        dropped += len(recs) - len(kept)
+        lines = []
+        for q, t, st, qb, qe, tb, te, _, _, matches, block in kept:
+            if identity is not None:
+                piece = qs[q][1][qb:qe]
+                cigar, dist = align_ref.align(piece.translate(_COMP)[::-1] if st else piece, targets[t][1][tb:te])
+                block = sum(int(x) for x in re.findall(r"(\d+)[MID]", cigar))
+                matches = block - dist
+                if not (float(matches) >= identity * float(block) and block >= 400):
+                    continue
+            lines.append("\t".join(str(x) for x in (qs[q][0], len(qs[q][1]), qb, qe, "-" if st else "+", targets[t][0], len(targets[t][1]), tb, te, matches, block, 255)) + "\n")
+        texts.append("".join(lines))
+    return tuple(texts), dropped
+
+
+def command_line_preconditions():
+    texts, dropped = command_line_expected()
+    assert dropped >= 1
+    for text in texts:
+        lines = text.splitlines()
+        assert len(lines) >= 4 and {l.split("\t")[4] for l in lines} == {"+", "-"}
+    return texts
+
+
+def test_command_line_case_has_lines_on_both_strands_and_a_name_to_drop():
+    texts = command_line_preconditions()
+    print(f"ava-pb command lines: {[len(t.splitlines()) for t in texts]} PAF lines expected, {command_line_expected()[1]} records dropped for their names")
 
 
 # ------------------------------------------------------------------------------------------------------- the C ABI

@@ -1,8 +1,12 @@
 """The overlapper on the device, pinned to the CPU restatement of its rule (tests/overlap_ref.py) array for array: the hand-built
-cases of tests/overlap_cases.py, a simulated read set with the default budget and cut into target pieces, identity() against
-the aligner's CPU DP, and one run of the two-round driver that never leaves the device for its overlaps."""
+cases of tests/overlap_cases.py, a simulated read set with the default budget and cut into target pieces, every class of k and w
+(hashes of 8 to 56 bits), reads full of tandem repeats, a seeded sweep over all parameters, many calls in one process, the command
+line with two files, identity() against the aligner's CPU DP, and one run of the two-round driver that never leaves the device
+for its overlaps."""
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -11,8 +15,11 @@ import align_ref
 import overlap_cases as OC
 import overlap_ref as R
 from test_driver import _fit_distance, simulate
+import test_overlap as TO
 from test_overlap import simulated
-from vechat_amd import driver, overlap
+from vechat_amd import capi, driver, overlap
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 _COMP = bytes.maketrans(b"ACGT", b"TGCA")
@@ -74,6 +81,112 @@ def test_simulated_reads_equal_the_restatement_whole_and_in_pieces(built, monkey
     two = overlap.find_overlaps(list(seqs[:20]), list(seqs[:20]))
     same_records(two, R.overlaps(list(seqs[:20]), list(seqs[:20])))
     assert sum(1 for r in two if r["q_id"] == r["t_id"] and r["strand"] == 0) == 20
+
+
+def same_counts(stats, keys):
+    assert stats["anchors"] == sum(len(a) for a in keys.values()) and stats["keys"] == len(keys)
+
+
+@pytest.mark.parametrize("k,w", TO.CLASSES)
+def test_every_k_and_w_class_equals_the_restatement(built, k, w, monkeypatch, capfd):
+    """hashes of 8 bits (k 4: a few buckets, all beyond max_occ or nearly), of exactly 32 (k 16), of 34, 38 and 56 (k 17, 19, 28), every
+    k-mer a minimizer (w 1) and the widest window (w 64): the minimizer table, the records and the seed counters"""
+    tab, want, keys = TO.class_preconditions(k, w)
+    seqs = list(TO.sixteen_reads())
+    monkeypatch.setenv("VC_OVL_LOG", "1")
+    monkeypatch.delenv("VC_OVL_BUDGET_MB", raising=False)
+    same_records(overlap.sketch(seqs, k=k, w=w), tab)
+    stats = {}
+    same_records(overlap.find_overlaps(seqs, None, stats=stats, k=k, w=w, min_overlap=300), want)
+    same_counts(stats, keys)
+    assert stats["minimizers"] == len(tab) and len(pieces(capfd)) == 1
+    if (k, w) == (19, 5):                                    # the product's preset once more, cut into target pieces
+        monkeypatch.setenv("VC_OVL_BUDGET_MB", "0.05")       # 936 anchors a piece
+        stats = {}
+        same_records(overlap.find_overlaps(seqs, None, stats=stats, k=k, w=w, min_overlap=300), want)
+        same_counts(stats, keys)
+        cut = pieces(capfd)
+        assert len(cut) >= 3 and sum(cut) == len(seqs)
+
+
+@pytest.mark.parametrize("max_occ", (100, 20))
+def test_repeat_reads_equal_the_restatement(built, max_occ, monkeypatch):
+    """reads across 30 copies of a 37-base unit: buckets at and beyond max_occ, a key of thousands of anchors with most of them off
+    the diagonal, anchors that share their t_pos -- and max_occ decides which records there are"""
+    TO.repeat_preconditions()
+    monkeypatch.delenv("VC_OVL_BUDGET_MB", raising=False)
+    want, keys = TO.restated_repeats(max_occ)
+    stats = {}
+    same_records(overlap.find_overlaps(OC.repeat_reads(), None, stats=stats, min_overlap=300, max_occ=max_occ), want)
+    same_counts(stats, keys)
+
+
+@pytest.mark.parametrize("part", range(4))
+def test_seeded_sweep_equals_the_restatement(built, part, monkeypatch):
+    """24 configurations from one seed (overlap_cases.sweep; tests/test_overlap.py holds them to >= 16 with records and >= 200 records),
+    six a part: the minimizer tables, the records and the seed counters.  Every mismatch of a part is reported, not the first."""
+    cs, res = OC.sweep(), TO.restated_sweep()
+    bad = []
+    for i in range(6 * part, 6 * part + 6):
+        c, (want, anchors, keys, tabs) = cs[i], res[i]
+        if c["budget_mb"] is None:
+            monkeypatch.delenv("VC_OVL_BUDGET_MB", raising=False)
+        else:
+            monkeypatch.setenv("VC_OVL_BUDGET_MB", str(c["budget_mb"]))
+        stats = {}
+        got = overlap.find_overlaps(c["targets"], c["queries"], stats=stats, **c["params"])
+        sk = [overlap.sketch(s, k=c["params"]["k"], w=c["params"]["w"]) for s in ((c["targets"],) if c["queries"] is None else (c["targets"], c["queries"]))]
+        why = []
+        if got.dtype != want.dtype or len(got) != len(want) or any(not np.array_equal(got[f], want[f]) for f in want.dtype.names):
+            why.append(("records", len(got), len(want)))
+        if (stats["anchors"], stats["keys"]) != (anchors, keys):
+            why.append(("counters", stats["anchors"], stats["keys"], anchors, keys))
+        if any(a.dtype != b.dtype or len(a) != len(b) or any(not np.array_equal(a[f], b[f]) for f in b.dtype.names) for a, b in zip(sk, tabs)):
+            why.append(("sketch", [len(a) for a in sk], [len(b) for b in tabs]))
+        if why:
+            bad.append((i, c["params"], c["queries"] is None, c["budget_mb"], why))
+    assert not bad, bad
+
+
+def test_many_calls_in_one_process(built, monkeypatch):
+    """The library keeps one set of result arrays a process: a small answer after a large one, an empty one, a sketch in between,
+    a call after vc_overlap_release() -- each equal to the restatement in length and content, the first and the last to each other."""
+    monkeypatch.delenv("VC_OVL_BUDGET_MB", raising=False)
+    seqs = list(TO.sixteen_reads())
+    tab, want, _ = TO.class_preconditions(19, 5)
+    first = overlap.find_overlaps(seqs, None, k=19, w=5, min_overlap=300)
+    assert len(first) == len(want) >= 50
+    same_records(first, want)
+    small, none = OC.OVERLAP_CASES["block_of_500_and_499"], OC.OVERLAP_CASES["bucket_of_one_sequence_only"]
+    got = overlap.find_overlaps(small["targets"], small["queries"], **small["params"])
+    assert [tuple(int(x) for x in r) for r in got] == small["expect"] and len(got) == 1
+    same_records(got, R.overlaps(small["targets"], small["queries"], **small["params"]))
+    got = overlap.find_overlaps(none["targets"], none["queries"], **none["params"])
+    assert none["expect"] == [] and len(got) == 0
+    same_records(got, R.overlaps(none["targets"], none["queries"], **none["params"]))
+    sk = overlap.sketch(seqs, k=19, w=5)
+    assert len(sk) == len(tab) > 0
+    same_records(sk, tab)
+    overlap.declare(capi.load_hip()).vc_overlap_release()
+    last = overlap.find_overlaps(seqs, None, k=19, w=5, min_overlap=300)
+    assert len(last) == len(want)
+    same_records(last, want)
+    same_records(last, first)
+
+
+def test_command_line_with_two_files_ava_pb(built, tmp_path):
+    """`python -m vechat_amd.overlap -x ava-pb` as a process of its own, with two different files and --min-identity and with one file
+    twice: stdout is, byte for byte, the PAF text tests/test_overlap.py works out from the restatement and the aligner's CPU DP."""
+    want = TO.command_line_preconditions()
+    targets, reads = TO.command_line_files()
+    for name, recs in (("targets.fa", targets), ("reads.fa", reads)):
+        (tmp_path / name).write_bytes(b"".join(b">%s\n%s\n" % (n.encode(), s) for n, s in recs))
+    env = dict(os.environ, PYTHONPATH=ROOT + (os.pathsep + os.environ["PYTHONPATH"] if os.environ.get("PYTHONPATH") else ""))
+    env.pop("VC_OVL_BUDGET_MB", None)
+    for args, text in zip(TO.CLI_ARGS, want):
+        p = subprocess.run([sys.executable, "-m", "vechat_amd.overlap", *args], cwd=tmp_path, env=env, capture_output=True, timeout=120)
+        assert p.returncode == 0, p.stderr.decode()
+        assert p.stdout == text.encode(), (args, p.stdout.decode().splitlines()[:3], text.splitlines()[:3])
 
 
 def test_identity_against_the_cpu_dp(built):
