@@ -952,6 +952,91 @@ int         vc_overlap_sketch(int32_t device, int32_t k, int32_t w, const vc_ove
 const char* vc_overlap_last_error(void);
 void        vc_overlap_release(void);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scrubbing of chimeric reads on the device (vechat_amd/csrc/vc_scrub.hip): the step the reference's wrapper leaves to
+ * `minimap2 -g ... | yacrd -c C -n F scrubb` (scripts/vechat:187-201).  A chimeric read joins two loci; no other read covers its
+ * junction, so the junction shows as a stretch of low coverage strictly inside the read, and the read is cut there.
+ *
+ * THIS IS THE LIBRARY'S OWN RULE, in the spirit of `yacrd -c C -n F scrubb` (coverage from overlap intervals, badly covered
+ * stretches, reads cut at them or dropped) and NOT a restatement of it.  Everything is integer arithmetic and every case is
+ * decided; tests/scrub_ref.py restates the rule position by position and the device is pinned to it array for array.
+ *
+ * Input.  n reads with lengths len[r] (each at most VC_OVL_MAX_LEN, n at most VC_OVL_MAX_SEQS) and m intervals
+ * (read, begin, end) with read < n and 0 <= begin < end <= len[read], in any order, 2 m < 2^31.  An interval says "another read
+ * overlaps this stretch"; where intervals come from is the caller's business.  Optionally the bases of the reads as offsets plus
+ * bytes (off[n + 1] with off[r + 1] - off[r] == len[r], and bases), and optionally their qualities, bytes under the same offsets.
+ *
+ * Coverage and bad regions.  cov_r(p) is the number of intervals of read r with begin <= p < end.  Position p is BAD when
+ * cov_r(p) <= coverage (the threshold c).  The bad regions of a read are the maximal runs of bad positions, as [b, e).  A read
+ * with no interval is one bad region [0, len).  A read of length 0 has no region.
+ *
+ * Class of a read.  bad_total is the sum of e - b over its regions.
+ *     VC_SCRUB_NOT_COVERED 3   1000 * bad_total > max_bad_permille * len (in 64 bits); this is decided first
+ *     VC_SCRUB_CHIMERIC    2   otherwise, some region has b > 0 and e < len
+ *     VC_SCRUB_BAD_ENDS    1   otherwise, at least one region
+ *     VC_SCRUB_CLEAN       0   otherwise
+ *
+ * Pieces.  A NOT_COVERED read has no pieces.  For every other read the pieces are the maximal runs of positions that are not
+ * bad and whose length is at least min_piece, in order.
+ *
+ * Output, library-owned.  Regions (read, begin, end) ordered by (read, begin), with reg_off[n + 1] into them; per read klass and
+ * bad_total; pieces (read, begin, end) ordered the same way, with pc_off[n_pieces + 1] into the cut bytes (filled in whether or
+ * not bases were given).  With bases, pc_bases holds the bases of every piece back to back; with qualities, pc_quals the same of
+ * the qualities.  Without, the pointer is NULL.  The result is a function of the input alone, not of the order of the intervals
+ * and not of any launch shape.
+ *
+ * Checked on the host before the device is touched, in this order: p, in or out NULL, lengths NULL with n > 0, an interval array
+ * NULL with m > 0, bases without offsets, qualities without bases; offsets that do not start at 0, decrease, or disagree with the
+ * lengths; coverage outside 0..2^30, max_bad_permille outside 0..1000, min_piece below 1; an interval with read >= n, empty, or
+ * ending beyond its read; n, a length or m beyond the envelope: VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these.  Device memory is
+ * taken per call, with no piece-by-piece budget: a call whose buffers the device refuses is VC_ERR_HIP with a text.
+ * Lifetime: the library owns every array of vc_scrub_out -- one set per process, not thread-safe -- until the next vc_scrub call
+ * or vc_scrub_release; a failed call leaves every pointer NULL.  vc_scrub_last_error has the text of the last failure.
+ * Test knob, read on every call: VC_SCRUB_LOG (one stderr line, "vc_scrub: intervals=M events=E segments=S regions=R pieces=P").
+ * ------------------------------------------------------------------------------------------------ */
+#define VC_SCRUB_CLEAN       0
+#define VC_SCRUB_BAD_ENDS    1
+#define VC_SCRUB_CHIMERIC    2
+#define VC_SCRUB_NOT_COVERED 3
+typedef struct vc_scrub_params {     /* vc_scrub_default_params fills in the defaults named here                      */
+    int32_t device;                  /* 0                                                                            */
+    int32_t coverage;                /* 0    the threshold c (0..2^30): a position covered c times or fewer is bad   */
+    int32_t max_bad_permille;        /* 400  (0..1000)                                                               */
+    int32_t min_piece;               /* 1    (at least 1)                                                            */
+} vc_scrub_params;
+typedef struct vc_scrub_in {
+    uint64_t        n;               /* reads                                                                        */
+    const uint32_t* len;             /* [n]                                                                          */
+    uint64_t        m;               /* intervals                                                                    */
+    const uint32_t* read;            /* [m]                                                                          */
+    const uint32_t* begin;           /* [m]                                                                          */
+    const uint32_t* end;             /* [m] exclusive                                                                */
+    const uint64_t* off;             /* NULL, or [n + 1] into bases and quals                                        */
+    const uint8_t*  bases;           /* NULL: nothing is cut                                                         */
+    const uint8_t*  quals;           /* NULL: no qualities                                                           */
+} vc_scrub_in;
+typedef struct vc_scrub_out {        /* library-owned                                                                */
+    uint64_t        n_regions;
+    const uint32_t* reg_read;        /* [n_regions] ordered by (read, begin)                                         */
+    const uint32_t* reg_begin;
+    const uint32_t* reg_end;
+    const uint64_t* reg_off;         /* [n + 1] the regions of read r are reg_off[r] .. reg_off[r + 1]               */
+    const uint8_t*  klass;           /* [n] VC_SCRUB_*                                                               */
+    const uint32_t* bad_total;       /* [n]                                                                          */
+    uint64_t        n_pieces;
+    const uint32_t* pc_read;         /* [n_pieces] ordered by (read, begin)                                          */
+    const uint32_t* pc_begin;
+    const uint32_t* pc_end;
+    const uint64_t* pc_off;          /* [n_pieces + 1] into pc_bases / pc_quals                                      */
+    const uint8_t*  pc_bases;        /* NULL without bases                                                           */
+    const uint8_t*  pc_quals;        /* NULL without qualities                                                       */
+    uint64_t n_intervals, n_events, n_segments;               /* what the call went through                          */
+} vc_scrub_out;
+void        vc_scrub_default_params(vc_scrub_params* p);
+int         vc_scrub(const vc_scrub_params* p, const vc_scrub_in* in, vc_scrub_out* out);
+const char* vc_scrub_last_error(void);
+void        vc_scrub_release(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ the temporaries are removed (scripts/vechat:371-397).
 The external tools are commands, not libraries, exactly as in the reference (minimap2 | awk | fpa, yacrd): this module
 only builds their command lines.  `--overlapper device` replaces the minimap2 pipeline of both rounds by this package's own
 overlapper on the GPU (`python -m vechat_amd.overlap`, a child process like the others), so a FASTQ nobody has overlapped
-goes to corrected reads without minimap2 or fpa installed.  The commands are pluggable templates so that another overlapper
+goes to corrected reads without minimap2 or fpa installed; `--scrubber device` does the same for `--scrub` (`python -m vechat_amd.scrub`
+in place of minimap2 and yacrd).  The commands are pluggable templates so that another overlapper
 -- or the stub of tests/test_driver.py -- can stand in:
   --overlapper-r1 / --overlapper-r2   fields {platform} {targets} {reads} {threads} {out} {min_ovlplen} {min_identity} {python}
   --polisher                          the command that replaces build/bin/vechat_racon; default: this package's
@@ -218,6 +219,12 @@ def scrub_reads(a, sequences, workdir):
         g, c = 500, 4
     else:
         raise ValueError("Invalid platform, must be: pb or ont")
+    if getattr(a, "scrubber", "yacrd") == "device":
+        # this package's own scrubber (vechat_amd.scrub over vc_overlap and vc_scrub), one child process: the self-overlap never
+        # becomes a file.  g, c and n are the reference's per platform; the rule is the library's, not yacrd's
+        _sh(f"{shlex.quote(sys.executable)} -m vechat_amd.scrub -x ava-{a.platform} -g {g} -c {c} -n 0.4 "
+            f"--report {shlex.quote(os.path.join(workdir, 'report.yacrd'))} -o {shlex.quote(scrubbed)} {shlex.quote(sequences)}", workdir)
+        return scrubbed
     _sh(f"minimap2 -x ava-{a.platform} -g {g} -t {a.threads} {shlex.quote(sequences)} {shlex.quote(sequences)} > {shlex.quote(overlap)}", workdir)
     _sh(f"yacrd -i {shlex.quote(overlap)} -o {shlex.quote(os.path.join(workdir, 'report.yacrd'))} -c {c} -n 0.4 scrubb -i {shlex.quote(sequences)} "
         f"-o {shlex.quote(scrubbed)}", workdir)
@@ -233,7 +240,7 @@ def main(argv=None):
     ap.add_argument("--platform", default="pb", help="sequencing platform: pb/ont")
     ap.add_argument("--split", action="store_true", help="split the target sequences into chunks")
     ap.add_argument("--split-size", default=1000000, type=int, help="chunk size in lines, with --split")
-    ap.add_argument("--scrub", action="store_true", help="scrub chimeric reads first (minimap2 + yacrd)")
+    ap.add_argument("--scrub", action="store_true", help="scrub chimeric reads first (minimap2 + yacrd, or --scrubber device)")
     ap.add_argument("-u", "--include-unpolished", action="store_true")
     ap.add_argument("--base", action="store_true", help="base-level alignment for the round-1 overlaps")
     # pass-through values stay the strings the user typed, as in the reference (they are only ever formatted into commands)
@@ -256,6 +263,8 @@ def main(argv=None):
     ap.add_argument("--workdir", default=".", help="where the round files live (the reference uses the current directory)")
     ap.add_argument("--overlapper", default="minimap2", choices=("minimap2", "device"), help="minimap2: the reference's minimap2|awk|fpa "
                     "pipelines; device: this package's overlapper on the GPU (python -m vechat_amd.overlap), no external tool needed")
+    ap.add_argument("--scrubber", default="yacrd", choices=("yacrd", "device"), help="with --scrub.  yacrd: the reference's minimap2 and yacrd "
+                    "commands; device: this package's scrubber on the GPU (python -m vechat_amd.scrub), no external tool needed")
     ap.add_argument("--overlapper-r1", default=None, help="command template replacing the minimap2|awk|fpa pipeline of round 1")
     ap.add_argument("--overlapper-r2", default=None, help="... of round 2")
     ap.add_argument("--polisher", default=None, help="command replacing `python -m vechat_amd.polish`")
