@@ -823,6 +823,88 @@ int         vc_poa_run_weighted(const vc_poa_gap_params* p, const vc_poa_weight_
                                 vc_poa_msa_out* o, vc_poa_strand_out* s, vc_poa_graph_out* g, vc_poa_profile_out* prof /* o, s, g, prof may be NULL */);
 
 /* ------------------------------------------------------------------------------------------------
+ * Haplotypes of a POA group: how many alleles a group holds, their sequences, and which member belongs to which.
+ * vc_poa_run_haplotypes builds every group exactly as vc_poa_run_gaps does -- r carries that call's consensus bytes and
+ * statuses, unchanged -- and then splits the members of every VC_WIN_OK group by the library's own rule.  The rule is all
+ * integer and every tie is decided; tests/poa_haplo_ref.py restates it and the device is pinned to that restatement.
+ *
+ * Terms.  S: the sequences that were added (empty members are not), labelled 0 .. S-1 in the order added.  C: the alignment
+ * columns of vc_poa_run_msa.  node(s,c): the node of sequence s in column c, if it has one.  first(s), last(s): the lowest and
+ * highest column of s.  sym(s,c): the code of node(s,c) where it exists; GAP where it does not and first(s) < c < last(s);
+ * NONE otherwise.  Codes are the graph's, in order of first appearance of their byte.
+ *   1 Counts.  n(c,a): the s with sym(s,c) = a, for every code a and for GAP.  span(c): the s with first(s) <= c <= last(s).
+ *   2 Sites.   The alleles are the codes in code order; with VC_POA_HAP_INDELS GAP is an allele too and comes last.  Allele a
+ *              qualifies at c when n(c,a) >= min_reads and 1000 * n(c,a) >= min_permille * span(c).  A column with at least two
+ *              qualifying alleles is a site; its major allele is the qualifying one with the largest count, a tie going to the
+ *              earlier allele, its minor allele the next by the same order.  Sites run in column order: m = 0 .. M-1.
+ *   3 Votes.   v(s,m) = +1 where sym(s, column of m) is the major allele, -1 where it is the minor allele, 0 otherwise (another
+ *              base, a GAP without the flag, a member that does not span the site).  agree(x,y) = sum over m of x[m] * y[m].
+ *   4 Seeds.   seed_0 is the member with the most non-zero votes, a tie going to the smallest label; without a non-zero vote
+ *              K = 1.  For k = 1 .. max_haplotypes - 1: d(s) = max over j < k of agree(v(s), v(seed_j)); the s with the smallest
+ *              d(s), a tie going to the smallest label, is seed_k unless its d(s) >= 0, which ends the seeding.
+ *   5 Rounds.  P_k = v(seed_k).  `rounds` times: every member joins the k with the largest agree(v(s), P_k), a tie going to the
+ *              smallest k; then P_k[m] = sign of the sum of its members' votes at m (0 on a tie and for an empty cluster).  A
+ *              round that moves no member ends the loop (the fixed point is the same).
+ *   6 Small clusters.  The clusters with fewer than min_reads members are removed together, and their members join the
+ *              surviving P_k they agree with best, a tie going to the smallest k; profiles are not recomputed.  If no cluster
+ *              survives all members form one cluster.
+ *   7 Order.   Haplotype ids run by size, largest first, a tie going to the cluster with the smaller smallest label.  A member
+ *              that was never added (an empty one) has VC_POA_HAP_NONE.
+ *   8 Consensus of haplotype k: spoa's GenerateConsensus (heaviest bundle with branch completion, graph.cpp) on the group's graph
+ *              restricted to the members of k.  A node belongs when a member of k has it on its path, an edge when a member of k
+ *              carries it; the weight of an edge is the sum over those members of w_s[i-1] + w_s[i] for the step i of the member's
+ *              path that takes the edge (w: the build's own base weight, vc_weight_lut of the quality or 1: what AddEdge added
+ *              for them).  The order of the nodes is the full graph's rank_to_node, every in-list keeps its order, and the
+ *              out-degree is taken inside the restricted graph.  With K = 1 nothing is removed, so haplotype 0 is r's consensus.
+ *
+ * Out, per group w: n_haps[w] haplotypes at hap_first[w] ..; per haplotype h its member count hap_size[h] and its bytes
+ * cons[cons_off[h] .. cons_off[h + 1]); per sequence of the batch hap_of; the sites of w at site_off[w] .. site_off[w + 1].
+ * A group that is not VC_WIN_OK has no haplotype and no site and its members carry VC_POA_HAP_NONE; a group without a non-empty
+ * member is VC_WIN_OK with one haplotype of zero members and the empty consensus.  The entry takes no spans, weights, strands,
+ * queries or stored graphs.
+ * One exception to "r unchanged": the stage needs, per group, a block and a scratch in device memory (4 bytes per member and
+ * column for the node ids, one for the votes, and per haplotype a copy of the edge weights and the bundle's tables).  A single
+ * group the device has no room for is VC_WIN_OVERFLOW in r with the empty consensus, as the other output stages
+ * (vc_poa_run_msa, vc_poa_run_graph) report a group whose output they cannot hold, although vc_poa_run_gaps alone would
+ * have computed it.
+ * Argument checks before the device, in this order: those of vc_poa_run_gaps on p and r (o NULL and h NULL count as null
+ * arguments); then the fields of h: max_haplotypes, min_reads, min_permille, rounds, unknown flag bits; then the batch:
+ * VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these.
+ * Not this stage: phasing across groups, sites with more than two alleles (the third allele votes 0), realignment per haplotype. */
+#define VC_POA_HAP_MAX     8u
+#define VC_POA_HAP_INDELS  1u      /* vc_poa_hap_params::flags: GAP is an allele                       */
+#define VC_POA_HAP_NONE    0xFFu   /* hap_of of a member that was not added, or of a group not VC_WIN_OK */
+
+typedef struct vc_poa_hap_params {
+    uint32_t max_haplotypes;      /* 1 .. VC_POA_HAP_MAX, default 2 */
+    uint32_t min_reads;           /* >= 1, default 2                */
+    uint32_t min_permille;        /* 0 .. 1000, default 250         */
+    uint32_t rounds;              /* >= 1, default 4                */
+    uint32_t flags;               /* VC_POA_HAP_INDELS              */
+} vc_poa_hap_params;
+
+typedef struct vc_poa_hap_out {       /* library-owned, lifetime as vc_poa_msa_out */
+    uint32_t        n_groups;
+    const uint32_t* n_haps;       /* [n_groups]                                                           */
+    const uint64_t* hap_first;    /* [n_groups + 1] first haplotype of the group                          */
+    const uint32_t* hap_size;     /* [haplotypes] members                                                 */
+    const uint64_t* cons_off;     /* [haplotypes + 1] into cons                                           */
+    const uint8_t*  cons;
+    const uint8_t*  hap_of;       /* [n_seqs of b] haplotype of the member within its group, or VC_POA_HAP_NONE */
+    const uint64_t* site_off;     /* [n_groups + 1] into the site arrays                                  */
+    const uint32_t* site_col;     /* column of the alignment                                              */
+    const uint8_t*  site_major;   /* decoded byte, or '-'                                                 */
+    const uint8_t*  site_minor;
+    const uint32_t* site_n_major;
+    const uint32_t* site_n_minor;
+    uint64_t        bytes;        /* copied out of the device                                             */
+} vc_poa_hap_out;
+
+void        vc_poa_hap_default_params(vc_poa_hap_params* h);
+int         vc_poa_run_haplotypes(const vc_poa_gap_params* p, const vc_poa_hap_params* h, const vc_batch* b, vc_result* r,
+                                  vc_poa_hap_out* o);
+
+/* ------------------------------------------------------------------------------------------------
  * All-vs-all read overlaps on the device (vechat_amd/csrc/vc_overlap.hip): the first step of both rounds, which the reference's
  * wrapper leaves to an external command (scripts/vechat:36-49).
  *

@@ -10,7 +10,7 @@ libvcref_sse41.so, vcref_spoa_consensus) on a sample of the same groups on 16 ho
 compared with the device's.
 
   python tools/gpu_poa_rate.py [--groups 4096] [--len 1000] [--depth 32] [--cpu-sample 256] [--out profiles/poa_rate.txt]
-                               [--gaps linear|affine|convex] [--msa] [--strand] [--graph [--parent-lib LIB]]
+                               [--gaps linear|affine|convex] [--msa] [--strand] [--graph [--parent-lib LIB]] [--haplotypes [--parent-lib LIB]]
 
 --msa measures the multiple sequence alignment instead (vc_poa_run_msa with the consensus row and the coverage, global
 alignment) and writes profiles/poa_msa_rate.txt: after one warm-up call on all groups, three consensus-only calls and three
@@ -74,6 +74,14 @@ stage (call minus the build alone), forward launches, ring_cells / full_cells of
 then one rocprofv3 --kernel-trace --stats run of its own with one call of each route on a quarter of the pairs for the shares of
 k_lg_sfwd, k_lg_qfwd, k_lg_slots and k_lg_assign.  The expectation is stated in the file before the figures.  Exits 1 if the
 assign call is slower than the existing route beyond that route's own spread between its two runs.
+--haplotypes [--parent-lib LIB]: the haplotype split (vc_poa_run_haplotypes; profiles/poa_haplo_rate.txt) on 4 096 groups of 32 x 1 kb
+reads, every second group drawn from two haplotypes (a SNP every 100 bases, half of the reads each), 8 % read errors, FASTA; global,
+5/-4/-8, the rule's defaults.  In one process, three calls of each kind after a warm-up: the plain call, the haplotype call and the
+graph call, with the bytes each copies out and the haplotype counts found.  With --parent-lib the plain path -- consensus only on
+the standard groups -- of this library beside the parent commit's in alternating processes; then one rocprofv3 --kernel-trace
+--stats run of its own of the haplotype call for the shares of k_lg_hap and k_lg_hapcons.  The expectation is stated in the file
+before the figures.  Nothing is asserted about the new stage's own speed: exits 1 only if the plain path falls outside the
+parent's own spread.
 """
 import argparse
 import csv
@@ -902,6 +910,129 @@ def main_weights(a):
     return 0 if ok else 1
 
 
+def haplo_groups(a, seed=4100, rate=0.08, snp_every=100):
+    """a.groups groups of a.depth reads of about a.len bases -> (capi.Batch, haplotypes per group): a random template per group;
+    every second group has a second haplotype with a SNP every snp_every bases, which the odd members are drawn from; every read
+    carries `rate` errors, a third each substitutions, deletions and insertions.  numpy only: one pass per group"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    groups, truth = [], []
+    for w in range(a.groups):
+        h0 = acgt[rng.integers(0, 4, a.len)]
+        h1 = h0.copy()
+        two = w % 2 == 1
+        if two:
+            pos = np.arange(snp_every // 2, a.len, snp_every)
+            h1[pos] = acgt[(np.searchsorted(acgt, h0[pos]) + rng.integers(1, 4, pos.size)) % 4]
+        reads = []
+        for k in range(a.depth):
+            src = h1 if two and k % 2 else h0
+            u = rng.random(a.len)
+            r = np.where((u >= rate / 3) & (u < 2 * rate / 3), acgt[rng.integers(0, 4, a.len)], src)
+            ins = (u >= 2 * rate / 3) & (u < rate)
+            keep = u >= rate / 3
+            r, ins = r[keep], ins[keep]
+            out = np.repeat(r, 1 + ins)
+            at = np.cumsum(1 + ins)[ins] - 1                             # the copy behind every base with an insertion
+            out[at] = acgt[rng.integers(0, 4, at.size)]
+            reads.append(out.tobytes())
+        groups.append(reads)
+        truth.append(2 if two else 1)
+    return poa.group_batch(groups), truth
+
+
+def timed_haplotypes(batch, hap=None):
+    """-> (seconds, bytes copied out beside consensus and status, consensus, haplotypes per group) of one global 5/-4/-8 linear call
+    of vc_poa_run_haplotypes with the rule's defaults"""
+    p = capi.VcPoaGapParams(**LINEAR_NW)
+    t0 = time.perf_counter()
+    cons, status, res, raw = poa.run_batch_haplotypes(batch, p, hap or poa.hap_params())
+    dt = time.perf_counter() - t0
+    if int((status != 0).sum()):
+        raise RuntimeError(f"{int((status != 0).sum())} groups not computed")
+    return dt, raw["bytes"], cons, [len(h.sizes) for h in res]
+
+
+def main_haplotypes(a):
+    """profiles/poa_haplo_rate.txt: (i) the plain path beside the parent commit's library in alternating processes, (ii) the
+    haplotype call beside the plain call and the graph call in one process with the bytes each copies out, (iii) the kernel
+    shares of a traced haplotype call"""
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "poa_rate.txt") else os.path.join(ROOT, "profiles", "poa_haplo_rate.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    lines = []
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        open(out, "w").write("\n".join(lines) + "\n")
+    med = lambda v: sorted(v)[len(v) // 2]                                # noqa: E731
+    emit(f"POA groups split into haplotypes: {a.groups} groups of {a.depth} x {a.len} bp, every second one from two haplotypes (a SNP every "
+         f"100 bases, half of the reads each), 8 % read errors, FASTA, numpy seed 4100; 5/-4/-8, global (kNW), the rule's defaults; one MI355X; "
+         f"synchronous; host clock around one call")
+    emit("expected before the run: (i) the plain call launches no new kernel and heaviest_bundle's whole-graph view folds to the code it "
+         "had, so it stays inside the parent's own spread; (ii) the haplotype call adds k_lg_graph<0>, k_lg_hap and k_lg_hapcons behind a "
+         "build that k_lg_apply and k_lg_fwd dominate: k_lg_hap's serial loops over members per column and k_lg_hapcons's lane-serial "
+         "bundle (one more bundle per haplotype) should stay a few per cent of the call, and it copies far fewer bytes than the graph "
+         "call; nothing is asserted about the stage's own speed")
+    ok = True
+    if a.parent_lib:
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "0", "--graph", "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth)]
+        secs = {"parent": [], "this": []}
+        for which in ("parent", "this", "parent", "this"):
+            p = subprocess.run(cmd + (["--parent-lib", os.path.abspath(a.parent_lib)] if which == "parent" else []),
+                               capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                emit(f"{which} library: run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+                return 1                          # nothing more is started on the device after a failed run
+            t = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]["seconds"]
+            secs[which] += t
+            name = "library of the parent commit" if which == "parent" else "this library"
+            emit(f"(i) {'plain path, ' + name:42s} " + "  ".join(f"{a.groups / x:7.1f}" for x in t) +
+                 f" groups/s  ({'  '.join(f'{x:.3f}' for x in t)} s; consensus only on the standard vc_synth groups, a process of its own)")
+        par, cur = sorted(secs["parent"]), sorted(secs["this"])
+        med2 = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2     # noqa: E731
+        slower, spread = med2(cur) - med2(par), par[-1] - par[0]
+        ok = slower <= spread
+        emit(f"(i) medians: parent {med2(par):.3f} s, this {med2(cur):.3f} s, difference {slower:+.3f} s ({slower / med2(par) * 100:+.2f} %); the "
+             f"parent's own runs of this session spread over {spread:.3f} s ({par[0]:.3f} .. {par[-1]:.3f}): "
+             f"{'inside the spread' if ok else 'OUTSIDE the spread'}")
+    else:
+        emit("(i) not run: no --parent-lib was given")
+    batch, truth = haplo_groups(a)
+    timed_graph(batch, graph=False)
+    plain = [timed_graph(batch, graph=False)[:2] for _ in range(3)]
+    haps = [timed_haplotypes(batch) for _ in range(3)]
+    graph = [timed_graph(batch, 0)[:2] for _ in range(3)]
+    row = lambda name, runs: emit(f"{name:46s} " + "  ".join(f"{a.groups / r[0]:7.1f}" for r in runs) +      # noqa: E731
+                                  f" groups/s  ({'  '.join(f'{r[0]:.3f}' for r in runs)} s; {runs[0][1]} bytes copied out beside the consensus)")
+    row("plain (vc_poa_run_gaps)", plain)
+    row("(ii) haplotypes (vc_poa_run_haplotypes)", haps)
+    row("(ii) graph tables (vc_poa_run_graph)", graph)
+    m = med([r[0] for r in plain])
+    found = haps[0][3]
+    emit(f"(ii) haplotypes / plain {med([r[0] for r in haps]) / m:.3f}, graph / plain {med([r[0] for r in graph]) / m:.3f} (medians); groups with the "
+         f"planted number of haplotypes: {sum(1 for x, y in zip(found, truth) if x == y)} of {a.groups} "
+         f"({sum(1 for x in truth if x == 2)} planted with two)")
+    large.release()
+    if not a.no_trace:
+        d = os.path.join(a.trace_dir, "haplotypes")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
+               sys.executable, os.path.abspath(__file__), "--child", "1", "--haplotypes", "--groups", str(a.groups), "--len", str(a.len), "--depth", str(a.depth)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            emit(f"kernel trace: rocprofv3 run failed ({p.returncode}): {p.stderr.strip().splitlines()[-1:]}")
+            return 1
+        ms = kernel_shares(d)
+        tot = sum(ms.values())
+        emit(f"(iii) kernel times of one haplotype call, a run of its own under rocprofv3 --kernel-trace --stats: {tot / 1e3:.2f} s: " +
+             ", ".join(f"{k} {v:.1f} ms ({v / tot * 100:.2f} %)" for k, v in sorted(ms.items(), key=lambda kv: -kv[1])))
+    else:
+        emit("(iii) not run: --no-trace")
+    print("wrote", out)
+    return 0 if ok else 1
+
+
 LINEAR_NW = dict(device=0, algorithm=1, match=5, mismatch=-4, gap_open=-8, gap_extend=-8, gap_open2=-8, gap_extend2=-8)
 
 
@@ -1208,6 +1339,10 @@ def child(a):
         dt = resume_call(tail, stored_graphs(head))[0]
         print(json.dumps(dict(seconds=dt)))
         return
+    if a.haplotypes:                              # the traced run: one haplotype call
+        dt, nbytes, _, found = timed_haplotypes(haplo_groups(a)[0])
+        print(json.dumps(dict(seconds=dt, bytes=nbytes, two=sum(1 for x in found if x == 2))))
+        return
     if a.weights:                                 # the traced run: one call with every member weighted per base and the profile
         batch = synth_groups(a)
         dt, nbytes, _ = timed_weighted(batch, weights=all_mode2(batch), profile=True)
@@ -1324,6 +1459,8 @@ def main():
                                                            "(profiles/poa_weights_rate.txt)")
     ap.add_argument("--assign", action="store_true", help="measure vc_poa_run_assign beside vc_poa_run_align without pairs on the queries repeated "
                                                           "per group (profiles/poa_assign_rate.txt; --groups defaults to 256)")
+    ap.add_argument("--haplotypes", action="store_true", help="measure vc_poa_run_haplotypes beside the plain and the graph call on groups half "
+                                                              "of which hold two haplotypes (profiles/poa_haplo_rate.txt)")
     ap.add_argument("--queries", type=int, default=1024, help="--assign: queries of the call")
     ap.add_argument("--locus", type=int, default=8000, help="--spans: bases of a group's backbone, tiled by reads of --len bases, --depth per tile")
     ap.add_argument("--prune-rounds", type=int, default=3, help="--correct: num_prune (default 3)")
@@ -1342,6 +1479,8 @@ def main():
         return child(a)
     if a.assign:
         return main_assign(a)
+    if a.haplotypes:
+        return main_haplotypes(a)
     if a.weights:
         return main_weights(a)
     if a.spans:

@@ -174,6 +174,28 @@ class VcPoaProfileOut(C.Structure):
                 ("codes", C.POINTER(C.c_uint8)), ("prof_off", C.POINTER(C.c_uint64)), ("counts", C.POINTER(C.c_uint32))]
 
 
+VC_POA_HAP_MAX, VC_POA_HAP_INDELS, VC_POA_HAP_NONE = 8, 1, 0xFF
+
+
+class VcPoaHapParams(C.Structure):
+    """vc_poa_hap_params: the haplotype rule's parameters (defaults 2 / 2 / 250 / 4 / 0, vc_poa_hap_default_params)"""
+    _fields_ = [("max_haplotypes", C.c_uint32), ("min_reads", C.c_uint32), ("min_permille", C.c_uint32), ("rounds", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class VcPoaHapOut(C.Structure):
+    """vc_poa_hap_out: everything out and owned by the library until its next vc_poa_* / vc_large_* call"""
+    _fields_ = [
+        ("n_groups", C.c_uint32),
+        ("n_haps", C.POINTER(C.c_uint32)), ("hap_first", C.POINTER(C.c_uint64)), ("hap_size", C.POINTER(C.c_uint32)),
+        ("cons_off", C.POINTER(C.c_uint64)), ("cons", C.POINTER(C.c_uint8)), ("hap_of", C.POINTER(C.c_uint8)),
+        ("site_off", C.POINTER(C.c_uint64)), ("site_col", C.POINTER(C.c_uint32)),
+        ("site_major", C.POINTER(C.c_uint8)), ("site_minor", C.POINTER(C.c_uint8)),
+        ("site_n_major", C.POINTER(C.c_uint32)), ("site_n_minor", C.POINTER(C.c_uint32)),
+        ("bytes", C.c_uint64),
+    ]
+
+
 class VcPoaPruneParams(C.Structure):
     """vc_poa_prune_params: the thresholds and rounds of vc_poa_run_correct (the reference's defaults: 0.22 / 0.19 / 3)"""
     _fields_ = [("min_confidence", C.c_double), ("min_support", C.c_double), ("num_prune", C.c_uint32)]
@@ -492,6 +514,13 @@ def load_hip():
                                                 C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut),
                                                 C.POINTER(VcPoaProfileOut)]
             lib.vc_poa_run_weighted.restype = C.c_int
+        # (likewise: tools/gpu_poa_rate.py --haplotypes measures beside the parent commit's library, which has no haplotype entry)
+        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_haplotypes"):
+            lib.vc_poa_hap_default_params.argtypes = [C.POINTER(VcPoaHapParams)]
+            lib.vc_poa_hap_default_params.restype = None
+            lib.vc_poa_run_haplotypes.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaHapParams), C.POINTER(VcBatch),
+                                                  C.POINTER(VcResult), C.POINTER(VcPoaHapOut)]
+            lib.vc_poa_run_haplotypes.restype = C.c_int
         lib.vc_stream.argtypes = [vp]
         lib.vc_stream.restype = vp
         _hip = lib

@@ -64,6 +64,9 @@
 //   k_lg_load   vc_poa_run_from only, one wave per group behind k_lg_init: the group starts as a stored graph -- nodes, out-lists and
 //               aligned lists from their CSR, in-lists and labels by replaying the paths in order; with a vc_poa_state_out
 //               k_lg_graph<1> also writes every node's aligned list behind the group's block.
+//   k_lg_hap    vc_poa_run_haplotypes only, one wave per finished group behind k_lg_graph<0>: sites, votes, seeds, rounds and the
+//               order of the haplotypes (the rule: vechat_hip.h); k_lg_hapcons, a grid of (groups, max_haplotypes): the heaviest
+//               bundle of the graph restricted to one haplotype's members, on weights rebuilt from their paths.
 //   The query stage, vc_poa_run_align only (spoa's engine->Align(sequence, graph, &score) for sequences that are NOT added), on the
 //   finished groups while their tables are resident; every (group, query) pair is a job (LJob) and independent of the others:
 //   k_lg_rows   one lane per finished group: the graph half of k_lg_prep (graph_rows) once per group, without a next sequence;
@@ -131,6 +134,7 @@
 //                           a member whose matrix the device refused is not counted),
 //                           "vc_large: profile launches=K bytes=B" (vc_poa_run_weighted with a profile: k_lg_profile launches, bytes
 //                           copied out),
+//                           "vc_large: haplotypes launches=K bytes=B" (vc_poa_run_haplotypes: k_lg_hap launches, bytes copied out),
 //                           and at the end of a call "vc_large: done alignments=A cells=C" (forward passes of the build, their rows x
 //                           columns summed; a regrown window's are counted again; vc_poa_run_strand counts both strands' passes;
 //                           vc_poa_run_correct counts the rounds' passes too, not the final stage's).
@@ -296,7 +300,7 @@ int check_device(int32_t device) {
 
 // What a call wants beside consensus and status, and where each output goes (the caller's out-structs); vc_large_run's is empty.
 struct PoaRequest {
-    enum : uint32_t { MSA = 1, STRAND = 2, GRAPH = 4, ALIGN = 8, CORRECT = 16, ASSIGN = 32 };
+    enum : uint32_t { MSA = 1, STRAND = 2, GRAPH = 4, ALIGN = 8, CORRECT = 16, ASSIGN = 32, HAPS = 64 };
     uint32_t required = 0;                             // the outputs the entry cannot do without; 0 leaves what an earlier call handed out alone
     vc_poa_msa_out* msa = nullptr;                     // rows, members and coverage as msa_flags say (0: n_groups only)
     vc_poa_strand_out* strand = nullptr;               // the strand flow, and its choices
@@ -315,10 +319,12 @@ struct PoaRequest {
     vc_poa_profile_out* profile = nullptr;             // the per-code profile of every consensus
     vc_poa_assign_out* assign = nullptr;               // vc_poa_run_assign: `queries` are the queries of every group, and their best groups go here
     uint32_t assign_flags = 0;
+    const vc_poa_hap_params* hap = nullptr;            // vc_poa_run_haplotypes: the rule's parameters, and the haplotypes of every group
+    vc_poa_hap_out* haps = nullptr;
     bool rows() const { return msa_flags != 0; }                           // k_lg_msa runs
     bool columns() const { return rows() || profile != nullptr; }          // k_lg_msa<0> runs
     // the edges keep sequence labels, and the windows sq_begin / sq_member beside them
-    bool keeps_labels() const { return msa_flags != 0 || graph != nullptr || profile != nullptr; }
+    bool keeps_labels() const { return msa_flags != 0 || graph != nullptr || profile != nullptr || haps != nullptr; }
     uint32_t strands() const { return strand ? 2 : 1; }                    // forward passes per alignment of the build
     bool has_queries() const { return nq != 0; }                           // the query stage runs (a call without a query is the call without it)
     bool query_pairs() const { return (align_flags & VC_POA_ALIGN_PAIRS) != 0; }
@@ -639,7 +645,7 @@ bool lock_step(Run& R, Group& G) {
         ok = hipGetLastError() == hipSuccess;
     }
     if (ok && R.q.columns()) hipLaunchKernelGGL(k_lg_msa<0>, dim3(n), dim3(64), 0, 0, a);
-    if (ok && R.q.graph) hipLaunchKernelGGL(k_lg_graph<0>, dim3(n), dim3(64), 0, 0, a);
+    if (ok && (R.q.graph || R.q.haps)) hipLaunchKernelGGL(k_lg_graph<0>, dim3(n), dim3(64), 0, 0, a);   // (the haplotype stage sizes itself from the same counts)
     ok = ok && hipGetLastError() == hipSuccess;
     return ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(G.hw.data(), G.d_win, n * sizeof(LWin), hipMemcpyDeviceToHost) == hipSuccess;
 }
@@ -1349,6 +1355,106 @@ struct AssignStage : Stage {
     }
 };
 
+// The haplotypes of every group (vc_poa_hap_out): a block and a scratch per group in the matrix buffer, laid out as the graph
+// stage's are.  k_lg_hap splits the members; k_lg_hapcons then runs on a grid of (groups, max_haplotypes), one block per
+// haplotype that exists, so no count has to come back in between.
+struct HapStage : Stage {
+    std::vector<uint32_t> n_haps, hap_size, site_col, site_n1, site_n2;
+    std::vector<uint64_t> hap_first, cons_off, site_off;
+    std::vector<uint8_t> cons, hap_of, site_major, site_minor;
+    uint64_t bytes = 0;                                // copied out of the device
+    // until assemble(), per window: its block and the counts that lay it out
+    struct Part { uint32_t S = 0, C = 0, N = 0; std::vector<uint8_t> blk; };
+    std::vector<Part> part;
+    uint64_t launches = 0;
+
+    void size(const Run& R) override { part.resize(R.nw); }
+    int collect(Run& R, Group& G) override {
+        const LArgs& a = R.a;
+        const vc_poa_hap_params& h = *R.q.hap;
+        const LHap hp{h.max_haplotypes, h.min_reads, h.min_permille, h.rounds, h.flags};
+        auto counts_of = [&](uint32_t k) {
+            const LWin& W = G.hw[k];
+            Part p;
+            p.S = W.gr[W.cur].nseq; p.C = W.gr_cols; p.N = W.gr[W.cur].n_nodes;
+            return p;
+        };
+        auto block_of = [&](uint32_t k) { const Part p = counts_of(k); return hap_block(p.S, p.C, p.N, hp.max_haps).bytes; };
+        auto scratch_of = [&](uint32_t k) {
+            const Part p = counts_of(k);
+            return hap_scratch(p.S, p.C, G.hw[k].gr_path, p.N, G.hw[k].gr[G.hw[k].cur].n_edges, hp.max_haps).bytes;
+        };
+        uint64_t blocks = 0;
+        std::vector<uint8_t> host;
+        auto body = [&](LArgs& f, const std::vector<uint32_t>& list, const std::vector<uint64_t>& hoff, uint64_t, void* dout) -> int {
+            const uint32_t nl = (uint32_t)list.size();
+            f.msa_out = (uint8_t*)dout;
+            hipLaunchKernelGGL(k_lg_hap, dim3(nl), dim3(64), 0, 0, f, hp);
+            hipLaunchKernelGGL(k_lg_hapcons, dim3(nl, hp.max_haps), dim3(64), 0, 0, f, hp);
+            auto part_of = [&](uint32_t q) -> std::vector<uint8_t>& {
+                Part& p = part[G.ids[list[q]]];
+                p = counts_of(list[q]);
+                return p.blk;
+            };
+            if (hipGetLastError() != hipSuccess || !blocks_out(dout, blocks, hoff, nl, host, part_of))
+                return fail(VC_ERR_HIP, "a haplotype kernel or its copy failed");
+            bytes += blocks;
+            return VC_OK;
+        };
+        return launch_loop(a, finished(R, G), R.mat_budget, 1, G.d_list, G.d_hoff,
+                           {"device allocation of the haplotype tables failed", "a haplotype kernel or its copy failed"}, launches,
+                           [&](uint32_t k) { return block_of(k) + scratch_of(k); },
+                           [&](const std::vector<uint32_t>& list, std::vector<uint64_t>& hoff) { blocks = blocks_first(list, hoff, block_of, scratch_of); },
+                           [&](uint32_t k) { return refuse_group(R, G.ids[k]); }, body);
+    }
+    // the tables in window order; the members from labels to sequences of the batch
+    void assemble(const Run& R) override {
+        const uint32_t maxh = R.q.hap->max_haplotypes;
+        hap_first.assign(1, 0); cons_off.assign(1, 0); site_off.assign(1, 0);
+        hap_of.assign(R.nseq_all, VC_POA_HAP_NONE);
+        for (uint32_t w = 0; w < R.nw; ++w) {
+            if (R.status[w] != VC_WIN_OK) part[w] = Part{};
+            const Part& p = part[w];
+            uint32_t K = 0;
+            if (!p.blk.empty()) {
+                const HapBlock B = hap_block(p.S, p.C, p.N, maxh);
+                const uint8_t* blk = p.blk.data();
+                const uint32_t* head = (const uint32_t*)blk;
+                K = head[0];
+                const uint32_t M = head[1];
+                for (uint32_t k = 0; k < K; ++k) {
+                    hap_size.push_back(head[2 + k]);
+                    const uint8_t* c = blk + B.cons + (uint64_t)k * p.N;
+                    cons.insert(cons.end(), c, c + head[2 + VC_POA_HAP_MAX + k]);
+                    cons_off.push_back(cons.size());
+                }
+                const uint32_t* mem = (const uint32_t*)(blk + B.member);
+                for (uint32_t s = 0; s < p.S; ++s) hap_of[R.b->win_seq_off[w] + mem[s]] = blk[B.hap_of + s];
+                const uint32_t *col = (const uint32_t*)(blk + B.s_col), *n1 = (const uint32_t*)(blk + B.s_n1), *n2 = (const uint32_t*)(blk + B.s_n2);
+                site_col.insert(site_col.end(), col, col + M); site_n1.insert(site_n1.end(), n1, n1 + M); site_n2.insert(site_n2.end(), n2, n2 + M);
+                site_major.insert(site_major.end(), blk + B.s_maj, blk + B.s_maj + M);
+                site_minor.insert(site_minor.end(), blk + B.s_min, blk + B.s_min + M);
+            }
+            n_haps.push_back(K);
+            hap_first.push_back(hap_size.size());
+            site_off.push_back(site_col.size());
+            part[w] = Part{};
+        }
+        if (R.kn.log) std::fprintf(stderr, "vc_large: haplotypes launches=%llu bytes=%llu\n", (unsigned long long)launches, (unsigned long long)bytes);
+    }
+    void publish(const PoaRequest& q, const vc_batch* b) override {
+        vc_poa_hap_out* o = q.haps;
+        if (!o) return;
+        o->n_groups = b->n_windows;
+        if (!b->n_windows) return;
+        o->n_haps = table(n_haps); o->hap_first = hap_first.data(); o->hap_size = table(hap_size);
+        o->cons_off = cons_off.data(); o->cons = table(cons); o->hap_of = table(hap_of);
+        o->site_off = site_off.data(); o->site_col = table(site_col); o->site_major = table(site_major); o->site_minor = table(site_minor);
+        o->site_n_major = table(site_n1); o->site_n_minor = table(site_n2);
+        o->bytes = bytes;
+    }
+};
+
 // The stages of the process, and with them what the vc_poa_* entries hand out: valid until the next call that has an output of
 // its own (poa_run clears them then, and when such a call fails) or vc_large_release.
 struct Outputs {
@@ -1358,6 +1464,7 @@ struct Outputs {
     CorrectStage correct;
     AlignStage align;
     AssignStage assign;
+    HapStage haps;
     // The stages that run in a call, in the order run_group collects and run_windows assembles them.  Correct stands before
     // align as run_group always had them, align before correct in run_windows: one order serves both, because the two never
     // occur in one call (only vc_poa_run_correct asks for correction, and it takes no query batch).
@@ -1369,9 +1476,10 @@ struct Outputs {
         if (q.correct) s.push_back(&correct);
         if (q.has_queries() && q.align) s.push_back(&align);
         if (q.has_queries() && q.assign) s.push_back(&assign);
+        if (q.haps) s.push_back(&haps);
         return s;
     }
-    std::vector<Stage*> all() { return {&msa, &profile, &graph, &correct, &align, &assign}; }
+    std::vector<Stage*> all() { return {&msa, &profile, &graph, &correct, &align, &assign, &haps}; }
     void clear() { *this = Outputs{}; }
 } g_out;
 
@@ -1381,7 +1489,7 @@ int run_group(Run& R, Group& G) {
     const uint32_t n = (uint32_t)G.ids.size();
     uint8_t* arena = (uint8_t*)cached(g_cache.arena, G.abytes);
     DevMem mem;
-    if (!arena || !mem.alloc(&G.d_win, n) || !mem.alloc(&G.d_list, n) || !mem.alloc(&G.d_hoff, R.q.graph || R.q.profile ? 2 * (size_t)n : n)) {
+    if (!arena || !mem.alloc(&G.d_win, n) || !mem.alloc(&G.d_list, n) || !mem.alloc(&G.d_hoff, R.q.graph || R.q.profile || R.q.haps ? 2 * (size_t)n : n)) {
         if (n == 1) { R.status[G.ids[0]] = VC_WIN_OVERFLOW; return VC_OK; }
         return fail(VC_ERR_HIP, "device allocation of the window tables failed");
     }
@@ -1762,7 +1870,8 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     if (q.state) *q.state = vc_poa_state_out{};
     if (q.profile) *q.profile = vc_poa_profile_out{};
     if (q.assign) { q.assign_flags = q.assign->flags; *q.assign = vc_poa_assign_out{}; q.assign->flags = q.assign_flags; }
-    if (!p || !b || !r || ((q.required & PoaRequest::MSA) && !o) || ((q.required & PoaRequest::CORRECT) && (!q.prune || !q.correct)) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
+    if (q.haps) *q.haps = vc_poa_hap_out{};
+    if (!p || !b || !r || ((q.required & PoaRequest::HAPS) && (!q.hap || !q.haps)) || ((q.required & PoaRequest::MSA) && !o) || ((q.required & PoaRequest::CORRECT) && (!q.prune || !q.correct)) || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
     if (p->algorithm < 0 || p->algorithm > 2) return fail(VC_ERR_ARG, "algorithm must be 0 (local), 1 (global) or 2 (semi-global)");
     if (p->gap_open > 0 || p->gap_open2 > 0) return fail(VC_ERR_ARG, "gap opening penalties must be <= 0");
     if (p->gap_extend > 0 || p->gap_extend2 > 0) return fail(VC_ERR_ARG, "gap extension penalties must be <= 0");
@@ -1773,6 +1882,15 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     if ((q.msa_flags & VC_POA_MSA_CONSENSUS) && !(q.msa_flags & VC_POA_MSA)) return fail(VC_ERR_ARG, "VC_POA_MSA_CONSENSUS needs VC_POA_MSA");
     if ((q.required & PoaRequest::GRAPH) && !q.graph) return fail(VC_ERR_ARG, "null graph output");
     if (((q.required & PoaRequest::STRAND) && !q.strand) || (q.strand && !q.strand->reversed)) return fail(VC_ERR_ARG, "null strand output (reversed is required)");
+    if (q.required & PoaRequest::HAPS) {
+        // vc_poa_run_haplotypes' own arguments, field by field in the struct's order, before the batch
+        const vc_poa_hap_params* h = q.hap;
+        if (h->max_haplotypes < 1 || h->max_haplotypes > VC_POA_HAP_MAX) return fail(VC_ERR_ARG, "max_haplotypes must lie in 1..VC_POA_HAP_MAX");
+        if (h->min_reads < 1) return fail(VC_ERR_ARG, "min_reads must be >= 1");
+        if (h->min_permille > 1000) return fail(VC_ERR_ARG, "min_permille must lie in 0..1000");
+        if (h->rounds < 1) return fail(VC_ERR_ARG, "rounds must be >= 1");
+        if (h->flags & ~(uint32_t)VC_POA_HAP_INDELS) return fail(VC_ERR_ARG, "unknown haplotype flag bits");
+    }
     // the subtype and its scores (alignment_engine.cpp:59-69)
     int32_t g = p->gap_open, e = p->gap_extend, g2 = p->gap_open2, c = p->gap_extend2;
     const uint32_t gaps = g >= e ? 0 : (g <= g2 || e >= c ? 1 : 2);
@@ -1782,7 +1900,7 @@ int poa_run(const vc_poa_gap_params* p, const vc_batch* b, vc_result* r, PoaRequ
     LArgs a{};
     a.match = p->match; a.mismatch = p->mismatch; a.gap = g; a.gap_e = e; a.gap_q = g2; a.gap_c = c; a.gaps = gaps;
     a.msa = q.msa_flags; a.strand = q.strand ? 1 : 0; a.graph = q.route; a.state = q.state ? 1 : 0;
-    a.profile = q.profile ? 1 : 0;
+    a.profile = q.profile ? 1 : 0; a.haps = q.haps ? 1 : 0;
     if (o) { *o = vc_poa_msa_out{}; o->flags = q.msa_flags; }
     const bool owns = q.required || q.profile;
     if (owns) g_out.clear();                                               // what an earlier call handed out ends here
@@ -1906,6 +2024,16 @@ int vc_poa_run_weighted(const vc_poa_gap_params* p, const vc_poa_weight_in* w, c
     PoaRequest rq{base_entry(nullptr, g, s, o), o, s, g};
     rq.weights = w; rq.profile = prof;
     return poa_run(p, b, r, rq);
+}
+
+void vc_poa_hap_default_params(vc_poa_hap_params* h) {
+    if (h) *h = vc_poa_hap_params{2, 2, 250, 4, 0};
+}
+
+int vc_poa_run_haplotypes(const vc_poa_gap_params* p, const vc_poa_hap_params* h, const vc_batch* b, vc_result* r, vc_poa_hap_out* o) {
+    PoaRequest q{PoaRequest::HAPS};
+    q.hap = h; q.haps = o;
+    return poa_run(p, b, r, q);
 }
 
 int vc_poa_run_correct(const vc_batch* b, const vc_poa_gap_params* p, const vc_poa_prune_params* pr, vc_result* r, vc_poa_correct_out* c) {

@@ -99,6 +99,7 @@ struct LArgs {
     const uint8_t* wmode;
     const uint32_t *seq_w, *base_w;
     uint32_t profile;                                  // mode 2, vc_poa_run_weighted with a vc_poa_profile_out: 1 k_lg_msa<0> runs for k_lg_profile; 0 elsewhere
+    uint32_t haps;                                     // mode 2, vc_poa_run_haplotypes: 1 the edges keep their labels for k_lg_hap; 0 elsewhere
     uint8_t *rc_bases, *rv_quals, *rt_bases;           // reverse complement, reversed quality, the bytes complemented twice
     uint8_t* s_rev;                                    // [sequences] 1: the reverse complement was kept
     int32_t *s_score, *s_score_rev;                    // [sequences] both strands' scores
@@ -474,26 +475,44 @@ __device__ bool add_weights(const LArgs& a, LWin& W, LGraph& g, const int32_t* A
     return true;
 }
 
+// The graph a bundle walks, its weights and its scratch.  BundleAll is the whole graph with its own weights on W's scratch, which
+// is what finish_linear and finish_poa always walked; HapView (k_lg_hapcons) restricts it to one haplotype's nodes and edges.
+struct BundleAll {
+    const LGraph& g;
+    int64_t* scores;
+    uint32_t *pred, *node_rank, *comp;
+    __device__ __forceinline__ bool node(uint32_t) const { return true; }
+    __device__ __forceinline__ bool edge(uint32_t) const { return true; }
+    __device__ __forceinline__ int64_t weight(uint32_t e) const { return g.weight[e]; }
+    __device__ __forceinline__ uint32_t out_n(uint32_t v) const { return g.out_n[v]; }
+};
+
 // g_branch_completion
-__device__ uint32_t branch_completion(LWin& W, const LGraph& g, uint32_t rank) {
-    int64_t* scores = W.scores;
-    uint32_t* pred = W.pred;
+template <class View>
+__device__ uint32_t branch_completion(const LGraph& g, const View& V, uint32_t rank) {
+    int64_t* scores = V.scores;
+    uint32_t* pred = V.pred;
     const uint32_t start = g.rank[rank];
     for (uint32_t o = g.out_h[start]; o != NONE; o = g.nx_out[o]) {
+        if (!V.edge(o)) continue;
         const uint32_t h = g.head[o];
         for (uint32_t e = g.in_h[h]; e != NONE; e = g.nx_in[e]) {
+            if (!V.edge(e)) continue;
             if (g.tail[e] != start) scores[g.tail[e]] = -1;
         }
     }
     uint32_t mx = NONE;
     for (uint32_t i = rank + 1; i < g.n_rank; ++i) {
         const uint32_t it = g.rank[i];
+        if (!V.node(it)) continue;
         scores[it] = -1; pred[it] = NONE;
         for (uint32_t e = g.in_h[it]; e != NONE; e = g.nx_in[e]) {
+            if (!V.edge(e)) continue;
             const uint32_t tl = g.tail[e];
             if (scores[tl] == -1) continue;
-            if (scores[it] < g.weight[e] || (scores[it] == g.weight[e] && pred[it] != NONE && scores[pred[it]] <= scores[tl])) {
-                scores[it] = g.weight[e]; pred[it] = tl;
+            const int64_t w = V.weight(e);
+            if (scores[it] < w || (scores[it] == w && pred[it] != NONE && scores[pred[it]] <= scores[tl])) {
+                scores[it] = w; pred[it] = tl;
             }
         }
         if (pred[it] != NONE) scores[it] += scores[pred[it]];
@@ -502,35 +521,40 @@ __device__ uint32_t branch_completion(LWin& W, const LGraph& g, uint32_t rank) {
     return mx;
 }
 
-// g_heaviest_bundle -> W.comp[0 .. n) (node ids, source first)
-__device__ uint32_t heaviest_bundle(LWin& W, const LGraph& g) {
+// g_heaviest_bundle -> V.comp[0 .. n) (node ids, source first)
+template <class View>
+__device__ uint32_t heaviest_bundle(const LGraph& g, const View& V) {
     if (g.n_rank == 0) return 0;
     const uint32_t N = g.n_nodes;
-    int64_t* scores = W.scores;
-    uint32_t* pred = W.pred;
+    int64_t* scores = V.scores;
+    uint32_t* pred = V.pred;
     for (uint32_t i = 0; i < N; ++i) { pred[i] = NONE; scores[i] = -1; }
     uint32_t mx = NONE;
     for (uint32_t r = 0; r < g.n_rank; ++r) {
         const uint32_t it = g.rank[r];
+        if (!V.node(it)) continue;
         for (uint32_t e = g.in_h[it]; e != NONE; e = g.nx_in[e]) {
+            if (!V.edge(e)) continue;
             const uint32_t tl = g.tail[e];
-            if (scores[it] < g.weight[e] || (scores[it] == g.weight[e] && pred[it] != NONE && scores[pred[it]] <= scores[tl])) {
-                scores[it] = g.weight[e]; pred[it] = tl;
+            const int64_t w = V.weight(e);
+            if (scores[it] < w || (scores[it] == w && pred[it] != NONE && scores[pred[it]] <= scores[tl])) {
+                scores[it] = w; pred[it] = tl;
             }
         }
         if (pred[it] != NONE) scores[it] += scores[pred[it]];
         if (mx == NONE || scores[mx] < scores[it]) mx = it;
     }
-    if (g.out_n[mx] != 0) {
-        for (uint32_t r = 0; r < g.n_rank; ++r) W.node_rank[g.rank[r]] = r;
-        while (g.out_n[mx] != 0) mx = branch_completion(W, g, W.node_rank[mx]);
+    if (V.out_n(mx) != 0) {
+        for (uint32_t r = 0; r < g.n_rank; ++r) V.node_rank[g.rank[r]] = r;
+        while (V.out_n(mx) != 0) mx = branch_completion(g, V, V.node_rank[mx]);
     }
     uint32_t n = 0;
-    while (pred[mx] != NONE) { W.comp[n++] = mx; mx = pred[mx]; }
-    W.comp[n++] = mx;
-    for (uint32_t x = 0, y = n - 1; x < y; ++x, --y) { const uint32_t t = W.comp[x]; W.comp[x] = W.comp[y]; W.comp[y] = t; }
+    while (pred[mx] != NONE) { V.comp[n++] = mx; mx = pred[mx]; }
+    V.comp[n++] = mx;
+    for (uint32_t x = 0, y = n - 1; x < y; ++x, --y) { const uint32_t t = V.comp[x]; V.comp[x] = V.comp[y]; V.comp[y] = t; }
     return n;
 }
+__device__ uint32_t heaviest_bundle(LWin& W, const LGraph& g) { return heaviest_bundle(g, BundleAll{g, W.scores, W.pred, W.node_rank, W.comp}); }
 
 // g_coverage: distinct labels on v's in- and out-edges
 __device__ uint32_t coverage(LWin& W, const LGraph& g, uint32_t v, uint32_t tick) {
@@ -668,7 +692,7 @@ __global__ __launch_bounds__(64) void k_lg_init(LArgs a) {
     for (int c = 0; c < 256; ++c) { W.coder[c] = -1; W.decoder[c] = -1; }
     W.num_codes = 0;
     reset_graph(W.gr[0]); reset_graph(W.gr[1]);
-    W.gr[0].labels = a.mode == 1 || a.msa != 0 || a.graph != 0 || a.profile != 0; W.gr[1].labels = 0;
+    W.gr[0].labels = a.mode == 1 || a.msa != 0 || a.graph != 0 || a.profile != 0 || a.haps != 0; W.gr[1].labels = 0;
     W.cur = 0; W.sub = 0; W.grow = 0; W.status = 0xFF; W.rows = 0; W.npairs = 0; W.cons_n = 0; W.total = 0.0; W.avg = 0.0;
     W.msa_rows = 0; W.row_size = 0; W.rev = 0; W.gr_cols = 0; W.gr_path = 0;
     if (a.mode == 2) {                                                     // POA group: sequence 0 meets the empty graph in k_lg_prep
@@ -1808,6 +1832,373 @@ __global__ __launch_bounds__(64) void k_lg_graph(LArgs a) {
             }
         }
     }
+}
+
+// ------------------------------------------------------------------ haplotypes (vc_poa_run_haplotypes; the rule: vechat_hip.h)
+// What the call's kernels read beside LArgs: the rule's parameters.
+struct LHap { uint32_t max_haps, min_reads, min_permille, rounds, flags; };
+
+// A finished group's block of k_lg_hap / k_lg_hapcons, the byte offset of every table in it (16-byte aligned and padded): the
+// header -- n_haps, sites, then per haplotype its members and its consensus length --, the haplotype and the group member of every
+// added sequence, the sites (at most one per column), and room for max_haps consensus paths of at most N nodes.
+struct HapBlock { uint64_t hap_of, member, s_col, s_n1, s_n2, s_maj, s_min, cons, bytes; };
+constexpr uint32_t kHapHead = 2 + 2 * VC_POA_HAP_MAX;  // uint32 entries of the header
+__host__ __device__ inline HapBlock hap_block(uint64_t S, uint64_t C, uint64_t N, uint64_t maxh) {
+    HapBlock B;
+    uint64_t off = 0;
+    auto take = [&](uint64_t bytes) { const uint64_t at = off; off += (bytes + 15) & ~15ull; return at; };
+    take(4 * kHapHead);
+    B.hap_of = take(S); B.member = take(4 * S);
+    B.s_col = take(4 * C); B.s_n1 = take(4 * C); B.s_n2 = take(4 * C); B.s_maj = take(C); B.s_min = take(C);
+    B.cons = take(maxh * N);
+    B.bytes = off;
+    return B;
+}
+// ... and its scratch, which never leaves the device: the S x C matrix of node ids, first and last column, path offsets and the
+// compact paths (T entries), the two alleles of every site, the S x M votes (M <= C), every member's count of non-zero votes
+// and its d(s), the profiles, and per haplotype the restricted graph of k_lg_hapcons with the bundle's scratch.  The votes live
+// here, in HBM behind the L2, not in LDS: S x M has no bound that LDS could promise, and every pass over them is a stream.
+struct HapScratch { uint64_t first, last, p_off, p_node, a1, a2, votes, nz, d, prof, per_hap, hap_bytes, h_wt, h_scores, h_pred, h_comp, h_outn, h_nrank, h_eset, h_nset, bytes; };
+__host__ __device__ inline HapScratch hap_scratch(uint64_t S, uint64_t C, uint64_t T, uint64_t N, uint64_t E, uint64_t maxh) {
+    HapScratch X;
+    uint64_t off = 0;
+    auto take = [&](uint64_t bytes) { const uint64_t at = off; off += (bytes + 15) & ~15ull; return at; };
+    take(4 * S * C);
+    X.first = take(4 * S); X.last = take(4 * S); X.p_off = take(4 * (S + 1)); X.p_node = take(4 * T);
+    X.a1 = take(4 * C); X.a2 = take(4 * C); X.votes = take(S * C); X.nz = take(4 * S); X.d = take(4 * S); X.prof = take(maxh * C);
+    X.per_hap = off;
+    off = 0;
+    X.h_wt = take(8 * E); X.h_scores = take(8 * N); X.h_pred = take(4 * N); X.h_comp = take(4 * N); X.h_outn = take(4 * N);
+    X.h_nrank = take(4 * N); X.h_eset = take(E); X.h_nset = take(N);
+    X.hap_bytes = off;
+    X.bytes = X.per_hap + maxh * X.hap_bytes;
+    return X;
+}
+
+// the lane-wise best of (value, index) over the wave, smaller value first and then the smaller index; every lane gets it
+__device__ __forceinline__ void wave_argmin(int32_t& v, uint32_t& i) {
+    for (uint32_t d = 32; d; d >>= 1) {
+        const int32_t ov = __shfl_xor(v, d, 64);
+        const uint32_t oi = __shfl_xor(i, d, 64);
+        if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+    }
+}
+
+// agree(x, y) of two vote (or profile) rows of M int8
+__device__ __forceinline__ int32_t hap_agree(const int8_t* x, const int8_t* y, uint32_t M) {
+    int32_t t = 0;
+    for (uint32_t m = 0; m < M; ++m) t += (int32_t)x[m] * (int32_t)y[m];
+    return t;
+}
+
+// The members of a finished POA group split into haplotypes, one wave per group (rules 1 to 7 of vechat_hip.h).
+// There is no sizing kernel of this stage's own: the sizing phase is k_lg_graph<0>, which leaves the columns in W.map /
+// W.gr_cols and the path entries in W.gr_path; the host sizes block and scratch from these two and from the group's sequences,
+// nodes and edges (hap_block, hap_scratch).  Then, for the groups of a.list, block at a.msa_out + a.hoff[block], scratch at
+// a.hoff[groups + block]: the nodes scattered into the S x C matrix as the path stage of
+// k_lg_graph<1> does; every row compacted into its path, which also finds first and last; counts with a lane per column (a row's
+// loads are coalesced), one allele at a time so that only the best two live in registers; sites compacted by a wave prefix sum
+// in tiles of 64 with a carried total; the votes; seeds with a lane per member and a wave arg-min that carries the label for the
+// tie; rounds with a lane per member for the assignment and a lane per site for the profiles; small clusters; the order.
+__global__ __launch_bounds__(64) void k_lg_hap(LArgs a, LHap hp) {
+    const uint32_t lane = threadIdx.x;
+    __shared__ uint32_t sh_size[VC_POA_HAP_MAX], sh_min[VC_POA_HAP_MAX], sh_map[VC_POA_HAP_MAX], sh_seed[VC_POA_HAP_MAX];
+    __shared__ uint32_t sh_k;
+    LWin& W = a.win[a.list[blockIdx.x]];
+    const LGraph& g = W.gr[W.cur];
+    const uint32_t S = g.nseq, C = W.gr_cols, T = W.gr_path, N = g.n_nodes, E = g.n_edges, nc = W.num_codes;
+    const uint32_t GAP = nc, maxh = hp.max_haps;
+    const HapBlock B = hap_block(S, C, N, maxh);
+    const HapScratch X = hap_scratch(S, C, T, N, E, maxh);
+    uint8_t* out = a.msa_out + a.hoff[blockIdx.x];
+    uint8_t* scr = a.msa_out + a.hoff[gridDim.x + blockIdx.x];
+    uint32_t* head = (uint32_t*)out;
+    uint8_t* hap_of = out + B.hap_of;
+    uint32_t *member = (uint32_t*)(out + B.member), *s_col = (uint32_t*)(out + B.s_col), *s_n1 = (uint32_t*)(out + B.s_n1), *s_n2 = (uint32_t*)(out + B.s_n2);
+    uint8_t *s_maj = out + B.s_maj, *s_min = out + B.s_min;
+    uint32_t *mat = (uint32_t*)scr, *first = (uint32_t*)(scr + X.first), *last = (uint32_t*)(scr + X.last), *p_off = (uint32_t*)(scr + X.p_off);
+    uint32_t *p_node = (uint32_t*)(scr + X.p_node), *a1 = (uint32_t*)(scr + X.a1), *a2 = (uint32_t*)(scr + X.a2), *nz = (uint32_t*)(scr + X.nz);
+    int32_t* dd = (int32_t*)(scr + X.d);
+    int8_t *votes = (int8_t*)(scr + X.votes), *prof = (int8_t*)(scr + X.prof);
+    if (lane < kHapHead) head[lane] = 0;
+    if (S == 0) {                                                      // no non-empty member: one haplotype without a member
+        if (lane == 0) head[0] = 1;
+        return;
+    }
+    const uint64_t cells = (uint64_t)S * C;
+    const uint4 none4 = make_uint4(NONE, NONE, NONE, NONE);
+    for (uint64_t k = lane; k < (cells + 3) / 4; k += 64) ((uint4*)mat)[k] = none4;
+    uint32_t carry = 0;
+    for (uint32_t s0 = 0; s0 < S; s0 += 64) {
+        const uint32_t s = s0 + lane;
+        uint32_t len = 0;
+        if (s < S) { len = seq_len(a, W, s); member[s] = seq_member(W, s); }
+        const uint32_t x = wave_scan(len, lane);
+        if (s < S) p_off[s] = carry + x - len;
+        carry += __shfl(x, 63, 64);
+    }
+    if (lane == 0) p_off[S] = carry;
+    __syncthreads();
+    for (uint32_t s = lane; s < S; s += 64) {
+        const uint32_t v = W.sq_begin[s];
+        mat[(uint64_t)s * C + W.map[v]] = v;
+    }
+    for (uint32_t e = lane; e < E; e += 64) {
+        const uint32_t h = g.head[e];
+        const uint64_t col = W.map[h];
+        for (uint32_t c = g.lb_h[e]; c != NONE; c = g.lb_nx[c]) mat[(uint64_t)g.lb_v[c] * C + col] = h;
+    }
+    __syncthreads();
+    // the paths, and with them first and last
+    for (uint32_t s = 0; s < S; ++s) {
+        const uint32_t* row = mat + (uint64_t)s * C;
+        const uint32_t end = p_off[s + 1];
+        uint32_t at = p_off[s];
+        for (uint32_t c0 = 0; c0 < C; c0 += 64) {
+            const uint32_t c = c0 + lane;
+            const uint32_t v = c < C ? row[c] : NONE;
+            const uint32_t x = wave_scan(v != NONE, lane);
+            const uint32_t tot = __shfl(x, 63, 64);
+            if (v != NONE) {
+                const uint32_t k = at + x - 1;
+                if (k < end) p_node[k] = v;
+                if (k == p_off[s]) first[s] = c;
+                if (x == tot) last[s] = c;                             // (a later tile with a node overwrites it)
+            }
+            at += tot;
+        }
+    }
+    __syncthreads();
+    // counts and sites
+    const bool indels = (hp.flags & VC_POA_HAP_INDELS) != 0;
+    const uint32_t n_alleles = nc + (indels ? 1u : 0u);
+    uint32_t M = 0;
+    for (uint32_t c0 = 0; c0 < C; c0 += 64) {
+        const uint32_t c = c0 + lane;
+        uint32_t b1 = NONE, b2 = NONE, n1 = 0, n2 = 0;
+        if (c < C) {
+            uint32_t span = 0;
+            for (uint32_t s = 0; s < S; ++s) span += first[s] <= c && c <= last[s];
+            for (uint32_t al = 0; al < n_alleles; ++al) {
+                uint32_t n = 0;
+                for (uint32_t s = 0; s < S; ++s) {
+                    const uint32_t v = mat[(uint64_t)s * C + c];
+                    n += v != NONE ? g.code[v] == al : (al == GAP && first[s] < c && c < last[s]);
+                }
+                if (n < hp.min_reads || 1000ull * n < (uint64_t)hp.min_permille * span) continue;
+                if (n > n1) { b2 = b1; n2 = n1; b1 = al; n1 = n; }
+                else if (n > n2) { b2 = al; n2 = n; }
+            }
+        }
+        const uint32_t site = b2 != NONE;
+        const uint32_t x = wave_scan(site, lane);
+        if (site) {
+            const uint32_t m = M + x - 1;
+            s_col[m] = c; s_n1[m] = n1; s_n2[m] = n2; a1[m] = b1; a2[m] = b2;
+            s_maj[m] = b1 == GAP ? (uint8_t)'-' : (uint8_t)W.decoder[b1];
+            s_min[m] = b2 == GAP ? (uint8_t)'-' : (uint8_t)W.decoder[b2];
+        }
+        M += __shfl(x, 63, 64);
+    }
+    __syncthreads();
+    // votes, and every member's count of non-zero ones
+    for (uint32_t s = 0; s < S; ++s) {
+        uint32_t cnt = 0;
+        for (uint32_t m = lane; m < M; m += 64) {
+            const uint32_t c = s_col[m], v = mat[(uint64_t)s * C + c];
+            const uint32_t sym = v != NONE ? g.code[v] : (first[s] < c && c < last[s] ? GAP : NONE);
+            const int8_t vote = sym == a1[m] ? 1 : sym == a2[m] ? -1 : 0;
+            votes[(uint64_t)s * M + m] = vote;
+            cnt += vote != 0;
+        }
+        for (uint32_t d = 32; d; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+        if (lane == 0) nz[s] = cnt;
+    }
+    __syncthreads();
+    // seeds
+    int32_t bv = INT32_MAX;
+    uint32_t bi = NONE;
+    for (uint32_t s = lane; s < S; s += 64) {
+        const int32_t v = -(int32_t)nz[s];
+        if (v < bv) { bv = v; bi = s; }                                // (a lane's own members come in rising label)
+        dd[s] = INT32_MIN;
+    }
+    wave_argmin(bv, bi);
+    uint32_t K = 1;
+    if (lane == 0) sh_seed[0] = bi;
+    __syncthreads();
+    if (bv != 0) {
+        for (; K < maxh; ++K) {
+            const int8_t* sv = votes + (uint64_t)sh_seed[K - 1] * M;
+            int32_t mv = INT32_MAX;
+            uint32_t mi = NONE;
+            for (uint32_t s = lane; s < S; s += 64) {
+                const int32_t ag = hap_agree(votes + (uint64_t)s * M, sv, M);
+                const int32_t d = dd[s] > ag ? dd[s] : ag;
+                dd[s] = d;
+                if (d < mv) { mv = d; mi = s; }
+            }
+            wave_argmin(mv, mi);
+            if (mv >= 0) break;
+            if (lane == 0) sh_seed[K] = mi;
+            __syncthreads();
+        }
+    }
+    // rounds
+    for (uint32_t k = 0; k < K; ++k)
+        for (uint32_t m = lane; m < M; m += 64) prof[(uint64_t)k * M + m] = votes[(uint64_t)sh_seed[k] * M + m];
+    for (uint32_t s = lane; s < S; s += 64) hap_of[s] = VC_POA_HAP_NONE;
+    __syncthreads();
+    for (uint32_t round = 0; round < hp.rounds; ++round) {
+        bool moved = false;
+        for (uint32_t s = lane; s < S; s += 64) {
+            int32_t best = INT32_MIN;
+            uint32_t bk = 0;
+            for (uint32_t k = 0; k < K; ++k) {
+                const int32_t ag = hap_agree(votes + (uint64_t)s * M, prof + (uint64_t)k * M, M);
+                if (ag > best) { best = ag; bk = k; }
+            }
+            moved |= hap_of[s] != bk;
+            hap_of[s] = (uint8_t)bk;
+        }
+        if (!__any(moved)) break;
+        __syncthreads();
+        for (uint32_t k = 0; k < K; ++k) {
+            for (uint32_t m = lane; m < M; m += 64) {
+                int32_t t = 0;
+                for (uint32_t s = 0; s < S; ++s) if (hap_of[s] == k) t += votes[(uint64_t)s * M + m];
+                prof[(uint64_t)k * M + m] = (int8_t)(t > 0 ? 1 : t < 0 ? -1 : 0);
+            }
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    // small clusters, then the order
+    if (lane < VC_POA_HAP_MAX) { sh_size[lane] = 0; sh_min[lane] = NONE; }
+    __syncthreads();
+    for (uint32_t s = lane; s < S; s += 64) { atomicAdd(&sh_size[hap_of[s]], 1u); atomicMin(&sh_min[hap_of[s]], s); }
+    __syncthreads();
+    bool any = false;
+    for (uint32_t k = 0; k < K; ++k) any |= sh_size[k] >= hp.min_reads;
+    for (uint32_t s = lane; s < S; s += 64) {
+        const uint32_t k0 = hap_of[s];
+        if (!any) { hap_of[s] = 0; continue; }
+        if (sh_size[k0] >= hp.min_reads) continue;
+        int32_t best = INT32_MIN;
+        uint32_t bk = 0;
+        for (uint32_t k = 0; k < K; ++k) {
+            if (sh_size[k] < hp.min_reads) continue;
+            const int32_t ag = hap_agree(votes + (uint64_t)s * M, prof + (uint64_t)k * M, M);
+            if (ag > best) { best = ag; bk = k; }
+        }
+        hap_of[s] = (uint8_t)(bk | 0x80u);                             // (marked: the sizes below are still the old ones)
+    }
+    __syncthreads();
+    if (lane == 0) {
+        if (!any) { sh_k = 1; sh_map[0] = 0; for (uint32_t k = 1; k < K; ++k) sh_map[k] = NONE; sh_size[0] = S; sh_min[0] = 0; }
+    }
+    if (any) {
+        __syncthreads();
+        const bool keep = lane < K && sh_size[lane] >= hp.min_reads;
+        __syncthreads();
+        if (lane < VC_POA_HAP_MAX && !keep) { sh_size[lane] = 0; sh_min[lane] = NONE; }
+        __syncthreads();
+        for (uint32_t s = lane; s < S; s += 64) {
+            if (!(hap_of[s] & 0x80u)) continue;
+            const uint32_t k = hap_of[s] & 0x7Fu;
+            hap_of[s] = (uint8_t)k;
+            atomicAdd(&sh_size[k], 1u); atomicMin(&sh_min[k], s);
+        }
+        __syncthreads();
+        if (lane == 0) {
+            uint32_t n = 0;
+            for (uint32_t k = 0; k < K; ++k) sh_map[k] = NONE;
+            for (;;) {                                                 // selection by (size, largest first; then the smaller smallest label)
+                uint32_t bk = NONE;
+                for (uint32_t k = 0; k < K; ++k) {
+                    if (sh_size[k] == 0 || sh_map[k] != NONE) continue;
+                    if (bk == NONE || sh_size[k] > sh_size[bk] || (sh_size[k] == sh_size[bk] && sh_min[k] < sh_min[bk])) bk = k;
+                }
+                if (bk == NONE) break;
+                sh_map[bk] = n++;
+            }
+            sh_k = n;
+        }
+    }
+    __syncthreads();
+    for (uint32_t s = lane; s < S; s += 64) hap_of[s] = (uint8_t)sh_map[hap_of[s]];
+    if (lane == 0) { head[0] = sh_k; head[1] = M; }
+    if (lane < K && sh_map[lane] != NONE) head[2 + sh_map[lane]] = sh_size[lane];
+}
+
+// one haplotype's restriction of the group's graph, and the bundle's scratch of this block (rule 8)
+struct HapView {
+    const LGraph& g;
+    int64_t* scores;
+    uint32_t *pred, *node_rank, *comp;
+    const int64_t* wt;
+    const uint32_t* outn;
+    const uint8_t *eset, *nset;
+    __device__ __forceinline__ bool node(uint32_t v) const { return nset[v] != 0; }
+    __device__ __forceinline__ bool edge(uint32_t e) const { return eset[e] != 0; }
+    __device__ __forceinline__ int64_t weight(uint32_t e) const { return wt[e]; }
+    __device__ __forceinline__ uint32_t out_n(uint32_t v) const { return outn[v]; }
+};
+
+// The consensus of every haplotype (rule 8), one block per (group, haplotype) so that the haplotypes of a group run side by side,
+// each on tables of its own behind the group's scratch: the restricted weights rebuilt from the members' paths -- a lane per step
+// i, which finds the edge in the tail's out-list as add_edge did and adds w[i - 1] + w[i] --, the restricted out-degrees with a
+// lane per edge, then the bundle on lane 0 as k_lg_apply runs the whole graph's.
+__global__ __launch_bounds__(64) void k_lg_hapcons(LArgs a, LHap hp) {
+    const uint32_t lane = threadIdx.x, q = blockIdx.x, k = blockIdx.y, groups = gridDim.x;
+    LWin& W = a.win[a.list[q]];
+    const LGraph& g = W.gr[W.cur];
+    const uint32_t S = g.nseq, C = W.gr_cols, T = W.gr_path, N = g.n_nodes, E = g.n_edges;
+    const HapBlock B = hap_block(S, C, N, hp.max_haps);
+    const HapScratch X = hap_scratch(S, C, T, N, E, hp.max_haps);
+    uint8_t* out = a.msa_out + a.hoff[q];
+    uint8_t* scr = a.msa_out + a.hoff[groups + q];
+    uint32_t* head = (uint32_t*)out;
+    const uint8_t* hap_of = out + B.hap_of;
+    const uint32_t *p_off = (const uint32_t*)(scr + X.p_off), *p_node = (const uint32_t*)(scr + X.p_node);
+    uint8_t* mine = scr + X.per_hap + (uint64_t)k * X.hap_bytes;
+    unsigned long long* wt = (unsigned long long*)(mine + X.h_wt);
+    uint32_t* outn = (uint32_t*)(mine + X.h_outn);
+    uint8_t *eset = mine + X.h_eset, *nset = mine + X.h_nset;
+    if (S == 0 || k >= head[0]) return;                                    // no such haplotype, or the empty consensus: its length is zero already
+    for (uint32_t e = lane; e < E; e += 64) { wt[e] = 0; eset[e] = 0; }
+    for (uint32_t v = lane; v < N; v += 64) { outn[v] = 0; nset[v] = 0; }
+    __syncthreads();
+    for (uint32_t s = 0; s < S; ++s) {
+        if (hap_of[s] != k) continue;
+        const uint32_t sq = W.s0 + W.sq_member[s], p0 = p_off[s], len = p_off[s + 1] - p0;
+        const bool uq = a.has_qual[sq] != 0;
+        for (uint32_t i = lane; i < len; i += 64) {
+            const uint32_t v = p_node[p0 + i];
+            if (v >= N) continue;                                          // (every path entry is a node: the labels fill them all)
+            nset[v] = 1;
+            if (i == 0) continue;
+            const uint32_t u = p_node[p0 + i - 1];
+            if (u >= N) continue;
+            const uint32_t w = weight_of(a, W, sq, i - 1, uq) + weight_of(a, W, sq, i, uq);
+            for (uint32_t e = g.out_h[u]; e != NONE; e = g.nx_out[e]) {
+                if (g.head[e] != v) continue;
+                atomicAdd(&wt[e], (unsigned long long)w);
+                eset[e] = 1;
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t e = lane; e < E; e += 64) if (eset[e]) atomicAdd(&outn[g.tail[e]], 1u);
+    __syncthreads();
+    if (lane != 0) return;
+    const HapView V{g, (int64_t*)(mine + X.h_scores), (uint32_t*)(mine + X.h_pred), (uint32_t*)(mine + X.h_nrank), (uint32_t*)(mine + X.h_comp),
+                    (const int64_t*)wt, outn, eset, nset};
+    const uint32_t n = heaviest_bundle(g, V);
+    uint8_t* cons = out + B.cons + (uint64_t)k * N;
+    for (uint32_t i = 0; i < n; ++i) cons[i] = (uint8_t)W.decoder[g.code[V.comp[i]]];
+    head[2 + VC_POA_HAP_MAX + k] = n;
 }
 
 }  // namespace

@@ -1051,6 +1051,98 @@ def poa_correct(groups, algorithm="global", match=5, mismatch=-4, gap=-8, device
     return [None if w in bad else c for w, c in enumerate(res)]
 
 
+class Haplotypes:
+    """One group's result of poa_haplotypes: consensus (one bytes per haplotype, largest first), sizes (members per haplotype),
+    members (per group member its haplotype, None for an empty member), sites ((column, major, minor, n_major, n_minor) with the
+    alleles as bytes, b"-" a gap), status."""
+    __slots__ = ("consensus", "sizes", "members", "sites", "status")
+
+    def __init__(self, consensus, sizes, members, sites, status):
+        self.consensus, self.sizes, self.members, self.sites, self.status = consensus, sizes, members, sites, status
+
+
+def hap_params(max_haplotypes=2, min_reads=2, min_fraction=0.25, indels=False, rounds=4):
+    """the checks of vc_poa_run_haplotypes' own parameters, before any batch is made; min_fraction becomes permille here, once"""
+    for name, v, lo, hi in (("max_haplotypes", max_haplotypes, 1, capi.VC_POA_HAP_MAX), ("min_reads", min_reads, 1, 2 ** 32 - 1),
+                            ("rounds", rounds, 1, 2 ** 32 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, not {v!r}")
+    if isinstance(min_fraction, bool) or not isinstance(min_fraction, (int, float, np.integer, np.floating)) or not 0 <= float(min_fraction) <= 1:
+        raise ValueError(f"min_fraction must be a number in 0..1, not {min_fraction!r}")
+    return capi.VcPoaHapParams(int(max_haplotypes), int(min_reads), int(round(1000 * float(min_fraction))), int(rounds),
+                               capi.VC_POA_HAP_INDELS if indels else 0)
+
+
+def run_batch_haplotypes(batch, params, hap, lib=None):
+    """vc_poa_run_haplotypes (params: capi.VcPoaGapParams; hap: capi.VcPoaHapParams) on a capi.Batch -> (consensus bytes per group,
+    status array, list of Haplotypes, the raw tables as a dict of numpy arrays).  Everything is copied out of the library's buffers
+    before returning.  Raises PoaError on a library error."""
+    lib = lib or capi.load_hip()
+    if not hasattr(lib, "vc_poa_run_haplotypes"):
+        raise PoaError("this libvechat_hip.so has no vc_poa_run_haplotypes: it was built before the entry point existed; rebuild it")
+    n = batch.n_windows
+    cons, off, status, r, vb = _result_buffers(batch)
+    o = capi.VcPoaHapOut()
+    rc = lib.vc_poa_run_haplotypes(C.byref(params), C.byref(hap), C.byref(vb), C.byref(r), C.byref(o))
+    if rc != 0:
+        raise PoaError(f"vc_poa_run_haplotypes failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
+    wso = [int(x) for x in batch.win_seq_off]
+    group_cons = [cons[int(off[w]):int(off[w + 1])].tobytes() for w in range(n)]
+    if n == 0:
+        return group_cons, status[:0], [], {}
+    hf, so = _table(o.hap_first, n + 1).astype(np.int64), _table(o.site_off, n + 1).astype(np.int64)
+    nh, ns = int(hf[-1]), int(so[-1])
+    co = _table(o.cons_off, nh + 1).astype(np.int64)
+    raw = dict(n_haps=_table(o.n_haps, n), hap_first=hf, hap_size=_table(o.hap_size, nh), cons_off=co, cons=_table(o.cons, int(co[-1])),
+               hap_of=_table(o.hap_of, wso[-1]), site_off=so, site_col=_table(o.site_col, ns), site_major=_table(o.site_major, ns),
+               site_minor=_table(o.site_minor, ns), site_n_major=_table(o.site_n_major, ns), site_n_minor=_table(o.site_n_minor, ns),
+               bytes=int(o.bytes))
+    hb = raw["cons"].tobytes()
+    res = []
+    for w in range(n):
+        hs = range(int(hf[w]), int(hf[w + 1]))
+        res.append(Haplotypes(
+            [hb[int(co[h]):int(co[h + 1])] for h in hs], [int(raw["hap_size"][h]) for h in hs],
+            [None if int(x) == capi.VC_POA_HAP_NONE else int(x) for x in raw["hap_of"][wso[w]:wso[w + 1]]],
+            [(int(raw["site_col"][k]), bytes([int(raw["site_major"][k])]), bytes([int(raw["site_minor"][k])]), int(raw["site_n_major"][k]),
+              int(raw["site_n_minor"][k])) for k in range(int(so[w]), int(so[w + 1]))],
+            int(status[w])))
+    return group_cons, status[:n], res, raw
+
+
+def poa_haplotypes(groups, max_haplotypes=2, min_reads=2, min_fraction=0.25, indels=False, rounds=4, algorithm="global", match=5,
+                   mismatch=-4, gap=-8, device=0, strict=True, lib=None, *, gap_extend=None, gap_open2=None, gap_extend2=None):
+    """The haplotypes of every group (vc_poa_run_haplotypes; the rule is in include/vechat_hip.h): the group's graph is built as
+    poa_consensus builds it, the columns in which at least two alleles reach min_reads members and min_fraction of the members
+    that span them become sites, the members are clustered by their alleles at the sites into at most max_haplotypes clusters,
+    and every cluster gets the consensus of the graph restricted to its members -> list of Haplotypes.  indels=True lets a gap be
+    an allele.  Parameters, PoaError and strict as poa_consensus: a group that was not computed raises, or with strict=False
+    comes back as None.  ValueError for a parameter outside its range."""
+    hap = hap_params(max_haplotypes, min_reads, min_fraction, indels, rounds)
+    p = _gap_params(algorithm, match, mismatch, gap, device, gap_extend, gap_open2, gap_extend2)
+    _, status, res, _ = run_batch_haplotypes(group_batch(groups), p, hap, lib)
+    bad = _not_computed(status, strict)
+    return [None if w in bad else h for w, h in enumerate(res)]
+
+
+def haplotype_fasta(group_names, results):
+    """The text of --haplotypes: >GROUP_hapK members=N and the haplotype's consensus, groups in input order"""
+    return b"".join(b">%s_hap%d members=%d\n%s\n" % (_bytes(g, "group name"), k, n, c)
+                    for g, h in zip(group_names, results) if h is not None for k, (c, n) in enumerate(zip(h.consensus, h.sizes)))
+
+
+def haplotype_members_tsv(group_names, records, results):
+    """The text of --hap-members: file, read name, haplotype (or - for a member that was not added)"""
+    return b"".join(b"%s\t%s\t%s\n" % (_bytes(g, "group name"), _bytes(name, "record name"), b"-" if m is None else b"%d" % m)
+                    for g, recs, h in zip(group_names, records, results) if h is not None for (name, _, _), m in zip(recs, h.members))
+
+
+def haplotype_sites_tsv(group_names, results):
+    """The text of --hap-sites: file, column, major, minor, n_major, n_minor"""
+    return b"".join(b"%s\t%d\t%s\t%s\t%d\t%d\n" % (_bytes(g, "group name"), c, a, b, na, nb)
+                    for g, h in zip(group_names, results) if h is not None for c, a, b, na, nb in h.sites)
+
+
 def corrected_fasta(records, results):
     """The text of --correct: records[w] the (name, data, quality) records of group w, results[w] its Corrected -> FASTA, one
     record per member under its own name, groups in input order; an empty correction has an empty sequence line."""
@@ -1251,6 +1343,19 @@ def parse_args(argv=None):
                     help="also write the per-base profile of every consensus to FILE: a header line per group naming its codes, then one "
                          "tab-separated line per consensus position: group, position, base, one count per code, gaps. Not with --align, "
                          "--correct, --spans, --save-graphs or --from-graphs")
+    ap.add_argument("--haplotypes", metavar="FILE", default=None,
+                    help="also split every input file's records into haplotypes and write their consensus sequences to FILE as FASTA, "
+                         "'>INPUT_hapK members=N' (the consensus on stdout is unchanged); only with the plain consensus output")
+    ap.add_argument("--hap-members", metavar="FILE", default=None,
+                    help="also write the haplotype of every record to FILE: tab-separated input file, record name, haplotype (- for an empty record)")
+    ap.add_argument("--hap-sites", metavar="FILE", default=None,
+                    help="also write the sites that separate the haplotypes to FILE: tab-separated input file, column, major, minor, n_major, n_minor")
+    ap.add_argument("--max-haplotypes", type=int, default=2, metavar="K", help="with --haplotypes / --hap-*: at most K haplotypes per file, 1..8 (default 2)")
+    ap.add_argument("--hap-min-reads", type=int, default=2, metavar="N",
+                    help="with --haplotypes / --hap-*: an allele and a haplotype need N records (default 2)")
+    ap.add_argument("--hap-min-fraction", type=float, default=0.25, metavar="F",
+                    help="with --haplotypes / --hap-*: an allele needs the fraction F of the records that span its column (default 0.25)")
+    ap.add_argument("--hap-indels", action="store_true", help="with --haplotypes / --hap-*: a gap is an allele too")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal (default 0)")
     ap.add_argument("files", nargs="*", metavar="FILE")
     a = ap.parse_args(argv)
@@ -1293,6 +1398,12 @@ def main(argv=None):
         return 1
     if (a.weights is not None or a.profile is not None) and (resume or a.correct is not None or a.align is not None or a.spans is not None):
         print("vechat_amd.poa: --weights / --profile do not go with --align, --correct, --spans, --save-graphs or --from-graphs", file=sys.stderr)
+        return 1
+    hap_out = a.haplotypes is not None or a.hap_members is not None or a.hap_sites is not None
+    if hap_out and (a.r != 0 or a.coverage or gfa or a.graphviz is not None or a.both_strands or a.align is not None or a.assign is not None or
+                    a.correct is not None or resume or a.spans is not None or a.weights is not None or a.profile is not None):
+        print("vechat_amd.poa: --haplotypes / --hap-members / --hap-sites go with the consensus only (vc_poa_run_haplotypes takes no "
+              "spans, weights, strands, queries or stored graphs): run the other outputs on their own", file=sys.stderr)
         return 1
     # what the command line asks for: the alignment rows or the coverage (a vc_poa_msa_out, which vc_poa_run_align does not carry),
     # the graph tables, the queries
@@ -1359,6 +1470,17 @@ def main(argv=None):
                 f.write(corrected_fasta(records, res))
             if not want_msa:
                 cons = [c.consensus for c in res]
+        elif hap_out:
+            # one call: the consensus of every file on stdout as always, and its haplotypes into the files asked for
+            hp = hap_params(a.max_haplotypes, a.hap_min_reads, a.hap_min_fraction, a.hap_indels)
+            cons, status, res, _ = run_batch_haplotypes(group_batch(groups), p, hp)
+            _not_computed(status, True)
+            for path, text in ((a.haplotypes, lambda: haplotype_fasta(a.files, res)),
+                               (a.hap_members, lambda: haplotype_members_tsv(a.files, records, res)),
+                               (a.hap_sites, lambda: haplotype_sites_tsv(a.files, res))):
+                if path is not None:
+                    with open(path, "wb") as f:
+                        f.write(text())
         if a.align is not None and not resume:
             # every query against every group.  Without rows or coverage this one call builds the groups once and gives the
             # consensus or the graph too; beside them it is a call of its own
