@@ -26,6 +26,8 @@
 //                cell as int16 and the 31 steps to its right neighbours (each 0, 1 or 2) as 2-bit fields --
 //                12 bytes per 32 cells, 0.375 B/cell, otherwise the stores would exceed HBM bandwidth.
 //   k_aln_trace  one thread per overlap, re-derives each move from the stored scores.
+//
+// Host: the buffers of a call and of a chunk are two DevMem scopes, and every copy is checked (vc_devutil.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +38,8 @@
 #include <vector>
 
 #include "vechat_hip.h"
+
+#include "vc_devutil.h"
 
 namespace {
 
@@ -226,14 +230,7 @@ __global__ void k_aln_trace(AlnArgs a) {
     a.n_ops[job] = k;
 }
 
-template <typename T>
-bool dalloc(std::vector<void*>& list, T** p, size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return false;
-    list.push_back(q);
-    *p = (T*)q;
-    return true;
-}
+using namespace vc_dev;
 
 thread_local std::string g_err;
 int fail(const char* m) { g_err = m; return VC_ERR_HIP; }
@@ -246,16 +243,9 @@ uint32_t* mat_buffer(int device, uint64_t dwords) {
     if (g_mat.p && g_mat.device == device && g_mat.dwords >= dwords) return g_mat.p;
     if (g_mat.p) { (void)hipFree(g_mat.p); g_mat = MatCache{}; }
     void* q = nullptr;
-    if (hipMalloc(&q, std::max<uint64_t>(dwords, 1) * 4) != hipSuccess) return nullptr;
+    if (hipMalloc(&q, std::max<uint64_t>(dwords, 1) * 4) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     g_mat.device = device; g_mat.p = (uint32_t*)q; g_mat.dwords = dwords;
     return g_mat.p;
-}
-
-// a knob in MiB as bytes (the header of this file lists them); 0: not set
-uint64_t env_mib(const char* name) {
-    const char* v = getenv(name);
-    const double x = v ? std::atof(v) : 0.0;
-    return x > 0 ? std::max<uint64_t>((uint64_t)(x * 1048576.0), 1) : 0;
 }
 
 }  // namespace
@@ -291,20 +281,16 @@ int vc_align(int device, const vc_align_batch* b, char* cigar, uint64_t cigar_ca
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     const uint64_t budget = knob_budget ? knob_budget : (uint64_t)((free_b + (g_mat.device == device ? g_mat.dwords * 4 : 0)) * 0.5);
-    std::vector<void*> fixed;
+    DevMem fixed;                                                   // the batch: to the end of the call
     uint8_t *d_q = nullptr, *d_t = nullptr;
     uint64_t *d_qo = nullptr, *d_to = nullptr;
     uint8_t* d_skip = nullptr;
     const uint64_t qbytes = b->q_off[n], tbytes = b->t_off[n];
-    auto cleanup = [&](std::vector<void*>& l) { for (void* p : l) (void)hipFree(p); l.clear(); };
-    if (!dalloc(fixed, &d_q, qbytes) || !dalloc(fixed, &d_t, tbytes) || !dalloc(fixed, &d_qo, (size_t)n + 1) || !dalloc(fixed, &d_to, (size_t)n + 1) || !dalloc(fixed, &d_skip, (size_t)n)) {
-        cleanup(fixed); return fail("hipMalloc failed");
-    }
-    (void)hipMemcpy(d_q, b->q, qbytes, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_t, b->t, tbytes, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_qo, b->q_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_to, b->t_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_skip, skip.data(), n, hipMemcpyHostToDevice);
+    if (!fixed.alloc(&d_q, qbytes) || !fixed.alloc(&d_t, tbytes) || !fixed.alloc(&d_qo, (uint64_t)n + 1) || !fixed.alloc(&d_to, (uint64_t)n + 1) || !fixed.alloc(&d_skip, n))
+        return fail("hipMalloc failed");
+    if (!to_device(d_q, b->q, qbytes) || !to_device(d_t, b->t, tbytes) || !to_device(d_qo, b->q_off, (uint64_t)n + 1) || !to_device(d_to, b->t_off, (uint64_t)n + 1) ||
+        !to_device(d_skip, skip.data(), n))
+        return fail("copying the batch to the device failed");
     uint64_t out = 0;
     std::string cg;
     for (uint32_t k0 = 0; k0 < n;) {
@@ -322,28 +308,23 @@ int vc_align(int device, const vc_align_batch* b, char* cigar, uint64_t cigar_ca
         }
         const uint32_t nj = k1 - k0;
         if (log) fprintf(stderr, "vc_align: chunk first=%u pairs=%u mat_dwords=%llu\n", k0, nj, (unsigned long long)mat_dw);
-        std::vector<void*> tmp;
+        DevMem tmp;                                                 // this chunk's
         AlnArgs a{};
         uint64_t *d_mo = nullptr, *d_bo = nullptr, *d_oo = nullptr;
         a.mat = mat_buffer(device, mat_dw);
-        if (!a.mat || !dalloc(tmp, &a.bnd, bnd_n) || !dalloc(tmp, &a.ops, ops_n) || !dalloc(tmp, &a.n_ops, nj) ||
-            !dalloc(tmp, &a.dist, nj) || !dalloc(tmp, &d_mo, nj) || !dalloc(tmp, &d_bo, nj) || !dalloc(tmp, &d_oo, nj)) {
-            cleanup(tmp); cleanup(fixed); return fail("hipMalloc failed (overlap too large for the device memory budget?)");
-        }
-        (void)hipMemcpy(d_mo, mat_off.data(), (size_t)nj * 8, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_bo, bnd_off.data(), (size_t)nj * 8, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_oo, ops_off.data(), (size_t)nj * 8, hipMemcpyHostToDevice);
+        if (!a.mat || !tmp.alloc(&a.bnd, bnd_n) || !tmp.alloc(&a.ops, ops_n) || !tmp.alloc(&a.n_ops, nj) ||
+            !tmp.alloc(&a.dist, nj) || !tmp.alloc(&d_mo, nj) || !tmp.alloc(&d_bo, nj) || !tmp.alloc(&d_oo, nj))
+            return fail("hipMalloc failed (overlap too large for the device memory budget?)");
+        if (!to_device(d_mo, mat_off.data(), nj) || !to_device(d_bo, bnd_off.data(), nj) || !to_device(d_oo, ops_off.data(), nj))
+            return fail("copying a chunk's offsets to the device failed");
         a.n_jobs = nj; a.q_off = d_qo + k0; a.q = d_q; a.t_off = d_to + k0; a.t = d_t; a.skip = d_skip + k0;
         a.mat_off = d_mo; a.bnd_off = d_bo; a.ops_off = d_oo;
         hipLaunchKernelGGL(k_aln_fwd, dim3(nj), dim3(64), 0, 0, a);
         hipLaunchKernelGGL(k_aln_trace, dim3((nj + 63) / 64), dim3(64), 0, 0, a);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { cleanup(tmp); cleanup(fixed); return fail("alignment kernels failed"); }
-        std::vector<uint8_t> ops(ops_n);
-        std::vector<uint32_t> nops(nj);
-        (void)hipMemcpy(ops.data(), a.ops, ops_n, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(nops.data(), a.n_ops, (size_t)nj * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(edit_distance + k0, a.dist, (size_t)nj * 4, hipMemcpyDeviceToHost);
-        cleanup(tmp);
+        if (!ran()) return fail("alignment kernels failed");
+        std::vector<uint8_t> ops;
+        std::vector<uint32_t> nops;
+        if (!to_host(ops, a.ops, ops_n) || !to_host(nops, a.n_ops, nj) || !to_host(edit_distance + k0, a.dist, nj)) return fail("copying a chunk's results failed");
         for (uint32_t k = 0; k < nj; ++k) {
             cg.clear();
             if (skip[k0 + k]) edit_distance[k0 + k] = -1;
@@ -355,14 +336,13 @@ int vc_align(int device, const vc_align_batch* b, char* cigar, uint64_t cigar_ca
                 cg += std::to_string(run);
                 cg += "MID"[op];
             }
-            if (out + cg.size() + 1 > cigar_cap) { cleanup(fixed); return fail("cigar buffer too small"); }
+            if (out + cg.size() + 1 > cigar_cap) return fail("cigar buffer too small");
             std::memcpy(cigar + out, cg.c_str(), cg.size() + 1);
             out += cg.size() + 1;
             cigar_off[k0 + k + 1] = out;
         }
         k0 = k1;
     }
-    cleanup(fixed);
     return VC_OK;
 }
 

@@ -96,7 +96,7 @@
 // that finished while its tables are resident, assemble in window order with its log line, publish into the caller's out-struct --
 // and the schedule walks the stages a call asks for without naming them.  Align and correct are one job stage (JobStage) with
 // two kinds; graph and profile share their launch layout, every block in front of every scratch, and the copy that takes the
-// blocks out.
+// blocks out.  The device buffers of a scope (DevMem), the device check and the knobs in MiB are vc_devutil.h's.
 //
 // Limits, every schedule: a sequence is shorter than 65 535 bases; beyond that only the device memory bounds a window or group,
 // and one whose tables or matrix it cannot hold at all comes back VC_WIN_OVERFLOW.  Where the reference throws (an invalid
@@ -152,9 +152,12 @@
 #include "vechat_hip.h"
 
 #include "vc_large_kernels.h"
+#include "vc_devutil.h"
 
 namespace {
 // ------------------------------------------------------------------ host
+using namespace vc_dev;                                // DevMem, ran(), env_mib(), check_device()
+
 thread_local std::string g_err;
 int fail(int rc, const char* m) { g_err = m; return rc; }
 
@@ -217,36 +220,14 @@ void release_cache() {
     g_cache = Cache{};
 }
 
-// the device allocations of one scope, freed when it ends
-struct DevMem {
-    std::vector<void*> held;
-    DevMem() = default;
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    ~DevMem() { for (void* q : held) (void)hipFree(q); }
-    // n elements (at least one), filled from src where there is one
-    template <class T> bool alloc(T** p, size_t n, const void* src = nullptr) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        held.push_back(q);
-        *p = (T*)q;
-        return !src || n == 0 || hipMemcpy(q, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
-    }
-};
-
 // the development knobs of the header comment; false: VC_LARGE_CAPS does not parse
 constexpr char kTables[] = "nealsp";                   // Knobs::shift order
 struct Knobs { uint32_t shift[6] = {0, 0, 0, 0, 0, 0}; uint64_t arena = 0, mat = 0; bool log = false; };
 
 bool read_knobs(Knobs& k) {
     k = Knobs{};
-    auto mib = [](const char* name) -> uint64_t {
-        const char* v = getenv(name);
-        const double x = v ? std::atof(v) : 0.0;
-        return x > 0 ? std::max<uint64_t>((uint64_t)(x * 1048576.0), 1) : 0;
-    };
-    k.arena = mib("VC_LARGE_ARENA_MB");
-    k.mat = mib("VC_LARGE_MAT_MB");
+    k.arena = env_mib("VC_LARGE_ARENA_MB");
+    k.mat = env_mib("VC_LARGE_MAT_MB");
     const char* lg = getenv("VC_LARGE_LOG");
     k.log = lg && std::atoi(lg) != 0;
     const char* c = getenv("VC_LARGE_CAPS");
@@ -282,20 +263,6 @@ Caps initial_caps(uint64_t sum, uint64_t mx, uint64_t nseq, const Knobs& kn) {
     c.NC = shrunk(c.NC, kn.shift[0]); c.EC = shrunk(c.EC, kn.shift[1]); c.AC = shrunk(c.AC, kn.shift[2]);
     c.LC = shrunk(c.LC, kn.shift[3]); c.SC = shrunk(c.SC, kn.shift[4]); c.PC = shrunk(c.PC, kn.shift[5]);
     return c;
-}
-
-// VC_OK, or the error of a device the kernels cannot run on
-int check_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VC_ERR_NO_DEVICE, "no HIP device visible; the large-graph path has no CPU fallback");
-    }
-    if (device < 0 || device >= ndev) return fail(VC_ERR_NO_DEVICE, "no HIP device with this ordinal");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(VC_ERR_HIP, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(VC_ERR_NO_DEVICE, "the kernels are built for gfx950 only");
-    return VC_OK;
 }
 
 // What a call wants beside consensus and status, and where each output goes (the caller's out-structs); vc_large_run's is empty.
@@ -595,7 +562,7 @@ bool align_step(Run& R, Group& G, const std::vector<uint32_t>& act) {
         const uint32_t nl = (uint32_t)list.size();
         f.H = (int32_t*)H;
         with_gap_model(f.gaps, [&](auto gm) { launch_align<decltype(gm)::value>(f, nl, R.ns); });
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, failed);
+        if (!ran()) return fail(VC_ERR_HIP, failed);
         for (const uint32_t k : list) R.n_cells += (uint64_t)G.hw[k].rows * G.hw[k].qlen * R.ns;
         R.n_align += (uint64_t)nl * R.ns;
         if (cells * 4 > R.mat_budget) over++;
@@ -1069,7 +1036,7 @@ struct JobStage : Stage {
                 const uint32_t nl = (uint32_t)list.size();
                 f.H = (int32_t*)H;
                 with_gap_model(f.gaps, [&](auto gm) { launch_query<decltype(gm)::value>(f, nl, K.ns, K.pairs); });
-                if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, K.no_kernel);
+                if (!ran()) return fail(VC_ERR_HIP, K.no_kernel);
                 for (const uint32_t j : list) n_cells += (uint64_t)jobs[j].rows * jobs[j].qlen * K.ns;
                 return VC_OK;
             };
@@ -1294,7 +1261,7 @@ struct AssignStage : Stage {
             s.t0 = t0; s.t1 = t1;
             const uint64_t lanes = (t1 - 1) / fin.size() - t0 / fin.size() + 1;
             hipLaunchKernelGGL(k_lg_assign, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, 0, a, s);
-            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(VC_ERR_HIP, failed);
+            if (!ran()) return fail(VC_ERR_HIP, failed);
             n_pairs += t1 - t0;
         }
         return VC_OK;
@@ -1852,7 +1819,7 @@ int run_groups(int32_t device, int32_t algorithm, LArgs a, const vc_batch* b, vc
         if (!(q.prune->min_confidence >= 0) || !(q.prune->min_support >= 0)) return fail(VC_ERR_ARG, "min_confidence and min_support must be >= 0 and not NaN");
         a.correct = 1; a.min_conf = q.prune->min_confidence; a.min_sup = q.prune->min_support; a.num_prune = q.prune->num_prune;
     }
-    if (const int rc = check_device(device)) return rc;
+    if (const int rc = check_device(device, "the large-graph path", g_err)) return rc;
     r->cons_off[0] = 0;
     if (nw == 0) return VC_OK;
     a.mode = 2; a.algorithm = (uint32_t)algorithm;
@@ -1927,7 +1894,7 @@ void vc_large_release(void) { release_cache(); g_out.clear(); }
 
 int vc_large_run(const vc_params* p, const vc_batch* b, vc_result* r) {
     if (!p || !b || !r || !r->cons_off || !r->status || (!r->cons && r->cons_cap)) return fail(VC_ERR_ARG, "null argument");
-    if (const int rc = check_device(p->device)) return rc;
+    if (const int rc = check_device(p->device, "the large-graph path", g_err)) return rc;
     if (p->mode != 0 && p->mode != 1) return fail(VC_ERR_ARG, "mode must be 0 or 1");
     if (p->num_prune == 0) return fail(VC_ERR_ARG, "num_prune must be >= 1");
     Knobs kn;

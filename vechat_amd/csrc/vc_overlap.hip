@@ -22,8 +22,10 @@
 //                  with a lane shuffle); a wave maximum and a ballot apply the tie rule.  f and pred of every anchor go to HBM
 //                  for the walk back, which lane 0 does together with the record.
 //   Sorting and scanning are hipcub's (DeviceRadixSort, DeviceScan); both are stable / deterministic for integers.
+//
+// Host: the device buffers of a scope (DevMem), the checked copies and the device check are vc_devutil.h's; the sort and the
+// prefix sums are vc_devscan.h's.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <climits>
@@ -34,6 +36,8 @@
 #include <vector>
 
 #include "vechat_hip.h"
+
+#include "vc_devscan.h"
 
 namespace {
 
@@ -316,79 +320,24 @@ __global__ __launch_bounds__(64) void k_ovl_chain(ChainArgs a) {
 
 // ---------------------------------------------------------------------------------------------------------------- host
 
+using namespace vc_dev;
+
 thread_local std::string g_err;
 int fail(int code, const std::string& m) { g_err = m; return code; }
-
-struct DevMem {                        // every device buffer of a call, released together
-    std::vector<void*> list;
-    template <typename T> bool get(T** p, uint64_t n) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<uint64_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        list.push_back(q);
-        *p = (T*)q;
-        return true;
-    }
-    void drop(void* p) {
-        for (size_t i = 0; i < list.size(); ++i) if (list[i] == p) { (void)hipFree(p); list.erase(list.begin() + (long)i); return; }
-    }
-    ~DevMem() { for (void* p : list) (void)hipFree(p); }
-};
-
-inline uint32_t grid(uint64_t n, uint32_t block = 256) { return (uint32_t)((n + block - 1) / block); }
-
-template <typename V>
-bool sort_pairs(DevMem& m, const uint64_t* ki, uint64_t* ko, const V* vi, V* vo, uint32_t n, int bits) {
-    size_t tb = 0;
-    if (hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ki, ko, vi, vo, n, 0, bits, (hipStream_t)0) != hipSuccess) return false;
-    uint8_t* tmp = nullptr;
-    if (!m.get(&tmp, tb)) return false;
-    const bool ok = hipcub::DeviceRadixSort::SortPairs(tmp, tb, ki, ko, vi, vo, n, 0, bits, (hipStream_t)0) == hipSuccess;
-    (void)hipDeviceSynchronize();
-    m.drop(tmp);
-    return ok;
-}
-template <typename T>
-bool scan(DevMem& m, const T* in, T* out, uint64_t n, bool inclusive) {
-    size_t tb = 0;
-    hipError_t e = inclusive ? hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, (hipStream_t)0)
-                             : hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, (hipStream_t)0);
-    if (e != hipSuccess) return false;
-    uint8_t* tmp = nullptr;
-    if (!m.get(&tmp, tb)) return false;
-    e = inclusive ? hipcub::DeviceScan::InclusiveSum(tmp, tb, in, out, (int)n, (hipStream_t)0)
-                  : hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, (hipStream_t)0);
-    (void)hipDeviceSynchronize();
-    m.drop(tmp);
-    return e == hipSuccess;
-}
 
 // the runs of equal keys of a sorted array: id[i] (1-based) and start[runs + 1]; returns the number of runs, or -1
 int64_t run_bounds(DevMem& m, const uint64_t* key, uint32_t n, uint32_t** id_out, uint32_t** start_out) {
     uint32_t *flag = nullptr, *id = nullptr, *start = nullptr;
-    if (!m.get(&flag, n) || !m.get(&id, n)) return -1;
+    if (!m.alloc(&flag, n) || !m.alloc(&id, n)) return -1;
     hipLaunchKernelGGL(k_ovl_heads, dim3(grid(n)), dim3(256), 0, 0, key, n, flag);
-    if (!scan(m, flag, id, n, true)) return -1;
+    if (!inclusive_sum(m, flag, id, n)) return -1;
     uint32_t runs = 0;
     if (hipMemcpy(&runs, id + (n - 1), 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     m.drop(flag);
-    if (!m.get(&start, (uint64_t)runs + 1)) return -1;
+    if (!m.alloc(&start, (uint64_t)runs + 1)) return -1;
     hipLaunchKernelGGL(k_ovl_bounds, dim3(grid(n)), dim3(256), 0, 0, key, id, n, start);
     *id_out = id; *start_out = start;
     return runs;
-}
-
-int check_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VC_ERR_NO_DEVICE, "no HIP device visible; the overlapper has no CPU fallback");
-    }
-    if (device < 0 || device >= ndev) return fail(VC_ERR_NO_DEVICE, "no HIP device with this ordinal");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(VC_ERR_HIP, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(VC_ERR_NO_DEVICE, "the kernels are built for gfx950 only");
-    if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
-    return VC_OK;
 }
 
 // NULL pointers, then the offsets, then the envelope of one set (the callers interleave k / w / limits between the last two)
@@ -440,44 +389,36 @@ int sketch(DevMem& m, const vc_overlap_seqs* a, const vc_overlap_seqs* b /* may 
     uint8_t* d_bases = nullptr;
     uint32_t *d_bs = nullptr, *d_bst = nullptr;
     uint64_t *d_cnt = nullptr, *d_boff = nullptr;
-    if (!m.get(&d_bases, off.back()) || !m.get(&t.off, off.size()) || !m.get(&d_bs, nb) || !m.get(&d_bst, nb) || !m.get(&d_cnt, nb) || !m.get(&d_boff, nb))
+    if (!m.alloc(&d_bases, off.back()) || !m.alloc(&t.off, off.size()) || !m.alloc(&d_bs, nb) || !m.alloc(&d_bst, nb) || !m.alloc(&d_cnt, nb) || !m.alloc(&d_boff, nb))
         return fail(VC_ERR_HIP, "hipMalloc failed (sketch)");
     uint64_t at = 0;
     for (const vc_overlap_seqs* s : sets) {
         if (!s || s->off[s->n] == 0) continue;
-        (void)hipMemcpy(d_bases + at, s->bases, s->off[s->n], hipMemcpyHostToDevice);
+        if (!to_device(d_bases + at, s->bases, s->off[s->n])) return fail(VC_ERR_HIP, "upload failed (sketch)");
         at += s->off[s->n];
     }
-    (void)hipMemcpy(t.off, off.data(), off.size() * 8, hipMemcpyHostToDevice);
+    if (!to_device(t.off, off.data(), off.size())) return fail(VC_ERR_HIP, "upload failed (sketch)");
     t.first.assign(t.n_seqs + 1, 0);
     if (nb == 0) return VC_OK;
-    (void)hipMemcpy(d_bs, blk_seq.data(), nb * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_bst, blk_start.data(), nb * 4, hipMemcpyHostToDevice);
+    if (!to_device(d_bs, blk_seq.data(), nb) || !to_device(d_bst, blk_start.data(), nb)) return fail(VC_ERR_HIP, "upload failed (sketch)");
     SketchArgs sa{};
     sa.n_blocks = (uint32_t)nb; sa.k = k; sa.w = w; sa.write = 0; sa.blk_seq = d_bs; sa.blk_start = d_bst; sa.off = t.off; sa.bases = d_bases;
     sa.blk_cnt = d_cnt; sa.blk_off = d_boff;
     hipLaunchKernelGGL(k_ovl_sketch, dim3((uint32_t)nb), dim3(kStretch), 0, 0, sa);
-    if (!scan(m, d_cnt, d_boff, nb, false)) return fail(VC_ERR_HIP, "scan failed (sketch)");
+    if (!exclusive_sum(m, d_cnt, d_boff, nb)) return fail(VC_ERR_HIP, "scan failed (sketch)");
     std::vector<uint64_t> boff(nb + 1);
     uint64_t last_cnt = 0;
-    if (hipMemcpy(boff.data(), d_boff, nb * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&last_cnt, d_cnt + (nb - 1), 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(VC_ERR_HIP, "sketch kernel failed");
+    if (!to_host(boff.data(), d_boff, nb) || !to_host(&last_cnt, d_cnt + (nb - 1), 1)) return fail(VC_ERR_HIP, "sketch kernel failed");
     boff[nb] = boff[nb - 1] + last_cnt;
     t.n = boff[nb];
     if (t.n >= (1ull << 31)) return fail(VC_ERR_HIP, "more minimizers than the envelope (2^31 entries per call)");
     for (uint64_t g = 0; g <= t.n_seqs; ++g) t.first[g] = boff[first_blk[g]];
-    if (!m.get(&t.hash, t.n) || !m.get(&t.seq, t.n) || !m.get(&t.pos, t.n) || !m.get(&t.strand, t.n)) return fail(VC_ERR_HIP, "hipMalloc failed (minimizer table)");
+    if (!m.alloc(&t.hash, t.n) || !m.alloc(&t.seq, t.n) || !m.alloc(&t.pos, t.n) || !m.alloc(&t.strand, t.n)) return fail(VC_ERR_HIP, "hipMalloc failed (minimizer table)");
     sa.write = 1; sa.hash = t.hash; sa.seq = t.seq; sa.pos = t.pos; sa.strand = t.strand;
     hipLaunchKernelGGL(k_ovl_sketch, dim3((uint32_t)nb), dim3(kStretch), 0, 0, sa);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "sketch kernel failed");
+    if (!ran()) return fail(VC_ERR_HIP, "sketch kernel failed");
     m.drop(d_cnt); m.drop(d_boff); m.drop(d_bs); m.drop(d_bst); m.drop(d_bases);
     return VC_OK;
-}
-
-uint64_t env_mib(const char* name) {
-    const char* v = getenv(name);
-    const double x = v ? std::atof(v) : 0.0;
-    return x > 0 ? std::max<uint64_t>((uint64_t)(x * 1048576.0), 1) : 0;
 }
 
 // what the library owns between calls (one set per process, like the vc_poa_*_out arrays)
@@ -513,16 +454,13 @@ int vc_overlap_sketch(int32_t device, int32_t k, int32_t w, const vc_overlap_seq
     if (k < 4 || k > kMaxK) return fail(VC_ERR_ARG, "k outside 4..28");
     if (w < 1 || w > kMaxW) return fail(VC_ERR_ARG, "w outside 1..64");
     if (const char* e = check_set_envelope(s)) return fail(VC_ERR_ARG, e);
-    if (int rc = check_device(device)) return rc;
+    if (int rc = check_device(device, "the overlapper", g_err)) return rc;
+    if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
     DevMem m;
     Table t;
     if (int rc = sketch(m, s, nullptr, k, w, t)) return rc;
-    g_own.s_hash.assign(t.n, 0); g_own.s_seq.assign(t.n, 0); g_own.s_pos.assign(t.n, 0); g_own.s_strand.assign(t.n, 0);
-    if (t.n) {
-        if (hipMemcpy(g_own.s_hash.data(), t.hash, t.n * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(g_own.s_seq.data(), t.seq, t.n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(g_own.s_pos.data(), t.pos, t.n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(g_own.s_strand.data(), t.strand, t.n, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(VC_ERR_HIP, "copying the minimizer table failed");
-    }
+    if (!to_host(g_own.s_hash, t.hash, t.n) || !to_host(g_own.s_seq, t.seq, t.n) || !to_host(g_own.s_pos, t.pos, t.n) || !to_host(g_own.s_strand, t.strand, t.n))
+        return fail(VC_ERR_HIP, "copying the minimizer table failed");
     o->n = t.n; o->hash = g_own.s_hash.data(); o->seq = g_own.s_seq.data(); o->pos = g_own.s_pos.data(); o->strand = g_own.s_strand.data();
     return VC_OK;
 }
@@ -544,7 +482,8 @@ int vc_overlap(const vc_overlap_params* p, const vc_overlap_seqs* targets, const
     if (p->max_occ > VC_OVL_MAX_OCC || p->max_gap > VC_OVL_MAX_GAP || p->bandwidth > VC_OVL_MAX_GAP) return fail(VC_ERR_ARG, "a limit beyond the envelope (VC_OVL_MAX_OCC, VC_OVL_MAX_GAP)");
     if (const char* e = check_set_envelope(targets)) return fail(VC_ERR_ARG, e);
     if (!same) if (const char* e = check_set_envelope(queries)) return fail(VC_ERR_ARG, e);
-    if (int rc = check_device(p->device)) return rc;
+    if (int rc = check_device(p->device, "the overlapper", g_err)) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
 
     const bool log = getenv("VC_OVL_LOG") != nullptr;
     DevMem m;
@@ -557,7 +496,7 @@ int vc_overlap(const vc_overlap_params* p, const vc_overlap_seqs* targets, const
         // by hash, stable: a bucket keeps its entries in (set, sequence, position) order
         uint64_t* hs = nullptr;
         uint32_t *iota = nullptr, *perm = nullptr, *bid = nullptr, *bstart = nullptr;
-        if (!m.get(&hs, n) || !m.get(&iota, n) || !m.get(&perm, n)) return fail(VC_ERR_HIP, "hipMalloc failed (seeds)");
+        if (!m.alloc(&hs, n) || !m.alloc(&iota, n) || !m.alloc(&perm, n)) return fail(VC_ERR_HIP, "hipMalloc failed (seeds)");
         hipLaunchKernelGGL(k_ovl_iota, dim3(grid(n)), dim3(256), 0, 0, iota, n);
         if (!sort_pairs(m, t.hash, hs, iota, perm, n, 2 * p->k)) return fail(VC_ERR_HIP, "radix sort failed (seeds)");
         m.drop(iota);
@@ -566,9 +505,9 @@ int vc_overlap(const vc_overlap_params* p, const vc_overlap_seqs* targets, const
         sa.n = n; sa.n_t = n_t; sa.same_set = same; sa.max_occ = p->max_occ; sa.k = p->k; sa.perm = perm; sa.bid = bid; sa.bstart = bstart;
         sa.seq = t.seq; sa.pos = t.pos; sa.strand = t.strand; sa.off = t.off; sa.n_targets = n_targets;
         uint64_t* cum = nullptr;
-        if (!m.get(&sa.cnt, n_t) || !m.get(&sa.lo, n_t) || !m.get(&sa.hi, n_t) || !m.get(&cum, n_t)) return fail(VC_ERR_HIP, "hipMalloc failed (seeds)");
+        if (!m.alloc(&sa.cnt, n_t) || !m.alloc(&sa.lo, n_t) || !m.alloc(&sa.hi, n_t) || !m.alloc(&cum, n_t)) return fail(VC_ERR_HIP, "hipMalloc failed (seeds)");
         hipLaunchKernelGGL(k_ovl_count, dim3(grid(n)), dim3(256), 0, 0, sa);
-        if (!scan(m, sa.cnt, cum, n_t, false)) return fail(VC_ERR_HIP, "scan failed (seeds)");
+        if (!exclusive_sum(m, sa.cnt, cum, n_t)) return fail(VC_ERR_HIP, "scan failed (seeds)");
         m.drop(hs);
         sa.cum = cum;
         uint64_t total = 0, last_cnt = 0;
@@ -579,8 +518,8 @@ int vc_overlap(const vc_overlap_params* p, const vc_overlap_seqs* targets, const
         std::vector<uint64_t> before(n_targets + 1);
         {
             uint64_t *d_idx = nullptr, *d_out = nullptr;
-            if (!m.get(&d_idx, (uint64_t)n_targets + 1) || !m.get(&d_out, (uint64_t)n_targets + 1)) return fail(VC_ERR_HIP, "hipMalloc failed (seeds)");
-            (void)hipMemcpy(d_idx, t.first.data(), ((size_t)n_targets + 1) * 8, hipMemcpyHostToDevice);
+            if (!m.alloc(&d_idx, (uint64_t)n_targets + 1) || !m.alloc(&d_out, (uint64_t)n_targets + 1)) return fail(VC_ERR_HIP, "hipMalloc failed (seeds)");
+            if (!to_device(d_idx, t.first.data(), (uint64_t)n_targets + 1)) return fail(VC_ERR_HIP, "upload failed (seeds)");
             hipLaunchKernelGGL(k_ovl_gather, dim3(grid((uint64_t)n_targets + 1)), dim3(256), 0, 0, cum, (uint64_t)n_t, total, d_idx, n_targets + 1, d_out);
             if (hipMemcpy(before.data(), d_out, ((size_t)n_targets + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(VC_ERR_HIP, "seed kernels failed");
             m.drop(d_idx); m.drop(d_out);
@@ -599,7 +538,7 @@ int vc_overlap(const vc_overlap_params* p, const vc_overlap_seqs* targets, const
             if (na) {
                 DevMem pm;
                 uint64_t *khi = nullptr, *klo = nullptr, *khi2 = nullptr, *klo2 = nullptr;
-                if (!pm.get(&khi, na) || !pm.get(&klo, na) || !pm.get(&khi2, na) || !pm.get(&klo2, na)) return fail(VC_ERR_HIP, "hipMalloc failed (anchors; lower VC_OVL_BUDGET_MB?)");
+                if (!pm.alloc(&khi, na) || !pm.alloc(&klo, na) || !pm.alloc(&khi2, na) || !pm.alloc(&klo2, na)) return fail(VC_ERR_HIP, "hipMalloc failed (anchors; lower VC_OVL_BUDGET_MB?)");
                 sa.e0 = (uint32_t)t.first[ta]; sa.e1 = (uint32_t)t.first[tb]; sa.khi = khi; sa.klo = klo;
                 hipLaunchKernelGGL(k_ovl_emit, dim3(grid(sa.e1 - sa.e0)), dim3(256), 0, 0, sa);
                 // by (t_pos, q_pos), then stable by (t_id, q_id, strand)
@@ -614,10 +553,10 @@ int vc_overlap(const vc_overlap_params* p, const vc_overlap_seqs* targets, const
                 ca.n_keys = n_keys; ca.kstart = kstart; ca.khi = khi; ca.klo = klo;
                 ca.k = p->k; ca.max_gap = p->max_gap; ca.bandwidth = p->bandwidth; ca.min_chain_score = p->min_chain_score; ca.min_anchors = p->min_anchors;
                 ca.min_overlap = p->min_overlap; ca.drop_internal = p->drop_internal; ca.same_set = same; ca.off = t.off; ca.n_targets = n_targets;
-                if (!pm.get(&ca.f, na) || !pm.get(&ca.pred, na) || !pm.get(&ca.rec, n_keys) || !pm.get(&ca.n_rec, 1)) return fail(VC_ERR_HIP, "hipMalloc failed (chains)");
+                if (!pm.alloc(&ca.f, na) || !pm.alloc(&ca.pred, na) || !pm.alloc(&ca.rec, n_keys) || !pm.alloc(&ca.n_rec, 1)) return fail(VC_ERR_HIP, "hipMalloc failed (chains)");
                 (void)hipMemset(ca.n_rec, 0, 4);
                 hipLaunchKernelGGL(k_ovl_chain, dim3(n_keys), dim3(64), 0, 0, ca);
-                if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "overlap kernels failed");
+                if (!ran()) return fail(VC_ERR_HIP, "overlap kernels failed");
                 if (hipMemcpy(&n_rec, ca.n_rec, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(VC_ERR_HIP, "overlap kernels failed");
                 const size_t had = recs.size();
                 recs.resize(had + n_rec);

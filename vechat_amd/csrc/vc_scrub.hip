@@ -22,8 +22,10 @@
 //   k_scr_classify  one thread per read over its regions: klass, bad_total, the number of pieces and of their bytes
 //   k_scr_pieces    after the scan of those: the pieces and their byte offsets
 //   k_scr_cut       the one bandwidth kernel: one thread per 16 output bytes, bases and qualities in one launch
+//
+// Host: vc_scrub() is the argument checks and four stages -- scr_segments, scr_regions, scr_pieces, scr_cut --, each with its scratch
+// in a DevMem of its own.  DevMem, the checked copies and the device check are vc_devutil.h's, the sort and the sums vc_devscan.h's.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstdio>
@@ -34,7 +36,11 @@
 
 #include "vechat_hip.h"
 
+#include "vc_devscan.h"
+
 namespace {
+
+using namespace vc_dev;
 
 constexpr uint64_t kPosMask = 0x7FFFFFFFull;          // key = read << 31 | position; a position is at most VC_OVL_MAX_LEN = 2^30
 
@@ -220,61 +226,6 @@ __global__ __launch_bounds__(256) void k_scr_cut(CutArgs a) {
 thread_local std::string g_err;
 int fail(int code, const std::string& m) { g_err = m; return code; }
 
-struct DevMem {                        // every device buffer of a call, released together
-    std::vector<void*> list;
-    template <typename T> bool get(T** p, uint64_t n) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<uint64_t>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        list.push_back(q);
-        *p = (T*)q;
-        return true;
-    }
-    void drop(void* p) {
-        for (size_t i = 0; i < list.size(); ++i) if (list[i] == p) { (void)hipFree(p); list.erase(list.begin() + (long)i); return; }
-    }
-    ~DevMem() { for (void* p : list) (void)hipFree(p); }
-};
-
-inline uint32_t grid(uint64_t n, uint32_t block = 256) { return (uint32_t)((n + block - 1) / block); }
-
-template <typename T>
-bool exclusive_sum(DevMem& m, const T* in, T* out, uint64_t n) {
-    size_t tb = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, (hipStream_t)0) != hipSuccess) return false;
-    uint8_t* tmp = nullptr;
-    if (!m.get(&tmp, tb)) return false;
-    const bool ok = hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, n, (hipStream_t)0) == hipSuccess;
-    (void)hipDeviceSynchronize();
-    m.drop(tmp);
-    return ok;
-}
-
-template <typename T>
-bool upload(DevMem& m, T** d, const T* h, uint64_t n) {
-    if (!m.get(d, n)) return false;
-    return n == 0 || hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
-}
-
-template <typename T>
-bool download(std::vector<T>& h, const T* d, uint64_t n) {
-    h.resize(n);
-    return n == 0 || hipMemcpy(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
-}
-
-int check_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VC_ERR_NO_DEVICE, "no HIP device visible; the scrubber has no CPU fallback");
-    }
-    if (device < 0 || device >= ndev) return fail(VC_ERR_NO_DEVICE, "no HIP device with this ordinal");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(VC_ERR_HIP, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(VC_ERR_NO_DEVICE, "the kernels are built for gfx950 only");
-    if (hipSetDevice(device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
-    return VC_OK;
-}
-
 // what the library owns between calls (one set per process, like the vc_overlap_out arrays)
 struct Owned {
     std::vector<uint32_t> reg_read, reg_begin, reg_end, bad_total, pc_read, pc_begin, pc_end;
@@ -307,6 +258,118 @@ const char* check_args(const vc_scrub_params* p, const vc_scrub_in* in) {
     return nullptr;
 }
 
+// The device arrays that cross the stages below, and their counts.  Every stage takes the DevMem that its results go into and
+// keeps its scratch in one of its own, so the scratch is gone when the stage returns; it returns VC_OK or the code of fail().
+struct Scr {
+    uint64_t n = 0, m = 0, n_ev = 0;
+    int32_t coverage = 0, permille = 0, min_piece = 0;
+    uint32_t* len = nullptr;                                                      // [n], the whole call
+    uint64_t n_seg = 0; uint64_t* seg_key = nullptr; int32_t* seg_cov = nullptr;  // segments -> regions
+    uint64_t n_reg = 0; uint32_t *reg_read = nullptr, *reg_begin = nullptr, *reg_end = nullptr; uint64_t* reg_off = nullptr;   // -> pieces
+    uint64_t n_pc = 0, total = 0; uint32_t *pc_read = nullptr, *pc_begin = nullptr; uint64_t* pc_off = nullptr;               // -> cut
+};
+
+// stage 1: intervals -> sorted events -> the coverage after each -> segments
+int scr_segments(DevMem& out, const vc_scrub_in* in, Scr& s) {
+    const uint64_t n = s.n, m = s.m, n_ev = s.n_ev;
+    if (m == 0) return out.alloc(&s.seg_key, 1) && out.alloc(&s.seg_cov, 1) ? VC_OK : fail(VC_ERR_HIP, "hipMalloc failed (segments)");
+    DevMem dm;
+    uint32_t *d_rd = nullptr, *d_b = nullptr, *d_e = nullptr, *flag = nullptr, *idx = nullptr;
+    uint64_t *key = nullptr, *key2 = nullptr;
+    int32_t *delta = nullptr, *delta2 = nullptr;
+    if (!dm.alloc(&d_rd, m, in->read) || !dm.alloc(&d_b, m, in->begin) || !dm.alloc(&d_e, m, in->end)) return fail(VC_ERR_HIP, "hipMalloc or upload failed (intervals)");
+    if (!dm.alloc(&key, n_ev) || !dm.alloc(&key2, n_ev) || !dm.alloc(&delta, n_ev) || !dm.alloc(&delta2, n_ev)) return fail(VC_ERR_HIP, "hipMalloc failed (events)");
+    hipLaunchKernelGGL(k_scr_events, dim3(grid(m)), dim3(256), 0, 0, m, d_rd, d_b, d_e, (ulonglong2*)key, (int2*)delta);
+    int bits = 32;
+    while (bits < 62 && ((n - 1) >> (bits - 31)) != 0) ++bits;
+    if (!sort_pairs(dm, key, key2, delta, delta2, n_ev, bits)) return fail(VC_ERR_HIP, "radix sort failed (events)");
+    dm.drop(key); dm.drop(d_rd); dm.drop(d_b); dm.drop(d_e);                      // the peak of the call is the sort: nothing of it stays for the runs
+    int32_t* cov = delta;                                                         // the unsorted deltas are done with
+    if (!inclusive_sum(dm, delta2, cov, n_ev)) return fail(VC_ERR_HIP, "scan failed (coverage)");
+    dm.drop(delta2);
+    // the runs of equal keys -> segments
+    if (!dm.alloc(&flag, n_ev + 1) || !dm.alloc(&idx, n_ev + 1)) return fail(VC_ERR_HIP, "hipMalloc failed (runs)");
+    (void)hipMemset(flag + n_ev, 0, 4);
+    hipLaunchKernelGGL(k_scr_runs, dim3(grid(n_ev)), dim3(256), 0, 0, n_ev, key2, cov, s.len, 0, flag, idx, s.seg_key, s.seg_cov);
+    if (!exclusive_sum(dm, flag, idx, n_ev + 1)) return fail(VC_ERR_HIP, "scan failed (runs)");
+    uint32_t s32 = 0;
+    if (!to_host(&s32, idx + n_ev, 1)) return fail(VC_ERR_HIP, "event kernels failed");
+    s.n_seg = s32;
+    if (!out.alloc(&s.seg_key, s.n_seg) || !out.alloc(&s.seg_cov, s.n_seg)) return fail(VC_ERR_HIP, "hipMalloc failed (segments)");
+    hipLaunchKernelGGL(k_scr_runs, dim3(grid(n_ev)), dim3(256), 0, 0, n_ev, key2, cov, s.len, 1, flag, idx, s.seg_key, s.seg_cov);
+    return ran() ? VC_OK : fail(VC_ERR_HIP, "event kernels failed");
+}
+
+// stage 2: segments -> regions
+int scr_regions(DevMem& out, Scr& s) {
+    const uint64_t n = s.n, n_seg = s.n_seg;
+    DevMem dm;
+    RegionArgs ra{};
+    uint32_t* first = nullptr;
+    uint64_t *sflag = nullptr, *hflag = nullptr, *sscan = nullptr, *hscan = nullptr;
+    if (!dm.alloc(&first, n + 1) || !dm.alloc(&sflag, n_seg + 1) || !dm.alloc(&hflag, n + 1) || !dm.alloc(&sscan, n_seg + 1) || !dm.alloc(&hscan, n + 1) || !out.alloc(&s.reg_off, n + 1))
+        return fail(VC_ERR_HIP, "hipMalloc failed (regions)");
+    hipLaunchKernelGGL(k_scr_first, dim3(grid(n + 1)), dim3(256), 0, 0, n, (uint32_t)n_seg, s.seg_key, first);
+    ra.n = n; ra.n_seg = (uint32_t)n_seg; ra.c = s.coverage; ra.write = 0; ra.len = s.len; ra.first = first; ra.seg_key = s.seg_key; ra.seg_cov = s.seg_cov;
+    ra.sflag = sflag; ra.hflag = hflag; ra.sscan = sscan; ra.hscan = hscan; ra.reg_off = s.reg_off;
+    hipLaunchKernelGGL(k_scr_regions, dim3(grid(n_seg + n)), dim3(256), 0, 0, ra);
+    if (!exclusive_sum(dm, sflag, sscan, n_seg + 1) || !exclusive_sum(dm, hflag, hscan, n + 1)) return fail(VC_ERR_HIP, "scan failed (regions)");
+    uint64_t s_last = 0, h_last = 0;
+    if (!to_host(&s_last, sscan + n_seg, 1) || !to_host(&h_last, hscan + n, 1)) return fail(VC_ERR_HIP, "region kernels failed");
+    s.n_reg = (uint64_t)(uint32_t)s_last + (uint32_t)h_last;
+    if (s.n_reg != (s_last >> 32) + (h_last >> 32)) return fail(VC_ERR_HIP, "region kernels failed: opens and closes differ");
+    if (!out.alloc(&s.reg_read, s.n_reg) || !out.alloc(&s.reg_begin, s.n_reg) || !out.alloc(&s.reg_end, s.n_reg)) return fail(VC_ERR_HIP, "hipMalloc failed (regions)");
+    ra.reg_read = s.reg_read; ra.reg_begin = s.reg_begin; ra.reg_end = s.reg_end; ra.write = 1;
+    hipLaunchKernelGGL(k_scr_regions, dim3(grid(n_seg + n)), dim3(256), 0, 0, ra);
+    return ran() ? VC_OK : fail(VC_ERR_HIP, "region kernels failed");          // the flags and scans go now: the launch must be through with them
+}
+
+// stage 3: regions -> classes and pieces, and every table of the call on the host
+int scr_pieces(DevMem& out, Scr& s, Owned& g) {
+    const uint64_t n = s.n;
+    DevMem dm;
+    PieceArgs pa{};
+    uint64_t *pidx = nullptr, *pboff = nullptr;
+    pa.n = n; pa.permille = s.permille; pa.min_piece = s.min_piece; pa.write = 0; pa.len = s.len;
+    pa.reg_off = s.reg_off; pa.reg_begin = s.reg_begin; pa.reg_end = s.reg_end;
+    if (!dm.alloc(&pa.klass, n) || !dm.alloc(&pa.bad_total, n) || !dm.alloc(&pa.pcnt, n + 1) || !dm.alloc(&pa.pbytes, n + 1) || !dm.alloc(&pidx, n + 1) || !dm.alloc(&pboff, n + 1))
+        return fail(VC_ERR_HIP, "hipMalloc failed (classes)");
+    hipLaunchKernelGGL(k_scr_classify, dim3(grid(n)), dim3(256), 0, 0, pa);
+    if (!exclusive_sum(dm, pa.pcnt, pidx, n + 1) || !exclusive_sum(dm, pa.pbytes, pboff, n + 1)) return fail(VC_ERR_HIP, "scan failed (pieces)");
+    if (!to_host(&s.n_pc, pidx + n, 1) || !to_host(&s.total, pboff + n, 1)) return fail(VC_ERR_HIP, "region or class kernels failed");
+    pa.pidx = pidx; pa.pboff = pboff; pa.write = 1;
+    if (!out.alloc(&s.pc_read, s.n_pc) || !out.alloc(&s.pc_begin, s.n_pc) || !dm.alloc(&pa.pc_end, s.n_pc) || !out.alloc(&s.pc_off, s.n_pc + 1)) return fail(VC_ERR_HIP, "hipMalloc failed (pieces)");
+    pa.pc_read = s.pc_read; pa.pc_begin = s.pc_begin; pa.pc_off = s.pc_off;
+    hipLaunchKernelGGL(k_scr_pieces, dim3(grid(n)), dim3(256), 0, 0, pa);
+    if (!ran()) return fail(VC_ERR_HIP, "piece kernels failed");
+    if (!to_host(g.reg_read, s.reg_read, s.n_reg) || !to_host(g.reg_begin, s.reg_begin, s.n_reg) || !to_host(g.reg_end, s.reg_end, s.n_reg) ||
+        !to_host(g.reg_off, s.reg_off, n + 1) || !to_host(g.klass, pa.klass, n) || !to_host(g.bad_total, pa.bad_total, n) ||
+        !to_host(g.pc_read, s.pc_read, s.n_pc) || !to_host(g.pc_begin, s.pc_begin, s.n_pc) || !to_host(g.pc_end, pa.pc_end, s.n_pc) ||
+        !to_host(g.pc_off, s.pc_off, s.n_pc + 1))
+        return fail(VC_ERR_HIP, "copying the regions and pieces failed");
+    return VC_OK;
+}
+
+// stage 4: the cut (total > 0, so there is a piece)
+int scr_cut(const vc_scrub_in* in, const Scr& s, Owned& g) {
+    DevMem dm;
+    CutArgs ca{};
+    const uint64_t n_bytes = in->off[s.n], padded = (s.total + 15) / 16 * 16;
+    uint8_t *d_bases = nullptr, *d_quals = nullptr;
+    uint64_t* d_off = nullptr;
+    if (!dm.alloc(&d_off, s.n + 1, in->off) || !dm.alloc(&d_bases, n_bytes + 16) || !dm.alloc(&ca.out_bases, padded) ||
+        (in->quals && (!dm.alloc(&d_quals, n_bytes + 16) || !dm.alloc(&ca.out_quals, padded))))
+        return fail(VC_ERR_HIP, "hipMalloc failed (the read image and the cut)");
+    if (!to_device(d_bases, in->bases, n_bytes) || (in->quals && !to_device(d_quals, in->quals, n_bytes))) return fail(VC_ERR_HIP, "upload failed (the read image)");
+    ca.total = s.total; ca.n_pieces = s.n_pc; ca.pc_off = s.pc_off; ca.pc_read = s.pc_read; ca.pc_begin = s.pc_begin; ca.off = d_off;
+    ca.bases = d_bases; ca.quals = d_quals;
+    const uint64_t blocks = std::min<uint64_t>((padded / 16 + 255) / 256, 1u << 20);
+    hipLaunchKernelGGL(k_scr_cut, dim3((uint32_t)blocks), dim3(256), 0, 0, ca);
+    if (!ran()) return fail(VC_ERR_HIP, "cut kernel failed");
+    if (!to_host(g.pc_bases, ca.out_bases, s.total) || (in->quals && !to_host(g.pc_quals, ca.out_quals, s.total))) return fail(VC_ERR_HIP, "copying the cut failed");
+    return VC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -324,136 +387,46 @@ int vc_scrub(const vc_scrub_params* p, const vc_scrub_in* in, vc_scrub_out* out)
     if (out) std::memset(out, 0, sizeof *out);
     if (!p || !in || !out) return fail(VC_ERR_ARG, "NULL argument");
     if (const char* e = check_args(p, in)) return fail(VC_ERR_ARG, e);
-    if (int rc = check_device(p->device)) return rc;
+    if (int rc = check_device(p->device, "the scrubber", g_err)) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return fail(VC_ERR_HIP, "hipSetDevice failed");
 
-    const uint64_t n = in->n, m = in->m, n_ev = 2 * m;
     Owned& g = g_own;
-    uint64_t n_seg = 0, n_reg = 0, n_pc = 0, total = 0;
+    Scr s;
+    s.n = in->n; s.m = in->m; s.n_ev = 2 * in->m; s.coverage = p->coverage; s.permille = p->max_bad_permille; s.min_piece = p->min_piece;
     const bool cut = in->bases != nullptr;
-    if (n == 0) {
+    g.pc_bases.clear(); g.pc_quals.clear();
+    if (s.n == 0) {
         g.reg_read.clear(); g.reg_begin.clear(); g.reg_end.clear(); g.bad_total.clear(); g.pc_read.clear(); g.pc_begin.clear(); g.pc_end.clear();
-        g.klass.clear(); g.pc_bases.clear(); g.pc_quals.clear();
+        g.klass.clear();
         g.reg_off.assign(1, 0); g.pc_off.assign(1, 0);
     } else {
-        DevMem dm;
-        uint32_t* d_len = nullptr;
-        if (!upload(dm, &d_len, in->len, n)) return fail(VC_ERR_HIP, "hipMalloc or upload failed (lengths)");
-        // events, sorted, and the coverage after each
-        uint64_t* seg_key = nullptr;
-        int32_t* seg_cov = nullptr;
-        if (m) {
-            uint32_t *d_rd = nullptr, *d_b = nullptr, *d_e = nullptr, *flag = nullptr, *idx = nullptr;
-            uint64_t *key = nullptr, *key2 = nullptr;
-            int32_t *delta = nullptr, *delta2 = nullptr;
-            if (!upload(dm, &d_rd, in->read, m) || !upload(dm, &d_b, in->begin, m) || !upload(dm, &d_e, in->end, m))
-                return fail(VC_ERR_HIP, "hipMalloc or upload failed (intervals)");
-            if (!dm.get(&key, n_ev) || !dm.get(&key2, n_ev) || !dm.get(&delta, n_ev) || !dm.get(&delta2, n_ev)) return fail(VC_ERR_HIP, "hipMalloc failed (events)");
-            hipLaunchKernelGGL(k_scr_events, dim3(grid(m)), dim3(256), 0, 0, m, d_rd, d_b, d_e, (ulonglong2*)key, (int2*)delta);
-            int bits = 32;
-            while (bits < 62 && ((n - 1) >> (bits - 31)) != 0) ++bits;
-            size_t tb = 0;
-            if (hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, delta, delta2, n_ev, 0, bits, (hipStream_t)0) != hipSuccess) return fail(VC_ERR_HIP, "radix sort failed (events)");
-            uint8_t* tmp = nullptr;
-            if (!dm.get(&tmp, tb)) return fail(VC_ERR_HIP, "hipMalloc failed (sort)");
-            if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, delta, delta2, n_ev, 0, bits, (hipStream_t)0) != hipSuccess) return fail(VC_ERR_HIP, "radix sort failed (events)");
-            (void)hipDeviceSynchronize();
-            dm.drop(tmp); dm.drop(key); dm.drop(d_rd); dm.drop(d_b); dm.drop(d_e);
-            int32_t* cov = delta;                                  // the unsorted deltas are done with
-            if (hipcub::DeviceScan::InclusiveSum(nullptr, tb, delta2, cov, n_ev, (hipStream_t)0) != hipSuccess || !dm.get(&tmp, tb)) return fail(VC_ERR_HIP, "scan failed (coverage)");
-            if (hipcub::DeviceScan::InclusiveSum(tmp, tb, delta2, cov, n_ev, (hipStream_t)0) != hipSuccess) return fail(VC_ERR_HIP, "scan failed (coverage)");
-            (void)hipDeviceSynchronize();
-            dm.drop(tmp); dm.drop(delta2);
-            // the runs of equal keys -> segments
-            if (!dm.get(&flag, n_ev + 1) || !dm.get(&idx, n_ev + 1)) return fail(VC_ERR_HIP, "hipMalloc failed (runs)");
-            (void)hipMemset(flag + n_ev, 0, 4);
-            hipLaunchKernelGGL(k_scr_runs, dim3(grid(n_ev)), dim3(256), 0, 0, n_ev, key2, cov, d_len, 0, flag, idx, seg_key, seg_cov);
-            if (!exclusive_sum(dm, flag, idx, n_ev + 1)) return fail(VC_ERR_HIP, "scan failed (runs)");
-            uint32_t s32 = 0;
-            if (hipMemcpy(&s32, idx + n_ev, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(VC_ERR_HIP, "event kernels failed");
-            n_seg = s32;
-            if (!dm.get(&seg_key, n_seg) || !dm.get(&seg_cov, n_seg)) return fail(VC_ERR_HIP, "hipMalloc failed (segments)");
-            hipLaunchKernelGGL(k_scr_runs, dim3(grid(n_ev)), dim3(256), 0, 0, n_ev, key2, cov, d_len, 1, flag, idx, seg_key, seg_cov);
-            if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "event kernels failed");
-            dm.drop(flag); dm.drop(idx); dm.drop(key2); dm.drop(cov);
-        } else if (!dm.get(&seg_key, 1) || !dm.get(&seg_cov, 1)) {
-            return fail(VC_ERR_HIP, "hipMalloc failed (segments)");
+        DevMem pieces;                                       // the lengths and the pieces: to the end of the call
+        if (!pieces.alloc(&s.len, s.n, in->len)) return fail(VC_ERR_HIP, "hipMalloc or upload failed (lengths)");
+        {
+            DevMem regions;                                  // gone before the cut uploads the read image
+            {
+                DevMem segments;                             // gone before the pieces are built
+                if (int rc = scr_segments(segments, in, s)) return rc;
+                if (int rc = scr_regions(regions, s)) return rc;
+            }
+            if (int rc = scr_pieces(pieces, s, g)) return rc;
         }
-        // regions
-        RegionArgs ra{};
-        uint32_t* first = nullptr;
-        uint64_t *sflag = nullptr, *hflag = nullptr, *sscan = nullptr, *hscan = nullptr;
-        if (!dm.get(&first, n + 1) || !dm.get(&sflag, n_seg + 1) || !dm.get(&hflag, n + 1) || !dm.get(&sscan, n_seg + 1) || !dm.get(&hscan, n + 1) || !dm.get(&ra.reg_off, n + 1))
-            return fail(VC_ERR_HIP, "hipMalloc failed (regions)");
-        hipLaunchKernelGGL(k_scr_first, dim3(grid(n + 1)), dim3(256), 0, 0, n, (uint32_t)n_seg, seg_key, first);
-        ra.n = n; ra.n_seg = (uint32_t)n_seg; ra.c = p->coverage; ra.write = 0; ra.len = d_len; ra.first = first; ra.seg_key = seg_key; ra.seg_cov = seg_cov;
-        ra.sflag = sflag; ra.hflag = hflag; ra.sscan = sscan; ra.hscan = hscan;
-        hipLaunchKernelGGL(k_scr_regions, dim3(grid(n_seg + n)), dim3(256), 0, 0, ra);
-        if (!exclusive_sum(dm, sflag, sscan, n_seg + 1) || !exclusive_sum(dm, hflag, hscan, n + 1)) return fail(VC_ERR_HIP, "scan failed (regions)");
-        uint64_t s_last = 0, h_last = 0;
-        if (hipMemcpy(&s_last, sscan + n_seg, 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&h_last, hscan + n, 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(VC_ERR_HIP, "region kernels failed");
-        n_reg = (uint64_t)(uint32_t)s_last + (uint32_t)h_last;
-        if (n_reg != (s_last >> 32) + (h_last >> 32)) return fail(VC_ERR_HIP, "region kernels failed: opens and closes differ");
-        if (!dm.get(&ra.reg_read, n_reg) || !dm.get(&ra.reg_begin, n_reg) || !dm.get(&ra.reg_end, n_reg)) return fail(VC_ERR_HIP, "hipMalloc failed (regions)");
-        ra.write = 1;
-        hipLaunchKernelGGL(k_scr_regions, dim3(grid(n_seg + n)), dim3(256), 0, 0, ra);
-        // classes and pieces
-        PieceArgs pa{};
-        uint64_t *pidx = nullptr, *pboff = nullptr;
-        pa.n = n; pa.permille = p->max_bad_permille; pa.min_piece = p->min_piece; pa.write = 0; pa.len = d_len;
-        pa.reg_off = ra.reg_off; pa.reg_begin = ra.reg_begin; pa.reg_end = ra.reg_end;
-        if (!dm.get(&pa.klass, n) || !dm.get(&pa.bad_total, n) || !dm.get(&pa.pcnt, n + 1) || !dm.get(&pa.pbytes, n + 1) || !dm.get(&pidx, n + 1) || !dm.get(&pboff, n + 1))
-            return fail(VC_ERR_HIP, "hipMalloc failed (classes)");
-        hipLaunchKernelGGL(k_scr_classify, dim3(grid(n)), dim3(256), 0, 0, pa);
-        if (!exclusive_sum(dm, pa.pcnt, pidx, n + 1) || !exclusive_sum(dm, pa.pbytes, pboff, n + 1)) return fail(VC_ERR_HIP, "scan failed (pieces)");
-        if (hipMemcpy(&n_pc, pidx + n, 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&total, pboff + n, 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(VC_ERR_HIP, "region or class kernels failed");
-        dm.drop(first); dm.drop(sflag); dm.drop(hflag); dm.drop(sscan); dm.drop(hscan); dm.drop(seg_key); dm.drop(seg_cov);
-        pa.pidx = pidx; pa.pboff = pboff; pa.write = 1;
-        if (!dm.get(&pa.pc_read, n_pc) || !dm.get(&pa.pc_begin, n_pc) || !dm.get(&pa.pc_end, n_pc) || !dm.get(&pa.pc_off, n_pc + 1)) return fail(VC_ERR_HIP, "hipMalloc failed (pieces)");
-        hipLaunchKernelGGL(k_scr_pieces, dim3(grid(n)), dim3(256), 0, 0, pa);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "piece kernels failed");
-        if (!download(g.reg_read, ra.reg_read, n_reg) || !download(g.reg_begin, ra.reg_begin, n_reg) || !download(g.reg_end, ra.reg_end, n_reg) ||
-            !download(g.reg_off, ra.reg_off, n + 1) || !download(g.klass, pa.klass, n) || !download(g.bad_total, pa.bad_total, n) ||
-            !download(g.pc_read, pa.pc_read, n_pc) || !download(g.pc_begin, pa.pc_begin, n_pc) || !download(g.pc_end, pa.pc_end, n_pc) ||
-            !download(g.pc_off, pa.pc_off, n_pc + 1))
-            return fail(VC_ERR_HIP, "copying the regions and pieces failed");
-        dm.drop(ra.reg_read); dm.drop(ra.reg_begin); dm.drop(ra.reg_end); dm.drop(ra.reg_off); dm.drop(pa.pcnt); dm.drop(pa.pbytes); dm.drop(pidx); dm.drop(pboff);
-        // the cut
-        g.pc_bases.clear(); g.pc_quals.clear();
-        if (cut && total) {
-            CutArgs ca{};
-            const uint64_t n_bytes = in->off[n];
-            uint8_t *d_bases = nullptr, *d_quals = nullptr;
-            uint64_t* d_off = nullptr;
-            const uint64_t padded = (total + 15) / 16 * 16;
-            if (!upload(dm, &d_off, in->off, n + 1) || !dm.get(&d_bases, n_bytes + 16) || !dm.get(&ca.out_bases, padded) ||
-                (in->quals && (!dm.get(&d_quals, n_bytes + 16) || !dm.get(&ca.out_quals, padded))))
-                return fail(VC_ERR_HIP, "hipMalloc failed (the read image and the cut)");
-            if (hipMemcpy(d_bases, in->bases, n_bytes, hipMemcpyHostToDevice) != hipSuccess || (in->quals && hipMemcpy(d_quals, in->quals, n_bytes, hipMemcpyHostToDevice) != hipSuccess))
-                return fail(VC_ERR_HIP, "upload failed (the read image)");
-            ca.total = total; ca.n_pieces = n_pc; ca.pc_off = pa.pc_off; ca.pc_read = pa.pc_read; ca.pc_begin = pa.pc_begin; ca.off = d_off;
-            ca.bases = d_bases; ca.quals = d_quals;
-            const uint64_t blocks = std::min<uint64_t>((padded / 16 + 255) / 256, 1u << 20);
-            hipLaunchKernelGGL(k_scr_cut, dim3((uint32_t)blocks), dim3(256), 0, 0, ca);
-            if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(VC_ERR_HIP, "cut kernel failed");
-            if (!download(g.pc_bases, ca.out_bases, total) || (in->quals && !download(g.pc_quals, ca.out_quals, total))) return fail(VC_ERR_HIP, "copying the cut failed");
-        }
+        if (cut && s.total) if (int rc = scr_cut(in, s, g)) return rc;
     }
     if (getenv("VC_SCRUB_LOG"))
-        fprintf(stderr, "vc_scrub: intervals=%llu events=%llu segments=%llu regions=%llu pieces=%llu\n", (unsigned long long)m, (unsigned long long)n_ev,
-                (unsigned long long)n_seg, (unsigned long long)n_reg, (unsigned long long)n_pc);
+        fprintf(stderr, "vc_scrub: intervals=%llu events=%llu segments=%llu regions=%llu pieces=%llu\n", (unsigned long long)s.m, (unsigned long long)s.n_ev,
+                (unsigned long long)s.n_seg, (unsigned long long)s.n_reg, (unsigned long long)s.n_pc);
     // a vector's data() may be NULL when it is empty: every array handed out is a real address
     static const uint32_t none32 = 0;
     static const uint8_t none8 = 0;
     auto p32 = [](const std::vector<uint32_t>& v) { return v.empty() ? &none32 : v.data(); };
     auto p8 = [](const std::vector<uint8_t>& v) { return v.empty() ? &none8 : v.data(); };
-    out->n_regions = n_reg; out->reg_read = p32(g.reg_read); out->reg_begin = p32(g.reg_begin); out->reg_end = p32(g.reg_end); out->reg_off = g.reg_off.data();
+    out->n_regions = s.n_reg; out->reg_read = p32(g.reg_read); out->reg_begin = p32(g.reg_begin); out->reg_end = p32(g.reg_end); out->reg_off = g.reg_off.data();
     out->klass = p8(g.klass); out->bad_total = p32(g.bad_total);
-    out->n_pieces = n_pc; out->pc_read = p32(g.pc_read); out->pc_begin = p32(g.pc_begin); out->pc_end = p32(g.pc_end); out->pc_off = g.pc_off.data();
+    out->n_pieces = s.n_pc; out->pc_read = p32(g.pc_read); out->pc_begin = p32(g.pc_begin); out->pc_end = p32(g.pc_end); out->pc_off = g.pc_off.data();
     out->pc_bases = cut ? p8(g.pc_bases) : nullptr;
     out->pc_quals = cut && in->quals ? p8(g.pc_quals) : nullptr;
-    out->n_intervals = m; out->n_events = n_ev; out->n_segments = n_seg;
+    out->n_intervals = s.m; out->n_events = s.n_ev; out->n_segments = s.n_seg;
     return VC_OK;
 }
 

@@ -16,7 +16,7 @@ import sys
 import numpy as np
 
 from . import capi
-from .overlap import PRESETS
+from .overlap import PRESETS, _take, pack
 
 CLEAN, BAD_ENDS, CHIMERIC, NOT_COVERED = 0, 1, 2, 3
 CLASS_NAMES = ("Clean", "BadEnds", "Chimeric", "NotCovered")
@@ -65,10 +65,6 @@ def default_params(lib=None, **kw):
     return p
 
 
-def _take(ptr, n, dtype):
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
-
-
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -89,17 +85,15 @@ def run(lengths, intervals, reads=None, quals=None, device=0, lib=None, **params
     if reads is not None:
         if len(reads) != len(lens) or (quals is not None and len(quals) != len(lens)):
             raise ValueError("as many reads and qualities as lengths")
-        off = np.zeros(len(lens) + 1, np.uint64)
-        off[1:] = np.cumsum([len(s) for s in reads], dtype=np.uint64)
-        bases = np.frombuffer(b"".join(bytes(s) for s in reads) + b"\0", np.uint8).copy()
-        a.off, a.bases = _ptr(off, C.c_uint64), _ptr(bases, C.c_uint8)
-        keep += [off, bases]
+        packed, arrays = pack(reads)                         # offsets, and the bases with one pad byte behind them
+        a.off, a.bases = packed.off, packed.bases
+        keep.append(arrays)
         if quals is not None:
             if any(len(q) != len(s) for q, s in zip(quals, reads)):
                 raise ValueError("a quality string of another length than its read")
-            qb = np.frombuffer(b"".join(bytes(q) for q in quals) + b"\0", np.uint8).copy()
-            a.quals = _ptr(qb, C.c_uint8)
-            keep.append(qb)
+            packed, arrays = pack(quals)
+            a.quals = packed.bases
+            keep.append(arrays)
     elif quals is not None:
         raise ValueError("qualities without reads")
     o = VcScrubOut()
