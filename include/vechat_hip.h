@@ -1119,6 +1119,98 @@ int         vc_scrub(const vc_scrub_params* p, const vc_scrub_in* in, vc_scrub_o
 const char* vc_scrub_last_error(void);
 void        vc_scrub_release(void);
 
+/* ------------------------------------------------------------------------------------------------
+ * Clustering of reads into POA groups on the device (vechat_amd/csrc/vc_cluster.hip): overlaps go in, read groups come out --
+ * the groups that vc_poa_run and its kin expect the caller to arrive with (UMI families, amplicon clusters, reads of one locus).
+ *
+ * THIS IS THE LIBRARY'S OWN RULE: single-linkage clustering on qualified overlaps, with the strand of every read worked out on
+ * the way.  It restates no other tool.  Everything is integer arithmetic in 64 bits and every tie is decided;
+ * tests/cluster_ref.py restates the rule with another algorithm and the device is pinned to it array for array.
+ *
+ * Input.  n reads with lengths len[r] and m overlap records with the fields of vc_overlap_out that matter here: q_id, t_id,
+ * strand, q_begin, q_end, t_begin, t_end, matches, block.  The records may come in any order, with duplicates and with both
+ * directions of a pair; where they come from is the caller's business, as for vc_scrub.
+ *
+ * Link.  A record links its two reads a = q_id and b = t_id when all of these hold:
+ *     a != b
+ *     block >= min_overlap
+ *     1000 * matches >= min_identity_permille * block      (min_identity_permille == 0 switches this test off; matches is read
+ *                                                           as given: the chain's figure, or the exact one if the caller aligned)
+ *     the cover test: with  ca = 1000 * (q_end - q_begin) >= min_cover_permille * len[a]
+ *                     and   cb = 1000 * (t_end - t_begin) >= min_cover_permille * len[b],
+ *                     cover_both == 1 requires ca && cb (reads that overlap end to end, such as amplicons),
+ *                     cover_both == 0 requires ca || cb (a short read contained in a long one).
+ * Equality passes every threshold.
+ *
+ * Components with strands.  The graph has 2 n nodes, node 2 r + s for read r in orientation s.  A linking record with strand g
+ * joins (2 a, 2 b + g) and (2 a + 1, 2 b + 1 - g).  label(v) is the smallest node of v's component.  Per read:
+ *     root[r]    = label(2 r) >> 1                  the smallest read index of the cluster
+ *     strand[r]  = label(2 r) & 1                   1: reverse-complement r to put it in the root's orientation
+ *     twisted[r] = label(2 r) == label(2 r + 1)     the records contradict each other about the orientation; then strand is 0
+ *                                                   for every read of the cluster
+ * So every output is a function of the record SET alone: not of the record order, the launch shape or who wins an atomic.
+ *
+ * Clusters.  The reads with equal root form a cluster; a read without a link is a cluster of one.  A cluster with fewer than
+ * min_size reads is dropped and its reads get cluster[r] = VC_CLUSTER_NONE.  Kept clusters are numbered from 0: with
+ * by_size == 0 by root ascending, with by_size == 1 by size descending, ties by root ascending.  The members of a cluster are
+ * ordered by read index ascending (longest_first == 0) or by len descending, ties by index ascending (longest_first == 1: the
+ * longest read becomes the POA backbone).
+ *
+ * Output, library-owned.  cl_off[n_clusters + 1] into members; members[cl_off[n_clusters]], the read indices cluster by cluster;
+ * cl_root[n_clusters]; cl_twisted[n_clusters]; per read cluster[n] and strand[n] (strand is given for dropped reads too).
+ * Counters: n_links, the records that link (duplicates counted); n_rounds, the hook launches of the call (the components come
+ * from one lock-free hook kernel: 1, or 0 when no record links); n_components, the clusters before min_size is applied.
+ *
+ * Envelope: n <= VC_CLUSTER_MAX_READS = 2^30 (2 n nodes fit 31 bits), m < 2^30, every length at most VC_OVL_MAX_LEN.
+ * Checked on the host before the device is touched, in this order: p, in or out NULL, lengths NULL with n > 0, a record array
+ * NULL with m > 0; min_overlap below 0, min_cover_permille outside 0..1000, cover_both other than 0 / 1, min_identity_permille
+ * outside 0..1000, min_size below 1, by_size or longest_first other than 0 / 1; a record with q_id or t_id >= n, with an empty
+ * interval, with an interval ending beyond its read, or with a strand other than 0 / 1; n, a length or m beyond the envelope:
+ * VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these.  Device memory is taken per call: a call whose buffers the device refuses is
+ * VC_ERR_HIP with a text.
+ * Lifetime: the library owns every array of vc_cluster_out -- one set per process, not thread-safe -- until the next vc_cluster
+ * call or vc_cluster_release; a failed call leaves every pointer NULL.  vc_cluster_last_error has the text of the last failure.
+ * Test knob, read on every call: VC_CLUSTER_LOG (one stderr line, "vc_cluster: records=M links=L rounds=R components=C kept=K").
+ * ------------------------------------------------------------------------------------------------ */
+#define VC_CLUSTER_NONE      0xFFFFFFFFu
+#define VC_CLUSTER_MAX_READS 0x40000000ull
+typedef struct vc_cluster_params {   /* vc_cluster_default_params fills in the defaults named here                    */
+    int32_t device;                  /* 0                                                                            */
+    int32_t min_overlap;             /* 500  (at least 0)                                                            */
+    int32_t min_cover_permille;      /* 800  (0..1000)                                                               */
+    int32_t cover_both;              /* 1    0: one side of the record is enough                                     */
+    int32_t min_identity_permille;   /* 0    (0..1000); 0: no identity test                                          */
+    int32_t min_size;                /* 2    (at least 1)                                                            */
+    int32_t by_size;                 /* 0    1: clusters numbered by size descending                                 */
+    int32_t longest_first;           /* 0    1: members by length descending                                         */
+} vc_cluster_params;
+typedef struct vc_cluster_in {
+    uint64_t        n;               /* reads                                                                        */
+    const uint32_t* len;             /* [n]                                                                          */
+    uint64_t        m;               /* records; [m] each of the nine arrays below                                   */
+    const uint32_t* q_id;
+    const uint32_t* t_id;
+    const uint8_t*  strand;
+    const uint32_t* q_begin; const uint32_t* q_end;
+    const uint32_t* t_begin; const uint32_t* t_end;
+    const uint32_t* matches;
+    const uint32_t* block;
+} vc_cluster_in;
+typedef struct vc_cluster_out {      /* library-owned                                                                */
+    uint64_t        n_clusters;
+    const uint64_t* cl_off;          /* [n_clusters + 1] the members of cluster c are cl_off[c] .. cl_off[c + 1]     */
+    const uint32_t* members;         /* [cl_off[n_clusters]] read indices                                            */
+    const uint32_t* cl_root;         /* [n_clusters] the smallest read index of the cluster                          */
+    const uint8_t*  cl_twisted;      /* [n_clusters] 1: the records contradict each other about the orientation      */
+    const uint32_t* cluster;         /* [n] the cluster of read r, or VC_CLUSTER_NONE                                */
+    const uint8_t*  strand;          /* [n] 1: reverse-complement r to put it in its root's orientation              */
+    uint64_t n_links, n_rounds, n_components;                 /* what the call went through                          */
+} vc_cluster_out;
+void        vc_cluster_default_params(vc_cluster_params* p);
+int         vc_cluster(const vc_cluster_params* p, const vc_cluster_in* in, vc_cluster_out* out);
+const char* vc_cluster_last_error(void);
+void        vc_cluster_release(void);
+
 #ifdef __cplusplus
 }
 #endif

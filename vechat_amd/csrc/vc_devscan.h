@@ -1,4 +1,4 @@
-// The hipcub calls of the overlapper and the scrubber: the stable radix sort of pairs over a bit range and the two prefix sums.
+// The hipcub calls of the overlapper, the scrubber and the clusterer: the stable radix sort of pairs over a bit range and the two prefix sums.
 // Each queries the size of the temporary storage, takes it from the caller's DevMem, runs on the null stream, waits and drops it.
 // Nothing is cached between calls.
 #pragma once

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the device paths beside the hot path: vc_align.hip, vc_large.hip, vc_overlap.hip and vc_scrub.hip.
+// Host-side plumbing shared by the device paths beside the hot path: vc_align.hip, vc_large.hip, vc_overlap.hip, vc_scrub.hip and vc_cluster.hip.
 // Host code only: the device buffers of a scope, checked copies, the check that a batch of launches ran, the device check and the
 // knobs in MiB.  The hipcub sorts and sums are in vc_devscan.h, so a file that includes this one alone compiles without hipcub.
 // Every file keeps its own thread_local error text and its own fail(): the *_last_error entries are separate by contract.
