@@ -384,15 +384,9 @@ def timed_graph(batch, flags=0, graph=True, lib=None):
 
 
 def parent_handle(path):
-    """The two entry points the consensus-only call needs, from a library that may lack the newer ones (capi.load_hip binds them all
-    and so refuses a library of the parent commit)."""
+    """The two entry points the consensus-only call needs, from a library that may lack the newer ones."""
     import ctypes as C
-    lib = C.CDLL(path)
-    lib.vc_poa_run_gaps.argtypes = [C.POINTER(capi.VcPoaGapParams), C.POINTER(capi.VcBatch), C.POINTER(capi.VcResult)]
-    lib.vc_poa_run_gaps.restype = C.c_int
-    lib.vc_poa_last_error.argtypes = []
-    lib.vc_poa_last_error.restype = C.c_char_p
-    return lib
+    return capi.bind(C.CDLL(path), ("vc_poa_run_gaps", "vc_poa_last_error"))
 
 
 def _gfa_job(args):

@@ -11,7 +11,6 @@ batch = capi.synth_batch(capi.synth_cfg(1002, 500, 64), 0, n)
 ctx = HipContext(device=0, n_streams=1, chunk_windows=n)
 ctx.submit(batch)
 f = ctx.lib.vc_debug_rows
-f.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
 for layer in (4, 16, 32, 48, 62):
     ctx.lib.vc_debug_stop_after(ctx.h, 1, layer)
     ctx.run(); ctx.sync()

@@ -5,19 +5,12 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-
-
-class VcAlignBatch(C.Structure):
-    _fields_ = [("n", C.c_uint32), ("q_off", C.POINTER(C.c_uint64)), ("q", C.POINTER(C.c_uint8)),
-                ("t_off", C.POINTER(C.c_uint64)), ("t", C.POINTER(C.c_uint8))]
+from .capi import VcAlignBatch
 
 
 def align_pairs(pairs, device=0, lib=None):
     """pairs: [(query bytes, target bytes)] -> ([cigar str], [edit distance])"""
-    lib = lib or capi.load_hip()
-    lib.vc_align.argtypes = [C.c_int, C.POINTER(VcAlignBatch), C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
-    lib.vc_align.restype = C.c_int
-    lib.vc_align_last_error.restype = C.c_char_p
+    lib = capi.bind(lib or capi.load_hip(), ("vc_align", "vc_align_last_error"))
     n = len(pairs)
     if n == 0:
         return [], []
@@ -40,6 +33,4 @@ def align_pairs(pairs, device=0, lib=None):
 
 def release(lib=None):
     """vc_align_release: the aligner's (large) matrix buffer goes back to the device."""
-    lib = lib or capi.load_hip()
-    lib.vc_align_release.restype = None
-    lib.vc_align_release()
+    capi.bind(lib or capi.load_hip(), ("vc_align_release",)).vc_align_release()

@@ -248,6 +248,71 @@ class VcSynthCfg(C.Structure):
     ]
 
 
+class VcAlignBatch(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("q_off", C.POINTER(C.c_uint64)), ("q", C.POINTER(C.c_uint8)),
+                ("t_off", C.POINTER(C.c_uint64)), ("t", C.POINTER(C.c_uint8))]
+
+
+class VcOverlapSeqs(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("off", C.POINTER(C.c_uint64)), ("bases", C.POINTER(C.c_uint8))]
+
+
+class VcOverlapParams(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("device", "k", "w", "max_occ", "max_gap", "bandwidth", "lookback", "min_chain_score", "min_anchors",
+                                         "min_overlap", "drop_internal", "same_set")]
+
+
+class VcOverlapOut(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("q_id", C.POINTER(C.c_uint32)), ("t_id", C.POINTER(C.c_uint32)), ("strand", C.POINTER(C.c_uint8)),
+                ("q_begin", C.POINTER(C.c_uint32)), ("q_end", C.POINTER(C.c_uint32)), ("t_begin", C.POINTER(C.c_uint32)),
+                ("t_end", C.POINTER(C.c_uint32)), ("n_anchors", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_int32)),
+                ("matches", C.POINTER(C.c_uint32)), ("block", C.POINTER(C.c_uint32)),
+                ("n_minimizers", C.c_uint64), ("n_anchors_total", C.c_uint64), ("n_keys_total", C.c_uint64)]
+
+
+class VcOverlapSketchOut(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("hash", C.POINTER(C.c_uint64)), ("seq", C.POINTER(C.c_uint32)), ("pos", C.POINTER(C.c_uint32)),
+                ("strand", C.POINTER(C.c_uint8))]
+
+
+class VcScrubParams(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("device", "coverage", "max_bad_permille", "min_piece")]
+
+
+class VcScrubIn(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("len", C.POINTER(C.c_uint32)), ("m", C.c_uint64), ("read", C.POINTER(C.c_uint32)),
+                ("begin", C.POINTER(C.c_uint32)), ("end", C.POINTER(C.c_uint32)), ("off", C.POINTER(C.c_uint64)),
+                ("bases", C.POINTER(C.c_uint8)), ("quals", C.POINTER(C.c_uint8))]
+
+
+class VcScrubOut(C.Structure):
+    _fields_ = [("n_regions", C.c_uint64), ("reg_read", C.POINTER(C.c_uint32)), ("reg_begin", C.POINTER(C.c_uint32)),
+                ("reg_end", C.POINTER(C.c_uint32)), ("reg_off", C.POINTER(C.c_uint64)), ("klass", C.POINTER(C.c_uint8)),
+                ("bad_total", C.POINTER(C.c_uint32)), ("n_pieces", C.c_uint64), ("pc_read", C.POINTER(C.c_uint32)),
+                ("pc_begin", C.POINTER(C.c_uint32)), ("pc_end", C.POINTER(C.c_uint32)), ("pc_off", C.POINTER(C.c_uint64)),
+                ("pc_bases", C.POINTER(C.c_uint8)), ("pc_quals", C.POINTER(C.c_uint8)),
+                ("n_intervals", C.c_uint64), ("n_events", C.c_uint64), ("n_segments", C.c_uint64)]
+
+
+class VcClusterParams(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("device", "min_overlap", "min_cover_permille", "cover_both", "min_identity_permille", "min_size",
+                                         "by_size", "longest_first")]
+
+
+CLUSTER_RECORD_FIELDS = (("q_id", C.c_uint32), ("t_id", C.c_uint32), ("strand", C.c_uint8), ("q_begin", C.c_uint32), ("q_end", C.c_uint32),
+                         ("t_begin", C.c_uint32), ("t_end", C.c_uint32), ("matches", C.c_uint32), ("block", C.c_uint32))
+
+
+class VcClusterIn(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("len", C.POINTER(C.c_uint32)), ("m", C.c_uint64)] + [(f, C.POINTER(t)) for f, t in CLUSTER_RECORD_FIELDS]
+
+
+class VcClusterOut(C.Structure):
+    _fields_ = [("n_clusters", C.c_uint64), ("cl_off", C.POINTER(C.c_uint64)), ("members", C.POINTER(C.c_uint32)),
+                ("cl_root", C.POINTER(C.c_uint32)), ("cl_twisted", C.POINTER(C.c_uint8)), ("cluster", C.POINTER(C.c_uint32)),
+                ("strand", C.POINTER(C.c_uint8)), ("n_links", C.c_uint64), ("n_rounds", C.c_uint64), ("n_components", C.c_uint64)]
+
+
 def default_params(**kw):
     """Defaults the Python driver ends up with (scripts/vechat:70-72: -d 0.2 -s 0.2; main.cpp:46-61)."""
     p = VcParams(device=0, match=3, mismatch=-5, gap=-4, sw_match=3, sw_mismatch=-5, sw_gap=-4,
@@ -260,6 +325,30 @@ def default_params(**kw):
 
 def _ptr(a, ct):
     return a.ctypes.data_as(C.POINTER(ct))
+
+
+def _take(ptr, n, dtype):
+    """a copy of n entries of a library-owned array"""
+    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+
+
+def pack(seqs):
+    """[bytes] -> (VcOverlapSeqs, the arrays that must outlive it)"""
+    off = np.zeros(len(seqs) + 1, np.uint64)
+    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    bases = np.frombuffer(b"".join(bytes(s) for s in seqs) + b"\0", np.uint8).copy()
+    return VcOverlapSeqs(len(seqs), _ptr(off, C.c_uint64), _ptr(bases, C.c_uint8)), (off, bases)
+
+
+def params_from_defaults(struct, c_default, fields, what, kw):
+    """a parameter struct as its C default function fills it, then kw: the one body of overlap / scrub / cluster.default_params"""
+    p = struct()
+    c_default(C.byref(p))
+    for name, v in kw.items():
+        if name != "device" and name not in fields:
+            raise TypeError(f"unknown {what} parameter {name!r}")
+        setattr(p, name, int(v))
+    return p
 
 
 class Batch:
@@ -344,70 +433,140 @@ class Batch:
                      np.array(fasta_flags), np.array(orig))
 
 
+_P = C.POINTER
+_vp, _str, _int, _u32, _u64, _f64 = C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double
+_u8p, _u32p, _i32p, _u64p = _P(C.c_uint8), _P(C.c_uint32), _P(C.c_int32), _P(C.c_uint64)
+_batch, _result, _params, _gap = _P(VcBatch), _P(VcResult), _P(VcParams), _P(VcPoaGapParams)
+_msa, _strand, _graph, _graph_in, _align = _P(VcPoaMsaOut), _P(VcPoaStrandOut), _P(VcPoaGraphOut), _P(VcPoaGraphIn), _P(VcPoaAlignOut)
+_oseqs = _P(VcOverlapSeqs)
+
+# Every entry of include/vechat_hip.h that Python calls: name -> (restype, argtypes), in the header's order.  A new entry point is one
+# row here (and one structure above if it has one); tests/test_capi_table.py holds the table against the header's prototypes.
+SIGNATURES = {
+    "vc_create": (_int, [_P(_vp), _params]),
+    "vc_destroy": (None, [_vp]),
+    "vc_last_error": (_str, [_vp]),
+    "vc_submit": (_int, [_vp, _batch]),
+    "vc_run": (_int, [_vp]),
+    "vc_sync": (_int, [_vp]),
+    "vc_result_windows": (_int, [_vp, _u32p]),
+    "vc_result_size": (_int, [_vp, _u64p]),
+    "vc_collect": (_int, [_vp, _result]),
+    "vc_collect_device": (_int, [_vp, _vp, _u64, _vp, _vp]),
+    "vc_get_stats": (_int, [_vp, _P(VcStats)]),
+    "vc_debug_errinfo": (_int, [_vp, _u32p]),
+    "vc_debug_stop_after": (_int, [_vp, _u32, _u32]),
+    "vc_debug_stage_digest": (_int, [_vp, _u32, _int, _u64p]),
+    "vc_debug_rows": (_int, [_vp, _u32, _u32p, _u32, _u32p]),
+    "vc_stream": (_vp, [_vp]),
+    "vc_set_profile": (_int, [_vp, _int]),
+    "vc_has_experiments": (_int, []),
+    "vc_reserve": (_int, [_vp, _u64]),
+    "vc_set_polish_params": (_int, [_vp, _params]),
+    "vc_release": (_int, [_vp]),
+    "vc_set_window_type": (_int, [_vp, _int]),
+    # host helpers: from here to vc_io_load the rows are HOST_ENTRIES, all that libvechat_host.so has
+    "vc_rank_layers": (None, [_u32p, _u32, _u32p]),
+    "vc_backbone_is_fasta": (_int, [_str, _u32]),
+    "vc_weight_lut": (None, [_u32p]),
+    "vc_synth_generate": (_vp, [_P(VcSynthCfg), _u64, _u32, _u32]),
+    "vc_synth_batch": (None, [_vp, _batch]),
+    "vc_synth_n_seqs": (_u64, [_vp]),
+    "vc_synth_orig_index": (_u32p, [_vp]),
+    "vc_synth_n_bytes": (_u64, [_vp]),
+    "vc_synth_free": (None, [_vp]),
+    "vc_wb_create": (_vp, [_u32, _f64]),
+    "vc_wb_destroy": (None, [_vp]),
+    "vc_wb_last_error": (_str, [_vp]),
+    "vc_wb_add_sequence": (_int, [_vp, _str, _str, _u32, _str]),
+    "vc_wb_set_targets": (_int, [_vp, _u32]),
+    "vc_wb_add_overlap": (_int, [_vp, _u32, _u32, _int, _u32, _u32, _u32, _u32, _u32, _str]),
+    "vc_wb_n_breaking_points": (_u32, [_vp, _u32]),
+    "vc_wb_breaking_points": (None, [_vp, _u32, _u32p, _u32p]),
+    "vc_wb_build": (_int, [_vp, _batch]),
+    "vc_wb_build_begin": (_int, [_vp, _batch]),
+    "vc_wb_build_fill": (_int, [_vp, _u32, _u32]),
+    "vc_wb_seq_orig": (_u32p, [_vp]),
+    "vc_wb_n_windows": (_u32, [_vp]),
+    "vc_wb_window_target": (_u32, [_vp, _u32]),
+    "vc_wb_window_rank": (_u32, [_vp, _u32]),
+    "vc_wb_window_ids": (None, [_vp, _u32p, _u32p]),
+    "vc_wb_stitch": (_int, [_vp, _result, _int, _int]),
+    "vc_wb_n_polished": (_u32, [_vp]),
+    "vc_wb_polished_name": (_str, [_vp, _u32]),
+    "vc_wb_polished_data": (_P(C.c_char), [_vp, _u32, _u64p]),
+    "vc_io_read_sequences": (_vp, [_str, _str, _int]),
+    "vc_seqset_free": (None, [_vp]),
+    "vc_seqset_error": (_str, [_vp]),
+    "vc_seqset_size": (_u64, [_vp]),
+    "vc_seqset_name_off": (_u64p, [_vp]),
+    "vc_seqset_names": (_vp, [_vp]),
+    "vc_seqset_data_off": (_u64p, [_vp]),
+    "vc_seqset_data": (_vp, [_vp]),
+    "vc_seqset_qual": (_vp, [_vp]),
+    "vc_seqset_has_qual": (_u8p, [_vp]),
+    "vc_seqset_lengths": (_u64p, [_vp]),
+    "vc_io_read_overlaps": (_vp, [_str]),
+    "vc_ovlset_free": (None, [_vp]),
+    "vc_ovlset_error": (_str, [_vp]),
+    "vc_ovlset_size": (_u64, [_vp]),
+    "vc_ovlset_get": (_int, [_vp, _u64, _P(VcOverlapRec)]),
+    "vc_ovlset_set_cigar": (_int, [_vp, _u64, _str]),
+    "vc_io_target_cost": (_int, [_vp, _vp, _P(_f64)]),
+    "vc_io_rank_names": (_vp, [_vp, _vp, _vp, _u64, _u64, _u64p]),
+    "vc_io_free": (None, [_vp]),
+    "vc_io_load": (C.c_int64, [_vp, _vp, _vp, _vp, _f64, _int, _P(_int), _str, _u64]),
+    "vc_align": (_int, [_int, _P(VcAlignBatch), _str, _u64, _u64p, _i32p]),
+    "vc_align_last_error": (_str, []),
+    "vc_align_release": (None, []),
+    "vc_large_run": (_int, [_params, _batch, _result]),
+    "vc_large_last_error": (_str, []),
+    "vc_large_release": (None, []),
+    "vc_poa_run": (_int, [_P(VcPoaParams), _batch, _result]),
+    "vc_poa_last_error": (_str, []),
+    "vc_poa_run_gaps": (_int, [_gap, _batch, _result]),
+    "vc_poa_run_msa": (_int, [_gap, _batch, _result, _msa]),
+    "vc_poa_run_strand": (_int, [_gap, _batch, _result, _msa, _strand]),
+    "vc_poa_run_graph": (_int, [_gap, _batch, _result, _msa, _strand, _graph]),
+    "vc_poa_run_align": (_int, [_gap, _batch, _result, _strand, _graph, _batch, _align]),
+    "vc_poa_run_correct": (_int, [_batch, _gap, _P(VcPoaPruneParams), _result, _P(VcPoaCorrectOut)]),
+    "vc_poa_run_from": (_int, [_gap, _graph_in, _batch, _result, _msa, _strand, _graph, _P(VcPoaStateOut), _batch, _align]),
+    "vc_poa_run_assign": (_int, [_gap, _graph_in, _batch, _result, _batch, _P(VcPoaAssignOut)]),
+    "vc_poa_run_spans": (_int, [_gap, _P(VcPoaSpanIn), _batch, _result, _msa, _strand, _graph]),
+    "vc_poa_run_weighted": (_int, [_gap, _P(VcPoaWeightIn), _batch, _result, _msa, _strand, _graph, _P(VcPoaProfileOut)]),
+    "vc_poa_hap_default_params": (None, [_P(VcPoaHapParams)]),
+    "vc_poa_run_haplotypes": (_int, [_gap, _P(VcPoaHapParams), _batch, _result, _P(VcPoaHapOut)]),
+    "vc_overlap_default_params": (None, [_P(VcOverlapParams)]),
+    "vc_overlap": (_int, [_P(VcOverlapParams), _oseqs, _oseqs, _P(VcOverlapOut)]),
+    "vc_overlap_sketch": (_int, [C.c_int32, C.c_int32, C.c_int32, _oseqs, _P(VcOverlapSketchOut)]),
+    "vc_overlap_last_error": (_str, []),
+    "vc_overlap_release": (None, []),
+    "vc_scrub_default_params": (None, [_P(VcScrubParams)]),
+    "vc_scrub": (_int, [_P(VcScrubParams), _P(VcScrubIn), _P(VcScrubOut)]),
+    "vc_scrub_last_error": (_str, []),
+    "vc_scrub_release": (None, []),
+    "vc_cluster_default_params": (None, [_P(VcClusterParams)]),
+    "vc_cluster": (_int, [_P(VcClusterParams), _P(VcClusterIn), _P(VcClusterOut)]),
+    "vc_cluster_last_error": (_str, []),
+    "vc_cluster_release": (None, []),
+}
+_names = list(SIGNATURES)
+HOST_ENTRIES = tuple(_names[_names.index("vc_rank_layers"):_names.index("vc_io_load") + 1])
+
+
+def bind(lib, names=None, optional=False):
+    """Sets restype and argtypes of the named entries of SIGNATURES (None: all of them) on a loaded library and returns it.  A symbol
+    the library lacks is an AttributeError naming it, or with optional=True is passed over: the library is older than this module."""
+    for name in SIGNATURES if names is None else names:
+        if optional and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    return lib
+
+
 _host = None
 _hip = None
-
-
-def _declare_host(lib):
-    lib.vc_rank_layers.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
-    lib.vc_rank_layers.restype = None
-    lib.vc_backbone_is_fasta.argtypes = [C.c_char_p, C.c_uint32]
-    lib.vc_backbone_is_fasta.restype = C.c_int
-    lib.vc_weight_lut.argtypes = [C.POINTER(C.c_uint32)]
-    lib.vc_weight_lut.restype = None
-    vp = C.c_void_p
-    u32 = C.c_uint32
-    lib.vc_wb_create.argtypes = [u32, C.c_double]; lib.vc_wb_create.restype = vp
-    lib.vc_wb_destroy.argtypes = [vp]; lib.vc_wb_destroy.restype = None
-    lib.vc_wb_last_error.argtypes = [vp]; lib.vc_wb_last_error.restype = C.c_char_p
-    lib.vc_wb_add_sequence.argtypes = [vp, C.c_char_p, C.c_char_p, u32, C.c_char_p]; lib.vc_wb_add_sequence.restype = C.c_int
-    lib.vc_wb_set_targets.argtypes = [vp, u32]; lib.vc_wb_set_targets.restype = C.c_int
-    lib.vc_wb_add_overlap.argtypes = [vp, u32, u32, C.c_int, u32, u32, u32, u32, u32, C.c_char_p]; lib.vc_wb_add_overlap.restype = C.c_int
-    lib.vc_wb_n_breaking_points.argtypes = [vp, u32]; lib.vc_wb_n_breaking_points.restype = u32
-    lib.vc_wb_breaking_points.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]; lib.vc_wb_breaking_points.restype = None
-    lib.vc_wb_build.argtypes = [vp, C.POINTER(VcBatch)]; lib.vc_wb_build.restype = C.c_int
-    lib.vc_wb_build_begin.argtypes = [vp, C.POINTER(VcBatch)]; lib.vc_wb_build_begin.restype = C.c_int
-    lib.vc_wb_build_fill.argtypes = [vp, C.c_uint32, C.c_uint32]; lib.vc_wb_build_fill.restype = C.c_int
-    lib.vc_wb_seq_orig.argtypes = [vp]; lib.vc_wb_seq_orig.restype = C.POINTER(u32)
-    lib.vc_wb_n_windows.argtypes = [vp]; lib.vc_wb_n_windows.restype = u32
-    lib.vc_wb_window_target.argtypes = [vp, u32]; lib.vc_wb_window_target.restype = u32
-    lib.vc_wb_window_rank.argtypes = [vp, u32]; lib.vc_wb_window_rank.restype = u32
-    lib.vc_wb_window_ids.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]; lib.vc_wb_window_ids.restype = None
-    lib.vc_wb_stitch.argtypes = [vp, C.POINTER(VcResult), C.c_int, C.c_int]; lib.vc_wb_stitch.restype = C.c_int
-    lib.vc_wb_n_polished.argtypes = [vp]; lib.vc_wb_n_polished.restype = u32
-    lib.vc_wb_polished_name.argtypes = [vp, u32]; lib.vc_wb_polished_name.restype = C.c_char_p
-    lib.vc_wb_polished_data.argtypes = [vp, u32, C.POINTER(C.c_uint64)]; lib.vc_wb_polished_data.restype = C.POINTER(C.c_char)
-    u64p = C.POINTER(C.c_uint64)
-    lib.vc_io_read_sequences.argtypes = [C.c_char_p, C.c_char_p, C.c_int]; lib.vc_io_read_sequences.restype = vp
-    lib.vc_seqset_free.argtypes = [vp]; lib.vc_seqset_free.restype = None
-    lib.vc_seqset_error.argtypes = [vp]; lib.vc_seqset_error.restype = C.c_char_p
-    lib.vc_seqset_size.argtypes = [vp]; lib.vc_seqset_size.restype = C.c_uint64
-    for name, rt in (("vc_seqset_name_off", u64p), ("vc_seqset_data_off", u64p), ("vc_seqset_lengths", u64p), ("vc_seqset_names", C.c_void_p),
-                     ("vc_seqset_data", C.c_void_p), ("vc_seqset_qual", C.c_void_p), ("vc_seqset_has_qual", C.POINTER(C.c_uint8))):
-        getattr(lib, name).argtypes = [vp]; getattr(lib, name).restype = rt
-    lib.vc_io_read_overlaps.argtypes = [C.c_char_p]; lib.vc_io_read_overlaps.restype = vp
-    lib.vc_ovlset_free.argtypes = [vp]; lib.vc_ovlset_free.restype = None
-    lib.vc_ovlset_error.argtypes = [vp]; lib.vc_ovlset_error.restype = C.c_char_p
-    lib.vc_ovlset_size.argtypes = [vp]; lib.vc_ovlset_size.restype = C.c_uint64
-    lib.vc_ovlset_get.argtypes = [vp, C.c_uint64, C.POINTER(VcOverlapRec)]; lib.vc_ovlset_get.restype = C.c_int
-    lib.vc_ovlset_set_cigar.argtypes = [vp, C.c_uint64, C.c_char_p]; lib.vc_ovlset_set_cigar.restype = C.c_int
-    lib.vc_io_load.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_uint64]; lib.vc_io_load.restype = C.c_int64
-    lib.vc_io_target_cost.argtypes = [vp, vp, C.POINTER(C.c_double)]; lib.vc_io_target_cost.restype = C.c_int
-    lib.vc_io_rank_names.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, u64p]; lib.vc_io_rank_names.restype = C.c_void_p
-    lib.vc_io_free.argtypes = [vp]; lib.vc_io_free.restype = None
-    lib.vc_synth_generate.argtypes = [C.POINTER(VcSynthCfg), C.c_uint64, C.c_uint32, C.c_uint32]
-    lib.vc_synth_generate.restype = C.c_void_p
-    lib.vc_synth_batch.argtypes = [C.c_void_p, C.POINTER(VcBatch)]
-    lib.vc_synth_batch.restype = None
-    lib.vc_synth_n_seqs.argtypes = [C.c_void_p]
-    lib.vc_synth_n_seqs.restype = C.c_uint64
-    lib.vc_synth_n_bytes.argtypes = [C.c_void_p]
-    lib.vc_synth_n_bytes.restype = C.c_uint64
-    lib.vc_synth_orig_index.argtypes = [C.c_void_p]
-    lib.vc_synth_orig_index.restype = C.POINTER(C.c_uint32)
-    lib.vc_synth_free.argtypes = [C.c_void_p]
-    lib.vc_synth_free.restype = None
-    return lib
 
 
 def load_host():
@@ -417,113 +576,22 @@ def load_host():
         path = os.path.join(LIB_DIR, "libvechat_host.so")
         if not os.path.exists(path):
             raise RuntimeError(f"{path} missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _host = _declare_host(C.CDLL(path))
+        _host = bind(C.CDLL(path), HOST_ENTRIES)
     return _host
 
 
 def load_hip():
-    """The product library.  Raises if it has not been built; never falls back to CPU code."""
+    """The product library.  Raises if it has not been built; never falls back to CPU code.  Only a library named by VECHAT_HIP_LIB
+    (development A/B builds, the parent commit's library beside which tools/gpu_poa_rate.py measures) may predate an entry point:
+    poa._entry says so when such an entry is asked for."""
     global _hip
     if _hip is None:
-        path = os.environ.get("VECHAT_HIP_LIB") or os.path.join(LIB_DIR, "libvechat_hip.so")   # override: development A/B builds
+        override = os.environ.get("VECHAT_HIP_LIB")
+        path = override or os.path.join(LIB_DIR, "libvechat_hip.so")
         if not os.path.exists(path):
             raise RuntimeError(f"{path} missing: the HIP extension is required (no CPU fallback); "
                                "run `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = _declare_host(C.CDLL(path))
-        vp = C.c_void_p
-        lib.vc_create.argtypes = [C.POINTER(vp), C.POINTER(VcParams)]
-        lib.vc_create.restype = C.c_int
-        lib.vc_destroy.argtypes = [vp]
-        lib.vc_destroy.restype = None
-        lib.vc_last_error.argtypes = [vp]
-        lib.vc_last_error.restype = C.c_char_p
-        lib.vc_submit.argtypes = [vp, C.POINTER(VcBatch)]
-        lib.vc_submit.restype = C.c_int
-        for name in ("vc_run", "vc_sync"):
-            getattr(lib, name).argtypes = [vp]
-            getattr(lib, name).restype = C.c_int
-        lib.vc_result_size.argtypes = [vp, C.POINTER(C.c_uint64)]
-        lib.vc_result_size.restype = C.c_int
-        lib.vc_result_windows.argtypes = [vp, C.POINTER(C.c_uint32)]
-        lib.vc_result_windows.restype = C.c_int
-        lib.vc_collect.argtypes = [vp, C.POINTER(VcResult)]
-        lib.vc_collect.restype = C.c_int
-        lib.vc_collect_device.argtypes = [vp, vp, C.c_uint64, vp, vp]
-        lib.vc_collect_device.restype = C.c_int
-        lib.vc_get_stats.argtypes = [vp, C.POINTER(VcStats)]
-        lib.vc_get_stats.restype = C.c_int
-        lib.vc_debug_errinfo.argtypes = [vp, C.POINTER(C.c_uint32)]
-        lib.vc_debug_errinfo.restype = C.c_int
-        lib.vc_debug_stop_after.argtypes = [vp, C.c_uint32, C.c_uint32]
-        lib.vc_debug_stop_after.restype = C.c_int
-        lib.vc_debug_stage_digest.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
-        lib.vc_debug_stage_digest.restype = C.c_int
-        lib.vc_set_profile.argtypes = [vp, C.c_int]
-        lib.vc_set_profile.restype = C.c_int
-        try:                                  # (development: an A/B variant library built before an entry point was added still loads)
-            lib.vc_set_polish_params.argtypes = [vp, C.POINTER(VcParams)]
-            lib.vc_set_polish_params.restype = C.c_int
-        except AttributeError:
-            pass
-        lib.vc_has_experiments.argtypes = []
-        lib.vc_has_experiments.restype = C.c_int
-        lib.vc_reserve.argtypes = [vp, C.c_uint64]; lib.vc_reserve.restype = C.c_int
-        lib.vc_release.argtypes = [vp]; lib.vc_release.restype = C.c_int
-        lib.vc_set_window_type.argtypes = [vp, C.c_int]; lib.vc_set_window_type.restype = C.c_int
-        lib.vc_poa_run.argtypes = [C.POINTER(VcPoaParams), C.POINTER(VcBatch), C.POINTER(VcResult)]; lib.vc_poa_run.restype = C.c_int
-        lib.vc_poa_last_error.argtypes = []; lib.vc_poa_last_error.restype = C.c_char_p
-        lib.vc_poa_run_gaps.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult)]
-        lib.vc_poa_run_gaps.restype = C.c_int
-        lib.vc_poa_run_msa.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut)]
-        lib.vc_poa_run_msa.restype = C.c_int
-        lib.vc_poa_run_strand.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut),
-                                          C.POINTER(VcPoaStrandOut)]
-        lib.vc_poa_run_strand.restype = C.c_int
-        lib.vc_poa_run_graph.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaMsaOut),
-                                         C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut)]
-        lib.vc_poa_run_graph.restype = C.c_int
-        # (development: only an A/B variant library named by VECHAT_HIP_LIB may predate this entry point; poa.run_batch_align says so)
-        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_align"):
-            lib.vc_poa_run_align.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcBatch), C.POINTER(VcResult), C.POINTER(VcPoaStrandOut),
-                                             C.POINTER(VcPoaGraphOut), C.POINTER(VcBatch), C.POINTER(VcPoaAlignOut)]
-            lib.vc_poa_run_align.restype = C.c_int
-        # (likewise: the parent commit's library, beside which tools/gpu_poa_rate.py --correct measures, has no correction entry)
-        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_correct"):
-            lib.vc_poa_run_correct.argtypes = [C.POINTER(VcBatch), C.POINTER(VcPoaGapParams), C.POINTER(VcPoaPruneParams), C.POINTER(VcResult),
-                                               C.POINTER(VcPoaCorrectOut)]
-            lib.vc_poa_run_correct.restype = C.c_int
-        # (likewise: the parent commit's library, beside which tools/gpu_poa_rate.py --resume measures, has no such entry)
-        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_from"):
-            lib.vc_poa_run_from.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaGraphIn), C.POINTER(VcBatch), C.POINTER(VcResult),
-                                            C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut),
-                                            C.POINTER(VcPoaStateOut), C.POINTER(VcBatch), C.POINTER(VcPoaAlignOut)]
-            lib.vc_poa_run_from.restype = C.c_int
-        # (likewise: tools/gpu_poa_rate.py --assign may be pointed at the parent commit's library for its own route)
-        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_assign"):
-            lib.vc_poa_run_assign.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaGraphIn), C.POINTER(VcBatch), C.POINTER(VcResult),
-                                              C.POINTER(VcBatch), C.POINTER(VcPoaAssignOut)]
-            lib.vc_poa_run_assign.restype = C.c_int
-        # (likewise: the parent commit's library, beside which tools/gpu_poa_rate.py --spans measures, has no such entry)
-        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_spans"):
-            lib.vc_poa_run_spans.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaSpanIn), C.POINTER(VcBatch), C.POINTER(VcResult),
-                                             C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut)]
-            lib.vc_poa_run_spans.restype = C.c_int
-        # (likewise: tools/gpu_poa_rate.py --weights measures beside the parent commit's library)
-        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_weighted"):
-            lib.vc_poa_run_weighted.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaWeightIn), C.POINTER(VcBatch), C.POINTER(VcResult),
-                                                C.POINTER(VcPoaMsaOut), C.POINTER(VcPoaStrandOut), C.POINTER(VcPoaGraphOut),
-                                                C.POINTER(VcPoaProfileOut)]
-            lib.vc_poa_run_weighted.restype = C.c_int
-        # (likewise: tools/gpu_poa_rate.py --haplotypes measures beside the parent commit's library, which has no haplotype entry)
-        if not os.environ.get("VECHAT_HIP_LIB") or hasattr(lib, "vc_poa_run_haplotypes"):
-            lib.vc_poa_hap_default_params.argtypes = [C.POINTER(VcPoaHapParams)]
-            lib.vc_poa_hap_default_params.restype = None
-            lib.vc_poa_run_haplotypes.argtypes = [C.POINTER(VcPoaGapParams), C.POINTER(VcPoaHapParams), C.POINTER(VcBatch),
-                                                  C.POINTER(VcResult), C.POINTER(VcPoaHapOut)]
-            lib.vc_poa_run_haplotypes.restype = C.c_int
-        lib.vc_stream.argtypes = [vp]
-        lib.vc_stream.restype = vp
-        _hip = lib
+        _hip = bind(C.CDLL(path), optional=bool(override))
     return _hip
 
 

@@ -16,48 +16,22 @@ import sys
 import numpy as np
 
 from . import capi
-from .overlap import _COMP, PRESETS, _take
+from .capi import VcClusterIn, VcClusterOut, VcClusterParams, _take
+from .overlap import COMPLEMENT, PRESETS
 
 NONE = 0xFFFFFFFF
-PARAMS = ("min_overlap", "min_cover_permille", "cover_both", "min_identity_permille", "min_size", "by_size", "longest_first")
-RECORD_FIELDS = (("q_id", C.c_uint32), ("t_id", C.c_uint32), ("strand", C.c_uint8), ("q_begin", C.c_uint32), ("q_end", C.c_uint32),
-                 ("t_begin", C.c_uint32), ("t_end", C.c_uint32), ("matches", C.c_uint32), ("block", C.c_uint32))
-
-
-class VcClusterParams(C.Structure):
-    _fields_ = [("device", C.c_int32)] + [(f, C.c_int32) for f in PARAMS]
-
-
-class VcClusterIn(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("len", C.POINTER(C.c_uint32)), ("m", C.c_uint64)] + [(f, C.POINTER(t)) for f, t in RECORD_FIELDS]
-
-
-class VcClusterOut(C.Structure):
-    _fields_ = [("n_clusters", C.c_uint64), ("cl_off", C.POINTER(C.c_uint64)), ("members", C.POINTER(C.c_uint32)),
-                ("cl_root", C.POINTER(C.c_uint32)), ("cl_twisted", C.POINTER(C.c_uint8)), ("cluster", C.POINTER(C.c_uint32)),
-                ("strand", C.POINTER(C.c_uint8)), ("n_links", C.c_uint64), ("n_rounds", C.c_uint64), ("n_components", C.c_uint64)]
+PARAMS = tuple(f for f, _ in VcClusterParams._fields_[1:])
+RECORD_FIELDS = capi.CLUSTER_RECORD_FIELDS
 
 
 def declare(lib):
     """argument types of the cluster entries (a missing symbol is an AttributeError: the library is older than this module)"""
-    lib.vc_cluster.argtypes = [C.POINTER(VcClusterParams), C.POINTER(VcClusterIn), C.POINTER(VcClusterOut)]
-    lib.vc_cluster.restype = C.c_int
-    lib.vc_cluster_default_params.argtypes = [C.POINTER(VcClusterParams)]
-    lib.vc_cluster_default_params.restype = None
-    lib.vc_cluster_last_error.restype = C.c_char_p
-    lib.vc_cluster_release.restype = None
-    return lib
+    return capi.bind(lib, ("vc_cluster_default_params", "vc_cluster", "vc_cluster_last_error", "vc_cluster_release"))
 
 
 def default_params(lib=None, **kw):
     lib = declare(lib or capi.load_hip())
-    p = VcClusterParams()
-    lib.vc_cluster_default_params(C.byref(p))
-    for name, v in kw.items():
-        if name != "device" and name not in PARAMS:
-            raise TypeError(f"unknown cluster parameter {name!r}")
-        setattr(p, name, int(v))
-    return p
+    return capi.params_from_defaults(VcClusterParams, lib.vc_cluster_default_params, PARAMS, "cluster", kw)
 
 
 def run(lengths, records, device=0, lib=None, **params):
@@ -111,7 +85,7 @@ def groups_of(result, reads):
     out = []
     for c in range(len(off) - 1):
         rows = members[int(off[c]):int(off[c + 1])]
-        out.append([bytes(reads[int(r)]).translate(_COMP)[::-1] if strand[int(r)] else bytes(reads[int(r)]) for r in rows])
+        out.append([bytes(reads[int(r)]).translate(COMPLEMENT)[::-1] if strand[int(r)] else bytes(reads[int(r)]) for r in rows])
     return out
 
 
@@ -135,21 +109,9 @@ def format_consensus(names, result, consensus):
 
 
 def records_from_paf(path, names):
-    """the records of a PAF file through the package's reader, as the dict of arrays run() takes: columns 10 and 11 as they stand"""
-    from . import seqio
-    index = {n: i for i, n in enumerate(names)}
-    rows = []
-    for o in seqio.read_paf(path):
-        for name in (o.q_name, o.t_name):
-            if name not in index:
-                raise ValueError(f"{path}: {name!r} is not a read of the input")
-        rows.append((index[o.q_name], index[o.t_name], int(bool(o.strand)), o.q_begin, o.q_end, o.t_begin, o.t_end))
-    cols = np.array(rows, np.int64).reshape(-1, 7)
-    with seqio._open(path) as f:                             # the reader keeps no column 10 or 11: they are taken from the same lines
-        ten = np.array([[int(x) for x in ln.split(b"\t")[9:11]] for ln in f if ln.strip()], np.int64).reshape(-1, 2)
-    rec = {f: cols[:, i] for i, (f, _) in enumerate(RECORD_FIELDS[:7])}
-    rec.update(matches=ten[:, 0], block=ten[:, 1])
-    return rec
+    """the records of a PAF file as the dict of arrays run() takes: columns 10 and 11 as they stand (overlap.records_from_paf)"""
+    from . import overlap
+    return overlap.records_from_paf(path, names, "is not a read of the input")
 
 
 def parse_args(argv=None):

@@ -15,13 +15,7 @@ class LargeError(RuntimeError):
 
 
 def _declare(lib):
-    lib.vc_large_run.argtypes = [C.POINTER(capi.VcParams), C.POINTER(capi.VcBatch), C.POINTER(capi.VcResult)]
-    lib.vc_large_run.restype = C.c_int
-    lib.vc_large_last_error.argtypes = []
-    lib.vc_large_last_error.restype = C.c_char_p
-    lib.vc_large_release.argtypes = []
-    lib.vc_large_release.restype = None
-    return lib
+    return capi.bind(lib, ("vc_large_run", "vc_large_last_error", "vc_large_release"))
 
 
 def large_consensus(batch: capi.Batch, params: capi.VcParams, lib=None):

@@ -15,69 +15,24 @@ import sys
 import numpy as np
 
 from . import capi
+from .capi import VcOverlapOut, VcOverlapParams, VcOverlapSeqs, VcOverlapSketchOut, _take, pack
 
 RECORD = np.dtype([("q_id", "<u4"), ("t_id", "<u4"), ("strand", "u1"), ("q_begin", "<u4"), ("q_end", "<u4"), ("t_begin", "<u4"),
                    ("t_end", "<u4"), ("n_anchors", "<u4"), ("score", "<i4"), ("matches", "<u4"), ("block", "<u4")])
 SKETCH = np.dtype([("hash", "<u8"), ("seq", "<u4"), ("pos", "<u4"), ("strand", "u1")])
-PARAMS = ("k", "w", "max_occ", "max_gap", "bandwidth", "lookback", "min_chain_score", "min_anchors", "min_overlap", "drop_internal", "same_set")
+PARAMS = tuple(f for f, _ in VcOverlapParams._fields_[1:])
 PRESETS = {"ava-ont": dict(k=15, w=5), "ava-pb": dict(k=19, w=5)}
-
-
-class VcOverlapSeqs(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("off", C.POINTER(C.c_uint64)), ("bases", C.POINTER(C.c_uint8))]
-
-
-class VcOverlapParams(C.Structure):
-    _fields_ = [("device", C.c_int32)] + [(f, C.c_int32) for f in PARAMS]
-
-
-class VcOverlapOut(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("q_id", C.POINTER(C.c_uint32)), ("t_id", C.POINTER(C.c_uint32)), ("strand", C.POINTER(C.c_uint8)),
-                ("q_begin", C.POINTER(C.c_uint32)), ("q_end", C.POINTER(C.c_uint32)), ("t_begin", C.POINTER(C.c_uint32)),
-                ("t_end", C.POINTER(C.c_uint32)), ("n_anchors", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_int32)),
-                ("matches", C.POINTER(C.c_uint32)), ("block", C.POINTER(C.c_uint32)),
-                ("n_minimizers", C.c_uint64), ("n_anchors_total", C.c_uint64), ("n_keys_total", C.c_uint64)]
-
-
-class VcOverlapSketchOut(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("hash", C.POINTER(C.c_uint64)), ("seq", C.POINTER(C.c_uint32)), ("pos", C.POINTER(C.c_uint32)),
-                ("strand", C.POINTER(C.c_uint8))]
+COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
 
 
 def declare(lib):
     """argument types of the overlap entries (a missing symbol is an AttributeError: the library is older than this module)"""
-    lib.vc_overlap.argtypes = [C.POINTER(VcOverlapParams), C.POINTER(VcOverlapSeqs), C.POINTER(VcOverlapSeqs), C.POINTER(VcOverlapOut)]
-    lib.vc_overlap.restype = C.c_int
-    lib.vc_overlap_sketch.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(VcOverlapSeqs), C.POINTER(VcOverlapSketchOut)]
-    lib.vc_overlap_sketch.restype = C.c_int
-    lib.vc_overlap_default_params.argtypes = [C.POINTER(VcOverlapParams)]
-    lib.vc_overlap_default_params.restype = None
-    lib.vc_overlap_last_error.restype = C.c_char_p
-    lib.vc_overlap_release.restype = None
-    return lib
+    return capi.bind(lib, ("vc_overlap_default_params", "vc_overlap", "vc_overlap_sketch", "vc_overlap_last_error", "vc_overlap_release"))
 
 
 def default_params(lib=None, **kw):
     lib = declare(lib or capi.load_hip())
-    p = VcOverlapParams()
-    lib.vc_overlap_default_params(C.byref(p))
-    for name, v in kw.items():
-        if name != "device" and name not in PARAMS:
-            raise TypeError(f"unknown overlap parameter {name!r}")
-        setattr(p, name, int(v))
-    return p
-
-
-def pack(seqs):
-    """[bytes] -> (VcOverlapSeqs, the arrays that must outlive it)"""
-    off = np.zeros(len(seqs) + 1, np.uint64)
-    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    bases = np.frombuffer(b"".join(bytes(s) for s in seqs) + b"\0", np.uint8).copy()
-    return VcOverlapSeqs(len(seqs), off.ctypes.data_as(C.POINTER(C.c_uint64)), bases.ctypes.data_as(C.POINTER(C.c_uint8))), (off, bases)
-
-
-def _take(ptr, n, dtype):
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+    return capi.params_from_defaults(VcOverlapParams, lib.vc_overlap_default_params, PARAMS, "overlap", kw)
 
 
 def sketch(seqs, k=15, w=5, device=0, lib=None):
@@ -120,7 +75,6 @@ def find_overlaps(targets, queries=None, device=0, lib=None, stats=None, **param
     return out
 
 
-_COMP = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
 _RUN = re.compile(r"(\d+)[MID]")
 
 
@@ -134,7 +88,7 @@ def identity(records, targets, queries=None, device=0, lib=None):
     for r in records:
         qp = bytes(queries[int(r["q_id"])])[int(r["q_begin"]):int(r["q_end"])]
         if r["strand"]:
-            qp = qp.translate(_COMP)[::-1]
+            qp = qp.translate(COMPLEMENT)[::-1]
         pairs.append((qp, bytes(targets[int(r["t_id"])])[int(r["t_begin"]):int(r["t_end"])]))
     cigars, dist = align_pairs(pairs, device=device, lib=lib)
     for i, (cg, d) in enumerate(zip(cigars, dist)):
@@ -158,6 +112,28 @@ def write_paf(path, records, target_names, target_lens, query_names, query_lens)
     finally:
         if fw is not path:
             fw.close()
+
+
+def records_from_paf(path, names, what):
+    """The records of a PAF file from one read of it, as the dict of arrays cluster.run and scrub.intervals_from_records take: the
+    nine columns of capi.CLUSTER_RECORD_FIELDS, a read as its index in names, columns 10 and 11 as they stand.  Lines and spans are
+    taken as seqio.read_paf takes them; a name that is not in names is a ValueError `<path>: <name> <what>`."""
+    from . import seqio
+    index = {n: i for i, n in enumerate(names)}
+    rows = []
+    with seqio._open(path) as f:
+        for ln in f:
+            if not ln.strip():
+                continue
+            c = ln.rstrip(b"\n").split(b"\t")
+            qb, qe, tb, te = int(c[2]), int(c[3]), int(c[7]), int(c[8])
+            seqio._check_spans("PAF", qb, qe, int(c[1]), tb, te)
+            for name in (c[0].decode(), c[5].decode()):
+                if name not in index:
+                    raise ValueError(f"{path}: {name!r} {what}")
+            rows.append((index[c[0].decode()], index[c[5].decode()], int(c[4] == b"-"), qb, qe, tb, te, int(c[9]), int(c[10])))
+    cols = np.array(rows, np.int64).reshape(-1, 9)
+    return {f: cols[:, i] for i, (f, _) in enumerate(capi.CLUSTER_RECORD_FIELDS)}
 
 
 def parse_args(argv=None):

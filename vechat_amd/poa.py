@@ -76,6 +76,13 @@ class PoaError(RuntimeError):
         self.groups = groups or {}
 
 
+def _entry(lib, name):
+    """the entry `name` of a loaded library; a library named by VECHAT_HIP_LIB may predate it (capi.load_hip)"""
+    if not hasattr(lib, name):
+        raise PoaError(f"this libvechat_hip.so has no {name}: it was built before the entry point existed; rebuild it")
+    return getattr(lib, name)
+
+
 def algorithm_code(algorithm):
     """0 / 1 / 2 or "local" / "global" / "semi-global" -> spoa::AlignmentType"""
     if isinstance(algorithm, str):
@@ -360,8 +367,6 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
     prof = None
     if weighted:
         name = "vc_poa_run_weighted"
-        if not hasattr(lib, name):
-            raise PoaError("this libvechat_hip.so has no vc_poa_run_weighted: it was built before the entry point existed; rebuild it")
         ref = lambda x: None if x is None else C.byref(x)
         win = None
         if weights is not None:
@@ -374,8 +379,6 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         args = (ref(o), so, ref(g), ref(prof))
     elif spans is not None:
         name = "vc_poa_run_spans"
-        if not hasattr(lib, name):
-            raise PoaError("this libvechat_hip.so has no vc_poa_run_spans: it was built before the entry point existed; rebuild it")
         sb, se = (np.ascontiguousarray(x, np.uint32) for x in spans)
         keep = (sb, se)                             # (the arrays the struct points into, until the call)
         ref = lambda x: None if x is None else C.byref(x)
@@ -383,8 +386,6 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         args = (ref(o), so, ref(g))
     elif start is not None or state:
         name = "vc_poa_run_from"
-        if not hasattr(lib, name):
-            raise PoaError("this libvechat_hip.so has no vc_poa_run_from: it was built before the entry point existed; rebuild it")
         if start is not None and len(start) != n:
             raise ValueError(f"{len(start)} graphs to start from for {n} groups")
         gin, keep = _graph_in(start) if start is not None else (None, None)     # (keep: the arrays gin points into, until the call)
@@ -393,8 +394,6 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         first, args = (ref(gin),), (ref(o), so, ref(g), ref(st), ref(qv), ref(a))
     elif qbatch is not None:
         name = "vc_poa_run_align"
-        if not hasattr(lib, name):
-            raise PoaError("this libvechat_hip.so has no vc_poa_run_align: it was built before the entry point existed; rebuild it")
         args = (so, C.byref(g) if graph else None, C.byref(qv), C.byref(a))
     elif graph:
         name, args = "vc_poa_run_graph", (C.byref(o), so, C.byref(g))
@@ -404,7 +403,7 @@ def _run(batch, params, *, lib=None, msa_flags=None, strands=False, strand_score
         name, args = "vc_poa_run_msa", (C.byref(o),)
     else:
         name, args = "vc_poa_run_gaps" if isinstance(params, capi.VcPoaGapParams) else "vc_poa_run", ()
-    rc = getattr(lib, name)(C.byref(params), *first, C.byref(vb), C.byref(r), *args)
+    rc = _entry(lib, name)(C.byref(params), *first, C.byref(vb), C.byref(r), *args)
     if rc != 0:
         raise PoaError(f"{name} failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     x = _Outputs()
@@ -933,8 +932,7 @@ def run_batch_assign(batch, qbatch, params, flags=0, lib=None, start=None):
     (consensus bytes per group, status array of the groups, list of Assignment, the (queries, groups) int32 score table or None,
     the uint8 pair status table or None).  Everything is copied out of the library's buffers.  Raises PoaError on a library error."""
     lib = lib or capi.load_hip()
-    if not hasattr(lib, "vc_poa_run_assign"):
-        raise PoaError("this libvechat_hip.so has no vc_poa_run_assign: it was built before the entry point existed; rebuild it")
+    run = _entry(lib, "vc_poa_run_assign")
     n = batch.n_windows
     if start is not None and len(start) != n:
         raise ValueError(f"{len(start)} graphs to start from for {n} groups")
@@ -943,7 +941,7 @@ def run_batch_assign(batch, qbatch, params, flags=0, lib=None, start=None):
     qv = qbatch.as_struct()
     qv.seq_begin = qv.seq_end = qv.win_fasta = qv.seq_has_qual = qv.quals = None
     a = capi.VcPoaAssignOut(flags=flags)
-    rc = lib.vc_poa_run_assign(C.byref(params), None if gin is None else C.byref(gin), C.byref(vb), C.byref(r), C.byref(qv), C.byref(a))
+    rc = run(C.byref(params), None if gin is None else C.byref(gin), C.byref(vb), C.byref(r), C.byref(qv), C.byref(a))
     del keep
     if rc != 0:
         raise PoaError(f"vc_poa_run_assign failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
@@ -1014,12 +1012,11 @@ def run_batch_correct(batch, params, prune, lib=None):
     """vc_poa_run_correct (params: capi.VcPoaGapParams; prune: capi.VcPoaPruneParams) on a capi.Batch -> (list of Corrected, status
     array per group).  Everything is copied out of the library's buffers before returning.  Raises PoaError on a library error."""
     lib = lib or capi.load_hip()
-    if not hasattr(lib, "vc_poa_run_correct"):
-        raise PoaError("this libvechat_hip.so has no vc_poa_run_correct: it was built before the entry point existed; rebuild it")
+    run = _entry(lib, "vc_poa_run_correct")
     n = batch.n_windows
     cons, off, status, r, vb = _result_buffers(batch)
     co = capi.VcPoaCorrectOut()
-    rc = lib.vc_poa_run_correct(C.byref(vb), C.byref(params), C.byref(prune), C.byref(r), C.byref(co))
+    rc = run(C.byref(vb), C.byref(params), C.byref(prune), C.byref(r), C.byref(co))
     if rc != 0:
         raise PoaError(f"vc_poa_run_correct failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     ns = int(co.n_seqs)
@@ -1078,12 +1075,11 @@ def run_batch_haplotypes(batch, params, hap, lib=None):
     status array, list of Haplotypes, the raw tables as a dict of numpy arrays).  Everything is copied out of the library's buffers
     before returning.  Raises PoaError on a library error."""
     lib = lib or capi.load_hip()
-    if not hasattr(lib, "vc_poa_run_haplotypes"):
-        raise PoaError("this libvechat_hip.so has no vc_poa_run_haplotypes: it was built before the entry point existed; rebuild it")
+    run = _entry(lib, "vc_poa_run_haplotypes")
     n = batch.n_windows
     cons, off, status, r, vb = _result_buffers(batch)
     o = capi.VcPoaHapOut()
-    rc = lib.vc_poa_run_haplotypes(C.byref(params), C.byref(hap), C.byref(vb), C.byref(r), C.byref(o))
+    rc = run(C.byref(params), C.byref(hap), C.byref(vb), C.byref(r), C.byref(o))
     if rc != 0:
         raise PoaError(f"vc_poa_run_haplotypes failed ({rc}): {lib.vc_poa_last_error().decode()}", rc=rc)
     wso = [int(x) for x in batch.win_seq_off]

@@ -10,63 +10,28 @@ are this package's own (vechat_amd.overlap on the device, internal matches kept)
 computes, and without a GPU the call fails."""
 import argparse
 import ctypes as C
-import gzip
 import sys
 
 import numpy as np
 
-from . import capi
-from .overlap import PRESETS, _take, pack
+from . import capi, seqio
+from .capi import VcScrubIn, VcScrubOut, VcScrubParams, _ptr, _take, pack
+from .overlap import PRESETS, records_from_paf
 
 CLEAN, BAD_ENDS, CHIMERIC, NOT_COVERED = 0, 1, 2, 3
 CLASS_NAMES = ("Clean", "BadEnds", "Chimeric", "NotCovered")
-PARAMS = ("coverage", "max_bad_permille", "min_piece")
+PARAMS = tuple(f for f, _ in VcScrubParams._fields_[1:])
 REGION = np.dtype([("read", "<u4"), ("begin", "<u4"), ("end", "<u4")])
-
-
-class VcScrubParams(C.Structure):
-    _fields_ = [("device", C.c_int32)] + [(f, C.c_int32) for f in PARAMS]
-
-
-class VcScrubIn(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("len", C.POINTER(C.c_uint32)), ("m", C.c_uint64), ("read", C.POINTER(C.c_uint32)),
-                ("begin", C.POINTER(C.c_uint32)), ("end", C.POINTER(C.c_uint32)), ("off", C.POINTER(C.c_uint64)),
-                ("bases", C.POINTER(C.c_uint8)), ("quals", C.POINTER(C.c_uint8))]
-
-
-class VcScrubOut(C.Structure):
-    _fields_ = [("n_regions", C.c_uint64), ("reg_read", C.POINTER(C.c_uint32)), ("reg_begin", C.POINTER(C.c_uint32)),
-                ("reg_end", C.POINTER(C.c_uint32)), ("reg_off", C.POINTER(C.c_uint64)), ("klass", C.POINTER(C.c_uint8)),
-                ("bad_total", C.POINTER(C.c_uint32)), ("n_pieces", C.c_uint64), ("pc_read", C.POINTER(C.c_uint32)),
-                ("pc_begin", C.POINTER(C.c_uint32)), ("pc_end", C.POINTER(C.c_uint32)), ("pc_off", C.POINTER(C.c_uint64)),
-                ("pc_bases", C.POINTER(C.c_uint8)), ("pc_quals", C.POINTER(C.c_uint8)),
-                ("n_intervals", C.c_uint64), ("n_events", C.c_uint64), ("n_segments", C.c_uint64)]
 
 
 def declare(lib):
     """argument types of the scrub entries (a missing symbol is an AttributeError: the library is older than this module)"""
-    lib.vc_scrub.argtypes = [C.POINTER(VcScrubParams), C.POINTER(VcScrubIn), C.POINTER(VcScrubOut)]
-    lib.vc_scrub.restype = C.c_int
-    lib.vc_scrub_default_params.argtypes = [C.POINTER(VcScrubParams)]
-    lib.vc_scrub_default_params.restype = None
-    lib.vc_scrub_last_error.restype = C.c_char_p
-    lib.vc_scrub_release.restype = None
-    return lib
+    return capi.bind(lib, ("vc_scrub_default_params", "vc_scrub", "vc_scrub_last_error", "vc_scrub_release"))
 
 
 def default_params(lib=None, **kw):
     lib = declare(lib or capi.load_hip())
-    p = VcScrubParams()
-    lib.vc_scrub_default_params(C.byref(p))
-    for name, v in kw.items():
-        if name != "device" and name not in PARAMS:
-            raise TypeError(f"unknown scrub parameter {name!r}")
-        setattr(p, name, int(v))
-    return p
-
-
-def _ptr(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+    return capi.params_from_defaults(VcScrubParams, lib.vc_scrub_default_params, PARAMS, "scrub", kw)
 
 
 def run(lengths, intervals, reads=None, quals=None, device=0, lib=None, **params):
@@ -150,7 +115,7 @@ def intervals_from_records(records, dual):
 def read_headers(path):
     """the header lines of a FASTA / FASTQ file without their first character, in file order (vechat_amd.seqio keeps the names only)"""
     out = []
-    with (gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")) as f:
+    with seqio._open(path) as f:
         while True:
             ln = f.readline()
             if not ln:
@@ -212,28 +177,20 @@ def parse_args(argv=None):
 
 def main(argv=None, out=None):
     a = parse_args(argv)
-    from . import overlap, seqio
+    from . import overlap
     recs = seqio.read_sequences(a.reads)
     headers = read_headers(a.reads)
     names, reads = [n for n, _, _ in recs], [d for _, d, _ in recs]
     if len(headers) != len(recs):
         raise ValueError(f"{a.reads}: {len(headers)} header lines for {len(recs)} records")
-    with (gzip.open(a.reads, "rb") if str(a.reads).endswith(".gz") else open(a.reads, "rb")) as f:
+    with seqio._open(a.reads) as f:
         fastq = f.read(1) == b"@"
     quals = [q if q is not None else b"!" * len(d) for _, d, q in recs] if fastq else None
     if a.paf is None:
         ov = overlap.find_overlaps(reads, None, device=a.device, drop_internal=0, max_gap=a.max_gap, **PRESETS[a.preset])
         intervals = intervals_from_records(ov, dual=True)
     else:
-        index = {n: i for i, n in enumerate(names)}
-        rows = []
-        for o in seqio.read_paf(a.paf):
-            for name in (o.q_name, o.t_name):
-                if name not in index:
-                    raise ValueError(f"{a.paf}: {name!r} is not a read of {a.reads}")
-            rows.append((index[o.q_name], o.q_begin, o.q_end, index[o.t_name], o.t_begin, o.t_end))
-        cols = np.array(rows, np.int64).reshape(-1, 6)
-        intervals = intervals_from_records({f: cols[:, i] for i, f in enumerate(("q_id", "q_begin", "q_end", "t_id", "t_begin", "t_end"))}, dual=False)
+        intervals = intervals_from_records(records_from_paf(a.paf, names, f"is not a read of {a.reads}"), dual=False)
     pieces, res = scrub(reads, intervals, quals=quals, coverage=a.coverage, max_bad_permille=a.max_bad_permille, min_piece=a.min_piece, device=a.device)
     text = format_pieces(pieces, res, names, headers, fastq)
     if out is not None:
