@@ -1211,6 +1211,131 @@ int         vc_cluster(const vc_cluster_params* p, const vc_cluster_in* in, vc_c
 const char* vc_cluster_last_error(void);
 void        vc_cluster_release(void);
 
+/* ------------------------------------------------------------------------------------------------
+ * Demultiplexing, orienting and trimming of reads by adapter, primer and barcode on the device (vechat_amd/csrc/vc_demux.hip):
+ * the step in front of the POA groups -- reads of several samples in one file, on both strands, each starting with a barcode
+ * or primer and ending with the reverse complement of one -- that otherwise goes to cutadapt, porechop or minibar.
+ *
+ * THIS IS THE LIBRARY'S OWN RULE, in the spirit of cutadapt and minibar (approximate matching of short patterns near the read
+ * ends) and a restatement of neither.  Nothing in the reference corresponds to it.  Everything is integer arithmetic and every
+ * tie is decided; tests/demux_ref.py restates the rule with full tables and the device is pinned to it array for array.
+ *
+ * Input.  n reads as offsets plus bytes (off[n + 1], bases), optionally their qualities under the same offsets.  P patterns as
+ * offsets plus bytes, pattern j of length m_j in 1..64, with label[j] < VC_DEMUX_MAX_LABELS (patterns of one label are one
+ * sample, barcode or amplicon) and side[j] in VC_DEMUX_ANY / _HEAD / _TAIL.  A pattern byte is an upper-case IUPAC code
+ * (ACGT RYSWKM BDHV N) and stands for its set of bases.  A read byte other than A C G T (N, lower case) matches no pattern byte.
+ *
+ * Views.  Every read has two views of length L = min(len, window).  View 0, the head, is read[0:L].  View 1, the tail, is the
+ * first L bases of the read's reverse complement: view position p of the tail is read position len - 1 - p, complemented; the
+ * complement of a byte outside ACGT is itself.  A barcode ligated to both ends, and the reverse primer of a + read, therefore
+ * appear in the tail view as written 5'->3'.
+ *
+ * Hit of a (read, view, pattern) triple, pattern of length m:
+ *     D[i][0] = i,  D[0][j] = 0,  D[i][j] = min(D[i-1][j-1] + mis, D[i-1][j] + 1, D[i][j-1] + 1),
+ *     mis = 0 iff view[j-1] is in the set of pattern[i-1]
+ *     d = min_j D[m][j];  e = the smallest j that attains d
+ *     start: the same recurrence on the reversed pattern and reverse(view[0:e]), anchored with E[0][j] = j;
+ *     k = the smallest j with E[m][j] == d;  s = e - k, the shortest hit that ends at e
+ * An empty view gives d = m, s = e = 0.  The hit is ACCEPTED iff 1000 * d <= max_err_permille * m.
+ *
+ * Per (read, view).  Accepted hits are ranked by smaller d, then larger m, then smaller j.  The best gives v_pat, v_dist,
+ * v_start, v_end.  v_second is the d of the best-ranked accepted hit whose label differs from the best's, 255 if there is none.
+ * The view is NONE when nothing is accepted (v_pat = VC_DEMUX_UNASSIGNED, v_dist = 255, v_start = v_end = 0, v_second = 255),
+ * AMBIG when v_second != 255 and v_second - v_dist < min_margin, and otherwise its best hit's label.
+ *
+ * Per read.  plus holds when the head view is a label whose best pattern has side HEAD or the tail view is a label whose best
+ * pattern has side TAIL; minus holds when the head's has side TAIL or the tail's has side HEAD.  The class, decided in this order:
+ *     1 both views NONE                                              VC_DEMUX_NONE 0
+ *     2 plus && minus, or both views are labels and differ            VC_DEMUX_CONFLICT 3
+ *     3 both views are the same label                                VC_DEMUX_BOTH_ENDS 2, that label
+ *     4 one view is a label and the other NONE                       VC_DEMUX_ONE_END 1, that label; with VC_DEMUX_REQUIRE_BOTH
+ *                                                                    the label is VC_DEMUX_UNASSIGNED
+ *     5 anything else                                                VC_DEMUX_AMBIGUOUS 4
+ * Classes 0, 3 and 4 have label VC_DEMUX_UNASSIGNED.  flip = minus && !plus; it is reported in every case and applied to the cut
+ * bytes only with VC_DEMUX_ORIENT.  The kept range [begin, end) is in read coordinates and comes from the views' best accepted
+ * hits whatever the class: begin = v_end(head) with trim 1, v_start(head) with trim 2, 0 with trim 0 or a NONE head;
+ * end = len - v_end(tail) with trim 1, len - v_start(tail) with trim 2, len with trim 0 or a NONE tail; begin >= end gives the
+ * empty piece end = begin.
+ *
+ * Output, library-owned.  The per-view arrays [2 n] at index 2 r + view; per read klass, label, flip, begin, end;
+ * piece_off[n + 1] into pc_bases and pc_quals, the kept bytes of every read back to back (with VC_DEMUX_ORIENT and flip
+ * reverse-complemented, the qualities reversed), NULL without the input; groups grp_off[n_labels + 1] into grp_reads, the reads
+ * with a label ordered by (label, read), n_labels = 1 + the largest label[j] (0 without patterns); with VC_DEMUX_ALL_HITS
+ * all_dist and all_end, [2 n P] at index (2 r + view) * P + j, else NULL; and the counts the call went through.  The result is
+ * a function of the input alone, not of any launch shape and not of how the reads are cut into pieces of the budget.
+ *
+ * The [2 n P] table of the search is produced per piece of consecutive reads; a piece's table fits the budget of
+ * VC_DEMUX_BUDGET_MB MiB (a test knob, fractions allowed; 256 when unset), one read at least.
+ * Envelope: n <= VC_OVL_MAX_SEQS, every read at most VC_OVL_MAX_LEN bases, P <= VC_DEMUX_MAX_PATTERNS.
+ * Checked on the host before the device is touched, in this order: p, in or out NULL, read offsets or bases NULL with
+ * n > 0, one of the four pattern arrays NULL with P > 0; read offsets, then pattern offsets, that do not start at 0 or decrease; window outside
+ * 1..4096, max_err_permille outside 0..1000, min_margin outside 0..64, trim outside 0..2, flag bits other than the three;
+ * P == 0 with n > 0; a pattern of length 0 or above 64, a pattern byte that is no IUPAC code, a side above 2, a label of
+ * VC_DEMUX_MAX_LABELS or more; n, a read length or P beyond the envelope: VC_ERR_ARG.  VC_ERR_NO_DEVICE only after these.
+ * Lifetime: the library owns every array of vc_demux_out -- one set per process, not thread-safe -- until the next vc_demux call
+ * or vc_demux_release; a failed call leaves every pointer NULL.  vc_demux_last_error has the text of the last failure.
+ * Test knob, read on every call: VC_DEMUX_LOG (one stderr line, "vc_demux: reads=N triples=T pieces=K accepted=A").
+ * ------------------------------------------------------------------------------------------------ */
+#define VC_DEMUX_ANY  0
+#define VC_DEMUX_HEAD 1
+#define VC_DEMUX_TAIL 2
+#define VC_DEMUX_NONE       0
+#define VC_DEMUX_ONE_END    1
+#define VC_DEMUX_BOTH_ENDS  2
+#define VC_DEMUX_CONFLICT   3
+#define VC_DEMUX_AMBIGUOUS  4
+#define VC_DEMUX_REQUIRE_BOTH 1
+#define VC_DEMUX_ORIENT       2
+#define VC_DEMUX_ALL_HITS     4
+#define VC_DEMUX_UNASSIGNED   0xFFFFFFFFu
+#define VC_DEMUX_MAX_LABELS   0x100000u
+#define VC_DEMUX_MAX_PATTERNS 65536
+typedef struct vc_demux_params {     /* vc_demux_default_params fills in the defaults named here                      */
+    int32_t device;                  /* 0                                                                            */
+    int32_t window;                  /* 150  (1..4096) bases of each read end that are searched                      */
+    int32_t max_err_permille;        /* 200  (0..1000)                                                               */
+    int32_t min_margin;              /* 2    (0..64)                                                                 */
+    int32_t trim;                    /* 1    0 keep everything, 1 cut the pattern and what lies outside it,          */
+                                     /*      2 keep the pattern and cut outside it                                   */
+    int32_t flags;                   /* 0    VC_DEMUX_REQUIRE_BOTH | VC_DEMUX_ORIENT | VC_DEMUX_ALL_HITS             */
+} vc_demux_params;
+typedef struct vc_demux_in {
+    uint64_t        n;               /* reads                                                                        */
+    const uint64_t* off;             /* [n + 1] into bases and quals                                                 */
+    const uint8_t*  bases;
+    const uint8_t*  quals;           /* NULL: no qualities                                                           */
+    uint64_t        n_patterns;      /* P                                                                            */
+    const uint64_t* pat_off;         /* [P + 1] into pat_bases                                                       */
+    const uint8_t*  pat_bases;       /* upper-case IUPAC codes                                                       */
+    const uint32_t* label;           /* [P]                                                                          */
+    const uint8_t*  side;            /* [P] VC_DEMUX_ANY / _HEAD / _TAIL                                             */
+} vc_demux_in;
+typedef struct vc_demux_out {        /* library-owned                                                                */
+    const uint32_t* v_pat;           /* [2 n] the best accepted pattern of the view, or VC_DEMUX_UNASSIGNED          */
+    const uint8_t*  v_dist;          /* [2 n] its distance, or 255                                                   */
+    const uint32_t* v_start;         /* [2 n] view coordinates                                                       */
+    const uint32_t* v_end;           /* [2 n] exclusive                                                              */
+    const uint8_t*  v_second;        /* [2 n] or 255                                                                 */
+    const uint8_t*  klass;           /* [n] VC_DEMUX_NONE .. VC_DEMUX_AMBIGUOUS                                      */
+    const uint32_t* label;           /* [n] or VC_DEMUX_UNASSIGNED                                                   */
+    const uint8_t*  flip;            /* [n]                                                                          */
+    const uint32_t* begin;           /* [n] read coordinates                                                         */
+    const uint32_t* end;             /* [n] exclusive                                                                */
+    const uint64_t* piece_off;       /* [n + 1] into pc_bases / pc_quals                                             */
+    const uint8_t*  pc_bases;        /* NULL without bases (n == 0)                                                  */
+    const uint8_t*  pc_quals;        /* NULL without qualities                                                       */
+    uint64_t        n_labels;
+    const uint64_t* grp_off;         /* [n_labels + 1] the reads of label g are grp_off[g] .. grp_off[g + 1]         */
+    const uint32_t* grp_reads;       /* [grp_off[n_labels]] ordered by (label, read)                                 */
+    const uint8_t*  all_dist;        /* NULL, or [2 n P] with VC_DEMUX_ALL_HITS                                      */
+    const uint32_t* all_end;         /* NULL, or [2 n P]                                                             */
+    uint64_t n_reads, n_triples, n_budget_pieces, n_accepted; /* what the call went through                          */
+} vc_demux_out;
+void        vc_demux_default_params(vc_demux_params* p);
+int         vc_demux(const vc_demux_params* p, const vc_demux_in* in, vc_demux_out* out);
+const char* vc_demux_last_error(void);
+void        vc_demux_release(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,26 @@ class VcClusterOut(C.Structure):
                 ("strand", C.POINTER(C.c_uint8)), ("n_links", C.c_uint64), ("n_rounds", C.c_uint64), ("n_components", C.c_uint64)]
 
 
+class VcDemuxParams(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("device", "window", "max_err_permille", "min_margin", "trim", "flags")]
+
+
+class VcDemuxIn(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("off", C.POINTER(C.c_uint64)), ("bases", C.POINTER(C.c_uint8)), ("quals", C.POINTER(C.c_uint8)),
+                ("n_patterns", C.c_uint64), ("pat_off", C.POINTER(C.c_uint64)), ("pat_bases", C.POINTER(C.c_uint8)),
+                ("label", C.POINTER(C.c_uint32)), ("side", C.POINTER(C.c_uint8))]
+
+
+class VcDemuxOut(C.Structure):
+    _fields_ = [("v_pat", C.POINTER(C.c_uint32)), ("v_dist", C.POINTER(C.c_uint8)), ("v_start", C.POINTER(C.c_uint32)),
+                ("v_end", C.POINTER(C.c_uint32)), ("v_second", C.POINTER(C.c_uint8)), ("klass", C.POINTER(C.c_uint8)),
+                ("label", C.POINTER(C.c_uint32)), ("flip", C.POINTER(C.c_uint8)), ("begin", C.POINTER(C.c_uint32)),
+                ("end", C.POINTER(C.c_uint32)), ("piece_off", C.POINTER(C.c_uint64)), ("pc_bases", C.POINTER(C.c_uint8)),
+                ("pc_quals", C.POINTER(C.c_uint8)), ("n_labels", C.c_uint64), ("grp_off", C.POINTER(C.c_uint64)),
+                ("grp_reads", C.POINTER(C.c_uint32)), ("all_dist", C.POINTER(C.c_uint8)), ("all_end", C.POINTER(C.c_uint32)),
+                ("n_reads", C.c_uint64), ("n_triples", C.c_uint64), ("n_budget_pieces", C.c_uint64), ("n_accepted", C.c_uint64)]
+
+
 def default_params(**kw):
     """Defaults the Python driver ends up with (scripts/vechat:70-72: -d 0.2 -s 0.2; main.cpp:46-61)."""
     p = VcParams(device=0, match=3, mismatch=-5, gap=-4, sw_match=3, sw_mismatch=-5, sw_gap=-4,
@@ -549,6 +569,10 @@ SIGNATURES = {
     "vc_cluster": (_int, [_P(VcClusterParams), _P(VcClusterIn), _P(VcClusterOut)]),
     "vc_cluster_last_error": (_str, []),
     "vc_cluster_release": (None, []),
+    "vc_demux_default_params": (None, [_P(VcDemuxParams)]),
+    "vc_demux": (_int, [_P(VcDemuxParams), _P(VcDemuxIn), _P(VcDemuxOut)]),
+    "vc_demux_last_error": (_str, []),
+    "vc_demux_release": (None, []),
 }
 _names = list(SIGNATURES)
 HOST_ENTRIES = tuple(_names[_names.index("vc_rank_layers"):_names.index("vc_io_load") + 1])
